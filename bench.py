@@ -652,6 +652,50 @@ def check_stats(stats, what):
         sys.exit(3)
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload in all
+
+
+def dump_selection(nrows, ncols, budget, seed):
+    """(rows, cols) of an (nrows, ncols) pair of fp64 arrays kept by --dump-outputs: everything when both fit in `budget`
+    bytes, else a fixed seeded choice of whole rows (realizations), and of columns too when not even one row fits.
+    None = all of them."""
+    if 2 * 8 * nrows * ncols <= budget:
+        return None, None
+    rng = np.random.default_rng(seed)
+    k = budget // (2 * 8 * ncols)
+    if k >= 1:
+        return np.sort(rng.choice(nrows, k, replace=False)), None
+    return np.sort(rng.choice(nrows, 1, replace=False)), np.sort(rng.choice(ncols, budget // 16, replace=False))
+
+
+def dump_outputs(path, farm, step, step_stats, seed, budget=DUMP_BYTES):
+    """What the last timed step handed its caller, as float64 .npy files under `path` (rank 0's lanes only):
+    xi.npy / field.npy = the white noise of Sample and the field of Eval, one row per realization (realization_ids.npy: its
+    id, first_id + column of the plugin call), stats.npy = Eval's per-realization stats (iterations, converged, initial_norm,
+    final_norm) of every realization of the step.  Larger than `budget` in all: a fixed seeded sample of the rows (and
+    cols, cell_ids.npy).  Called after the timed region, before anything else reuses the lanes' buffers."""
+    os.makedirs(path, exist_ok=True)
+    ns, nb, n = farm.ns, farm.nb, farm.n
+    stats = np.asarray(step_stats, np.float64).reshape(ns * nb, -1)
+    ids = np.arange(ns * nb, dtype=np.float64) + (step * ns) * nb      # batch index step * ns + lane, first_id = that * nb
+    rows, cols = dump_selection(ns * nb, n, budget - stats.nbytes - ids.nbytes - 1024, seed)   # 1 kB: .npy headers
+    rows = np.arange(ns * nb) if rows is None else rows
+    xi, s = [], []
+    for lane, (_, _, xi_d, s_d) in enumerate(farm.lanes):
+        pick = rows[(rows >= lane * nb) & (rows < (lane + 1) * nb)] - lane * nb
+        if pick.size == 0:
+            continue
+        for dev_buf, dst in ((xi_d, xi), (s_d, s)):
+            a = dev_buf.download().reshape(nb, n)[pick]
+            dst.append(a if cols is None else a[:, cols])
+    np.save(os.path.join(path, "xi.npy"), np.concatenate(xi))
+    np.save(os.path.join(path, "field.npy"), np.concatenate(s))
+    np.save(os.path.join(path, "realization_ids.npy"), ids[rows])
+    np.save(os.path.join(path, "stats.npy"), stats)
+    if cols is not None:
+        np.save(os.path.join(path, "cell_ids.npy"), cols.astype(np.float64))
+
+
 def operator_roofline(farm, problem, nb, tag, next_batch, solver_bytes, iters_total, dt):
     """Roofline block of the dominant kernel, the block saddle-point SpMM K5, measured after the timed region:
     `achieved` is the instantiation the MINRES loop launches (fused <u, Au>), every launch of three solo batches of lane 0
@@ -1218,7 +1262,13 @@ def main():
                          "default MINRES-BJ-GS on the saddle-point system (pmc_sampler_create).  The other one is measured "
                          "under extra.")
     ap.add_argument("--seed", type=int, default=20261003)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0: white noise, field, per-realization "
+                         "stats) as float64 DIR/<name>.npy, at most 64 MB in all (a fixed seeded sample of the realizations "
+                         "beyond that); the same arguments give the same inputs, so two builds can be compared file by file")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself and never touches the GPU
@@ -1316,6 +1366,8 @@ def main():
 
     out = None
     zb = farm.lanes[0][1].z_bytes()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, farm, args.warmup + args.steps - 1, stats[-ns * nb:], args.seed)
     if rank == 0:
         next_batch = (args.warmup + args.steps + 1) * ns
         solver_text = (f"solver: hybridization (the reference's alternative to its default, src/PDESampler.cpp:291,307-311: "

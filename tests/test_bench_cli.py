@@ -1,8 +1,13 @@
 """bench.py command line without a GPU: the rank launcher of `--gpus N` propagates a failing rank's exit code, and a launcher
-environment that contradicts `--gpus` is refused before anything heavy happens."""
+environment that contradicts `--gpus` is refused before anything heavy happens.  --dump-outputs: the selection logic here, the
+real run on the GPU (marked)."""
+import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -124,3 +129,93 @@ def test_compact_line_of_the_round5_record_carries_the_event_overhead_fields():
     assert r["frac"] < r["frac_net_of_event_overhead"] < r["frac"] * 1.06      # a 4-5 us bracket on a ~147 us launch
     assert 0.003 < r["event_overhead_ms"] < 0.008
     assert d["cpu_baseline"]["solver"].startswith("PCG") and d["config"]["solver"] == "hybridization"
+
+
+class _Buf:
+    def __init__(self, a):
+        self.a = a
+
+    def download(self):
+        return self.a.ravel().copy()
+
+
+class _Farm:
+    """the part of bench.SamplerFarm dump_outputs reads: ns lanes of (ctx, sampler, xi buffer, field buffer), nb x n each;
+    entry (row, col) of a step holds 1000 * realization id + col (field: its negative)"""
+
+    def __init__(self, ns, nb, n, step):
+        self.ns, self.nb, self.n = ns, nb, n
+        ids = step * ns * nb + np.arange(ns * nb)
+        v = 1000.0 * ids[:, None] + np.arange(n)[None, :]
+        self.lanes = [(None, None, _Buf(v[k * nb:(k + 1) * nb]), _Buf(-v[k * nb:(k + 1) * nb])) for k in range(ns)]
+
+
+def _dumped(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+@pytest.mark.parametrize("budget", [1 << 20, 6 << 10, 2 << 10])
+def test_dump_outputs_fits_its_budget_and_keeps_rows_whole(tmp_path, budget):
+    """--dump-outputs: float64 files only, within the byte budget, the same selection on every call; every dumped row is the
+    realization realization_ids names (whole when one row fits, a fixed set of columns otherwise)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    ns, nb, n, step = 3, 4, 100, 7
+    stats = [(20 + i, 1, 1.0, 1e-7) for i in range(ns * nb)]
+    outs = []
+    for k in range(2):
+        d = str(tmp_path / f"d{k}")
+        bench.dump_outputs(d, _Farm(ns, nb, n, step), step, stats, seed=11, budget=budget)
+        outs.append(_dumped(d))
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= budget
+    a, b = outs
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype == np.float64 for v in a.values())
+    ids, xi, s = a["realization_ids"], a["xi"], a["field"]
+    cols = a.get("cell_ids", np.arange(n, dtype=np.float64))
+    assert len(ids) >= 1 and len(set(ids)) == len(ids)
+    assert set(ids) <= set(range(step * ns * nb, (step + 1) * ns * nb))
+    assert np.array_equal(xi, 1000.0 * ids[:, None] + cols[None, :]) and np.array_equal(s, -xi)
+    assert np.array_equal(a["stats"], np.asarray(stats, np.float64))
+    if budget == 1 << 20:
+        assert len(ids) == ns * nb and "cell_ids" not in a
+    else:
+        assert len(ids) < ns * nb
+    assert ("cell_ids" in a) == (budget == 2 << 10)
+
+
+def test_steps_below_one_are_refused():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_what_the_timed_path_computed(tmp_path):
+    """bench.py --dump-outputs on a small headline: --steps timed steps (ms_per_step in the line), two runs with the same
+    arguments dump the same arrays, and the dumped field is the sampler field of the dumped white noise (oracle direct solve)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle.sampler_oracle import SamplerOracle
+    lines, dumps = [], []
+    for k in range(2):
+        d = str(tmp_path / f"run{k}")
+        r = _run(["--refine", "3", "--streams", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+                  "--dump-outputs", d])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append(_dumped(d))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    nb, ns = line["config"]["batch"], line["config"]["streams"]
+    assert abs(line["value"] - nb * ns / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    a, b = dumps
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES
+    ids = a["realization_ids"]
+    assert ids.min() >= (1 + 3 - 1) * ns * nb and ids.max() < (1 + 3) * ns * nb     # the last timed step's realizations
+    assert a["stats"].shape == (ns * nb, 4) and np.all(a["stats"][:, 1] == 1)
+    so = SamplerOracle(bench.build_problem(3))
+    for j in (0, len(ids) - 1):
+        ref = so.eval(0, 0, a["xi"][j])[0]
+        assert np.linalg.norm(a["field"][j] - ref) / np.linalg.norm(ref) < 1e-5
