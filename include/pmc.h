@@ -374,6 +374,25 @@ int pmc_darcy_solve_fwd(pmc_darcy* d, int level, int nbatch, const double* k, do
 int pmc_darcy_solve_fwd_pressure(pmc_darcy* d, int level, int nbatch, const double* k, double* p_out, double* C,
                                  double* Q, int compute_Q, int memspace, pmc_stats* stats);
 
+/* z = B(k)^-1 r: ONE application of the block-diagonal preconditioner the MINRES solve of `level` uses, column b with its
+ * own permeability k[b*n_p .. (b+1)*n_p) (the same per-realization setup and the same kernels as pmc_darcy_solve_fwd).
+ * r, z: nbatch x (n_u + n_p) sample-major, fp64 in and out; on a handle from pmc_darcy_create_hybrid they are multiplier
+ * vectors (the V-cycle of H(kappa)), nbatch x n_lambda.  nbatch: one of the level's launch widths (1, 2, 4, ... up to
+ * pmc_darcy_batch_width).  All arrays in `memspace`.  With PMC_STORAGE_FP32 the solver additionally rounds z to fp32. */
+int pmc_darcy_apply_preconditioner(pmc_darcy* d, int level, int nbatch, const double* k, const double* r, double* z,
+                                   int memspace);
+/* y = A(k) x, the operator of the same solve: [M(k) B^T; B 0] with the essential rows and columns eliminated (unit
+ * diagonal), or H(kappa) on a hybridized handle.  Arguments as pmc_darcy_apply_preconditioner. */
+int pmc_darcy_apply_operator(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, double* y, int memspace);
+/* Setup values of level `vlevel` (0 = the first) of the Schur-block V-cycle the solves of `level` run (what a reference of
+ * B(k)^-1 cannot derive from the caller's data): info[0] = rows, [1] = lmax of the diagonally scaled level operator, [2] = 1
+ * when the cycle ends on this level, [3] / [4] = smoothing degree / ratio (interval [lmax / ratio, lmax]), [5] / [6] = degree /
+ * ratio of the polynomial solve that ends the cycle, [7] = s of the caller's hierarchy S_{l+1}(k) = s P^T S_l(k) P (0 for an
+ * internal hierarchy), [8] = ratio_M and [9] = degree of the l1-scaled Chebyshev polynomial of the M-block (lmax 1),
+ * [10] = 0: the caller's hierarchy (P of the level structs), 1: an internal aggregation hierarchy, 2: the multiplier
+ * hierarchy of a hybridized handle.  Returns the number of V-cycle levels through *nvlevels; vlevel out of range is an error. */
+int pmc_darcy_vcycle_level(const pmc_darcy* d, int level, int vlevel, int* nvlevels, double info[11]);
+
 /* Bayesian observation operator (src/BayesianInverseProblem.cpp:178-186, ComputeG): Gobs is nobs x n_p(level), row i
  * = the observation functional g_obs_i (e.g. the indicator of the cells around an observation point, restricted to the
  * level).  pmc_darcy_compute_G solves like SolveFwd and returns G[b*nobs + i] = <g_i, p_b> / sum(g_i) (host array) plus

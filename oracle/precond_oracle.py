@@ -1,0 +1,105 @@
+"""ORACLE (test infrastructure): fp64 restatement of the MINRES preconditioner B(k)^-1 of the mixed Darcy solver on the
+caller's level hierarchy, written from the mathematics (include/pmc.h: pmc_solver_opts; csrc/solver.hpp: ChebParams,
+Multigrid), not from the kernels.
+
+    B(k)^-1 = diag( p_M(D_l1^-1 M(k)) D_l1^-1 ,  V(S(k)) )
+
+- M-block: Chebyshev polynomial of degree `degree_M` in D_l1^-1 M(k) on [1 / ratio_M, 1] (lmax 1: the l1 row sums bound the
+  spectrum), D_l1 = the l1 row sums of M(k) after the elimination of the essential rows (DarcyOracle.assemble);
+- S-block: one V-cycle on S_0(k) = B diag(M(k))^-1 B^T (essential u-dofs eliminated) and S_{l+1} = s P_l^T S_l P_l with
+  s = 1/2, Jacobi-scaled Chebyshev smoothers of degree `smooth_degree` on [lmax / smooth_ratio, lmax], lmax = 2 * 1.0001
+  (a weakly diagonally dominant M-matrix has spec(D^-1 S) in (0, 2]), pre-smoothing from zero, post-smoothing from the
+  corrected iterate, and a Chebyshev polynomial of degree `coarse_degree` on [lmax / coarse_ratio, lmax] on the last level.
+"""
+from __future__ import annotations
+
+import numpy as np
+import scipy.sparse as sp
+
+from .darcy_oracle import DarcyOracle
+
+GALERKIN_SCALE = 0.5            # S_{l+1} = 1/2 P^T S_l P on the caller's hierarchy
+LMAX_SCHUR = 2.0 * 1.0001       # Gershgorin bound of D^-1 S with a 1e-4 margin
+
+
+def cheb2_coefficients(lmax, ratio):
+    """closed form of the degree-2 Chebyshev polynomial: p(D^-1 A) D^-1 r = D^-1 (c0 r - c1 A D^-1 r).  From
+    1 - l p(l) = T_2((theta - l) / delta) / T_2(sigma): p(l) = (4 theta / delta^2) / T_2(sigma) - (2 / delta^2) / T_2(sigma) l."""
+    lmin = lmax / ratio
+    theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+    t2 = 2.0 * (theta / delta) ** 2 - 1.0
+    return 4.0 * theta / (delta * delta * t2), 2.0 / (delta * delta * t2)
+
+
+def chebyshev(A, dinv, r, degree, lmax, ratio, x0=None):
+    """Chebyshev semi-iteration of `degree` steps for A x = r preconditioned by diag(dinv), spectrum of D^-1 A assumed in
+    [lmax / ratio, lmax] (Saad, Iterative Methods, Alg. 12.1).  x0 None: from a zero guess (x = p(D^-1 A) D^-1 r); else
+    x0 + p(D^-1 A) D^-1 (r - A x0)."""
+    lmin = lmax / ratio
+    theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+    sigma = theta / delta
+    rho_old = 1.0 / sigma
+    if x0 is None:
+        d = dinv * r / theta
+        x = d.copy()
+    else:
+        d = dinv * (r - A @ x0) / theta
+        x = x0 + d
+    for _ in range(1, degree):
+        rho = 1.0 / (2.0 * sigma - rho_old)
+        d = rho * rho_old * d + (2.0 * rho / delta) * dinv * (r - A @ x)
+        x = x + d
+        rho_old = rho
+    return x
+
+
+def vcycle(levels, r, smooth_degree, smooth_ratio, coarse_degree, coarse_ratio, l=0, coarse_solve=None):
+    """One V(1,1)-cycle from level l.  levels[i] = (S_i, lmax_i, P_i) with P_i: level i+1 -> i (None on the last level).
+    coarse_solve (optional): exact solve on the last level instead of the polynomial (the textbook two-grid method)."""
+    S, lmax, P = levels[l]
+    dinv = 1.0 / S.diagonal()
+    if l == len(levels) - 1:
+        if coarse_solve is not None:
+            return coarse_solve(r)
+        return chebyshev(S, dinv, r, coarse_degree, lmax, coarse_ratio)
+    x = chebyshev(S, dinv, r, smooth_degree, lmax, smooth_ratio)
+    xc = vcycle(levels, P.T @ (r - S @ x), smooth_degree, smooth_ratio, coarse_degree, coarse_ratio, l + 1, coarse_solve)
+    x = x + P @ xc
+    return chebyshev(S, dinv, r, smooth_degree, lmax, smooth_ratio, x0=x)
+
+
+class DarcyPrecondOracle:
+    """B(k)^-1 of a saddle-point Darcy handle on the caller's hierarchy, one realization at a time."""
+
+    def __init__(self, problem, smooth_degree=2, smooth_ratio=8.0, coarse_degree=12, coarse_ratio=100.0):
+        self.p = problem
+        self.do = DarcyOracle(problem)
+        self.smooth = (smooth_degree, smooth_ratio, coarse_degree, coarse_ratio)
+
+    def mass(self, level, k):
+        """M(k) with the essential rows / columns eliminated (unit diagonal there), and the essential mask"""
+        L = self.p.levels[level]
+        A = self.do.assemble(level, np.asarray(k, dtype=np.float64))[0].tocsr()
+        return A[:L.n_u, :L.n_u].tocsr(), L.ess_mask.astype(bool)
+
+    def schur_levels(self, level, k):
+        """[(S_l, lmax, P_l)] from `level` down to the last level of the problem"""
+        L = self.p.levels[level]
+        M, ess = self.mass(level, k)
+        Bk = (L.B @ sp.diags((~ess).astype(np.float64))).tocsr()
+        S = (Bk @ sp.diags(1.0 / M.diagonal()) @ Bk.T).tocsr()
+        out = []
+        for l in range(level, len(self.p.levels)):
+            P = self.p.levels[l].P if l + 1 < len(self.p.levels) else None
+            out.append((S, LMAX_SCHUR, P))
+            if P is not None:
+                S = (GALERKIN_SCALE * (P.T @ S @ P)).tocsr()
+        return out
+
+    def apply(self, level, k, r, ratio_M, degree_M):
+        L = self.p.levels[level]
+        M, _ = self.mass(level, k)
+        l1inv = 1.0 / np.asarray(abs(M).sum(axis=1)).ravel()
+        zu = chebyshev(M, l1inv, r[:L.n_u], degree_M, 1.0, ratio_M)
+        zp = vcycle(self.schur_levels(level, k), r[L.n_u:], *self.smooth)
+        return np.concatenate([zu, zp])

@@ -145,6 +145,9 @@ SYMBOLS = {
                                       C.c_int, C.POINTER(pmc_stats)]),
     "pmc_darcy_solve_fwd_pressure": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.POINTER(C.c_double),
                                                C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_darcy_apply_preconditioner": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
+    "pmc_darcy_apply_operator": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
+    "pmc_darcy_vcycle_level": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "pmc_darcy_set_observations": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_csr)]),
     "pmc_darcy_num_observations": (C.c_int, [_VP, C.c_int]),
     "pmc_darcy_compute_G": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -697,6 +700,40 @@ class DarcySolver:
         if return_stats:
             out.append([(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in stats])
         return tuple(out)
+
+    def _apply(self, fn, level, k, v):
+        k = _f64(np.atleast_2d(k))
+        v = _f64(np.atleast_2d(v))
+        if k.shape[0] != v.shape[0]:
+            raise ValueError("k and the vectors must have the same number of columns")
+        out = np.empty_like(v)
+        _check(fn(self.h, level, v.shape[0], _ptr(k, C.c_double), _ptr(v, C.c_double), _ptr(out, C.c_double),
+                  PMC_MEM_HOST))
+        return out
+
+    def ApplyPreconditioner(self, level, k, r):
+        """z = B(k)^-1 r, one application of the MINRES preconditioner of `level` (pmc_darcy_apply_preconditioner): column j
+        with its own permeability k[j].  k: (nbatch, n_p), r: (nbatch, n_u + n_p) - hybridized handle: (nbatch, n_lambda),
+        multipliers in the numbering of parelagmc_amd.fe.darcy_hybrid - nbatch one of 1, 2, 4, ... up to BatchWidth(level)."""
+        return self._apply(self.ctx.lib.pmc_darcy_apply_preconditioner, level, k, r)
+
+    def ApplyOperator(self, level, k, x):
+        """y = A(k) x, the operator of the MINRES solve of `level` (pmc_darcy_apply_operator): [M(k) B^T; B 0] after the
+        elimination of the essential rows, or H(kappa) on a hybridized handle; shapes as ApplyPreconditioner."""
+        return self._apply(self.ctx.lib.pmc_darcy_apply_operator, level, k, x)
+
+    def vcycle_levels(self, level):
+        """setup values of every level of the Schur-block V-cycle of `level` (pmc_darcy_vcycle_level): a list of dicts"""
+        keys = ("rows", "lmax", "bottom", "smooth_degree", "smooth_ratio", "last_degree", "last_ratio", "galerkin_scale",
+                "ratio_M", "degree_M", "hierarchy")
+        out, nv, v = [], C.c_int(0), 0
+        while True:
+            info = (C.c_double * 11)()
+            _check(self.ctx.lib.pmc_darcy_vcycle_level(self.h, level, v, C.byref(nv), info))
+            out.append(dict(zip(keys, list(info))))
+            v += 1
+            if v >= nv.value:
+                return out
 
     def SetObservations(self, level, Gobs):
         """Gobs: scipy sparse (nobs, n_p): rows are the observation functionals g_obs_i of the level."""

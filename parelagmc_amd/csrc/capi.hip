@@ -580,6 +580,27 @@ int pmc_darcy_solve_fwd_pressure(pmc_darcy* d, int level, int nbatch, const doub
     });
 }
 
+int pmc_darcy_apply_preconditioner(pmc_darcy* d, int level, int nbatch, const double* k, const double* r, double* z,
+                                   int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.apply_preconditioner(level, nbatch, k, r, z, memspace);
+    });
+}
+int pmc_darcy_apply_operator(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, double* y, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.apply_operator(level, nbatch, k, x, y, memspace);
+    });
+}
+int pmc_darcy_vcycle_level(const pmc_darcy* d, int level, int vlevel, int* nvlevels, double info[11]) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr && nvlevels != nullptr && info != nullptr, "pmc_darcy_vcycle_level: NULL argument");
+        d->impl.vcycle_level(level, vlevel, nvlevels, info);
+    });
+}
 int pmc_darcy_set_observations(pmc_darcy* d, int level, const pmc_csr* Gobs) {
     return guarded([&] {
         PMC_REQUIRE(d != nullptr, "darcy is NULL");

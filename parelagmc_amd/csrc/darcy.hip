@@ -403,7 +403,7 @@ Darcy::Darcy(Ctx& c, int nlevels_, int n_mc_, const pmc_darcy_level* in, bool kd
                 const int e2 = S.colind[p];
                 for (int a = P.rowptr[e]; a < P.rowptr[e + 1]; ++a)
                     for (int b = P.rowptr[e2]; b < P.rowptr[e2 + 1]; ++b)
-                        tr.push_back({P.colind[a], P.colind[b], p, 0.5 * P.vals[a] * P.vals[b]});
+                        tr.push_back({P.colind[a], P.colind[b], p, galerkin_scale * P.vals[a] * P.vals[b]});
             }
         const HostCsr& own = schur[l + 1].pat;
         for (int e = 0; e < own.nrows; ++e)
@@ -618,13 +618,12 @@ void Darcy::compute_G(int level, int nbatch, const double* kf, double* G, double
     }
 }
 
-void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
-                        int nrows, double* G_host) {
+// Per-realization setup of a saddle-point launch (buffers sized by ensure): M(k), elimination, rhs_bc and the values of
+// the Schur hierarchy.  solve_chunk and apply_preconditioner / apply_operator enqueue exactly these kernels.
+void Darcy::setup_chunk(int level, int nb, const double* k_d) {
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
-    const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p;
-    ensure(level, nb);
-    if (stats) ctx.phase_mark(0);
+    const int n_u = d.n_u, n_p = d.n_p;
     // K12/K13: M(k), elimination, rhs_bc
     const bool eg = use_eg(d);
     k::darcy_coef(st, nb, n_p, k_d, k_divides, d.coef.p);
@@ -668,17 +667,22 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
         }
         mg.refresh_bv_tail(st, nb, level);
     }
-    if (stats) ctx.phase_mark(1);   // "Darcy: Build Solver" ends here: everything below is the solve
-    // operator [M(k) Bt; B 0] and block-diagonal preconditioner
+}
+
+// The operator [M(k) Bt; B 0] and the block-diagonal preconditioner of a saddle-point launch, over the values setup_chunk
+// wrote.  timing_ok: the in-loop event brackets may be recorded (when the timers are on).
+void Darcy::chunk_ops(int level, int nb, bool timing_ok, LinOp& A, PrecFn& prec) {
+    DarcyLevel& d = lv[level];
+    const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p;
+    const bool eg = use_eg(d);
+    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
     const SellView Mv = view_bv(d.M, d.mvals.p);
     const SellView Bv = view(d.B), Btv = view(d.Bt);
     const EgView Mg{d.n_u, d.Meg.nslices, d.eg_gw, d.Meg.cols.p, d.Meg.vals.p, d.eg_e12.p};
     const double* coefp = d.coef.p;
-    LinOp A;
+    A = LinOp();
     A.n = n;
     A.n0 = n_u;
-    // in-loop event brackets are not recorded while the MINRES iterations may be captured into a hipGraph (as the sampler's)
-    const bool timing_ok = opts.use_graph == 0;
     OpTimer* tm = &op_timer;
     OpTimer* tp = &poly_timer;
     // (the Darcy solves start from zero: only the product from a preconditioned vector is ever needed)
@@ -703,7 +707,7 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     double* cdp = cd.p;
     Multigrid* mgp = chain ? &chain->mg : &mg;
     const int mg_l0 = chain ? 0 : level;
-    PrecFn prec = [=](const Lanes& L, int nb_, const double* r, zvec z, double* dot_partial, double* dot_partial2) {
+    prec = [=](const Lanes& L, int nb_, const double* r, zvec z, double* dot_partial, double* dot_partial2) {
         // independent diagonal blocks: V-cycle of the S-block on the main stream, the M-block polynomial on the second
         // stream beside the V-cycle's coarse levels (see the sampler's preconditioner)
         int nblk_u = 0;
@@ -730,6 +734,24 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
         L.join();
         return k::DotParts{dot_partial, nblk_s, dot_partial2, nblk_u};
     };
+}
+
+void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
+                        int nrows, double* G_host) {
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    const int n = d.n_u + d.n_p;
+    ensure(level, nb);
+    if (stats) ctx.phase_mark(0);
+    setup_chunk(level, nb, k_d);
+    if (stats) ctx.phase_mark(1);   // "Darcy: Build Solver" ends here: everything below is the solve
+    LinOp A;
+    PrecFn prec;
+    // in-loop event brackets are not recorded while the MINRES iterations may be captured into a hipGraph (as the sampler's)
+    chunk_ops(level, nb, opts.use_graph == 0, A, prec);
+    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
+    Multigrid* mgp = chain ? &chain->mg : &mg;
+    const int mg_l0 = chain ? 0 : level;
     // SolveFwd only needs Q = <obs, sol>: unless the solution itself is requested, MINRES maintains just the rows in
     // the support of obs (compact w / x vectors)
     const bool gmode = G_host != nullptr;
@@ -928,17 +950,20 @@ void Darcy::build_hybrid(int level, const pmc_darcy_level& L) {
     hyb[level] = std::move(hy);
 }
 
-// SolveFwd through the hybridized form: H(kappa) lambda = R kappa + b_0 by MINRES with one V-cycle of the per-realization
-// aggregation hierarchy, then the element-local back-substitution into the full solution vector (what Q, the returned
-// solution and the pressure block are taken from, exactly as after the saddle-point solve).
-void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
-                               int nrows) {
+// V(1,1) with the finest level in element-grouped form (see hybrid_ops)
+bool Darcy::hybrid_eg_cycle(int level) const {
+    static const bool eg_off = lab_env("PMC_DARCY_HYB_NO_EG") != nullptr;   // laboratory A/B: generic V-cycle on explicit values
+    const Multigrid& g = hyb[level]->chain->mg;
+    return g.L.size() >= 2 && g.smooth_degree == 2 && !eg_off;
+}
+
+// Buffers of a hybridized launch at width nb (on top of what ensure sizes)
+void Darcy::ensure_hybrid(int level, int nb) {
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     DarcyHybrid& hy = *hyb[level];
     const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p, nl = hy.n_lambda;
     DarcyChain& ch = *hy.chain;
-    // sizes at this launch width
     ch.mg.ensure_bv_tail_width(st, nb);
     for (MgLevel& m : ch.mg.L) {
         m.vals_bv.ensure((size_t)m.S.nslots * nb);
@@ -959,9 +984,7 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
     qpartial.ensure((size_t)dot_capacity(n, nb) * nb);
     qout.ensure(kMaxBatch);
     gwork.ensure(kMaxBatch);
-    static const bool eg_off = lab_env("PMC_DARCY_HYB_NO_EG") != nullptr;   // laboratory A/B: generic V-cycle on explicit values
-    const bool eg_cycle = ch.mg.L.size() >= 2 && ch.mg.smooth_degree == 2 && !eg_off;
-    if (eg_cycle) {
+    if (hybrid_eg_cycle(level)) {
         hy.negcoef.ensure((size_t)(n_p + 1) * nb);
         hy.vx.ensure((size_t)nl * nb);
         hy.vres.ensure((size_t)nl * nb);
@@ -969,8 +992,17 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
         hy.vxc.ensure((size_t)ch.mg.L[1].n * nb);
         ch.mg.L[1].ensure(nb);
     }
-    if (stats) ctx.phase_mark(0);
-    // kappa = 1 / c(k); operators of the hierarchy; right-hand side
+}
+
+// Per-realization setup of a hybridized launch (buffers sized by ensure_hybrid): kappa and the values of the multiplier
+// hierarchy.  solve_chunk_hybrid and apply_preconditioner / apply_operator enqueue exactly these kernels.
+void Darcy::setup_chunk_hybrid(int level, int nb, const double* k_d) {
+    hipStream_t st = ctx.stream;
+    const int n_p = lv[level].n_p;
+    DarcyHybrid& hy = *hyb[level];
+    DarcyChain& ch = *hy.chain;
+    const bool eg_cycle = hybrid_eg_cycle(level);
+    // kappa = 1 / c(k); operators of the hierarchy
     k::darcy_coef(st, nb, n_p, k_d, !k_divides, hy.coef.p);
     k::fill(st, (size_t)nb, hy.coef.p + (size_t)n_p * nb, 1.0);
     if (eg_cycle) k::scale(st, (size_t)(n_p + 1) * nb, hy.coef.p, -1.0, hy.negcoef.p);
@@ -986,9 +1018,14 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
         else k::scale_cols_bv(st, nb, m.S.nslots, m.S.cols.p, m.vals_bv.p, m.dinv.p, m.vals_scaled.p);
     }
     ch.mg.refresh_bv_tail(st, nb);
-    k::broadcast(st, nb, nl, hy.b0.p, hy.rhs.p);
-    k::spmm(st, nb, view(hy.R), hy.coef.p, hy.rhs.p, true, nullptr, nullptr);
-    if (stats) ctx.phase_mark(1);
+}
+
+// The operator H(kappa) and the V-cycle preconditioner of a hybridized launch, over the values setup_chunk_hybrid wrote
+void Darcy::hybrid_ops(int level, LinOp& A, PrecFn& prec) {
+    DarcyHybrid& hy = *hyb[level];
+    const int nl = hy.n_lambda;
+    DarcyChain& ch = *hy.chain;
+    const bool eg_cycle = hybrid_eg_cycle(level);
     const EgView Hg{nl, hy.Heg.nslices, hy.eg_gw, hy.Heg.cols.p, hy.Heg.vals.p, hy.eg_e12.p};
     SellView none;                    // the element-grouped operator kernel adds a second, shared-value operator: none here
     none.nrows = nl;
@@ -996,14 +1033,13 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
     none.slice_off = hy.no_rows.p;
     none.ncols_hint = nl;
     const double* coefp = hy.coef.p;
-    LinOp A;
+    A = LinOp();
     A.n = nl;
     A.n0 = 0;
     A.apply_z = [Hg, none, coefp](const Lanes& L, int nb_, zvec x, double* y, double* partial, double*) {
         return k::DotParts{partial, k::eg_pair_spmm_z(L.main, nb_, Hg, coefp, x, none, x, y, partial, x)};
     };
     Multigrid* mgp = &ch.mg;
-    PrecFn prec;
     if (!eg_cycle) {
         prec = [mgp](const Lanes& L, int nb_, const double* r, zvec z, double* dot_partial, double*) {
             const int nblk = mgp->vcycle_z(L.main, nb_, 0, r, z, dot_partial);
@@ -1033,6 +1069,28 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
             return k::DotParts{dot_partial, dot_partial ? nblk : 0, nullptr, 0};
         };
     }
+}
+
+// SolveFwd through the hybridized form: H(kappa) lambda = R kappa + b_0 by MINRES with one V-cycle of the per-realization
+// aggregation hierarchy, then the element-local back-substitution into the full solution vector (what Q, the returned
+// solution and the pressure block are taken from, exactly as after the saddle-point solve).
+void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
+                               int nrows) {
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    DarcyHybrid& hy = *hyb[level];
+    const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p, nl = hy.n_lambda;
+    ensure_hybrid(level, nb);
+    if (stats) ctx.phase_mark(0);
+    setup_chunk_hybrid(level, nb, k_d);
+    // right-hand side
+    k::broadcast(st, nb, nl, hy.b0.p, hy.rhs.p);
+    k::spmm(st, nb, view(hy.R), hy.coef.p, hy.rhs.p, true, nullptr, nullptr);
+    if (stats) ctx.phase_mark(1);
+    LinOp A;
+    PrecFn prec;
+    hybrid_ops(level, A, prec);
+    Multigrid* mgp = &hy.chain->mg;
     work.want_r32 = false;
     GraphHint hint;
     hint.key = hash_mix(hash_mix(hash_mix(0xdb, (uint64_t)level + 1), (uint64_t)nb), 7);
@@ -1092,6 +1150,78 @@ void Darcy::solve_fwd(int level, int nbatch, const double* kf, double* Q, double
             for (int b = 0; b < nb; ++b) C[done + b] = (double)n;   // global true dofs (DarcySolver.cpp:429)
         done += nb;
     }
+}
+
+void Darcy::apply_one(int level, int nb, const double* k_in, const double* in, double* out, int memspace, bool precond) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "apply: level out of range");
+    DarcyLevel& d = lv[level];
+    PMC_REQUIRE(valid_batch(nb) && nb <= batch_width((size_t)d.n_u + d.n_p, true, ctx.device) && k_in != nullptr &&
+                    in != nullptr && out != nullptr,
+                "apply: nbatch must be a launch width of the level");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const size_t n = hybrid ? (size_t)hyb[level]->n_lambda : (size_t)d.n_u + d.n_p;
+    ensure(level, nb);
+    if (hybrid) ensure_hybrid(level, nb);
+    DevBuf<double> stage, vi(n * nb), vo(n * nb), part((size_t)2 * dot_capacity((int)n, nb) * nb);
+    const double* k_d = k_in;
+    const double* in_d = in;
+    if (memspace == PMC_MEM_HOST) {
+        PMC_HIP(hipMemcpyAsync(stage_k.p, k_in, sizeof(double) * d.n_p * nb, hipMemcpyHostToDevice, st));
+        k_d = stage_k.p;
+        stage.alloc(n * nb);
+        PMC_HIP(hipMemcpyAsync(stage.p, in, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
+        in_d = stage.p;
+    }
+    LinOp A;
+    PrecFn prec;
+    if (hybrid) {
+        setup_chunk_hybrid(level, nb, k_d);
+        hybrid_ops(level, A, prec);
+    } else {
+        setup_chunk(level, nb, k_d);
+        chunk_ops(level, nb, false, A, prec);
+    }
+    k::interleave(st, nb, (int)n, in_d, nullptr, 1.0, vi.p);
+    // the fused dot products of the MINRES loop are requested as there; results are taken in fp64 (with PMC_STORAGE_FP32
+    // the solver additionally rounds a preconditioned vector to fp32)
+    double* part2 = part.p + (size_t)dot_capacity((int)n, nb) * nb;
+    if (precond) prec(ctx.lanes(false), nb, vi.p, zvec(vo.p, false), part.p, part2);
+    else A.apply_z(ctx.lanes(false), nb, zvec(vi.p, false), vo.p, part.p, part2);
+    double* out_d = memspace == PMC_MEM_HOST ? stage.p : out;
+    k::deinterleave(st, nb, (int)n, vo.p, nullptr, nullptr, false, out_d);
+    if (memspace == PMC_MEM_HOST) PMC_HIP(hipMemcpyAsync(out, stage.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+void Darcy::apply_preconditioner(int level, int nbatch, const double* k, const double* r, double* z, int memspace) {
+    apply_one(level, nbatch, k, r, z, memspace, true);
+}
+
+void Darcy::apply_operator(int level, int nbatch, const double* k, const double* x, double* y, int memspace) {
+    apply_one(level, nbatch, k, x, y, memspace, false);
+}
+
+void Darcy::vcycle_level(int level, int vlevel, int* nvlevels, double* info) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_vcycle_level: level out of range");
+    const bool own = hybrid || (level < (int)chains.size() && chains[level]);
+    const Multigrid& g = hybrid ? hyb[level]->chain->mg : own ? chains[level]->mg : mg;
+    const int first = own ? 0 : level;
+    *nvlevels = (int)g.L.size() - first;
+    PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_darcy_vcycle_level: vlevel out of range");
+    const MgLevel& m = g.L[(size_t)(first + vlevel)];
+    const bool bottom = first + vlevel == (int)g.L.size() - 1 || m.is_last;
+    info[0] = m.n;
+    info[1] = m.lmax;
+    info[2] = bottom ? 1.0 : 0.0;
+    info[3] = g.smooth_degree;
+    info[4] = g.smooth_ratio;
+    info[5] = m.is_last ? m.last_degree : g.coarse_degree;
+    info[6] = m.is_last ? m.last_ratio : g.coarse_ratio;
+    info[7] = own ? 0.0 : galerkin_scale;
+    info[8] = lv[level].ratio_M;
+    info[9] = opts.cheb_degree_M > 0 ? opts.cheb_degree_M : 2;
+    info[10] = hybrid ? 2.0 : own ? 1.0 : 0.0;
 }
 
 }  // namespace pmc

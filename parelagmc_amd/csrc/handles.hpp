@@ -182,12 +182,28 @@ struct Darcy {
     // sol_kind: 0 none, 1 full solution (n_u+n_p per realization), 2 pressure block only (n_p per realization)
     void solve_fwd(int level, int nbatch, const double* k, double* Q, double* C, double* sol_out, int memspace,
                    pmc_stats* stats, int sol_kind = 1);
+    // one application of the MINRES preconditioner / operator of a launch of nbatch realizations with permeabilities k
+    // (pmc_darcy_apply_preconditioner / _apply_operator): the same setup and the same closures as solve_fwd
+    void apply_preconditioner(int level, int nbatch, const double* k, const double* r, double* z, int memspace);
+    void apply_operator(int level, int nbatch, const double* k, const double* x, double* y, int memspace);
+    // setup values of one level of the V-cycle `level`'s solves run (pmc_darcy_vcycle_level)
+    void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
+    // caller's hierarchy: S_{l+1}(k) = galerkin_scale P^T S_l(k) P
+    double galerkin_scale = 0.5;
 
   private:
     void ensure(int level, int nb);
+    void setup_chunk(int level, int nb, const double* k_d);
+    void chunk_ops(int level, int nb, bool timing_ok, LinOp& A, PrecFn& prec);
     void solve_chunk(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                      int nrows, double* G_host);
     void build_hybrid(int level, const pmc_darcy_level& L);
+    bool hybrid_eg_cycle(int level) const;
+    void ensure_hybrid(int level, int nb);
+    void setup_chunk_hybrid(int level, int nb, const double* k_d);
+    void hybrid_ops(int level, LinOp& A, PrecFn& prec);
+    // one launch of the seams below: applies the preconditioner (true) or the operator to the [nb][rows] vectors in
+    void apply_one(int level, int nb, const double* k, const double* in, double* out, int memspace, bool precond);
     void solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                             int nrows);
 };
