@@ -248,6 +248,29 @@ int pmc_hybrid_system_level(const pmc_hybrid_system* sys, pmc_hybrid_level* view
 void pmc_hybrid_system_destroy(pmc_hybrid_system* sys);
 int pmc_sampler_create_hybrid_from_elements(pmc_ctx* ctx, int nlevels, const pmc_hybrid_elements* levels, double alpha,
                                             double matern_g, int lognormal, const pmc_solver_opts* opts, pmc_sampler** out);
+/* ---- KLSampler (src/KLSampler.cpp:144-223) ------------------------------------------------ */
+/* One level of the truncated Karhunen-Loeve sampler: the P0 space of the level, its mass diagonal and the prolongator to the
+ * next coarser level (ParELAG's L2 projector onto the coarser P0 space is D^-1 P^T W with D = P^T W P, which must be
+ * diagonal: every fine element in at most one agglomerate). */
+typedef struct pmc_kl_level {
+    int32_t n_s;          /* elements of the level                                               */
+    const double* w_diag; /* n_s, diag(W) > 0 (P0 mass)                                          */
+    pmc_csr P;            /* n_s(level) x n_s(level+1); ignored (may be zeroed) on the last level */
+} pmc_kl_level;
+/* KLSampler over what CovarianceFunction::Eigenvalues() / Eigenvectors() hold after SolveEigenvalue() (the caller runs its
+ * own eigensolver on the host, as the reference does): evals (nmodes, each finite and >= 0) and evect0 (n_s(0) x nmodes,
+ * column-major = mfem::DenseMatrix::Data()).  The handle projects Phi to the coarser levels itself at create,
+ * Phi_{l+1} = D^-1 P^T W_l Phi_l, without renormalising the coarse columns (KLSampler::BuildHierarchy).  Every level is a
+ * Monte Carlo level.  nmodes > n_s of a level is refused: the reference reads past xi there (Sample draws n_s normals,
+ * Eval reads the first nmodes of them).
+ * pmc_sampler_sample / _xi_size (= n_s) / _sample_size / _nnz (0) / _true_p / _batch_width / _num_levels and the managers
+ * take the handle like any other.  pmc_sampler_eval computes s = Phi_level Lambda^1/2 xi[:nmodes] (exp() if lognormal) for
+ * every realization in one fp64 launch, whichever level xi was drawn on; embed_s_out receives the Gaussian field;
+ * init_s / init_level / use_init are ignored; pmc_stats: iterations 0, converged 1.  pmc_sampler_mult, _apply_preconditioner,
+ * _apply_operator, _vcycle_info and _set_projection return PMC_ERR_INVALID on a KL handle. */
+int pmc_sampler_create_kl(pmc_ctx* ctx, int nlevels, const pmc_kl_level* levels, int nmodes, const double* evals,
+                          const double* evect0, int lognormal, pmc_sampler** out);
+int pmc_sampler_is_kl(const pmc_sampler* s);
 void pmc_sampler_destroy(pmc_sampler* s);
 /* Output map of the embedded variants.  PMC_PROJ_GATHER: s = sbar[gather_idx]
  * (src/EmbeddedPDESampler.cpp:552-556); PMC_PROJ_L2: s = inv_w_orig .* (Gt sbar)

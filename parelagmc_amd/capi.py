@@ -63,6 +63,10 @@ class pmc_hybrid_elements(C.Structure):
                 ("w_diag", C.POINTER(C.c_double)), ("P", pmc_csr)]
 
 
+class pmc_kl_level(C.Structure):
+    _fields_ = [("n_s", C.c_int32), ("w_diag", C.POINTER(C.c_double)), ("P", pmc_csr)]
+
+
 class pmc_darcy_level(C.Structure):
     _fields_ = [("n_u", C.c_int32), ("n_p", C.c_int32), ("M_pattern", pmc_csr), ("c_ptr", C.POINTER(C.c_int32)),
                 ("c_elem", C.POINTER(C.c_int32)), ("c_val", C.POINTER(C.c_double)), ("B", pmc_csr),
@@ -100,6 +104,9 @@ SYMBOLS = {
     "pmc_sampler_create_hybrid": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_hybrid_level), C.c_double, C.c_double, C.c_int,
                                             C.POINTER(pmc_solver_opts), C.POINTER(_VP)]),
     "pmc_sampler_is_hybrid": (C.c_int, [_VP]),
+    "pmc_sampler_create_kl": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_kl_level), C.c_int, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.c_int, C.POINTER(_VP)]),
+    "pmc_sampler_is_kl": (C.c_int, [_VP]),
     "pmc_hybrid_build": (C.c_int, [C.POINTER(pmc_hybrid_elements), C.c_double, C.POINTER(_VP)]),
     "pmc_hybrid_system_level": (C.c_int, [_VP, C.POINTER(pmc_hybrid_level)]),
     "pmc_hybrid_system_destroy": (None, [_VP]),
@@ -613,6 +620,32 @@ class PDESampler:
             self.close()
         except Exception:
             pass
+
+
+class KLSampler(PDESampler):
+    """Device truncated Karhunen-Loeve sampler (pmc_sampler_create_kl); mirrors parelagmc::KLSampler (Sample, Eval,
+    SampleSize, GetNNZ, GetTrueP).  problem: fe.KLProblem - the eigenpairs of the covariance on the finest level and the
+    level hierarchy; the handle projects the modes to the coarser levels itself."""
+
+    def __init__(self, ctx: Context, problem):
+        self.ctx, self.problem = ctx, problem
+        self.hybrid = False
+        keep = _Keep()
+        nl = len(problem.levels)
+        arr = (pmc_kl_level * nl)()
+        for i, L in enumerate(problem.levels):
+            arr[i] = pmc_kl_level(L.n_s, keep.f64(L.w_diag), keep.csr(L.P))
+        evect0 = np.asfortranarray(problem.evect0, dtype=np.float64)     # column-major n_s(0) x m (DenseMatrix::Data())
+        h = _VP()
+        _check(ctx.lib.pmc_sampler_create_kl(ctx.h, nl, arr, int(problem.evals.size), keep.f64(problem.evals),
+                                             _ptr(evect0.ravel(order="K"), C.c_double), 1 if problem.lognormal else 0,
+                                             C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        self.nlevels = nl
+
+    def is_kl(self):
+        return self.ctx.lib.pmc_sampler_is_kl(self.h) == 1
 
 
 class DarcySolver:

@@ -326,6 +326,19 @@ int pmc_sampler_create_hybrid(pmc_ctx* c, int nlevels, const pmc_hybrid_level* l
     });
 }
 int pmc_sampler_is_hybrid(const pmc_sampler* s) { return s ? (s->impl.hybrid ? 1 : 0) : PMC_ERR_INVALID; }
+int pmc_sampler_create_kl(pmc_ctx* c, int nlevels, const pmc_kl_level* levels, int nmodes, const double* evals,
+                          const double* evect0, int lognormal, pmc_sampler** out) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr && out != nullptr, "pmc_sampler_create_kl: NULL argument");
+        *out = nullptr;
+        *out = new pmc_sampler(*c, nlevels, levels, nmodes, evals, evect0, lognormal != 0);
+    });
+}
+int pmc_sampler_is_kl(const pmc_sampler* s) { return s ? (s->impl.kl ? 1 : 0) : PMC_ERR_INVALID; }
+// entry points that act on the linear system of an SPDE sampler: a KL handle has none
+static void refuse_kl(const pmc_sampler* s, const char* what) {
+    PMC_REQUIRE(!s->impl.kl, std::string(what) + " is not defined on a KL sampler handle (pmc_sampler_create_kl)");
+}
 void pmc_sampler_destroy(pmc_sampler* s) {
     if (!s) return;
     (void)hipSetDevice(s->impl.ctx.device);
@@ -336,6 +349,7 @@ int pmc_sampler_set_projection(pmc_sampler* s, int level, int kind, const pmc_cs
                                const double* inv_w, int orig_size) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        refuse_kl(s, "pmc_sampler_set_projection");
         s->impl.set_projection(level, kind, Gt, idx, inv_w, orig_size);
     });
 }
@@ -358,6 +372,7 @@ int pmc_sampler_mult(pmc_sampler* s, int level, int nbatch, const double* rhs, d
                      int memspace, pmc_stats* stats) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        refuse_kl(s, "pmc_sampler_mult");
         PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
         s->impl.mult(level, nbatch, rhs, sol, use_sol_as_guess != 0, memspace, stats);
     });
@@ -365,12 +380,14 @@ int pmc_sampler_mult(pmc_sampler* s, int level, int nbatch, const double* rhs, d
 int pmc_sampler_apply_preconditioner(pmc_sampler* s, int level, int nbatch, const double* r, double* z, int memspace) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        refuse_kl(s, "pmc_sampler_apply_preconditioner");
         PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
         s->impl.apply_preconditioner(level, nbatch, r, z, memspace);
     });
 }
 int pmc_sampler_batch_width(const pmc_sampler* s, int level) {
     if (!s || level < 0 || level >= s->impl.nlevels) return PMC_ERR_INVALID;
+    if (s->impl.kl) return 128;   // one workgroup column of the MFMA kernel streams Phi once for 128 realizations (kl.hip)
     return batch_width((size_t)s->impl.lv[level].n_u + s->impl.lv[level].n_s, false, s->impl.ctx.device);
 }
 int pmc_sampler_true_p(const pmc_sampler* s, int level, pmc_csr* out) {
@@ -405,6 +422,7 @@ int pmc_sampler_apply_operator(pmc_sampler* s, int level, int nbatch, const doub
                                int repeat, double* avg_ms, double* bytes) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        refuse_kl(s, "pmc_sampler_apply_operator");
         s->impl.apply_operator(level, nbatch, x, y, memspace, repeat, avg_ms, bytes);
     });
 }
@@ -445,6 +463,7 @@ int pmc_sampler_smoother_bytes(const pmc_sampler* s, int level, int nbatch, doub
 int pmc_sampler_vcycle_info(const pmc_sampler* s, int level, int vlevel, int* nvlevels, int64_t info[7]) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr && nvlevels != nullptr && info != nullptr, "pmc_sampler_vcycle_info: NULL argument");
+        refuse_kl(s, "pmc_sampler_vcycle_info");
         PMC_REQUIRE(level >= 0 && level < s->impl.n_mc, "pmc_sampler_vcycle_info: level out of range");
         const bool own = level < (int)s->impl.amg.size() && s->impl.amg[level];
         const Multigrid& mg = own ? *s->impl.amg[level] : s->impl.mg;

@@ -45,6 +45,11 @@ struct Sampler {
     std::vector<std::unique_ptr<Multigrid>> amg;   // per MC level: internal smoothed-aggregation hierarchy (if selected)
     double anisotropy = 1.0;
     bool hybrid = false;                           // pmc_sampler_create_hybrid: multiplier system, amg[l] its V-cycle
+    // pmc_sampler_create_kl (kl.hip): truncated Karhunen-Loeve expansion, no linear system.  kl_phi[l] = Phi_l diag(sqrt(lambda)),
+    // column-major n_s x kl_m (Phi_0 as handed over, the coarser levels projected on the device at create)
+    bool kl = false;
+    int kl_m = 0;
+    std::vector<DevBuf<double>> kl_phi;
     OpTimer vc_timer;                              // hybrid: the finest level's post-smoothing launches (with work.op_timer.on)
     MinresWork work;
     DevBuf<double> rhs, sol, tA, tB, cx, cd, cx2, stage_in, stage_out, stage_emb, mini_scratch;
@@ -53,6 +58,7 @@ struct Sampler {
     Sampler(Ctx& c, int nlevels, int n_mc, const pmc_sampler_level* in, double alpha, double g, bool lognormal,
             const pmc_solver_opts& o);
     Sampler(Ctx& c, int nlevels, const pmc_hybrid_level* in, double alpha, double g, bool lognormal, const pmc_solver_opts& o);
+    Sampler(Ctx& c, int nlevels, const pmc_kl_level* in, int nmodes, const double* evals, const double* evect0, bool lognormal);
     // rows of the vectors the Krylov solver of `level` iterates on
     // algorithmic bytes of one launch of the timed post-smoothing kernel (level 0 of the hybrid V-cycle of `level`)
     double smoother_bytes(int level, int nb) const;
@@ -74,7 +80,15 @@ struct Sampler {
     PrecFn preconditioner(int level, int nb, int degM, Multigrid* mgp, int mg_l0);
     void eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                     int init_level, bool use_init, double* emb_d, pmc_stats* stats);
+    // Eval of a KL handle: every realization in one launch
+    void eval_kl(int level, int xi_level, int nbatch, const double* xi, double* s_out, double* emb_out, int memspace,
+                 pmc_stats* stats);
 };
+
+// kl.hip: s[b n + i] = sum_k phi[k n + i] xi[b n_xi + k] (exp() if lognormal, the Gaussian value to emb when non-NULL) for
+// b < nb, i < n, k < m, in fp64 (MFMA for nb > 4, a bandwidth GEMV below); phi column-major n x m.
+void kl_eval(hipStream_t st, int n, int m, int nb, const double* phi, const double* xi, int n_xi, double* s, double* emb,
+             bool lognormal);
 
 struct DarcyLevel {
     int n_u = 0, n_p = 0, n_coef = 0;

@@ -876,6 +876,10 @@ void Sampler::eval(int level, int xi_level, int nbatch, const double* xi, double
     PMC_REQUIRE(level >= 0 && level < n_mc, "Eval: level out of range");
     PMC_REQUIRE(xi_level >= 0 && xi_level <= level, "Eval: xi_level must satisfy 0 <= xi_level <= level");
     PMC_REQUIRE(nbatch >= 1 && xi != nullptr && s_out != nullptr, "Eval: bad arguments");
+    if (kl) {   // the 5-argument Eval of KLSampler ignores u and use_init (KLSampler.hpp:69-77)
+        eval_kl(level, xi_level, nbatch, xi, s_out, emb_out, memspace, stats);
+        return;
+    }
     if (use_init) {
         PMC_REQUIRE(init_s != nullptr, "Eval: use_init without init_s");
         PMC_REQUIRE(init_level >= level && init_level < nlevels, "Eval: init_level must be coarser than or equal to level");

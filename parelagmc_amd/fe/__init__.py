@@ -13,5 +13,7 @@ from .darcy_hybrid import DarcyHybridLevel, darcy_hybrid_level  # noqa: F401
 from .rt0 import build_spaces, mass_contributions, mass_matrix, prolongation_p0  # noqa: F401
 from .transfer import (box_intersection_gt, clipped_intersection_gt, intersection_gt,  # noqa: F401
                        l2_projection_hierarchy)
+from .kl import (KLLevel, KLProblem, analytic_exponential_eigs, build_kl_sampler_problem, compute_omega,  # noqa: F401
+                 matern_eigs, project_kl_levels)
 from .output import (compute_l2_error, compute_max_error, prolongate_to_fine_grid, read_gridfunction_p0,  # noqa: F401
                      save_field_glvis, save_mesh_glvis, write_mfem_mesh)

@@ -10,6 +10,7 @@
 // The two classes carry the reference's method names and argument meaning:
 //   DevicePDESampler   MLSampler / PDESampler / EmbeddedPDESampler / L2ProjectionPDESampler
 //                      (/root/reference/src/MLSampler.hpp:33-87, src/PDESampler.cpp:336-535)
+//   DeviceKLSampler    MLSampler / KLSampler (src/KLSampler.cpp:144-223)
 //   DeviceDarcySolver  PhysicalMLSolver / DarcySolver (src/PhysicalMLSolver.hpp:33-62, src/DarcySolver.cpp:416-470)
 // and throw std::runtime_error where the reference throws through PARELAG_TEST_FOR_EXCEPTION.
 #pragma once
@@ -175,6 +176,21 @@ class DevicePDESampler {
     pmc_sampler* handle() { return h_; }
     pmc_ctx* context() { return ctx_; }
 
+  protected:
+    /// for samplers of another kind behind the same handle type: create(ctx, &handle) makes the handle on a fresh seeded context
+    template <class Create>
+    DevicePDESampler(int device_id, uint64_t seed, Create&& create) {
+        check(pmc_ctx_create(device_id, &ctx_), "pmc_ctx_create");
+        try {
+            check(pmc_rng_seed(ctx_, seed, 1, 0), "pmc_rng_seed");
+            create(ctx_, &h_);
+            nlevels_ = pmc_sampler_num_levels(h_);
+        } catch (...) {
+            pmc_ctx_destroy(ctx_);
+            throw;
+        }
+    }
+
   private:
     int level_of(int size) const {                            // level_size.Find(xi.Size()), src/PDESampler.cpp:419
         for (int l = 0; l < nlevels_; ++l)
@@ -183,9 +199,39 @@ class DevicePDESampler {
     }
     pmc_ctx* ctx_ = nullptr;
     pmc_sampler* h_ = nullptr;
-    int nlevels_;
+    int nlevels_ = 0;
     uint64_t next_id_ = 0;
     pmc_stats stats_{};
+};
+
+/// One level of KLSampler::BuildHierarchy (src/KLSampler.cpp:144-191): the P0 mass diagonal and ComputeTrueP(nDim) to the
+/// next coarser level (null on the last)
+struct KLLevelOps {
+    const mfem::Vector* w_diag = nullptr;
+    const mfem::SparseMatrix* P = nullptr;
+};
+
+/// KLSampler over a covariance whose SolveEigenvalue() the caller ran on the host: evals = Eigenvalues(), evect0 =
+/// Eigenvectors().Data() (n0 x evals.Size(), column-major).  Sample / Eval are DevicePDESampler's one-realization calls; the
+/// 5-argument Eval ignores use_init and returns the Gaussian field in u, as the reference's does (KLSampler.hpp:69-77).
+class DeviceKLSampler : public DevicePDESampler {
+  public:
+    DeviceKLSampler(int device_id, const mfem::Vector& evals, const double* evect0, int n0, const std::vector<KLLevelOps>& levels,
+                    bool lognormal, uint64_t seed = 0)
+        : DevicePDESampler(device_id, seed, [&](pmc_ctx* ctx, pmc_sampler** h) {
+              std::vector<pmc_kl_level> lv(levels.size());
+              for (size_t i = 0; i < levels.size(); ++i) {
+                  if (!levels[i].w_diag) throw std::runtime_error("DeviceKLSampler: w_diag missing");
+                  lv[i] = pmc_kl_level{};
+                  lv[i].n_s = levels[i].w_diag->Size();
+                  lv[i].w_diag = levels[i].w_diag->GetData();
+                  if (levels[i].P) lv[i].P = as_csr(*levels[i].P);
+              }
+              if (lv.empty() || lv[0].n_s != n0) throw std::runtime_error("DeviceKLSampler: evect0 rows != n_s of level 0");
+              check(pmc_sampler_create_kl(ctx, (int)lv.size(), lv.data(), evals.Size(), evals.GetData(), evect0,
+                                          lognormal ? 1 : 0, h),
+                    "pmc_sampler_create_kl");
+          }) {}
 };
 
 /// What DarcySolver precomputes on one level (src/DarcySolver.cpp:194-227,297-319,360-414) plus the element

@@ -6,6 +6,7 @@
 //   PhysicalMLSolver          src/PhysicalMLSolver.hpp:33-62
 //   NormalDistributionSampler src/NormalDistributionSampler.hpp:27-64
 //   PDESampler                src/PDESampler.hpp (Sample/Eval/SampleSize/GetNNZ)
+//   KLSampler                 src/KLSampler.hpp (the same methods over a pmc_sampler_create_kl handle)
 //   DarcySolver               src/DarcySolver.hpp (SolveFwd/GetNumberOfDofs/GetNNZ)
 //   MLMC_Manager              src/MLMC_Manager.hpp:24-181
 //   MC_Manager                src/MC_Manager.hpp
@@ -169,6 +170,12 @@ class PDESampler : public MLSampler {
     pmc_sampler* h_;
     int last_iters_ = -1;
     std::vector<PhaseTimes> times_;
+};
+
+/// Device truncated Karhunen-Loeve sampler: a handle from pmc_sampler_create_kl behind the same calls (GetNumIters() = 0).
+class KLSampler : public PDESampler {
+  public:
+    using PDESampler::PDESampler;
 };
 
 class DarcySolver : public PhysicalMLSolver {
