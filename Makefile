@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip
+SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/field_stats.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -73,3 +73,13 @@ $(ABIBIN)/kl_adapter_smoke: tests/c/kl_adapter_smoke.cpp tests/c/kl_io.h tests/c
 	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/kl_adapter_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-kl: $(ABIBIN)/kl_smoke $(ABIBIN)/kl_adapter_smoke
 .PHONY: test-kl
+
+# the drivers' result table from C and C++ (tests/test_gpu_field_stats.py builds and runs them)
+$(ABIBIN)/field_stats_smoke: tests/c/field_stats_smoke.c tests/c/kl_io.h include/pmc.h | $(LIB)
+	@mkdir -p $(ABIBIN)
+	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/field_stats_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+$(ABIBIN)/field_stats_adapter_smoke: tests/c/field_stats_adapter_smoke.cpp tests/c/kl_io.h tests/c/mfem_shim.hpp parelagmc_amd/host/mfem_adapter.hpp parelagmc_amd/host/parelagmc.hpp include/pmc.h include/pmc_host.h | $(HOSTLIB)
+	@mkdir -p $(ABIBIN)
+	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/field_stats_adapter_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-field-stats: $(ABIBIN)/field_stats_smoke $(ABIBIN)/field_stats_adapter_smoke
+.PHONY: test-field-stats

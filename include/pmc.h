@@ -303,6 +303,51 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
                      const double* init_s, int init_level, int use_init, double* embed_s_out, int memspace,
                      pmc_stats* stats);
 
+/* ---- Field statistics and errors of the sampler drivers (examples/PDESamplerTest.cpp:205-274) ---------------------- */
+/* Accumulators of ONE level's Eval output s (pmc_sampler_sample_size(level) entries per realization) on the device:
+ * per element the sums of s, s^2 and <chi, s> s as (sum, compensation) pairs (Neumaier), added in ascending sample id.
+ * The result is bit-identical however the N realizations were split into calls and launches.
+ * chi (may be NULL: no chi_cov): sample_size(level) entries in `memspace`, already on `level` (the drivers restrict the
+ * level-0 indicator by P^T level by level); <chi, s> is the plain Euclidean dot of the drivers (no mass weighting). */
+typedef struct pmc_field_stats pmc_field_stats;
+int pmc_field_stats_create(pmc_sampler* s, int level, const double* chi, int memspace, pmc_field_stats** out);
+void pmc_field_stats_destroy(pmc_field_stats* fs);   /* before the sampler it was created on */
+int pmc_field_stats_reset(pmc_field_stats* fs);
+/* add nbatch realizations the caller holds (sample-major, as pmc_sampler_eval writes them) */
+int pmc_field_stats_accumulate(pmc_field_stats* fs, int nbatch, const double* s, int memspace);
+/* the drivers' loop on the device: Sample(level) + Eval(level) of the ids first_sample_id .. first_sample_id + nsamples - 1,
+ * each launch accumulated in place; nothing crosses to the host.  Launches cover the fixed id ranges
+ * [t W, (t + 1) W), W = pmc_sampler_batch_width(level), so that every realization is evaluated beside the same others
+ * whatever the split into calls; a range that does not start and end on multiples of W evaluates the whole launches at its
+ * ends and accumulates only its own ids. */
+int pmc_field_stats_run(pmc_field_stats* fs, uint64_t first_sample_id, int64_t nsamples);
+/* expectation = (1/N) sum s, second_moment = (1/N) sum s^2, chi_cov = (1/N) sum <chi, s> s, count = N; any pointer may be
+ * NULL.  second_moment is what the drivers call the "marginal variance": the moment about ZERO, not about the mean
+ * (PDESamplerTest.cpp:240,251; compared with exp(s2) (exp(s2) - 1) for a lognormal field).  Centre it yourself:
+ * Var = second_moment - expectation^2.  chi_cov from accumulators created without chi, and N = 0, are refused. */
+int pmc_field_stats_read(const pmc_field_stats* fs, double* expectation, double* second_moment, double* chi_cov,
+                         int64_t* count, int memspace);
+/* the raw accumulators, (4 or 6) x sample_size(level) doubles: [sum s | comp | sum s^2 | comp | sum <chi,s> s | comp]
+ * (the last two only with chi); sum + comp is the compensated sum.  Readable so that ranks can combine them. */
+int pmc_field_stats_read_sums(const pmc_field_stats* fs, double* sums, int64_t* count, int memspace);
+/* <chi, s_c> of nbatch realizations exactly as accumulate forms them (a fixed reduction tree: the same bits for a column
+ * alone or inside any launch) */
+int pmc_field_stats_chi_dot(const pmc_field_stats* fs, int nbatch, const double* s, double* dots, int memspace);
+/* MLSampler::ComputeL2Error / ComputeMaxError for nbatch fields of sample_size(level) entries at once (coeff, err in
+ * `memspace`).  l2: err[c] = || P_0 .. P_{level-1} coeff_c - exact ||^2_L2 with the level-0 P0 mass (the squared error,
+ * as the reference returns; src/PDESampler.cpp:613-623).  max: err[c] = max(max coeff_c - exact, exact - min coeff_c)
+ * (:625-633) on the level itself.  EmbeddedPDESampler's abs() in EmbedComputeMaxError changes nothing: the two terms sum
+ * to max - min >= 0.  The output of an embedded / L2-projected level lives on the ORIGINAL mesh: both calls are refused
+ * there until pmc_sampler_set_output_hierarchy has handed over that mesh's hierarchy. */
+int pmc_sampler_l2_error(pmc_sampler* s, int level, int nbatch, const double* coeff, double exact, double* err,
+                         int memspace);
+int pmc_sampler_max_error(pmc_sampler* s, int level, int nbatch, const double* coeff, double exact, double* err,
+                          int memspace);
+/* the original mesh's P0 hierarchy behind the output of the projected variants: P_orig[l] (l < nlevels - 1) maps
+ * sample_size(l + 1) -> sample_size(l) in the output numbering, w0_orig the P0 mass diagonal of its level 0
+ * (sample_size(0) entries, > 0).  Copied; nlevels in [1, number of Monte Carlo levels]. */
+int pmc_sampler_set_output_hierarchy(pmc_sampler* s, int nlevels, const pmc_csr* P_orig, const double* w0_orig);
+
 /* invA[level]->Mult(rhs, sol) (src/PDESampler.cpp:397,521), the narrowest seam of the reference: the whole linear solve
  * A [u; s] = rhs on FULL vectors of n_u + n_s entries per realization (sample-major), every row of the solution maintained.
  * use_sol_as_guess != 0 = mfem::Solver::iterative_mode (:510): sol holds the initial guess on entry.  pmc_sampler_eval is this

@@ -6,6 +6,7 @@ visible when a context is created, the call raises.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 import os
 from typing import Optional, Sequence
 
@@ -140,6 +141,17 @@ SYMBOLS = {
     "pmc_sampler_set_operator_timing": (C.c_int, [_VP, C.c_int]),
     "pmc_sampler_operator_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pmc_sampler_operator_event_overhead": (C.c_int, [_VP, C.POINTER(C.c_double)]),
+    "pmc_field_stats_create": (C.c_int, [_VP, C.c_int, _DP, C.c_int, C.POINTER(_VP)]),
+    "pmc_field_stats_destroy": (None, [_VP]),
+    "pmc_field_stats_reset": (C.c_int, [_VP]),
+    "pmc_field_stats_accumulate": (C.c_int, [_VP, C.c_int, _DP, C.c_int]),
+    "pmc_field_stats_run": (C.c_int, [_VP, C.c_uint64, C.c_int64]),
+    "pmc_field_stats_read": (C.c_int, [_VP, _DP, _DP, _DP, C.POINTER(C.c_int64), C.c_int]),
+    "pmc_field_stats_read_sums": (C.c_int, [_VP, _DP, C.POINTER(C.c_int64), C.c_int]),
+    "pmc_field_stats_chi_dot": (C.c_int, [_VP, C.c_int, _DP, _DP, C.c_int]),
+    "pmc_sampler_l2_error": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.c_double, _DP, C.c_int]),
+    "pmc_sampler_max_error": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.c_double, _DP, C.c_int]),
+    "pmc_sampler_set_output_hierarchy": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_csr), C.POINTER(C.c_double)]),
     "pmc_darcy_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(pmc_darcy_level), C.c_int,
                                    C.POINTER(pmc_solver_opts), C.POINTER(_VP)]),
     "pmc_darcy_create_hybrid": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(pmc_darcy_level), C.c_int,
@@ -309,6 +321,14 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+def _batch_of(x, n):
+    """realizations of n entries a DeviceArray / torch tensor holds (its length must be a multiple of n)"""
+    total = x.n if isinstance(x, DeviceArray) else int(x.numel())
+    if n <= 0 or total == 0 or total % n:
+        raise PmcError(-1, f"a buffer of {total} entries does not hold whole fields of {n}")
+    return total // n
 
 
 def _addr(x):
@@ -538,6 +558,50 @@ class PDESampler:
         """Bracket every K5 launch of the MINRES loop with HIP events (in-situ kernel time for the roofline)."""
         _check(self.ctx.lib.pmc_sampler_set_operator_timing(self.h, 1 if on else 0))
 
+    def _error(self, fn, level, coeff, exact):
+        n = self.SampleSize(level)
+        if n < 0:
+            raise PmcError(-1, f"level {level} out of range")
+        if isinstance(coeff, np.ndarray):
+            single = coeff.ndim == 1
+            coeff = _f64(np.atleast_2d(coeff))
+            nbatch = coeff.shape[0]
+            if coeff.shape[1] != n:
+                raise PmcError(-1, "coefficient vectors do not match SampleSize(level)")
+        else:
+            single, nbatch = False, _batch_of(coeff, n)
+        err = np.empty(nbatch)
+        p, ms = _addr(coeff)
+        _check(fn(self.h, level, nbatch, p, float(exact), err.ctypes.data, PMC_MEM_HOST) if ms == PMC_MEM_HOST else
+               self._error_dev(fn, level, nbatch, p, exact, err))
+        return float(err[0]) if single else err
+
+    def _error_dev(self, fn, level, nbatch, p, exact, err):
+        out = self.ctx.empty(nbatch)
+        rc = fn(self.h, level, nbatch, p, float(exact), out.ptr, PMC_MEM_DEVICE)
+        if rc == 0:
+            err[:] = out.download()
+        out.free()
+        return rc
+
+    def ComputeL2Error(self, level, coeff, exact):
+        """MLSampler::ComputeL2Error: || P_0 .. P_{level-1} coeff - exact ||^2_L2 (squared, as the reference returns) of one
+        field (a float) or of each row of a (nbatch, SampleSize(level)) array / device array (an array)."""
+        return self._error(self.ctx.lib.pmc_sampler_l2_error, level, coeff, exact)
+
+    def ComputeMaxError(self, level, coeff, exact):
+        """MLSampler::ComputeMaxError: max(max coeff - exact, exact - min coeff), per field."""
+        return self._error(self.ctx.lib.pmc_sampler_max_error, level, coeff, exact)
+
+    def SetOutputHierarchy(self, P_orig, w0_orig):
+        """the original mesh's prolongators (P_orig[l]: SampleSize(l) x SampleSize(l + 1)) and level-0 P0 mass behind the
+        output of an embedded / L2-projected handle (pmc_sampler_set_output_hierarchy)"""
+        keep = _Keep()
+        arr = (pmc_csr * max(1, len(P_orig)))()
+        for i, P in enumerate(P_orig):
+            arr[i] = keep.csr(P)
+        _check(self.ctx.lib.pmc_sampler_set_output_hierarchy(self.h, len(P_orig) + 1, arr, keep.f64(w0_orig)))
+
     def operator_time(self):
         """(total ms, launches) of the timed K5 launches since the last call."""
         ms, n = C.c_double(0.0), C.c_int64(0)
@@ -612,7 +676,94 @@ class PDESampler:
 
     def close(self):
         if getattr(self, "h", None):
+            for ref in getattr(self, "_stats", []):     # FieldStatistics of this handle die first
+                obj = ref()
+                if obj is not None:
+                    obj.close()
             self.ctx.lib.pmc_sampler_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FieldStatistics:
+    """Accumulators of one sampler level's output on the device (pmc_field_stats_*): the expectation, the second moment
+    about zero (the drivers' "marginal variance") and the covariance with an indicator chi of PDESamplerTest's loop."""
+
+    def __init__(self, sampler: PDESampler, level: int, chi=None):
+        self.sampler, self.level, self.ctx = sampler, level, sampler.ctx
+        self.n = sampler.SampleSize(level)
+        self.has_chi = chi is not None
+        h = _VP()
+        if chi is None:
+            p, ms = None, PMC_MEM_HOST
+        else:
+            if isinstance(chi, np.ndarray):
+                chi = _f64(chi).ravel()
+                if chi.size != self.n:
+                    raise PmcError(-1, "chi does not match SampleSize(level)")
+            p, ms = _addr(chi)
+        _check(self.ctx.lib.pmc_field_stats_create(sampler.h, level, p, ms, C.byref(h)))
+        self.h = h
+        if not hasattr(sampler, "_stats"):
+            sampler._stats = []
+        sampler._stats.append(weakref.ref(self))
+
+    def run(self, first_id, nsamples):
+        """Sample + Eval + accumulate the realizations first_id .. first_id + nsamples - 1 on the device"""
+        _check(self.ctx.lib.pmc_field_stats_run(self.h, C.c_uint64(first_id), C.c_int64(nsamples)))
+        return self
+
+    def accumulate(self, s, nbatch=None):
+        """add realizations the caller holds: (nbatch, n) numpy, or a DeviceArray / torch tensor (nbatch=...)"""
+        if isinstance(s, np.ndarray):
+            s = _f64(np.atleast_2d(s))
+            nbatch = s.shape[0]
+        else:
+            nb = _batch_of(s, self.n)
+            if nbatch is None:
+                nbatch = nb
+            elif not 1 <= nbatch <= nb:
+                raise PmcError(-1, f"nbatch {nbatch} exceeds the {nb} realizations the buffer holds")
+        p, ms = _addr(s)
+        _check(self.ctx.lib.pmc_field_stats_accumulate(self.h, int(nbatch), p, ms))
+        return self
+
+    def reset(self):
+        _check(self.ctx.lib.pmc_field_stats_reset(self.h))
+        return self
+
+    def read(self, chi_cov=None):
+        """(expectation, second_moment, chi_cov or None, N); chi_cov defaults to whether chi was given"""
+        want = self.has_chi if chi_cov is None else chi_cov
+        e, m2 = np.empty(self.n), np.empty(self.n)
+        cc = np.empty(self.n) if want else None
+        cnt = C.c_int64(0)
+        _check(self.ctx.lib.pmc_field_stats_read(self.h, e.ctypes.data, m2.ctypes.data, None if cc is None else cc.ctypes.data,
+                                                 C.byref(cnt), PMC_MEM_HOST))
+        return e, m2, cc, cnt.value
+
+    def read_sums(self):
+        """((4 or 6), n) raw accumulators [sum s, comp, sum s^2, comp, sum <chi,s> s, comp] and N"""
+        out = np.empty(((6 if self.has_chi else 4), self.n))
+        cnt = C.c_int64(0)
+        _check(self.ctx.lib.pmc_field_stats_read_sums(self.h, out.ctypes.data, C.byref(cnt), PMC_MEM_HOST))
+        return out, cnt.value
+
+    def chi_dot(self, s):
+        """<chi, s_c> of each row of s exactly as the accumulation forms them"""
+        s = _f64(np.atleast_2d(s))
+        out = np.empty(s.shape[0])
+        _check(self.ctx.lib.pmc_field_stats_chi_dot(self.h, s.shape[0], s.ctypes.data, out.ctypes.data, PMC_MEM_HOST))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pmc_field_stats_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -387,8 +387,7 @@ int pmc_sampler_apply_preconditioner(pmc_sampler* s, int level, int nbatch, cons
 }
 int pmc_sampler_batch_width(const pmc_sampler* s, int level) {
     if (!s || level < 0 || level >= s->impl.nlevels) return PMC_ERR_INVALID;
-    if (s->impl.kl) return 128;   // one workgroup column of the MFMA kernel streams Phi once for 128 realizations (kl.hip)
-    return batch_width((size_t)s->impl.lv[level].n_u + s->impl.lv[level].n_s, false, s->impl.ctx.device);
+    return s->impl.launch_width(level);
 }
 int pmc_sampler_true_p(const pmc_sampler* s, int level, pmc_csr* out) {
     return guarded([&] {
@@ -418,6 +417,75 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
     });
 }
 
+int pmc_field_stats_create(pmc_sampler* s, int level, const double* chi, int memspace, pmc_field_stats** out) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr && out != nullptr, "pmc_field_stats_create: NULL argument");
+        *out = new pmc_field_stats(s->impl, level, chi, memspace);
+    });
+}
+void pmc_field_stats_destroy(pmc_field_stats* fs) {
+    if (!fs) return;
+    (void)hipSetDevice(fs->impl.smp.ctx.device);
+    (void)hipStreamSynchronize(fs->impl.smp.ctx.stream);
+    delete fs;
+}
+int pmc_field_stats_reset(pmc_field_stats* fs) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        fs->impl.reset();
+    });
+}
+int pmc_field_stats_accumulate(pmc_field_stats* fs, int nbatch, const double* s, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        fs->impl.accumulate(nbatch, s, memspace);
+    });
+}
+int pmc_field_stats_run(pmc_field_stats* fs, uint64_t first_sample_id, int64_t nsamples) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        fs->impl.run(first_sample_id, nsamples);
+    });
+}
+int pmc_field_stats_read(const pmc_field_stats* fs, double* expectation, double* second_moment, double* chi_cov,
+                         int64_t* count, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        const_cast<pmc_field_stats*>(fs)->impl.read(expectation, second_moment, chi_cov, count, memspace);
+    });
+}
+int pmc_field_stats_read_sums(const pmc_field_stats* fs, double* sums, int64_t* count, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        const_cast<pmc_field_stats*>(fs)->impl.read_sums(sums, count, memspace);
+    });
+}
+int pmc_field_stats_chi_dot(const pmc_field_stats* fs, int nbatch, const double* s, double* dots, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(fs != nullptr, "field stats is NULL");
+        const_cast<pmc_field_stats*>(fs)->impl.chi_dots(nbatch, s, dots, memspace);
+    });
+}
+int pmc_sampler_l2_error(pmc_sampler* s, int level, int nbatch, const double* coeff, double exact, double* err,
+                         int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.field_error(level, nbatch, coeff, exact, err, memspace, false);
+    });
+}
+int pmc_sampler_max_error(pmc_sampler* s, int level, int nbatch, const double* coeff, double exact, double* err,
+                          int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.field_error(level, nbatch, coeff, exact, err, memspace, true);
+    });
+}
+int pmc_sampler_set_output_hierarchy(pmc_sampler* s, int nlevels, const pmc_csr* P_orig, const double* w0_orig) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.set_output_hierarchy(nlevels, P_orig, w0_orig);
+    });
+}
 int pmc_sampler_apply_operator(pmc_sampler* s, int level, int nbatch, const double* x, double* y, int memspace,
                                int repeat, double* avg_ms, double* bytes) {
     return guarded([&] {

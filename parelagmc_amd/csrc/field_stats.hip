@@ -1,0 +1,457 @@
+// Field statistics of the sampler drivers (the reference's PDESamplerTest.cpp:205-274 loop) and
+// MLSampler::ComputeL2Error / ComputeMaxError (src/PDESampler.cpp:613-635, src/KLSampler.cpp:225-245), on the device.
+//
+//   column reductions (col_partial_kernel + col_final_kernel): one value per column of a launch (<chi, s_c>, the weighted
+//     squares of an error, a max or a min) by a FIXED tree: 2048-element chunks (8 strided elements per thread, then a
+//     256-leaf LDS tree), then the chunk partials of the column by the same tree.  The tree depends on n only, so a column
+//     gives the same bits alone or inside a launch of any width.
+//   accumulate_kernel: one thread per element walks the launch's columns in ascending sample id and adds s, s^2 and d_c s
+//     into (sum, compensation) pairs with Neumaier's two-sum.  Every element sees the same sequence of additions however
+//     the N samples were split into calls and launches, so the accumulators are bit-identical for every split.
+// Everything is fp64 and bandwidth-bound; products are rounded before they are summed (fp contraction off).
+#include "handles.hpp"
+#include "kernels.hpp"
+
+#include <cmath>
+
+namespace pmc {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPer = 8;
+constexpr int kChunk = kThreads * kPer;   // elements behind one partial
+constexpr int kMaxCols = 256;             // columns of one launch of the reductions / the accumulate kernel
+
+enum { kDot = 0, kWsq = 1, kMax = 2, kMin = 3 };
+
+template <int OP>
+__device__ inline double red_init() {
+    return OP == kMax ? -INFINITY : (OP == kMin ? INFINITY : 0.0);
+}
+template <int OP>
+__device__ inline double red_op(double a, double b) {
+    return OP == kMax ? fmax(a, b) : (OP == kMin ? fmin(a, b) : a + b);
+}
+
+// part[c nchunks + j] = reduction over chunk j of column c: kDot w_i x_i, kWsq w_i (x_i - e)^2, kMax / kMin x_i
+template <int OP>
+__global__ __launch_bounds__(kThreads) void col_partial_kernel(int n, int nchunks, const double* __restrict__ s,
+                                                               const double* __restrict__ w, double e, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    __shared__ double red[kThreads];
+    const int t = threadIdx.x, j = blockIdx.x, c = blockIdx.y;
+    const double* x = s + (size_t)c * n;
+    double v[kPer], wv[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        const int i = j * kChunk + k * kThreads + t;
+        v[k] = i < n ? x[i] : 0.0;
+        wv[k] = (OP == kDot || OP == kWsq) && i < n ? w[i] : 0.0;
+    }
+    double acc = red_init<OP>();
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        if (j * kChunk + k * kThreads + t >= n) break;
+        double term;
+        if (OP == kDot) {
+            term = wv[k] * v[k];
+        } else if (OP == kWsq) {
+            const double d = v[k] - e;
+            const double d2 = d * d;
+            term = wv[k] * d2;
+        } else {
+            term = v[k];
+        }
+        acc = red_op<OP>(acc, term);
+    }
+    red[t] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (t < h) red[t] = red_op<OP>(red[t], red[t + h]);
+        __syncthreads();
+    }
+    if (t == 0) part[(size_t)c * nchunks + j] = red[0];
+}
+
+// out[c] = reduction of the nchunks partials of column c (the same tree)
+template <int OP>
+__global__ __launch_bounds__(kThreads) void col_final_kernel(int nchunks, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double red[kThreads];
+    const int t = threadIdx.x, c = blockIdx.x;
+    double acc = red_init<OP>();
+    for (int j = t; j < nchunks; j += kThreads) acc = red_op<OP>(acc, part[(size_t)c * nchunks + j]);
+    red[t] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (t < h) red[t] = red_op<OP>(red[t], red[t + h]);
+        __syncthreads();
+    }
+    if (t == 0) out[c] = red[0];
+}
+
+// Neumaier's two-sum: (s, c) += x
+__device__ inline void two_sum(double& s, double& c, double x) {
+#pragma clang fp contract(off)
+    const double t = s + x;
+    c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
+    s = t;
+}
+
+// acc = [sum s | comp | sum s^2 | comp | sum d_c s | comp] (n each; the last two only with chi); columns in ascending order
+constexpr int kUnroll = 8;
+__global__ __launch_bounds__(kThreads) void accumulate_kernel(int n, int nb, const double* __restrict__ s,
+                                                              const double* __restrict__ d, double* __restrict__ acc,
+                                                              int with_chi) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    double s1 = acc[i], c1 = acc[(size_t)n + i], s2 = acc[2 * (size_t)n + i], c2 = acc[3 * (size_t)n + i];
+    double s3 = 0.0, c3 = 0.0;
+    if (with_chi) {
+        s3 = acc[4 * (size_t)n + i];
+        c3 = acc[5 * (size_t)n + i];
+    }
+    for (int c0 = 0; c0 < nb; c0 += kUnroll) {
+        double x[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) x[u] = c0 + u < nb ? s[(size_t)(c0 + u) * n + i] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            if (c0 + u >= nb) break;
+            two_sum(s1, c1, x[u]);
+            const double q = x[u] * x[u];
+            two_sum(s2, c2, q);
+            if (with_chi) {
+                const double p = d[c0 + u] * x[u];
+                two_sum(s3, c3, p);
+            }
+        }
+    }
+    acc[i] = s1;
+    acc[(size_t)n + i] = c1;
+    acc[2 * (size_t)n + i] = s2;
+    acc[3 * (size_t)n + i] = c2;
+    if (with_chi) {
+        acc[4 * (size_t)n + i] = s3;
+        acc[5 * (size_t)n + i] = c3;
+    }
+}
+
+// out[i] = (sum + comp) * scale of one moment
+__global__ void finalize_kernel(int n, const double* __restrict__ sum, const double* __restrict__ comp, double scale,
+                                double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (sum[i] + comp[i]) * scale;
+}
+
+// y[c nr + r] = sum_p v[p] x[c nc + ci[p]] over row r of a CSR matrix (CSR order), c < nb
+__global__ void csr_spmm_kernel(int nr, int nc, int nb, const int* __restrict__ rp, const int* __restrict__ ci,
+                                const double* __restrict__ v, const double* __restrict__ x, double* __restrict__ y) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (r >= nr) return;
+    double a = 0.0;
+    for (int p = rp[r]; p < rp[r + 1]; ++p) a += v[p] * x[(size_t)c * nc + ci[p]];
+    y[(size_t)c * nr + r] = a;
+}
+
+// err[c] = max(mx[c] - e, e - mn[c])
+__global__ void max_error_kernel(int nb, const double* __restrict__ mx, const double* __restrict__ mn, double e,
+                                 double* __restrict__ err) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < nb) err[c] = fmax(mx[c] - e, e - mn[c]);
+}
+
+int num_chunks(int n) { return (n + kChunk - 1) / kChunk; }
+
+// out[c], c < nb <= kMaxCols: the column reduction OP of s (n x nb, sample-major); part holds nb num_chunks(n) doubles
+template <int OP>
+void column_reduce(hipStream_t st, int n, int nb, const double* s, const double* w, double e, double* part, double* out) {
+    const int nch = num_chunks(n);
+    col_partial_kernel<OP><<<dim3((unsigned)nch, (unsigned)nb), kThreads, 0, st>>>(n, nch, s, w, e, part);
+    col_final_kernel<OP><<<(unsigned)nb, kThreads, 0, st>>>(nch, part, out);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(2);
+}
+
+void copy_in(DevBuf<double>& dst, const double* src, size_t cnt, int memspace, hipStream_t st) {
+    dst.ensure(cnt);
+    PMC_HIP(hipMemcpyAsync(dst.p, src, cnt * sizeof(double),
+                           memspace == PMC_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+}
+
+}  // namespace
+
+// ---- FieldStats ----------------------------------------------------------------------------------------------------------
+FieldStats::FieldStats(Sampler& s, int level_, const double* chi_in, int memspace) : smp(s), level(level_) {
+    PMC_REQUIRE(level >= 0 && level < smp.n_mc, "field stats: level out of range");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field stats: bad memspace");
+    n = smp.lv[level].out_size;
+    has_chi = chi_in != nullptr;
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    if (has_chi) copy_in(chi, chi_in, (size_t)n, memspace, st);
+    acc.alloc((size_t)(has_chi ? 6 : 4) * n);
+    acc.zero(st);
+    dots.alloc(kMaxCols);
+    part.alloc((size_t)kMaxCols * num_chunks(n));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+void FieldStats::reset() {
+    smp.ctx.activate();
+    acc.zero(smp.ctx.stream);
+    PMC_HIP(hipStreamSynchronize(smp.ctx.stream));
+    count = 0;
+}
+
+// the projection of the level may have changed since create: the accumulators (and run()'s scratch) are sized for n
+void FieldStats::check_size() const {
+    PMC_REQUIRE(smp.lv[level].out_size == n, "field stats: sample_size(level) changed since pmc_field_stats_create "
+                                             "(pmc_sampler_set_projection); create the accumulators again");
+}
+
+void FieldStats::accumulate_device(int nbatch, const double* s_d) {
+    check_size();
+    hipStream_t st = smp.ctx.stream;
+    for (int done = 0; done < nbatch;) {
+        const int nb = std::min(kMaxCols, nbatch - done);
+        const double* x = s_d + (size_t)done * n;
+        if (has_chi) column_reduce<kDot>(st, n, nb, x, chi.p, 0.0, part.p, dots.p);
+        accumulate_kernel<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, st>>>(n, nb, x, dots.p, acc.p,
+                                                                                          has_chi ? 1 : 0);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
+        done += nb;
+    }
+    count += nbatch;
+}
+
+void FieldStats::accumulate(int nbatch, const double* s, int memspace) {
+    PMC_REQUIRE(nbatch >= 1 && s != nullptr, "field stats accumulate: bad arguments");
+    check_size();
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field stats accumulate: bad memspace");
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    if (memspace == PMC_MEM_DEVICE) {
+        accumulate_device(nbatch, s);
+        return;
+    }
+    const int cols = 64;   // host input: staged 64 realizations at a time (the additions are the same for every split)
+    for (int done = 0; done < nbatch;) {
+        const int nb = std::min(cols, nbatch - done);
+        copy_in(sbuf, s + (size_t)done * n, (size_t)nb * n, PMC_MEM_HOST, st);
+        accumulate_device(nb, sbuf.p);
+        PMC_HIP(hipStreamSynchronize(st));   // sbuf is overwritten by the next chunk's copy from pageable memory
+        done += nb;
+    }
+}
+
+void FieldStats::run(uint64_t first, int64_t nsamples) {
+    PMC_REQUIRE(nsamples >= 1, "field stats run: nsamples must be >= 1");
+    check_size();
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    const int W = smp.launch_width(level);
+    const int n_xi = smp.lv[level].n_s;
+    xi.ensure((size_t)n_xi * W);
+    sbuf.ensure((size_t)n * W);
+    const uint64_t last = first + (uint64_t)nsamples;   // exclusive
+    // launches on the fixed grid of sample ids [t W, (t + 1) W): a realization is always evaluated beside the same others,
+    // so its field (and the statistics) do not depend on how a caller splits the ids into calls
+    for (uint64_t t = first / W; t * W < last; ++t) {
+        const uint64_t id0 = t * W;
+        smp.sample(level, id0, W, xi.p, PMC_MEM_DEVICE);
+        smp.eval(level, level, W, xi.p, sbuf.p, nullptr, -1, false, nullptr, PMC_MEM_DEVICE, nullptr);
+        const uint64_t lo = std::max(first, id0) - id0, hi = std::min(last, id0 + W) - id0;
+        accumulate_device((int)(hi - lo), sbuf.p + lo * (size_t)n);
+    }
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+void FieldStats::read(double* expectation, double* second_moment, double* chi_cov, int64_t* cnt, int memspace) {
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field stats read: bad memspace");
+    PMC_REQUIRE(chi_cov == nullptr || has_chi, "field stats read: chi_cov requested from accumulators created without chi");
+    PMC_REQUIRE(count > 0, "field stats read: no realization accumulated (N = 0)");
+    check_size();
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    const double scale = 1.0 / (double)count;   // the drivers' `*= 1./nsamples`
+    double* outs[3] = {expectation, second_moment, chi_cov};
+    for (int k = 0; k < 3; ++k) {
+        if (!outs[k]) continue;
+        double* dst = memspace == PMC_MEM_DEVICE ? outs[k] : nullptr;
+        if (!dst) {
+            sbuf.ensure((size_t)n);
+            dst = sbuf.p;
+        }
+        finalize_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, acc.p + 2 * k * (size_t)n,
+                                                                    acc.p + (2 * k + 1) * (size_t)n, scale, dst);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
+        if (memspace == PMC_MEM_HOST) {
+            PMC_HIP(hipMemcpyAsync(outs[k], dst, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+            PMC_HIP(hipStreamSynchronize(st));
+        }
+    }
+    if (cnt) *cnt = count;
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+void FieldStats::read_sums(double* sums, int64_t* cnt, int memspace) {
+    PMC_REQUIRE(sums != nullptr, "field stats read_sums: sums is NULL");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field stats read_sums: bad memspace");
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    PMC_HIP(hipMemcpyAsync(sums, acc.p, sizeof(double) * acc.n,
+                           memspace == PMC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    PMC_HIP(hipStreamSynchronize(st));
+    if (cnt) *cnt = count;
+}
+
+void FieldStats::chi_dots(int nbatch, const double* s, double* out, int memspace) {
+    PMC_REQUIRE(has_chi, "field stats chi_dot: the accumulators were created without chi");
+    PMC_REQUIRE(nbatch >= 1 && s != nullptr && out != nullptr, "field stats chi_dot: bad arguments");
+    check_size();
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field stats chi_dot: bad memspace");
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    const double* x = s;
+    if (memspace == PMC_MEM_HOST) {
+        copy_in(sbuf, s, (size_t)nbatch * n, PMC_MEM_HOST, st);
+        x = sbuf.p;
+    }
+    DevBuf<double> d((size_t)nbatch);
+    for (int done = 0; done < nbatch; done += kMaxCols)
+        column_reduce<kDot>(st, n, std::min(kMaxCols, nbatch - done), x + (size_t)done * n, chi.p, 0.0, part.p, d.p + done);
+    PMC_HIP(hipMemcpyAsync(out, d.p, sizeof(double) * nbatch,
+                           memspace == PMC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+// ---- ComputeL2Error / ComputeMaxError --------------------------------------------------------------------------------------
+int Sampler::launch_width(int level) const {
+    if (kl) return 128;   // one workgroup column of the MFMA kernel streams Phi once for 128 realizations (kl.hip)
+    return batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
+}
+
+void Sampler::set_output_hierarchy(int nlev, const pmc_csr* P_orig, const double* w0_orig) {
+    PMC_REQUIRE(nlev >= 1 && nlev <= n_mc, "set_output_hierarchy: nlevels must be in [1, number of Monte Carlo levels]");
+    PMC_REQUIRE(w0_orig != nullptr, "set_output_hierarchy: w0_orig is NULL");
+    PMC_REQUIRE(nlev == 1 || P_orig != nullptr, "set_output_hierarchy: P_orig is NULL");
+    std::vector<HostCsr> P;
+    for (int l = 0; l + 1 < nlev; ++l) {
+        P.push_back(csr_from_c(P_orig[l], true, "output P"));
+        PMC_REQUIRE(P.back().nrows == lv[l].out_size && P.back().ncols == lv[l + 1].out_size,
+                    "set_output_hierarchy: P_orig[" + std::to_string(l) + "] is not sample_size(l) x sample_size(l + 1)");
+    }
+    const int n0 = lv[0].out_size;
+    for (int i = 0; i < n0; ++i)
+        PMC_REQUIRE(std::isfinite(w0_orig[i]) && w0_orig[i] > 0.0, "set_output_hierarchy: w0_orig must be positive");
+    out_P = std::move(P);
+    out_w0.assign(w0_orig, w0_orig + n0);
+    ctx.activate();
+    std::vector<const HostCsr*> chain;
+    for (const HostCsr& m : out_P) chain.push_back(&m);
+    err_out.upload(chain, out_w0, ctx.stream);
+}
+
+void Sampler::ErrChain::upload(const std::vector<const HostCsr*>& P, const std::vector<double>& w, hipStream_t st) {
+    const size_t k = P.size();
+    nrows.assign(k, 0);
+    ncols.assign(k, 0);
+    rp.resize(k);
+    ci.resize(k);
+    v.resize(k);
+    for (size_t l = 0; l < k; ++l) {
+        nrows[l] = P[l]->nrows;
+        ncols[l] = P[l]->ncols;
+        rp[l].upload(P[l]->rowptr, st);
+        ci[l].upload(P[l]->colind, st);
+        v[l].upload(P[l]->vals, st);
+    }
+    w0.upload(w, st);
+    PMC_HIP(hipStreamSynchronize(st));
+    ready = true;
+}
+
+void Sampler::field_error(int level, int nbatch, const double* coeff, double exact, double* err, int memspace, bool max_err) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "field error: level out of range");
+    PMC_REQUIRE(nbatch >= 1 && coeff != nullptr && err != nullptr, "field error: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "field error: bad memspace");
+    // the output of a projected level lives on the original mesh: its hierarchy must have been handed over
+    bool projected = false;
+    for (int l = 0; l <= level; ++l) projected = projected || lv[l].proj != PMC_PROJ_NONE;
+    if (projected) {
+        PMC_REQUIRE(!out_w0.empty() && (int)out_P.size() >= level,
+                    "field error: the output of an embedded / L2-projected level lives on the original mesh - hand its "
+                    "hierarchy over with pmc_sampler_set_output_hierarchy first");
+        PMC_REQUIRE((int)out_w0.size() == lv[0].out_size, "field error: output hierarchy does not match sample_size(0)");
+        for (int l = 0; l < level; ++l)
+            PMC_REQUIRE(out_P[l].nrows == lv[l].out_size && out_P[l].ncols == lv[l + 1].out_size,
+                        "field error: output hierarchy does not match the current projections");
+    }
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    ErrChain& ch = projected ? err_out : err_own;
+    if (!projected && !ch.ready && !max_err) {   // the handle's own chain: uploaded once, at the first L2 error call
+        std::vector<const HostCsr*> chain;
+        for (int l = 0; l + 1 < nlevels && l + 1 < n_mc; ++l) chain.push_back(&lv[l].P_host);
+        ch.upload(chain, w0_host, st);
+    }
+    const int n = lv[level].out_size;
+    DevBuf<double> x, part_buf, res((size_t)std::min(nbatch, kMaxCols) * 2);
+    std::vector<DevBuf<double>> levels_d;
+    const double* cur = coeff;
+    if (memspace == PMC_MEM_HOST) {
+        copy_in(x, coeff, (size_t)nbatch * n, PMC_MEM_HOST, st);
+        cur = x.p;
+    }
+    int nrow = n;
+    if (!max_err) {
+        for (int l = level - 1; l >= 0; --l) {   // PDESampler::prolongate_to_fine_grid
+            PMC_REQUIRE(l < (int)ch.rp.size() && ch.ncols[l] == nrow, "field error: prolongator chain does not match the level");
+            const int nr = ch.nrows[l];
+            DevBuf<double> nxt((size_t)nr * nbatch);
+            for (int c0 = 0; c0 < nbatch; c0 += kMaxCols) {
+                const int nb = std::min(kMaxCols, nbatch - c0);
+                csr_spmm_kernel<<<dim3((unsigned)((nr + 255) / 256), (unsigned)nb), 256, 0, st>>>(
+                    nr, nrow, nb, ch.rp[l].p, ch.ci[l].p, ch.v[l].p, cur + (size_t)c0 * nrow, nxt.p + (size_t)c0 * nr);
+                PMC_HIP(hipGetLastError());
+                count_kernel_launches(1);
+            }
+            cur = nxt.p;
+            levels_d.push_back(std::move(nxt));   // every level stays alive until the synchronisation at the end
+            nrow = nr;
+        }
+        PMC_REQUIRE((size_t)nrow == ch.w0.n, "field error: level-0 mass does not match the prolongated field");
+    }
+    DevBuf<double> err_d;
+    double* out = err;
+    if (memspace == PMC_MEM_HOST) {
+        err_d.alloc((size_t)nbatch);
+        out = err_d.p;
+    }
+    part_buf.alloc((size_t)std::min(nbatch, kMaxCols) * num_chunks(nrow));
+    for (int done = 0; done < nbatch; done += kMaxCols) {
+        const int nb = std::min(kMaxCols, nbatch - done);
+        const double* xc = cur + (size_t)done * nrow;
+        if (max_err) {
+            column_reduce<kMax>(st, nrow, nb, xc, nullptr, 0.0, part_buf.p, res.p);
+            column_reduce<kMin>(st, nrow, nb, xc, nullptr, 0.0, part_buf.p, res.p + nb);
+            max_error_kernel<<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(nb, res.p, res.p + nb, exact, out + done);
+            PMC_HIP(hipGetLastError());
+            count_kernel_launches(1);
+        } else {
+            column_reduce<kWsq>(st, nrow, nb, xc, ch.w0.p, exact, part_buf.p, out + done);
+        }
+    }
+    if (memspace == PMC_MEM_HOST)
+        PMC_HIP(hipMemcpyAsync(err, err_d.p, sizeof(double) * nbatch, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace pmc

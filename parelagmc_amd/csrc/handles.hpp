@@ -50,6 +50,22 @@ struct Sampler {
     bool kl = false;
     int kl_m = 0;
     std::vector<DevBuf<double>> kl_phi;
+    // ComputeL2Error / ComputeMaxError (field_stats.hip): diag(W) of level 0 as handed over, and the hierarchy of the output
+    // space of the embedded / L2-projected variants (pmc_sampler_set_output_hierarchy: out_P[l] maps sample_size(l + 1) ->
+    // sample_size(l), out_w0 the P0 mass of the original mesh's level 0; empty = not set)
+    std::vector<double> w0_host;
+    std::vector<HostCsr> out_P;
+    std::vector<double> out_w0;
+    // device copies of the two chains (the handle's own uploaded at the first error call, the output one by the setter)
+    struct ErrChain {
+        std::vector<int> nrows, ncols;
+        std::vector<DevBuf<int>> rp, ci;
+        std::vector<DevBuf<double>> v;
+        DevBuf<double> w0;
+        bool ready = false;
+        void upload(const std::vector<const HostCsr*>& P, const std::vector<double>& w, hipStream_t st);
+    };
+    ErrChain err_own, err_out;
     OpTimer vc_timer;                              // hybrid: the finest level's post-smoothing launches (with work.op_timer.on)
     MinresWork work;
     DevBuf<double> rhs, sol, tA, tB, cx, cd, cx2, stage_in, stage_out, stage_emb, mini_scratch;
@@ -74,6 +90,13 @@ struct Sampler {
     // z = B^-1 r: one application of the MINRES preconditioner (diagnostics: true preconditioned residual norms)
     void apply_preconditioner(int level, int nbatch, const double* r, double* z, int memspace);
 
+    void set_output_hierarchy(int nlev, const pmc_csr* P_orig, const double* w0_orig);
+    // err[c] of nbatch fields of sample_size(level) entries (coeff, err in `memspace`): the squared L2 distance to `exact`
+    // after prolongation to level 0 (max_err false) or max(max c - exact, exact - min c) (max_err true)
+    void field_error(int level, int nbatch, const double* coeff, double exact, double* err, int memspace, bool max_err);
+    // realizations of `level` one launch carries (pmc_sampler_batch_width)
+    int launch_width(int level) const;
+
   private:
     void ensure(int level, int nb);
     void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats);
@@ -83,6 +106,27 @@ struct Sampler {
     // Eval of a KL handle: every realization in one launch
     void eval_kl(int level, int xi_level, int nbatch, const double* xi, double* s_out, double* emb_out, int memspace,
                  pmc_stats* stats);
+};
+
+// Accumulators of one sampler level's output (field_stats.hip, pmc_field_stats_*): (sum, compensation) pairs of s, s^2 and
+// <chi, s> s per element, in device memory between calls
+struct FieldStats {
+    Sampler& smp;
+    int level, n;
+    bool has_chi;
+    int64_t count = 0;
+    DevBuf<double> chi, acc, dots, part, xi, sbuf;
+    FieldStats(Sampler& s, int level, const double* chi, int memspace);
+    void reset();
+    void accumulate(int nbatch, const double* s, int memspace);
+    void run(uint64_t first_id, int64_t nsamples);
+    void read(double* expectation, double* second_moment, double* chi_cov, int64_t* count, int memspace);
+    void read_sums(double* sums, int64_t* count, int memspace);
+    void chi_dots(int nbatch, const double* s, double* out, int memspace);
+
+  private:
+    void check_size() const;
+    void accumulate_device(int nbatch, const double* s_d);
 };
 
 // kl.hip: s[b n + i] = sum_k phi[k n + i] xi[b n_xi + k] (exp() if lognormal, the Gaussian value to emb when non-NULL) for
@@ -225,4 +269,5 @@ struct Darcy {
 }  // namespace pmc
 
 struct pmc_sampler { pmc::Sampler impl; template <class... A> explicit pmc_sampler(A&&... a) : impl(std::forward<A>(a)...) {} };
+struct pmc_field_stats { pmc::FieldStats impl; template <class... A> explicit pmc_field_stats(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_darcy { pmc::Darcy impl; template <class... A> explicit pmc_darcy(A&&... a) : impl(std::forward<A>(a)...) {} };

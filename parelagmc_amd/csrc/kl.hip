@@ -212,6 +212,7 @@ Sampler::Sampler(Ctx& c, int nlevels_, const pmc_kl_level* in, int nmodes, const
                                          " (KLSampler::Eval would read past xi)");
         for (int e = 0; e < L.n_s; ++e)
             PMC_REQUIRE(std::isfinite(L.w_diag[e]) && L.w_diag[e] > 0.0, "KL sampler level: w_diag must be positive");
+        if (l == 0) w0_host.assign(L.w_diag, L.w_diag + L.n_s);
         d.n_u = 0;
         d.n_s = L.n_s;
         d.out_size = L.n_s;

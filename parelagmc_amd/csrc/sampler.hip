@@ -263,6 +263,7 @@ Sampler::Sampler(Ctx& c, int nlevels_, int n_mc_, const pmc_sampler_level* in, d
             aw[i] = alpha * L.w_diag[i];
             wsq[i] = std::sqrt(L.w_diag[i]);
         }
+        if (l == 0) w0_host.assign(L.w_diag, L.w_diag + L.n_s);
         HostCsr A = csr_block2x2(M, Bt, B, maw.data());
         d.nnz = A.nnz();
         sell_build(d.A, A, true, false, st, diag_last_on());
@@ -386,6 +387,7 @@ Sampler::Sampler(Ctx& c, int nlevels_, const pmc_hybrid_level* in, double alpha_
             PMC_REQUIRE(L.z_diag[i] != 0.0, "hybrid z_diag must not vanish");
             zw[i] = L.z_diag[i] * std::sqrt(L.w_diag[i]);
         }
+        if (l == 0) w0_host.assign(L.w_diag, L.w_diag + L.n_s);
         d.zw_sqrt.upload(zw, st);
         {
             std::vector<double> wsq(L.n_s);

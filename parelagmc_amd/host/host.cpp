@@ -133,6 +133,73 @@ pmc_csr PDESampler::GetTrueP(int level) const {
 }
 int PDESampler::SampleSize(int level) const { return pmc_sampler_sample_size(h_, level); }
 size_t PDESampler::GetNNZ(int level) const { return (size_t)pmc_sampler_nnz(h_, level); }
+void PDESampler::ComputeL2Error(int level, const Vector& coeff, double exact, double* err) const {
+    const int n = SampleSize(level);
+    if (n < 0) throw std::out_of_range("PDESampler::ComputeL2Error: level");
+    if (coeff.Size() != n || coeff.Batch() < 1 || !coeff.GetData() || !err)
+        throw std::invalid_argument("PDESampler::ComputeL2Error: coeff does not match SampleSize(level)");
+    if (coeff.MemSpace() == PMC_MEM_HOST) {
+        check(pmc_sampler_l2_error(h_, level, coeff.Batch(), coeff.GetData(), exact, err, PMC_MEM_HOST), "PDESampler::ComputeL2Error");
+        return;
+    }
+    double* d = nullptr;
+    check(pmc_malloc(ctx_, sizeof(double) * coeff.Batch(), reinterpret_cast<void**>(&d)), "PDESampler::ComputeL2Error");
+    const int rc = pmc_sampler_l2_error(h_, level, coeff.Batch(), coeff.GetData(), exact, d, PMC_MEM_DEVICE);
+    if (rc == PMC_OK) pmc_memcpy_d2h(ctx_, err, d, sizeof(double) * coeff.Batch());
+    pmc_free(ctx_, d);
+    check(rc, "PDESampler::ComputeL2Error");
+}
+void PDESampler::ComputeMaxError(int level, const Vector& coeff, double exact, double* err) const {
+    const int n = SampleSize(level);
+    if (n < 0) throw std::out_of_range("PDESampler::ComputeMaxError: level");
+    if (coeff.Size() != n || coeff.Batch() < 1 || !coeff.GetData() || !err)
+        throw std::invalid_argument("PDESampler::ComputeMaxError: coeff does not match SampleSize(level)");
+    if (coeff.MemSpace() == PMC_MEM_HOST) {
+        check(pmc_sampler_max_error(h_, level, coeff.Batch(), coeff.GetData(), exact, err, PMC_MEM_HOST), "PDESampler::ComputeMaxError");
+        return;
+    }
+    double* d = nullptr;
+    check(pmc_malloc(ctx_, sizeof(double) * coeff.Batch(), reinterpret_cast<void**>(&d)), "PDESampler::ComputeMaxError");
+    const int rc = pmc_sampler_max_error(h_, level, coeff.Batch(), coeff.GetData(), exact, d, PMC_MEM_DEVICE);
+    if (rc == PMC_OK) pmc_memcpy_d2h(ctx_, err, d, sizeof(double) * coeff.Batch());
+    pmc_free(ctx_, d);
+    check(rc, "PDESampler::ComputeMaxError");
+}
+double PDESampler::ComputeL2Error(int level, const Vector& coeff, double exact) const {
+    if (coeff.Batch() != 1) throw std::invalid_argument("PDESampler::ComputeL2Error: one field expected");
+    double e = 0.0;
+    ComputeL2Error(level, coeff, exact, &e);
+    return e;
+}
+double PDESampler::ComputeMaxError(int level, const Vector& coeff, double exact) const {
+    if (coeff.Batch() != 1) throw std::invalid_argument("PDESampler::ComputeMaxError: one field expected");
+    double e = 0.0;
+    ComputeMaxError(level, coeff, exact, &e);
+    return e;
+}
+
+// ---- FieldStatistics ---------------------------------------------------------------------------
+FieldStatistics::FieldStatistics(PDESampler& sampler, int level, const Vector* chi) {
+    n_ = sampler.SampleSize(level);
+    if (n_ < 0) throw std::out_of_range("FieldStatistics: level");
+    if (chi && chi->Size() != n_) throw std::invalid_argument("FieldStatistics: chi does not match SampleSize(level)");
+    check(pmc_field_stats_create(sampler.Handle(), level, chi ? chi->GetData() : nullptr,
+                                 chi ? chi->MemSpace() : PMC_MEM_HOST, &fs_),
+          "FieldStatistics");
+}
+void FieldStatistics::Run(uint64_t first_id, int64_t nsamples) {
+    check(pmc_field_stats_run(fs_, first_id, nsamples), "FieldStatistics::Run");
+}
+void FieldStatistics::Accumulate(const Vector& s) {
+    if (s.Size() != n_) throw std::invalid_argument("FieldStatistics::Accumulate: size");
+    check(pmc_field_stats_accumulate(fs_, s.Batch(), s.GetData(), s.MemSpace()), "FieldStatistics::Accumulate");
+}
+void FieldStatistics::Reset() { check(pmc_field_stats_reset(fs_), "FieldStatistics::Reset"); }
+int64_t FieldStatistics::Read(double* expectation, double* second_moment, double* chi_cov) const {
+    int64_t n = 0;
+    check(pmc_field_stats_read(fs_, expectation, second_moment, chi_cov, &n, PMC_MEM_HOST), "FieldStatistics::Read");
+    return n;
+}
 
 // ---- DarcySolver ------------------------------------------------------------------------------
 void DarcySolver::SolveFwd(int ilevel, Vector& k, double* Q, double* C) {

@@ -167,6 +167,24 @@ class DevicePDESampler {
     }
     int SampleSize(int level) const { return pmc_sampler_sample_size(h_, level); }
     size_t GetNNZ(int level) const { return (size_t)pmc_sampler_nnz(h_, level); }
+    /// MLSampler::ComputeL2Error (src/PDESampler.cpp:613-623): the SQUARED L2 distance of coeff, prolongated to level 0, to
+    /// `exact` (pmc_sampler_l2_error).  coeff has SampleSize(level) entries.
+    double ComputeL2Error(int level, const mfem::Vector& coeff, double exact) const {
+        return field_error(pmc_sampler_l2_error, level, coeff, exact, "ComputeL2Error");
+    }
+    /// MLSampler::ComputeMaxError (:625-633): max(max coeff - exact, exact - min coeff) (pmc_sampler_max_error)
+    double ComputeMaxError(int level, const mfem::Vector& coeff, double exact) const {
+        return field_error(pmc_sampler_max_error, level, coeff, exact, "ComputeMaxError");
+    }
+    /// embedded / L2-projected samplers: the original mesh's P0 prolongators (P_orig[l]: SampleSize(l) x SampleSize(l + 1))
+    /// and level-0 volumes behind the two error calls (pmc_sampler_set_output_hierarchy)
+    void SetOutputHierarchy(const std::vector<const mfem::SparseMatrix*>& P_orig, const mfem::Vector& w0_orig) {
+        if (w0_orig.Size() != SampleSize(0)) throw std::runtime_error("SetOutputHierarchy: w0_orig does not match SampleSize(0)");
+        std::vector<pmc_csr> P;
+        for (const mfem::SparseMatrix* m : P_orig) P.push_back(as_csr(*m));
+        check(pmc_sampler_set_output_hierarchy(h_, (int)P.size() + 1, P.empty() ? nullptr : P.data(), w0_orig.GetData()),
+              "SetOutputHierarchy");
+    }
     int GetNumIters() const { return stats_.iterations; }     // the reference returns -1 (src/PDESampler.hpp:142-145)
     pmc_csr GetTrueP(int level) const {
         pmc_csr P{};
@@ -192,6 +210,15 @@ class DevicePDESampler {
     }
 
   private:
+    using ErrorFn = int (*)(pmc_sampler*, int, int, const double*, double, double*, int);
+    double field_error(ErrorFn fn, int level, const mfem::Vector& coeff, double exact, const char* what) const {
+        const int n = SampleSize(level);
+        if (n < 0) throw std::runtime_error(std::string(what) + ": level out of range");
+        if (coeff.Size() != n) throw std::runtime_error(std::string(what) + ": coeff does not match SampleSize(level)");
+        double err = 0.0;
+        check(fn(h_, level, 1, coeff.GetData(), exact, &err, PMC_MEM_HOST), what);
+        return err;
+    }
     int level_of(int size) const {                            // level_size.Find(xi.Size()), src/PDESampler.cpp:419
         for (int l = 0; l < nlevels_; ++l)
             if (pmc_sampler_xi_size(h_, l) == size) return l;

@@ -157,6 +157,14 @@ class PDESampler : public MLSampler {
     PhaseTimes GetPhaseTimes(int level) const override { return level < (int)times_.size() ? times_[level] : PhaseTimes(); }
     void ResetPhaseTimes() override { times_.clear(); }
     int GetNumIters() const { return last_iters_; }   // the reference returns -1 (PDESampler.hpp:142-145)
+    /// MLSampler::ComputeL2Error / ComputeMaxError of ONE field (coeff.Batch() == 1; pmc_sampler_l2_error / _max_error).
+    /// L2: the squared error, as the reference returns.
+    double ComputeL2Error(int level, const Vector& coeff, double exact) const;
+    double ComputeMaxError(int level, const Vector& coeff, double exact) const;
+    /// the batched forms: err[c] of each of coeff.Batch() fields (err: coeff.Batch() host doubles)
+    void ComputeL2Error(int level, const Vector& coeff, double exact, double* err) const;
+    void ComputeMaxError(int level, const Vector& coeff, double exact, double* err) const;
+    pmc_sampler* Handle() const { return h_; }
 
   private:
     int level_of_xi(int size) const;
@@ -176,6 +184,27 @@ class PDESampler : public MLSampler {
 class KLSampler : public PDESampler {
   public:
     using PDESampler::PDESampler;
+};
+
+/// The drivers' per-level statistics (PDESamplerTest.cpp:205-274) on the device: an owning wrapper of pmc_field_stats.
+/// Destroy it before the sampler it was created on.
+class FieldStatistics {
+  public:
+    /// chi: SampleSize(level) entries (host or device, chi.MemSpace()), or nullptr for no chi_cov
+    FieldStatistics(PDESampler& sampler, int level, const Vector* chi = nullptr);
+    ~FieldStatistics() { pmc_field_stats_destroy(fs_); }
+    FieldStatistics(const FieldStatistics&) = delete;
+    FieldStatistics& operator=(const FieldStatistics&) = delete;
+    void Run(uint64_t first_id, int64_t nsamples);          // Sample + Eval + accumulate on the device
+    void Accumulate(const Vector& s);                        // s.Batch() realizations the caller holds
+    void Reset();
+    /// (1/N) sum s, (1/N) sum s^2 (about zero), (1/N) sum <chi, s> s into host arrays of SampleSize(level); any may be NULL
+    int64_t Read(double* expectation, double* second_moment, double* chi_cov) const;
+    int Size() const { return n_; }
+
+  private:
+    pmc_field_stats* fs_ = nullptr;
+    int n_ = 0;
 };
 
 class DarcySolver : public PhysicalMLSolver {
