@@ -5,15 +5,18 @@ PDESampler on cube_tet refined 5x -> 595 968 DoF, single Monte Carlo level) on N
 A step = Sample + Eval of `--streams` batches of `--batch` realizations, white noise drawn on the device so
 all inputs are resident in HBM when the timed region starts.  Contract: W untimed warm-up steps,
 then exactly K steps bracketed by barrier + torch.cuda.synchronize(); MAX over ranks; rank 0
-prints ONE JSON line.  The timed region carries no instrumentation; the roofline figures are taken in
-separate short passes after it.  Behind the headline the default run (N = 1) also measures, under "extra", every other
-BASELINE configuration on this GPU with bounded work: config 3 (MLMC Darcy + SPDE), the 1 060 864-DoF hex sampler point,
-the HBM-bound r = 6 point, configs 4 and 5 (GPU legs), the all-fp64 storage option and the drop-in one-realization-per-call
-path; the finite-element SETUP of those configurations (numpy, no GPU) is built by background worker processes while the
-GPU works on the earlier ones.  N > 1: one process per GPU (torch.distributed, backend nccl = RCCL),
-every rank owns a full replica of the operators and its own realizations (weak scaling, no data-path
-collective); the one exchange of a sample farm - the SUM all-reduce of the MLMC accumulators - is exercised
-through the library's own communicator (pmc_comm_* / pmc_allreduce_sum_f64, RCCL) under extra.mlmc_farm.
+prints ONE JSON line.  The timed region carries no instrumentation.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line.  Everything else is behind --full: the roofline figures, taken in separate short passes after the timed region,
+the CPU baseline and, under "extra" (N = 1), every other BASELINE configuration on this GPU with bounded work: config 3
+(MLMC Darcy + SPDE), the 1 060 864-DoF hex sampler point, the HBM-bound r = 6 point, configs 4 and 5 (GPU legs), the
+all-fp64 storage option and the drop-in one-realization-per-call path; the finite-element SETUP of those configurations
+(numpy, no GPU) is built by background worker processes while the GPU works on the earlier ones.  N > 1: one process per
+GPU (torch.distributed, backend nccl = RCCL), every rank owns a full replica of the operators and its own realizations
+(weak scaling, no data-path collective); with --full the one exchange of a sample farm - the SUM all-reduce of the MLMC
+accumulators - is exercised through the library's own communicator (pmc_comm_* / pmc_allreduce_sum_f64, RCCL) under
+extra.mlmc_farm.
 """
 import argparse
 import json
@@ -60,9 +63,10 @@ def _get(d, *path):
 
 
 def compact_line(full):
-    """The ONE stdout line of bench.py: headline, config, roofline, cpu_baseline and an `extra` of SCALARS (and short lists of
-    scalars) only, at most LINE_CAP bytes whatever the rank count.  Everything else - per-rank dicts, timer tables, prose, the
-    nested roofline blocks of every secondary figure - is in the full record (bench_full.json, path in `full_record`)."""
+    """The ONE stdout line of bench.py: headline, config and - when the run measured them (--full) - roofline, cpu_baseline
+    and an `extra` of SCALARS (and short lists of scalars) only, at most LINE_CAP bytes whatever the rank count.  Everything
+    else - per-rank dicts, timer tables, prose, the nested roofline blocks of every secondary figure - is in the full record
+    that a --full run writes (bench_full.json, path in `full_record`)."""
     cfg = full.get("config", {})
     rf = full.get("roofline", {}) or {}
     hybrid = cfg.get("solver") == "hybridization"
@@ -78,18 +82,19 @@ def compact_line(full):
                      "streams": cfg.get("streams"), "precond_storage": cfg.get("precond_storage"),
                      "mean_minres_iterations": _r(cfg.get("mean_minres_iterations")), "parallelism": cfg.get("parallelism"),
                      "tolerance": cfg.get("tolerance")}
-    out["roofline"] = {"bound": "hbm", "kernel": str(rf.get("kernel", ""))[:80], "achieved": _r(rf.get("achieved")),
-                       "peak": rf.get("peak", PEAK_GBS), "unit": "GB/s", "frac": _r(rf.get("frac")),
-                       "traffic": _r(rf.get("traffic"), 6), "bytes_per_launch": _r(rf.get("bytes_per_launch"), 9),
-                       "avg_kernel_ms": _r(rf.get("avg_kernel_ms")), "launches": rf.get("launches"),
-                       "event_overhead_ms": _r(rf.get("event_overhead_ms")),
-                       "frac_net_of_event_overhead": _r(rf.get("frac_net_of_event_overhead")),
-                       "operator_frac": _r(_get(rf, "operator", "frac")) if hybrid else _r(rf.get("frac")),
-                       "operator_traffic": _r(_get(rf, "operator", "traffic"), 6) if hybrid else _r(rf.get("traffic"), 6),
-                       "operator_bytes_per_launch": _r(_get(rf, "operator", "bytes_per_launch"), 9) if hybrid else None,
-                       "saddle_k5_frac": _r(saddle_k5), "spmv_nb1_frac": _r(_get(sad if hybrid else full, "roofline", "spmv_nb1", "frac")),
-                       "solver_frac": _r(_get(rf, "solver", "frac")),
-                       "traffic_matches_library": _get(rf, "traffic_provenance", "matches_running_library")}
+    if rf:
+        out["roofline"] = {"bound": "hbm", "kernel": str(rf.get("kernel", ""))[:80], "achieved": _r(rf.get("achieved")),
+                           "peak": rf.get("peak", PEAK_GBS), "unit": "GB/s", "frac": _r(rf.get("frac")),
+                           "traffic": _r(rf.get("traffic"), 6), "bytes_per_launch": _r(rf.get("bytes_per_launch"), 9),
+                           "avg_kernel_ms": _r(rf.get("avg_kernel_ms")), "launches": rf.get("launches"),
+                           "event_overhead_ms": _r(rf.get("event_overhead_ms")),
+                           "frac_net_of_event_overhead": _r(rf.get("frac_net_of_event_overhead")),
+                           "operator_frac": _r(_get(rf, "operator", "frac")) if hybrid else _r(rf.get("frac")),
+                           "operator_traffic": _r(_get(rf, "operator", "traffic"), 6) if hybrid else _r(rf.get("traffic"), 6),
+                           "operator_bytes_per_launch": _r(_get(rf, "operator", "bytes_per_launch"), 9) if hybrid else None,
+                           "saddle_k5_frac": _r(saddle_k5), "spmv_nb1_frac": _r(_get(sad if hybrid else full, "roofline", "spmv_nb1", "frac")),
+                           "solver_frac": _r(_get(rf, "solver", "frac")),
+                           "traffic_matches_library": _get(rf, "traffic_provenance", "matches_running_library")}
     cb = full.get("cpu_baseline")
     if isinstance(cb, dict):
         out["cpu_baseline"] = {"value": _r(cb.get("value")), "unit": cb.get("unit", "samples/s"), "cores": cb.get("cores"),
@@ -160,7 +165,8 @@ def compact_line(full):
     put("errors", errs or None)
     if e:
         out["extra"] = e
-    out["full_record"] = full.get("full_record")
+    if "full_record" in full:
+        out["full_record"] = full["full_record"]
     line = json.dumps(out, separators=(",", ":"))
     while len(line) >= LINE_CAP and out.get("extra"):       # cannot happen with the fields above; the cap holds regardless
         out["extra"].pop(next(reversed(out["extra"])))
@@ -1230,6 +1236,27 @@ def dropin_mlmc(probs, dev, seed, ns=(2, 8, 32), use_graph=0):
             "round_64_256_1024_realizations_per_s": float(w.sum() / sum(w[l] * cost[l] for l in range(3)))}
 
 
+def extras_planned(args, world):
+    """whether this run measures the figures of extra.* beside the headline on its one rank (a --full run only)"""
+    # (--no-mlmc --no-r6 together: the headline-only command line of the older development scripts)
+    return args.full and world == 1 and not args.no_extras and not (args.no_mlmc and args.no_r6)
+
+
+def setup_kinds(args, world):
+    """the configurations whose one-time finite-element setup the background workers build (SetupPool): none in a plain run"""
+    extras = extras_planned(args, world)
+    kinds = []
+    if (extras or (args.full and world > 1 and not args.no_extras)) and not args.no_mlmc:
+        kinds.append("c3")
+    if extras:
+        if not args.no_r6 and args.refine != 6:
+            kinds.append("r6")
+        for k in (4, 5):
+            if args.only_config in (None, k):
+                kinds.append(f"c{k}")
+    return kinds
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1242,6 +1269,11 @@ def main():
                     help="independent batches in flight per GPU (one context + host thread each): the launch-latency-"
                          "bound coarse-level kernels of one batch overlap the bandwidth-bound kernels of the other")
     ap.add_argument("--refine", type=int, default=5, help="uniform refinements of cube_tet (5 -> 595 968 DoF)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything behind the headline as well: the roofline passes, the CPU baseline, the other "
+                         "configurations under extra (N > 1: the MLMC farm round) and the full record in bench_full.json.  A "
+                         "plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the --no-* "
+                         "options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mlmc", action="store_true", help="skip the secondary config-3 (MLMC Darcy+SPDE) figure")
     ap.add_argument("--no-r6", action="store_true", help="skip the HBM-bound point (cube_tet r=6, 4.74 M DoF) under extra.r6")
@@ -1249,9 +1281,10 @@ def main():
                     help="headline only: no extra.* at all (neither configs 3 / 4 / 5, r = 6, the hex point, the fp64 storage "
                          "run nor the drop-in path)")
     ap.add_argument("--all-configs", action="store_true",
-                    help="configs 4 and 5 with their CPU columns as well (the default run measures their GPU legs only)")
+                    help="with --full: configs 4 and 5 with their CPU columns as well (--full alone measures their GPU legs "
+                         "only)")
     ap.add_argument("--only-config", type=int, choices=(4, 5), default=None,
-                    help="of configs 4 and 5 run only this one")
+                    help="with --full: of configs 4 and 5 run only this one")
     ap.add_argument("--inline-setup", action="store_true",
                     help="build the configurations' operators in this process instead of in background worker processes "
                          "(use it under rocprofv3: its preloaded library may have initialised the GPU, and a process that has "
@@ -1259,8 +1292,8 @@ def main():
     ap.add_argument("--solver", choices=("hybrid", "saddle"), default="hybrid",
                     help="solver of the headline: hybrid = the reference's Hybridization option (element-local elimination to "
                          "the SPD multiplier system, MINRES + aggregation V-cycle; pmc_sampler_create_hybrid), saddle = its "
-                         "default MINRES-BJ-GS on the saddle-point system (pmc_sampler_create).  The other one is measured "
-                         "under extra.")
+                         "default MINRES-BJ-GS on the saddle-point system (pmc_sampler_create).  With --full the other one is "
+                         "measured under extra.")
     ap.add_argument("--seed", type=int, default=20261003)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed (rank 0: white noise, field, per-realization "
@@ -1269,6 +1302,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.all_configs and not args.full:
+        ap.error("--all-configs adds to what --full measures: give --full as well")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself and never touches the GPU
@@ -1282,18 +1317,8 @@ def main():
 
     # one-time finite-element setup of the configurations behind the headline: in worker processes, started before this
     # process initialises the GPU (they never touch it)
-    # (--no-mlmc --no-r6 together: the headline-only command line of the older development scripts)
-    extras = world == 1 and not args.no_extras and not (args.no_mlmc and args.no_r6)
-    kinds = []
-    if extras or (world > 1 and not args.no_mlmc and not args.no_extras):
-        if not args.no_mlmc:
-            kinds.append("c3")
-    if extras:
-        if not args.no_r6 and args.refine != 6:
-            kinds.append("r6")
-        for k in (4, 5):
-            if args.only_config in (None, k):
-                kinds.append(f"c{k}")
+    extras = extras_planned(args, world)
+    kinds = setup_kinds(args, world)
     pool = SetupPool([] if args.inline_setup else kinds)
 
     import torch
@@ -1393,11 +1418,12 @@ def main():
                        # preconditioner is stored (extra.fp64_storage: the same run with everything stored fp64)
                        "precond_storage": "fp32" if zb == 4 else "fp64"},
             "devices": min(world, ndev), "ranks": per_rank,
-            "roofline": (hybrid_roofline(farm, head, nb, f"r{args.refine}", next_batch, acc[2], dt) if hybrid else
-                         operator_roofline(farm, problem, nb, f"r{args.refine}", next_batch,
-                                           solver_bytes_per_iteration(problem, nb, zb), acc[2], dt)),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = (hybrid_roofline(farm, head, nb, f"r{args.refine}", next_batch, acc[2], dt) if hybrid else
+                               operator_roofline(farm, problem, nb, f"r{args.refine}", next_batch,
+                                                 solver_bytes_per_iteration(problem, nb, zb), acc[2], dt))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(problem, args.seed, 8, hybrid_problem=head if hybrid else None)
             except Exception as e:   # noqa: BLE001
@@ -1440,7 +1466,7 @@ def main():
             "config2_hipgraph": dropin_sampler(head, dev, args.seed, 16, 1),
             "config2_saddle_point_minres": dropin_sampler(problem, dev, args.seed, 16, 0),
             "config2_saddle_point_minres_hipgraph": dropin_sampler(problem, dev, args.seed, 16, 1)})
-    if not args.no_mlmc and not args.no_extras:
+    if args.full and not args.no_mlmc and not args.no_extras:
         probs3 = pool.get("c3")
         if world == 1:
             def c3():
@@ -1534,7 +1560,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        out["full_record"] = write_full_record(out)
+        if args.full:
+            out["full_record"] = write_full_record(out)
         print(json.dumps(out), file=sys.stderr)          # the full record on stderr as well (a log keeps it)
         sys.stderr.flush()
         print(compact_line(out))                         # stdout: ONE line, < LINE_CAP bytes

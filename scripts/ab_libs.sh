@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-.}
 L=$R/parelagmc_amd/lib
 for v in "$@"; do
   cp $L/libpmc_$v.so $L/libpmc.so || exit 1
-  timeout -k 10 300 python $R/bench.py --steps 40 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout -k 10 300 python $R/bench.py --full --steps 40 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']; m = d['extra']['mlmc_config3']; r6 = d['extra']['r6']

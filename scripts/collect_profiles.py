@@ -22,16 +22,16 @@ def find(d, suffix):
     return max(hits, key=os.path.getmtime)
 
 
-for src, dst, what in (("prof_bench", "bench", "python bench.py --steps 20 --warmup 5 --inline-setup"),
-                       ("prof_l4", "bench_l4", "python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras"),
-                       ("prof_s1", "bench_s1", "python bench.py --streams 1 --steps 40 --no-cpu-baseline --no-extras"),
-                       ("prof_s1_saddle", "bench_s1_saddle", "python bench.py --solver saddle --streams 1 --steps 40 --no-cpu-baseline --no-extras"),
-                       ("prof_s1_r6", "bench_s1_r6", "python bench.py --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras"),
-                       ("prof_s1_r6_saddle", "bench_s1_r6_saddle", "python bench.py --solver saddle --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras"),
+for src, dst, what in (("prof_bench", "bench", "python bench.py --full --steps 20 --warmup 5 --inline-setup"),
+                       ("prof_l4", "bench_l4", "python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras"),
+                       ("prof_s1", "bench_s1", "python bench.py --full --streams 1 --steps 40 --no-cpu-baseline --no-extras"),
+                       ("prof_s1_saddle", "bench_s1_saddle", "python bench.py --full --solver saddle --streams 1 --steps 40 --no-cpu-baseline --no-extras"),
+                       ("prof_s1_r6", "bench_s1_r6", "python bench.py --full --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras"),
+                       ("prof_s1_r6_saddle", "bench_s1_r6_saddle", "python bench.py --full --solver saddle --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras"),
                        ("prof_c3", "c3_darcy_op", "python scripts/c3_darcy_op.py"),
                        ("prof_s1_onestream", "lab_s1_onestream",
                         "LABORATORY library (libpmc_lab.so, PMC_SPLIT_MIN=0: one lane on ONE stream, every kernel alone on the chip) "
-                        "python bench.py --solver saddle --streams 1 --steps 20 --warmup 3 --no-cpu-baseline --no-extras")):
+                        "python bench.py --full --solver saddle --streams 1 --steps 20 --warmup 3 --no-cpu-baseline --no-extras")):
     try:
         stats = find(src, "kernel_stats.csv")
     except FileNotFoundError:
@@ -179,7 +179,7 @@ try:
                         "the tree's sources differ from the ones the passes ran, or are uncommitted: no commit named")
 except Exception:   # noqa: BLE001
     out["head"] = None
-out["command"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py [--solver saddle] [--refine 6] "
+out["command"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py --full [--solver saddle] [--refine 6] "
                   "--steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-extras (separate passes, scripts/make_profiles.sh)")
 json.dump(out, open(os.path.join(P, "pmc_traffic.json"), "w"), indent=1)
 print(json.dumps(out, indent=1))

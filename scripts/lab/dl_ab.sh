@@ -5,21 +5,22 @@ R=$GRAFT_REPO_ROOT
 cd $R
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_round2.py -x -q -m gpu -k "block_operator or two_stream or full_size_config2 or matches_direct or hipgraph" > gpurun_out/dl_test.log 2>&1 || { tail -30 gpurun_out/dl_test.log; exit 1; }
 tail -2 gpurun_out/dl_test.log
+J=$(mktemp)   # the bench line of the current variant
 for s in 1 4; do
 for v in 1 0 1 0; do
-  PMC_DIAG_LAST=$v python bench.py --streams $s --steps 60 --warmup 5 --no-cpu-baseline --no-mlmc --no-r6 > gpurun_out/dl_ab.json 2> gpurun_out/dl_ab.err
+  PMC_DIAG_LAST=$v python bench.py --full --streams $s --steps 60 --warmup 5 --no-cpu-baseline --no-mlmc --no-r6 > $J 2> $J.err
   python - <<PY
 import json
-d=json.loads(open("gpurun_out/dl_ab.json").read().strip().splitlines()[-1])
+d=json.loads(open("$J").read().strip().splitlines()[-1])
 print("streams=$s DIAG_LAST=$v", round(d["value"],1), "K5 us", round(d["roofline"]["avg_kernel_ms"]*1e3,1), round(d["roofline"]["frac"],3), "solver", round(d["roofline"]["solver"]["frac"],3))
 PY
 done
 done
 for v in 1 0; do
-  PMC_DIAG_LAST=$v python bench.py --refine 6 --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-mlmc --no-r6 > gpurun_out/dl_ab.json 2> gpurun_out/dl_ab.err
+  PMC_DIAG_LAST=$v python bench.py --full --refine 6 --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-mlmc --no-r6 > $J 2> $J.err
   python - <<PY
 import json
-d=json.loads(open("gpurun_out/dl_ab.json").read().strip().splitlines()[-1])
+d=json.loads(open("$J").read().strip().splitlines()[-1])
 print("r6 DIAG_LAST=$v", round(d["value"],1), "K5 us", round(d["roofline"]["avg_kernel_ms"]*1e3,1), round(d["roofline"]["frac"],3), "solver", round(d["roofline"]["solver"]["frac"],3))
 PY
 done

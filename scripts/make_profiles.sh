@@ -3,7 +3,7 @@
 #   0. gpurun_out/profile_stamp.json: sha256 of the libpmc.so and of the sources the passes below RUN (written here, on the
 #      GPU box, at run time - scripts/collect_profiles.py copies it into profiles/pmc_traffic.json instead of hashing whatever
 #      sits in the tree when it is called)
-#   1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command (the driver's)  -> gpurun_out/prof_bench/
+#   1. rocprofv3 --kernel-trace --stats of the full bench command (--full)          -> prof_bench/
 #   1b. the headline alone (--no-extras: four lanes, hybridized), the kernel mix `value` is measured on -> gpurun_out/prof_l4/
 #   2. the same for one lane per GPU (--streams 1): per-kernel time without overlap   -> gpurun_out/prof_s1/
 #      (the headline's solver, hybridization) and gpurun_out/prof_s1_saddle/ (--solver saddle: MINRES-BJ-GS on the
@@ -56,23 +56,23 @@ pmc_pass() {   # suffix, bench arguments: the FETCH_SIZE and WRITE_SIZE passes o
 }
 PROF=(--kernel-trace --stats)
 if want 1; then
-  if [ -z "$SKIP_BENCH_PROFILE" ]; then run prof_bench --steps 20 --warmup 5 --inline-setup || exit 1; fi
-  run prof_l4 --steps 40 --warmup 5 --no-cpu-baseline --no-extras || exit 1     # the headline's own kernel mix: four lanes, hybridized
+  if [ -z "$SKIP_BENCH_PROFILE" ]; then run prof_bench --full --steps 20 --warmup 5 --inline-setup || exit 1; fi
+  run prof_l4 --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras || exit 1     # the headline's own kernel mix: four lanes, hybridized
 fi
 if want 2; then
-  run prof_s1 --streams 1 --steps 40 --no-cpu-baseline --no-extras || exit 1
-  run prof_s1_saddle --solver saddle --streams 1 --steps 40 --no-cpu-baseline --no-extras || exit 1
-  pmc_pass r5 --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
-  pmc_pass r5s --solver saddle --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
+  run prof_s1 --full --streams 1 --steps 40 --no-cpu-baseline --no-extras || exit 1
+  run prof_s1_saddle --full --solver saddle --streams 1 --steps 40 --no-cpu-baseline --no-extras || exit 1
+  pmc_pass r5 --full --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
+  pmc_pass r5s --full --solver saddle --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
   # per-kernel roofline table of the one-lane hybridized profile (sizes from the library, durations and counters from the passes)
   python3 $R/scripts/roofline_table.py $R/gpurun_out/prof_s1_by_grid.csv $R/gpurun_out/pmc_fetch_r5_by_grid.csv $R/gpurun_out/pmc_write_r5_by_grid.csv > $R/gpurun_out/roofline_table.txt 2>&1 || exit 1
   echo "roofline table done"
 fi
 if want 3; then
-  run prof_s1_r6 --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras || exit 1
-  run prof_s1_r6_saddle --solver saddle --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras || exit 1
-  pmc_pass r6 --refine 6 --steps 1 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
-  pmc_pass r6s --solver saddle --refine 6 --steps 1 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
+  run prof_s1_r6 --full --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras || exit 1
+  run prof_s1_r6_saddle --full --solver saddle --refine 6 --streams 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extras || exit 1
+  pmc_pass r6 --full --refine 6 --steps 1 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
+  pmc_pass r6s --full --solver saddle --refine 6 --steps 1 --warmup 1 --streams 1 --no-cpu-baseline --no-extras || exit 1
   runpy prof_c3 scripts/c3_darcy_op.py || exit 1
   for c in FETCH_SIZE WRITE_SIZE; do
     PROF=(--kernel-trace --pmc $c)
@@ -82,6 +82,6 @@ if want 3; then
   if [ -f $R/parelagmc_amd/lib/libpmc_lab.so ]; then
     PROF=(--kernel-trace --stats)
     # the laboratory library is SELECTED through the harness's loader override, never copied over the product's file
-    PMC_LIB=$R/parelagmc_amd/lib/libpmc_lab.so PMC_SPLIT_MIN=0 run prof_s1_onestream --solver saddle --streams 1 --steps 20 --warmup 3 --no-cpu-baseline --no-extras || exit 1
+    PMC_LIB=$R/parelagmc_amd/lib/libpmc_lab.so PMC_SPLIT_MIN=0 run prof_s1_onestream --full --solver saddle --streams 1 --steps 20 --warmup 3 --no-cpu-baseline --no-extras || exit 1
   fi
 fi

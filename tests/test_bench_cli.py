@@ -1,6 +1,7 @@
 """bench.py command line without a GPU: the rank launcher of `--gpus N` propagates a failing rank's exit code, and a launcher
 environment that contradicts `--gpus` is refused before anything heavy happens.  --dump-outputs: the selection logic here, the
-real run on the GPU (marked)."""
+real run on the GPU (marked).  A plain run measures the headline alone, --full everything behind it."""
+import argparse
 import json
 import os
 import subprocess
@@ -189,6 +190,48 @@ def test_steps_below_one_are_refused():
     assert r.returncode == 2 and "--steps" in r.stderr
 
 
+def test_all_configs_without_full_is_refused():
+    r = _run(["--all-configs"])
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def _args(**kw):
+    a = dict(full=False, no_extras=False, no_mlmc=False, no_r6=False, refine=5, only_config=None)
+    a.update(kw)
+    return argparse.Namespace(**a)
+
+
+def test_only_a_full_run_sets_up_the_other_configurations():
+    """a plain run starts no background setup worker and plans no extra.* figure, whatever --no-* options it is given"""
+    sys.path.insert(0, ROOT)
+    import bench
+    for world in (1, 2):
+        for kw in ({}, {"no_mlmc": True}, {"no_extras": True}, {"only_config": 4}):
+            assert not bench.extras_planned(_args(**kw), world) and bench.setup_kinds(_args(**kw), world) == []
+    assert bench.extras_planned(_args(full=True), 1) and not bench.extras_planned(_args(full=True), 2)
+    assert bench.setup_kinds(_args(full=True), 1) == ["c3", "r6", "c4", "c5"]
+    assert bench.setup_kinds(_args(full=True, refine=6, only_config=5), 1) == ["c3", "c5"]
+    assert bench.setup_kinds(_args(full=True), 2) == ["c3"]
+    assert bench.setup_kinds(_args(full=True, no_mlmc=True), 2) == []
+    assert bench.setup_kinds(_args(full=True, no_extras=True), 1) == []
+    assert bench.setup_kinds(_args(full=True, no_mlmc=True, no_r6=True), 1) == []
+
+
+def test_compact_line_of_a_plain_run_is_the_headline_alone():
+    """the record of a plain run has no roofline, cpu_baseline, extra or full record: the line carries none of them, not even
+    as a block of nulls"""
+    sys.path.insert(0, ROOT)
+    import bench
+    full = _canned_full_record()
+    for k in ("roofline", "cpu_baseline", "extra", "full_record"):
+        full.pop(k, None)
+    d = json.loads(bench.compact_line(full))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert not {"roofline", "cpu_baseline", "extra", "full_record"} & d.keys()
+    assert d["value"] == float(f"{full['value']:.6g}") and d["ms_per_step"] == float(f"{full['ms_per_step']:.6g}")
+
+
 @pytest.mark.gpu
 def test_dump_outputs_is_what_the_timed_path_computed(tmp_path):
     """bench.py --dump-outputs on a small headline: --steps timed steps (ms_per_step in the line), two runs with the same
@@ -219,3 +262,23 @@ def test_dump_outputs_is_what_the_timed_path_computed(tmp_path):
     for j in (0, len(ids) - 1):
         ref = so.eval(0, 0, a["xi"][j])[0]
         assert np.linalg.norm(a["field"][j] - ref) / np.linalg.norm(ref) < 1e-5
+
+
+@pytest.mark.gpu
+def test_plain_run_times_what_a_full_run_times(tmp_path):
+    """a plain run prints the headline alone (no roofline, cpu_baseline, extra or full record); --full adds the roofline
+    block after the timed region, and both runs' last timed step dumps the same arrays"""
+    lines, dumps = [], []
+    for full in ([], ["--full", "--no-cpu-baseline", "--no-extras"]):
+        d = str(tmp_path / f"run{len(full)}")
+        r = _run(["--refine", "3", "--streams", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", d] + full)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append(_dumped(d))
+    plain, full = lines
+    assert not {"roofline", "cpu_baseline", "extra", "full_record"} & plain.keys()
+    assert full["roofline"]["frac"] > 0 and full["full_record"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    a, b = dumps
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)

@@ -99,8 +99,8 @@ def _worker8(rank, world, port, out_dir):
 
 
 def test_eight_rank_farm_rehearsal(tmp_path):
-    """What `bench.py --gpus 8` asks of the manager (extra.mlmc_farm), rehearsed with EIGHT gloo ranks on the CPU (a GPU box
-    admits at most six processes on its card): InitRun [512, 2048, 8192] sharded over 8 ranks, every realization id drawn
+    """What `bench.py --full --gpus 8` asks of the manager (extra.mlmc_farm), rehearsed with EIGHT gloo ranks on the CPU (a
+    GPU box admits at most six processes on its card): InitRun [512, 2048, 8192] sharded over 8 ranks, every realization id drawn
     exactly once, ONE reduction per round on every rank, the reduced counts and sums identical on all ranks and equal to
     the serial manager's (the reference's manager is serial: /root/reference/src/MLMC_Manager.hpp:24, :113-179)."""
     from parelagmc_amd import host_api

@@ -24,14 +24,15 @@ def test_bench_starts_its_own_ranks():
     ranks under mpirun, examples/MLMC.cpp:43-50).  Rehearsed with FOUR ranks x one lane on one GPU (the box admits at most six
     processes on its card, so eight cannot be rehearsed here; tests/test_farm_gloo.py runs eight ranks of the manager on the
     CPU): the ranks share device 0, torch.distributed falls back to gloo, RCCL refuses several ranks on one device and the
-    farm's accumulators are summed over gloo instead - same manager, same sharding, same single reduction per round."""
+    farm's accumulators are summed over gloo instead - same manager, same sharding, same single reduction per round (a
+    --full run: a plain one measures the headline alone)."""
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     W = 4
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(W), "--streams", "1", "--refine", "3",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-r6"], env=env, capture_output=True,
-                       text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-r6"], env=env,
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
