@@ -269,7 +269,8 @@ typedef struct pmc_kl_level {
  * take the handle like any other.  pmc_sampler_eval computes s = Phi_level Lambda^1/2 xi[:nmodes] (exp() if lognormal) for
  * every realization in one fp64 launch, whichever level xi was drawn on; embed_s_out receives the Gaussian field;
  * init_s / init_level / use_init are ignored; pmc_stats: iterations 0, converged 1.  pmc_sampler_mult, _apply_preconditioner,
- * _apply_operator, _vcycle_info and _set_projection return PMC_ERR_INVALID on a KL handle. */
+ * _apply_operator, _vcycle_info, _vcycle_level, _vcycle_prolongator and _set_projection return PMC_ERR_INVALID on a KL
+ * handle. */
 int pmc_sampler_create_kl(pmc_ctx* ctx, int nlevels, const pmc_kl_level* levels, int nmodes, const double* evals,
                           const double* evect0, int lognormal, pmc_sampler** out);
 int pmc_sampler_is_kl(const pmc_sampler* s);
@@ -395,6 +396,26 @@ int pmc_sampler_smoother_bytes(const pmc_sampler* s, int level, int nbatch, doub
  * split), [6] = 1 when its restriction is fused into the residual kernel.
  * Returns the number of V-cycle levels through *nvlevels; vlevel out of range is an error. */
 int pmc_sampler_vcycle_info(const pmc_sampler* s, int level, int vlevel, int* nvlevels, int64_t info[7]);
+/* Setup values of level `vlevel` (0 = the first) of the Schur-block (hybridized: multiplier) V-cycle the solves of `level`
+ * run - what a reference of the preconditioner cannot derive from the caller's data.  Reads setup only.
+ * info[0] = rows, [1] = lmax of the diagonally scaled level operator, [2] = what a launch of more than dense_nb realizations
+ * does on the level: 0 = smooths and descends, 1 = ends its cycle with a polynomial of degree [5] on [lmax / [6], lmax],
+ * 2 = ends it with an exact solve (the level's dense inverse), 3 = does not reach it; [3] / [4] = smoothing degree / ratio
+ * (interval [lmax / ratio, lmax]); [5] / [6] = degree / ratio of the polynomial a cycle ending here runs (the level's own
+ * values when its spectrum is provably narrow, else mg_coarse_*); [7] = s of an internal hierarchy S_{l+1} = s P^T S_l P
+ * (0: the caller's levels, each rediscretized from its level struct); [8] = ratio_M and [9] = degree of the l1-scaled
+ * Chebyshev polynomial of the M-block (lmax 1; 0 on a hybridized handle); [10] = 0: the caller's levels, 1: internal smoothed
+ * aggregation (mg_coarsening), 2: the multiplier aggregation of a hybridized handle; [11] = dense_nb (0: launches of every
+ * width run the same cycle); [12] = [2] for launches of at most dense_nb realizations (2 there: the exact solve that ends
+ * their cycle early); [13] / [14] = 1 when launches of more than / at most dense_nb realizations run the level inside the LDS
+ * tail kernel.  Returns the number of V-cycle levels through *nvlevels; vlevel out of range is an error. */
+int pmc_sampler_vcycle_level(const pmc_sampler* s, int level, int vlevel, int* nvlevels, double info[15]);
+/* The prolongator P from V-cycle level vlevel + 1 to vlevel (0 <= vlevel < nvlevels - 1) as CSR: *nrows x *ncols with *nnz
+ * entries.  Call with rowptr, colind and vals NULL for the sizes, then with arrays of nrows + 1 / nnz / nnz entries and *nnz
+ * set to their capacity.  The rows of vlevel 0 are in the caller's numbering (a hybridized handle's internal renumbering of
+ * the multipliers undone); coarser levels are numbered by the library, consistently from one level to the next. */
+int pmc_sampler_vcycle_prolongator(const pmc_sampler* s, int level, int vlevel, int* nrows, int* ncols, int64_t* nnz,
+                                   int32_t* rowptr, int32_t* colind, double* vals);
 
 /* ---- DarcySolver ------------------------------------------------------------------------ */
 int pmc_darcy_create(pmc_ctx* ctx, int nlevels, int n_mc_levels, const pmc_darcy_level* levels,

@@ -10,10 +10,15 @@ Multigrid), not from the kernels.
   s = 1/2, Jacobi-scaled Chebyshev smoothers of degree `smooth_degree` on [lmax / smooth_ratio, lmax], lmax = 2 * 1.0001
   (a weakly diagonally dominant M-matrix has spec(D^-1 S) in (0, 2]), pre-smoothing from zero, post-smoothing from the
   corrected iterate, and a Chebyshev polynomial of degree `coarse_degree` on [lmax / coarse_ratio, lmax] on the last level.
+
+SamplerPrecondOracle: the same for the SPDE sampler's handles (csrc/sampler.hip), whose cycles may also end with an exact
+solve (the dense inverse of the bottom level, or of an inner level for narrow launches), and whose hierarchies are either the
+caller's levels, each rediscretized, or internal Galerkin hierarchies over a prolongator the library exports.
 """
 from __future__ import annotations
 
 import numpy as np
+import scipy.linalg as sla
 import scipy.sparse as sp
 
 from .darcy_oracle import DarcyOracle
@@ -53,10 +58,15 @@ def chebyshev(A, dinv, r, degree, lmax, ratio, x0=None):
     return x
 
 
-def vcycle(levels, r, smooth_degree, smooth_ratio, coarse_degree, coarse_ratio, l=0, coarse_solve=None):
-    """One V(1,1)-cycle from level l.  levels[i] = (S_i, lmax_i, P_i) with P_i: level i+1 -> i (None on the last level).
-    coarse_solve (optional): exact solve on the last level instead of the polynomial (the textbook two-grid method)."""
-    S, lmax, P = levels[l]
+def vcycle(levels, r, smooth_degree, smooth_ratio, coarse_degree=None, coarse_ratio=None, l=0, coarse_solve=None):
+    """One V(1,1)-cycle from level l.  levels[i] = (S_i, lmax_i, P_i) with P_i: level i+1 -> i (None on the last level), or
+    (S_i, lmax_i, P_i, bottom_i) with bottom_i None (smooth and descend) or a callable r -> x that ends the cycle on level i
+    (bottom_polynomial / bottom_exact).  A 3-tuple last level runs the polynomial of degree coarse_degree on
+    [lmax / coarse_ratio, lmax], or coarse_solve (optional: an exact solve, the textbook two-grid method)."""
+    S, lmax, P = levels[l][:3]
+    bottom = levels[l][3] if len(levels[l]) > 3 else None
+    if bottom is not None:
+        return bottom(r)
     dinv = 1.0 / S.diagonal()
     if l == len(levels) - 1:
         if coarse_solve is not None:
@@ -66,6 +76,18 @@ def vcycle(levels, r, smooth_degree, smooth_ratio, coarse_degree, coarse_ratio, 
     xc = vcycle(levels, P.T @ (r - S @ x), smooth_degree, smooth_ratio, coarse_degree, coarse_ratio, l + 1, coarse_solve)
     x = x + P @ xc
     return chebyshev(S, dinv, r, smooth_degree, lmax, smooth_ratio, x0=x)
+
+
+def bottom_polynomial(S, lmax, degree, ratio):
+    """the cycle ends with a Chebyshev polynomial of `degree` in D^-1 S on [lmax / ratio, lmax]"""
+    dinv = 1.0 / S.diagonal()
+    return lambda r: chebyshev(S, dinv, r, degree, lmax, ratio)
+
+
+def bottom_exact(S):
+    """the cycle ends with an exact solve S^-1 r (Cholesky of the dense level operator)"""
+    c = sla.cho_factor(S.toarray() if sp.issparse(S) else S)
+    return lambda r: sla.cho_solve(c, r)
 
 
 class DarcyPrecondOracle:
@@ -103,3 +125,76 @@ class DarcyPrecondOracle:
         zu = chebyshev(M, l1inv, r[:L.n_u], degree_M, 1.0, ratio_M)
         zp = vcycle(self.schur_levels(level, k), r[L.n_u:], *self.smooth)
         return np.concatenate([zu, zp])
+
+
+# pmc_sampler_vcycle_level: role of a level in a cycle, and the kinds of hierarchy
+ROLE_DESCEND, ROLE_POLY, ROLE_EXACT, ROLE_UNREACHED = 0, 1, 2, 3
+KIND_CALLER, KIND_SA, KIND_HYBRID = 0, 1, 2
+
+
+def sampler_schur(level, alpha, schur_scale):
+    """S = B (diag(M) / schur_scale)^-1 B^T + alpha W of one caller's sampler level (B with its essential columns removed)"""
+    d = level.M.diagonal() / schur_scale
+    return (level.B @ sp.diags(1.0 / d) @ level.B.T + alpha * sp.diags(level.w_diag)).tocsr()
+
+
+class SamplerPrecondOracle:
+    """B^-1 of ONE Monte Carlo level of a sampler handle (pmc_sampler_apply_preconditioner) in fp64, from the problem the
+    handle was created with, the setup values of pmc_sampler_vcycle_level (`setup`: a list of dicts, CAPI
+    PDESampler.vcycle_setup) and the prolongators of pmc_sampler_vcycle_prolongator (`prolongators[v]`: vlevel v + 1 -> v).
+
+    - saddle-point handles: diag(p_M(D_l1^-1 M) D_l1^-1, V(S)), p_M of degree_M on [1 / ratio_M, 1] (D_l1: l1 row sums of M);
+      hybridized handles: V(H) alone;
+    - kind 0 (the caller's levels): S_v of level `level` + v rediscretized from its own level struct (sampler_schur), not a
+      Galerkin product; kind 1 (mg_coarsening): S_0 the same Schur complement, S_{v+1} = s P_v^T S_v P_v with the exported P;
+      kind 2 (hybridized): S_0 = the caller's H, Galerkin below;
+    - per level: Chebyshev smoothing of smooth_degree on [lmax / smooth_ratio, lmax] before and after the coarse correction;
+      the cycle ends where `role_wide` (launches of more than dense_nb realizations) or `role_narrow` says, with the polynomial
+      of (last_degree, last_ratio) or an exact solve."""
+
+    def __init__(self, problem, level, setup, prolongators, schur_scale=1.0):
+        self.p, self.level, self.setup, self.P = problem, level, setup, prolongators
+        kind = int(setup[0]["hierarchy"])
+        self.kind = kind
+        self.hybrid = kind == KIND_HYBRID
+        if kind == KIND_CALLER:
+            S = [sampler_schur(problem.levels[level + v], problem.alpha, schur_scale) for v in range(len(setup))]
+        else:
+            S0 = problem.levels[level].H.tocsr() if self.hybrid else sampler_schur(problem.levels[level], problem.alpha,
+                                                                                     schur_scale)
+            S = [S0]
+            for v in range(len(setup) - 1):
+                s = setup[v]["galerkin_scale"]
+                S.append((s * (prolongators[v].T @ S[v] @ prolongators[v])).tocsr())
+        self.S = S
+        self._levels = {}
+
+    def levels(self, narrow):
+        """[(S_v, lmax_v, P_v, bottom_v)] of the cycle a narrow (at most dense_nb realizations) or wide launch runs"""
+        if narrow not in self._levels:
+            out = []
+            for v, m in enumerate(self.setup):
+                role = int(m["role_narrow" if narrow else "role_wide"])
+                if role == ROLE_DESCEND:
+                    out.append((self.S[v], m["lmax"], self.P[v], None))
+                    continue
+                assert role in (ROLE_POLY, ROLE_EXACT), (v, role)
+                bottom = (bottom_exact(self.S[v]) if role == ROLE_EXACT else
+                          bottom_polynomial(self.S[v], m["lmax"], int(m["last_degree"]), m["last_ratio"]))
+                out.append((self.S[v], m["lmax"], None, bottom))
+                break
+            self._levels[narrow] = out
+        return self._levels[narrow]
+
+    def vcycle(self, r, narrow=False):
+        m = self.setup[0]
+        return vcycle(self.levels(narrow), r, int(m["smooth_degree"]), m["smooth_ratio"])
+
+    def apply(self, r, narrow=False):
+        if self.hybrid:
+            return self.vcycle(r, narrow)
+        L = self.p.levels[self.level]
+        m = self.setup[0]
+        l1inv = 1.0 / np.asarray(abs(L.M).sum(axis=1)).ravel()
+        zu = chebyshev(L.M, l1inv, r[:L.n_u], int(m["degree_M"]), 1.0, m["ratio_M"])
+        return np.concatenate([zu, self.vcycle(r[L.n_u:], narrow)])

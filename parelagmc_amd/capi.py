@@ -117,6 +117,10 @@ SYMBOLS = {
     "pmc_sampler_smoother_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "pmc_sampler_smoother_bytes": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "pmc_sampler_vcycle_info": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "pmc_sampler_vcycle_level": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "pmc_sampler_vcycle_prolongator": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_double)]),
     "pmc_sampler_destroy": (None, [_VP]),
     "pmc_sampler_set_projection": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(pmc_csr), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.c_int]),
@@ -498,6 +502,37 @@ class PDESampler:
             v += 1
             if v >= nv.value:
                 return out
+
+    def vcycle_setup(self, level):
+        """setup values of every level of the V-cycle of `level` (pmc_sampler_vcycle_level): a list of dicts.  role_wide /
+        role_narrow: what launches of more than / at most dense_nb realizations do on the level (0 smooth and descend,
+        1 end with a polynomial, 2 end with an exact solve, 3 not reached); tail_wide / tail_narrow: inside the LDS tail"""
+        keys = ("rows", "lmax", "role_wide", "smooth_degree", "smooth_ratio", "last_degree", "last_ratio", "galerkin_scale",
+                "ratio_M", "degree_M", "hierarchy", "dense_nb", "role_narrow", "tail_wide", "tail_narrow")
+        out, nv, v = [], C.c_int(0), 0
+        while True:
+            info = (C.c_double * 15)()
+            _check(self.ctx.lib.pmc_sampler_vcycle_level(self.h, level, v, C.byref(nv), info))
+            out.append(dict(zip(keys, list(info))))
+            v += 1
+            if v >= nv.value:
+                return out
+
+    def vcycle_prolongator(self, level, vlevel):
+        """P from V-cycle level vlevel + 1 to vlevel of `level` (pmc_sampler_vcycle_prolongator) as a scipy CSR matrix; the
+        rows of vlevel 0 in the caller's numbering"""
+        import scipy.sparse as sp
+        nr, nc, nnz = C.c_int(0), C.c_int(0), C.c_int64(0)
+        _check(self.ctx.lib.pmc_sampler_vcycle_prolongator(self.h, level, vlevel, C.byref(nr), C.byref(nc), C.byref(nnz),
+                                                           None, None, None))
+        rp = np.empty(nr.value + 1, dtype=np.int32)
+        ci = np.empty(nnz.value, dtype=np.int32)
+        va = np.empty(nnz.value, dtype=np.float64)
+        _check(self.ctx.lib.pmc_sampler_vcycle_prolongator(self.h, level, vlevel, C.byref(nr), C.byref(nc), C.byref(nnz),
+                                                           rp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           ci.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           va.ctypes.data_as(C.POINTER(C.c_double))))
+        return sp.csr_matrix((va, ci, rp), shape=(nr.value, nc.value))
 
     def z_bytes(self):
         """bytes per entry of the preconditioned Krylov vectors of this handle (4: PMC_STORAGE_FP32, 8: PMC_STORAGE_FP64)"""

@@ -552,6 +552,34 @@ int pmc_sampler_vcycle_info(const pmc_sampler* s, int level, int vlevel, int* nv
     });
 }
 
+int pmc_sampler_vcycle_level(const pmc_sampler* s, int level, int vlevel, int* nvlevels, double info[15]) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr && nvlevels != nullptr && info != nullptr, "pmc_sampler_vcycle_level: NULL argument");
+        refuse_kl(s, "pmc_sampler_vcycle_level");
+        s->impl.vcycle_level(level, vlevel, nvlevels, info);
+    });
+}
+int pmc_sampler_vcycle_prolongator(const pmc_sampler* s, int level, int vlevel, int* nrows, int* ncols, int64_t* nnz,
+                                   int32_t* rowptr, int32_t* colind, double* vals) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr && nrows != nullptr && ncols != nullptr && nnz != nullptr,
+                    "pmc_sampler_vcycle_prolongator: NULL argument");
+        refuse_kl(s, "pmc_sampler_vcycle_prolongator");
+        HostCsr scratch;
+        const HostCsr& P = s->impl.vcycle_prolongator(level, vlevel, scratch);
+        const int64_t cap = *nnz;
+        *nrows = P.nrows;
+        *ncols = P.ncols;
+        *nnz = (int64_t)P.colind.size();
+        if (rowptr == nullptr && colind == nullptr && vals == nullptr) return;   // size query
+        PMC_REQUIRE(rowptr != nullptr && colind != nullptr && vals != nullptr && cap >= *nnz,
+                    "pmc_sampler_vcycle_prolongator: arrays missing or smaller than nnz");
+        std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
+        std::copy(P.colind.begin(), P.colind.end(), colind);
+        std::copy(P.vals.begin(), P.vals.end(), vals);
+    });
+}
+
 int pmc_sampler_operator_event_overhead(pmc_sampler* s, double* total_ms) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr && total_ms != nullptr, "operator_event_overhead: bad arguments");

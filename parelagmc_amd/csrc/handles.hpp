@@ -32,6 +32,7 @@ struct SamplerLevel {
     // internal numbering of the multipliers (aggregates of the V-cycle's finest level contiguous, agg_pack_rows): internal
     // row i is the caller's row lam_new2old[i]; empty = the caller's numbering
     DevBuf<int> lam_new2old, lam_old2new;
+    std::vector<int> lam_n2o_host;   // lam_new2old on the host (setup export of the V-cycle's finest prolongator)
 };
 
 struct Sampler {
@@ -78,6 +79,9 @@ struct Sampler {
     // rows of the vectors the Krylov solver of `level` iterates on
     // algorithmic bytes of one launch of the timed post-smoothing kernel (level 0 of the hybrid V-cycle of `level`)
     double smoother_bytes(int level, int nb) const;
+    // setup values / prolongator of level `vlevel` of the V-cycle `level`'s solves run (pmc_sampler_vcycle_level / _prolongator)
+    void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
+    const HostCsr& vcycle_prolongator(int level, int vlevel, HostCsr& scratch) const;
     size_t system_rows(int level) const { return hybrid ? (size_t)lv[level].n_u : (size_t)lv[level].n_u + lv[level].n_s; }
     void set_projection(int level, int kind, const pmc_csr* Gt, const int32_t* idx, const double* inv_w, int orig_size);
     void sample(int level, uint64_t first_id, int nbatch, double* xi, int memspace);

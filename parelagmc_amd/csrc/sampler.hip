@@ -128,6 +128,7 @@ static std::unique_ptr<Multigrid> build_chain(const std::vector<AmgLevelHost>& l
         if (m.is_last) { mg->L.resize(l + 1); break; }
         if (l + 1 < lv.size()) {
             const HostCsr& P = lv[l].P;
+            m.P_host = P;
             sell_build(m.P, P, true, false, st);
             sell_build(m.Pt, csr_transpose(P), true, false, st);
             // indicator prolongator (plain aggregation): the coarse correction is folded into the post-smoothing
@@ -425,6 +426,7 @@ Sampler::Sampler(Ctx& c, int nlevels_, const pmc_hybrid_level* in, double alpha_
                 G = csr_permute(G, new2old, true, false);
                 hier[0].S = H;
                 d.lam_new2old.upload(new2old, st);
+                d.lam_n2o_host = new2old;
                 d.lam_old2new.upload(old2new, st);
             } else {
                 hier[(size_t)pl].S = csr_permute(hier[(size_t)pl].S, new2old, true, true);
@@ -928,6 +930,54 @@ void Sampler::eval(int level, int xi_level, int nbatch, const double* xi, double
         done += nb;
     }
     if (init_copy.p) PMC_HIP(hipStreamSynchronize(st));   // the private copy is released on return
+}
+
+// setup values of the V-cycle of `level` (pmc_sampler_vcycle_level; layout in include/pmc.h).  Reads setup only.
+void Sampler::vcycle_level(int level, int vlevel, int* nvlevels, double* info) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_sampler_vcycle_level: level out of range");
+    const bool own = level < (int)amg.size() && amg[level];
+    const Multigrid& g = own ? *amg[level] : mg;
+    const int first = own ? 0 : level;
+    *nvlevels = (int)g.L.size() - first;
+    PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_sampler_vcycle_level: vlevel out of range");
+    const MgLevel& m = g.L[(size_t)(first + vlevel)];
+    bool tail_wide = false, tail_narrow = false;
+    const int role_wide = g.cycle_role(first, kMaxBatch + 1, first + vlevel, &tail_wide);
+    const int role_narrow = g.cycle_role(first, std::max(1, g.dense_nb), first + vlevel, &tail_narrow);
+    const SamplerLevel& d = lv[level];
+    info[0] = m.n;
+    info[1] = m.lmax;
+    info[2] = role_wide;
+    info[3] = g.smooth_degree;
+    info[4] = g.smooth_ratio;
+    info[5] = m.is_last ? m.last_degree : g.coarse_degree;
+    info[6] = m.is_last ? m.last_ratio : g.coarse_ratio;
+    info[7] = own ? 1.0 : 0.0;   // internal hierarchies are plain Galerkin products; the caller's levels are rediscretized
+    info[8] = hybrid ? 0.0 : d.ratio_M;
+    info[9] = hybrid ? 0.0 : (opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (d.ratio_M > 16.0 ? 4 : 2));
+    info[10] = hybrid ? 2.0 : own ? 1.0 : 0.0;
+    info[11] = g.dense_nb;
+    info[12] = role_narrow;
+    info[13] = tail_wide ? 1.0 : 0.0;
+    info[14] = tail_narrow ? 1.0 : 0.0;
+}
+
+// P from vlevel + 1 to vlevel of the V-cycle of `level` (pmc_sampler_vcycle_prolongator): vlevel 0 of a hybridized handle in
+// the caller's multiplier numbering (the agg_pack_rows renumbering undone into `scratch`)
+const HostCsr& Sampler::vcycle_prolongator(int level, int vlevel, HostCsr& scratch) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_sampler_vcycle_prolongator: level out of range");
+    const bool own = level < (int)amg.size() && amg[level];
+    const Multigrid& g = own ? *amg[level] : mg;
+    const int first = own ? 0 : level;
+    PMC_REQUIRE(vlevel >= 0 && first + vlevel + 1 < (int)g.L.size(), "pmc_sampler_vcycle_prolongator: vlevel out of range");
+    const HostCsr& P = own ? g.L[(size_t)vlevel].P_host : lv[(size_t)(first + vlevel)].P_host;
+    PMC_REQUIRE(P.nrows == g.L[(size_t)(first + vlevel)].n, "pmc_sampler_vcycle_prolongator: no prolongator kept");
+    const std::vector<int>& n2o = lv[level].lam_n2o_host;
+    if (!(hybrid && vlevel == 0 && !n2o.empty())) return P;
+    std::vector<int> old2new(n2o.size());
+    for (size_t i = 0; i < n2o.size(); ++i) old2new[(size_t)n2o[i]] = (int)i;
+    scratch = csr_permute(P, old2new, true, false);   // row i of the result: the library's row old2new[i]
+    return scratch;
 }
 
 }  // namespace pmc

@@ -349,6 +349,31 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
     return cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, x, oth, lv.d.p, false, dot_partial, dot_blocks, ztarget);
 }
 
+int Multigrid::cycle_role(int l0, int nb, int l, bool* in_tail) const {
+    bool tail_on = false;
+    for (int q = l0; q < (int)L.size(); ++q) {
+        const MgLevel& lv = L[(size_t)q];
+        const bool last = q == (int)L.size() - 1 || lv.is_last;
+        int role = -1;
+        if (!tail_on) {
+            if (q > l0 && nb <= dense_nb && lv.dense_inv.p) {
+                role = 2;
+            } else {
+                const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && !last && q + 1 < (int)tail.size() && tail[q + 1].p;
+                tail_on = use_tail && q < (int)tail.size() && tail[q].p && !tail_later;
+            }
+        }
+        if (role < 0) role = !last ? 0 : (tail_on && lv.ainv.p) ? 2 : 1;
+        if (q == l) {
+            if (in_tail) *in_tail = tail_on;
+            return role;
+        }
+        if (role != 0) break;
+    }
+    if (in_tail) *in_tail = false;
+    return 3;
+}
+
 int Multigrid::vcycle(hipStream_t st, int nb, int l0, const double* r, double* xout, double* dot_partial,
                       const std::function<void()>& side) {
     int nblk = 0;

@@ -79,6 +79,7 @@ struct MgLevel {
     int last_degree = 12;
     double last_ratio = 100.0;
     Sell P, Pt;                  // to/from the next coarser level (absent on the last)
+    HostCsr P_host;              // internal hierarchies (sampler build_chain): P as uploaded, for pmc_sampler_vcycle_prolongator
     // Injection-type prolongators (one unit entry per row: P0 on nested meshes) with shared values: the coarse
     // correction never materialises on this level.  SP = S P lets the post-smoothing residual be formed from the
     // pre-restriction one, r - S (x + P xc) = res - SP xc, and `parent` adds xc[parent[i]] inside the smoother pass.
@@ -158,6 +159,11 @@ struct Multigrid {
     int bv_tail_width = 0;
     void ensure_bv_tail_width(hipStream_t st, int nb);
     void refresh_bv_tail(hipStream_t st, int nb, int first_level = 0);
+    // what a cycle from level l0 at width nb does with level l (the choices of cycle(), for the setup export
+    // pmc_sampler_vcycle_level): 0 = smooths and descends, 1 = ends the cycle with a polynomial, 2 = ends it with an exact
+    // solve (dense inverse: ainv at the bottom of the LDS tail, dense_inv of a narrow launch), 3 = not reached.
+    // *in_tail: the level runs inside the LDS tail kernel
+    int cycle_role(int l0, int nb, int l, bool* in_tail) const;
     // hash of the work-buffer pointers a V-cycle from level l0 touches (for GraphHint::sig)
     uint64_t signature(int l0) const;
     // x = V(r) starting at level l0 with zero initial guess; result written to xout (n(l0)*nb).

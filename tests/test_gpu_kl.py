@@ -140,6 +140,8 @@ def test_entry_points_without_a_linear_system_are_refused(gpu_ctx):
     y = np.zeros(2 * n)
     nv = C.c_int(0)
     info = (C.c_int64 * 7)()
+    dinfo = (C.c_double * 15)()
+    nc, nnz = C.c_int(0), C.c_int64(0)
     t, b = C.c_double(), C.c_double()
     calls = {
         "pmc_sampler_mult": lambda: lib.pmc_sampler_mult(smp.h, 0, 1, x.ctypes.data, y.ctypes.data, 0, 0, None),
@@ -148,6 +150,9 @@ def test_entry_points_without_a_linear_system_are_refused(gpu_ctx):
         "pmc_sampler_apply_operator": lambda: lib.pmc_sampler_apply_operator(smp.h, 0, 1, x.ctypes.data, y.ctypes.data, 0, 1,
                                                                              C.byref(t), C.byref(b)),
         "pmc_sampler_vcycle_info": lambda: lib.pmc_sampler_vcycle_info(smp.h, 0, 0, C.byref(nv), info),
+        "pmc_sampler_vcycle_level": lambda: lib.pmc_sampler_vcycle_level(smp.h, 0, 0, C.byref(nv), dinfo),
+        "pmc_sampler_vcycle_prolongator": lambda: lib.pmc_sampler_vcycle_prolongator(smp.h, 0, 0, C.byref(nv), C.byref(nc),
+                                                                                     C.byref(nnz), None, None, None),
         "pmc_sampler_set_projection": lambda: lib.pmc_sampler_set_projection(smp.h, 0, capi.PMC_PROJ_GATHER, None,
                                                                              np.arange(n, dtype=np.int32).ctypes.data_as(
                                                                                  C.POINTER(C.c_int32)), None, n),

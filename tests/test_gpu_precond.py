@@ -15,18 +15,25 @@ These tests pin what a solve cannot:
   permuting the columns of (r, k) permutes z, and swapping k between two columns with equal r swaps their results;
 - the block structure (u- and p-rows preconditioned independently) and the symmetry of B(k)^-1 per column.
 
-Not covered by this file: a reference of B^-1 on the internal aggregation hierarchies (Darcy mg_coarsening, the hybridized
-Darcy and sampler handles) and of the sampler's preconditioner (its dense-inverse path at nb <= dense_nb included); the
-fp32-intermediate V-cycle kernels of per-realization levels above 8 192 rows (the levels here all run in the LDS tail); the
-preconditioner inside mini_sampler_kernel (covered indirectly by test_persistent_small_level_solver_equals_the_batched_kernels)
-and the r32_top input of the hybridized sampler's cycle, which only the MINRES loop provides.
+The hex32 handle (32^3, one MC level) puts the finest level (32 768 rows) outside the LDS tail, which takes per-realization
+levels of at most 8 192 rows: with PMC_STORAGE_FP32 it runs the fp32-value kernels vc_presmooth32_bv, vc_restrict8_32_bv,
+vc_prolong8_32, vc_residual32_bv and vc_postsmooth32_bv_z, with PMC_STORAGE_FP64 the bv Chebyshev polynomial and
+residual_restrict8.  The sampler's preconditioner (every hierarchy kind, both width regimes) is compared with a reference in
+test_gpu_sampler_precond.py.
+
+Not covered by this file: a reference of B^-1 on the Darcy internal hierarchies (mg_coarsening and the hybridized Darcy
+handle); the preconditioner inside mini_sampler_kernel (covered indirectly by
+test_persistent_small_level_solver_equals_the_batched_kernels) and the r32_top input of the hybridized sampler's cycle, which
+only the MINRES loop provides.
 
 Measured on the MI355X (the printed lines), widths 1 .. 256 on every level:
 - against the fp64 reference: at most 2.8e-15 with PMC_STORAGE_FP64, 2.6e-9 with PMC_STORAGE_FP32 (these levels keep the
-  fp64 values inside the LDS tail; z is returned in fp64);
+  fp64 values inside the LDS tail; z is returned in fp64); hex32: 5.1e-16 (fp64) and 8.1e-8 (fp32: the finest level's values,
+  iterate and residuals in fp32 - REF_TOL's 1e-5 holds with two orders of margin);
 - operator, saddle-point (hex, tet with and without the element-grouped M-block): max |y - Ax| / (|A||x|) 1.9 .. 2.8 eps;
   hybridized: 2.7 .. 3.4 eps on hexahedra, relative L2 error at most 1.1e-15 on tetrahedra;
-- preconditioner at width nb against the column alone: bit for bit equal on every path and in both storages, except the
+- preconditioner at width nb against the column alone: bit for bit equal on every path (hex32 included) and in both
+  storages, except the
   materialised M-block (cheb_degree_M = 3), where the polynomial's rounding depends on the width: 1.5e-16 (fp64) and 2.5e-16
   (fp32 storage);
 - every bitwise column-independence check held on every path, both storages.
@@ -65,16 +72,24 @@ def _tet_hierarchy(nref):
 @pytest.fixture(scope="module")
 def problems(hex_hierarchy):
     """name -> (hierarchy, Darcy problem): the octree hierarchy (hexahedra) and tetrahedra"""
-    from parelagmc_amd.fe import build_darcy_problem
+    from parelagmc_amd.fe import box_mesh, build_darcy_problem, build_hierarchy
     out = {"hex": (hex_hierarchy, build_darcy_problem(hex_hierarchy, [0, 1, 1, 1, 1, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 1]))}
     ht = _tet_hierarchy(2)
     out["tet"] = (ht, build_darcy_problem(ht, [0, 1, 1, 1, 1, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 1], n_mc_levels=2))
+    # 32^3 hexahedra, one MC level: a per-realization level above 8 192 rows (outside the LDS tail)
+    h32 = build_hierarchy(box_mesh([4, 4, 4], [2, 2, 2], "hex"), 3)
+    out["hex32"] = (h32, build_darcy_problem(h32, [0, 1, 1, 1, 1, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 1], n_mc_levels=1))
     return out
 
 
 # handle kinds: (problem, hybridized, cheb_degree_M) - degree 2 takes the element-grouped M-block, 3 the materialised M(k)
 HANDLES = [("hex", False, 0), ("tet", False, 0), ("tet", False, 3), ("hex", True, 0), ("tet", True, 0)]
 HANDLE_IDS = ["hex-saddle", "tet-saddle-eg", "tet-saddle-noeg", "hex-hybrid", "tet-hybrid"]
+# ... and the saddle-point handle whose finest level (32^3: 32 768 rows) runs the per-realization V-cycle kernels outside the
+# LDS tail: fp32 storage vc_presmooth32_bv / vc_restrict8_32_bv / vc_prolong8_32 / vc_residual32_bv / vc_postsmooth32_bv_z,
+# fp64 storage the bv Chebyshev polynomial and residual_restrict8
+PRECOND_HANDLES = HANDLES + [("hex32", False, 0)]
+PRECOND_IDS = HANDLE_IDS + ["hex32-saddle"]
 
 
 def _solver(ctx, problems, name, hybrid, degM, storage="fp32"):
@@ -159,7 +174,7 @@ def test_darcy_operator_matches_assembled_matrix(gpu_ctx, problems, seeded_rng, 
 
 
 @pytest.mark.parametrize("storage", ["fp64", "fp32"])
-@pytest.mark.parametrize("name,hybrid,degM", HANDLES, ids=HANDLE_IDS)
+@pytest.mark.parametrize("name,hybrid,degM", PRECOND_HANDLES, ids=PRECOND_IDS)
 def test_darcy_preconditioner_is_the_same_at_every_width(gpu_ctx, problems, seeded_rng, name, hybrid, degM, storage):
     """every column of a launch of width 1, 2, 4, ... BatchWidth equals the same (r, k) launched alone; the column's own k is
     what it is preconditioned with (a width-1 launch has no other column to read)"""
@@ -219,7 +234,7 @@ def _check_independence(apply, rng, nb, n, n_p):
 
 
 @pytest.mark.parametrize("storage", ["fp64", "fp32"])
-@pytest.mark.parametrize("name,hybrid,degM", HANDLES, ids=HANDLE_IDS)
+@pytest.mark.parametrize("name,hybrid,degM", PRECOND_HANDLES, ids=PRECOND_IDS)
 def test_darcy_preconditioner_columns_are_independent(gpu_ctx, problems, seeded_rng, name, hybrid, degM, storage):
     """zero / duplicate / permuted / k-swapped columns at the widest launch of every level (bit for bit)"""
     _, dp = problems[name]
@@ -289,7 +304,8 @@ REF_TOL = {"fp64": 1e-12, "fp32": 1e-5}
 
 
 @pytest.mark.parametrize("storage", ["fp64", "fp32"])
-@pytest.mark.parametrize("name,degM", [("hex", 0), ("tet", 0), ("tet", 3)], ids=["hex-eg", "tet-eg", "tet-noeg"])
+@pytest.mark.parametrize("name,degM", [("hex", 0), ("tet", 0), ("tet", 3), ("hex32", 0)],
+                         ids=["hex-eg", "tet-eg", "tet-noeg", "hex32-eg"])
 def test_darcy_preconditioner_matches_fp64_reference(gpu_ctx, problems, seeded_rng, name, degM, storage):
     """B(k_j)^-1 r_j of every compared column at every launch width 1 .. BatchWidth against the fp64 restatement
     (oracle/precond_oracle.py: M-block polynomial, Schur V-cycle over the caller's P with S_{l+1} = 1/2 P^T S_l P), each column
@@ -303,6 +319,14 @@ def test_darcy_preconditioner_matches_fp64_reference(gpu_ctx, problems, seeded_r
     po = DarcyPrecondOracle(dp, o.mg_smooth_degree, o.mg_smooth_ratio, o.mg_coarse_degree, o.mg_coarse_ratio)
     ds = _solver(gpu_ctx, problems, name, False, degM, storage)
     nlev = len(dp.levels)
+    if name == "hex32":
+        # the finest level really takes the kernels outside the tail: more than 8 192 rows (Multigrid::enable_bv_tail) and
+        # the 8-children injection csr_is_oct_injection accepts (the fused restriction / prolongation of the bv kernels)
+        L0 = dp.levels[0]
+        P = L0.P.tocsr()
+        assert L0.n_p > 8192 and P.shape == (L0.n_p, dp.levels[1].n_p) and P.shape[0] == 8 * P.shape[1]
+        assert np.array_equal(np.diff(P.indptr), np.ones(P.shape[0])) and np.all(P.data == 1.0)
+        assert np.array_equal(P.indices, np.arange(P.shape[0]) // 8)
     for lvl in range(dp.n_mc_levels):
         info = ds.vcycle_levels(lvl)
         assert len(info) == nlev - lvl

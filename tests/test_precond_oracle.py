@@ -4,8 +4,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from oracle.precond_oracle import (DarcyPrecondOracle, chebyshev, cheb2_coefficients, vcycle, GALERKIN_SCALE,
-                                   LMAX_SCHUR)
+from oracle.precond_oracle import (DarcyPrecondOracle, SamplerPrecondOracle, bottom_exact, bottom_polynomial, chebyshev,
+                                   cheb2_coefficients, sampler_schur, vcycle, GALERKIN_SCALE, LMAX_SCHUR)
 
 
 def _spd(rng, n=40):
@@ -103,3 +103,110 @@ def test_two_grid_with_exact_coarse_solve_is_the_textbook_formula(darcy_small):
     I = np.eye(n)
     E = (I - Msm @ Sd) @ (I - P @ np.linalg.solve(Sc, P.T @ Sd)) @ (I - Msm @ Sd)
     assert np.allclose(I - V @ Sd, E, rtol=0, atol=1e-11)
+
+
+def _aggregate(A):
+    """indicator prolongator of a greedy aggregation: each unaggregated row takes its unaggregated neighbours"""
+    A = A.tocsr()
+    n = A.shape[0]
+    agg = -np.ones(n, dtype=np.int64)
+    nc = 0
+    for i in range(n):
+        if agg[i] >= 0:
+            continue
+        nbrs = A.indices[A.indptr[i]:A.indptr[i + 1]]
+        agg[nbrs[agg[nbrs] < 0]] = nc
+        agg[i] = nc
+        nc += 1
+    return sp.csr_matrix((np.ones(n), (np.arange(n), agg)), shape=(n, nc))
+
+
+def _gershgorin_lmax(S):
+    return float((np.asarray(abs(S).sum(axis=1)).ravel() / S.diagonal()).max()) * 1.0001
+
+
+@pytest.fixture(scope="module")
+def hybrid_small(hex_hierarchy_small):
+    from parelagmc_amd.fe import build_hybrid_sampler_problem
+    return build_hybrid_sampler_problem(hex_hierarchy_small, corlen=0.3)
+
+
+def _setup(kind, lmax, roles_wide, roles_narrow=None, smooth_ratio=16.0, scale=1.0, last=(12, 100.0)):
+    """pmc_sampler_vcycle_level's dicts for a hand-built hierarchy"""
+    roles_narrow = roles_wide if roles_narrow is None else roles_narrow
+    return [dict(hierarchy=kind, lmax=l, role_wide=w, role_narrow=q, smooth_degree=2, smooth_ratio=smooth_ratio,
+                 galerkin_scale=scale, last_degree=last[0], last_ratio=last[1], ratio_M=0.0, degree_M=0)
+            for l, w, q in zip(lmax, roles_wide, roles_narrow)]
+
+
+def test_two_grid_with_exact_bottom_on_aggregation_is_the_textbook_formula(hybrid_small):
+    """two levels over an aggregation P, the bottom an exact solve (bottom_exact):
+    I - V H = (I - M H)(I - P H_c^-1 P^T H)(I - M H), M = p(D^-1 H) D^-1 the smoother's matrix on [lmax / 16, lmax]"""
+    H = hybrid_small.levels[1].H.tocsr()
+    P = _aggregate(H)
+    Hc = (P.T @ H @ P).tocsr()
+    lmax = _gershgorin_lmax(H)
+    levels = [(H, lmax, P, None), (Hc, _gershgorin_lmax(Hc), None, bottom_exact(Hc))]
+    n = H.shape[0]
+    V = _matrix(lambda e: vcycle(levels, e, 2, 16.0), n)
+    Hd = H.toarray()
+    Msm = _matrix(lambda e: chebyshev(H, 1.0 / H.diagonal(), e, 2, lmax, 16.0), n)
+    I = np.eye(n)
+    E = (I - Msm @ Hd) @ (I - P.toarray() @ np.linalg.solve(Hc.toarray(), P.T.toarray() @ Hd)) @ (I - Msm @ Hd)
+    assert np.allclose(I - V @ Hd, E, rtol=0, atol=1e-11)
+    # the oracle of a hybridized handle runs exactly this cycle (kind 2: S_0 = H, Galerkin below with the exported P)
+    class _Prob:
+        levels = [hybrid_small.levels[1]]
+    po = SamplerPrecondOracle(_Prob, 0, _setup(2, [lmax, levels[1][1]], [0, 2]), [P])
+    r = np.random.default_rng(5).standard_normal(n)
+    assert np.allclose(po.apply(r), V @ r, rtol=0, atol=1e-12 * np.abs(V @ r).max())
+
+
+@pytest.mark.parametrize("schur_scale", [1.0, 0.7])
+def test_kind0_schur_level_is_the_dense_block_elimination(darcy_small, hex_hierarchy_small, schur_scale):
+    """S_l of the caller's levels = the Schur complement of the block matrix [D B^T; B -alpha W] with D = diag(M) /
+    schur_scale, by dense elimination of the first block, on every level (each rediscretized, no Galerkin product)"""
+    from parelagmc_amd.fe import build_sampler_problem
+    sp_ = build_sampler_problem(hex_hierarchy_small, corlen=0.3)
+    po = SamplerPrecondOracle(sp_, 0, _setup(0, [2.0] * len(sp_.levels), [0] * len(sp_.levels)),
+                              [L.P for L in sp_.levels[:-1]], schur_scale)
+    for v, L in enumerate(sp_.levels):
+        D = np.diag(L.M.diagonal() / schur_scale)
+        Bd = L.B.toarray()
+        A = np.block([[D, Bd.T], [Bd, -sp_.alpha * np.diag(L.w_diag)]])
+        nu = L.n_u
+        elim = A[nu:, nu:] - A[nu:, :nu] @ np.linalg.solve(A[:nu, :nu], A[:nu, nu:])
+        S = sampler_schur(L, sp_.alpha, schur_scale).toarray()
+        assert np.allclose(S, -elim, rtol=0, atol=1e-13 * np.abs(elim).max())
+        assert np.allclose(po.S[v].toarray(), S, rtol=0, atol=0)
+        if v + 1 < len(sp_.levels):   # not the Galerkin product of the finer level
+            Sg = (L.P.T @ po.S[v] @ L.P).toarray()
+            assert not np.allclose(po.S[v + 1].toarray(), Sg)
+
+
+@pytest.mark.parametrize("narrow", [False, True])
+def test_vcycle_on_an_aggregation_hierarchy_is_spd_and_contracting(hybrid_small, narrow):
+    """a three-level cycle over greedy aggregations of a hybridized problem's H (kind 2): wide - smoothing down to a
+    polynomial bottom on its Gershgorin interval; narrow - ending on level 1 with an exact solve.  V is SPD and
+    spec(V H) lies in (0, 2)"""
+    H = hybrid_small.levels[0].H.tocsr()
+    P0 = _aggregate(H)
+    H1 = (P0.T @ H @ P0).tocsr()
+    P1 = _aggregate(H1)
+    H2 = (P1.T @ H1 @ P1).tocsr()
+    d2 = 1.0 / np.sqrt(H2.diagonal())
+    ev2 = np.linalg.eigvalsh((H2.toarray() * d2).T * d2)
+    lmax = [_gershgorin_lmax(H), _gershgorin_lmax(H1), _gershgorin_lmax(H2)]
+    setup = _setup(2, lmax, [0, 0, 1], [0, 2, 3], last=(8, lmax[2] / (0.999 * ev2[0])))
+    class _Prob:
+        levels = [hybrid_small.levels[0]]
+    po = SamplerPrecondOracle(_Prob, 0, setup, [P0, P1])
+    assert all(np.allclose(po.S[v].toarray(), Sv.toarray()) for v, Sv in enumerate((H, H1, H2)))
+    n = H.shape[0]
+    V = _matrix(lambda e: po.apply(e, narrow), n)
+    assert np.abs(V - V.T).max() <= 1e-12 * np.abs(V).max()
+    assert np.linalg.eigvalsh(0.5 * (V + V.T)).min() > 0
+    ev = np.linalg.eigvals(V @ H.toarray()).real
+    assert ev.min() > 0 and ev.max() < 2
+    # the polynomial bottom's interval contains the spectrum of its level
+    assert ev2[-1] <= lmax[2] and ev2[0] >= lmax[2] / setup[2]["last_ratio"]
