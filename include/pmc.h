@@ -500,14 +500,25 @@ int pmc_darcy_apply_preconditioner(pmc_darcy* d, int level, int nbatch, const do
 /* y = A(k) x, the operator of the same solve: [M(k) B^T; B 0] with the essential rows and columns eliminated (unit
  * diagonal), or H(kappa) on a hybridized handle.  Arguments as pmc_darcy_apply_preconditioner. */
 int pmc_darcy_apply_operator(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, double* y, int memspace);
-/* Setup values of level `vlevel` (0 = the first) of the Schur-block V-cycle the solves of `level` run (what a reference of
- * B(k)^-1 cannot derive from the caller's data): info[0] = rows, [1] = lmax of the diagonally scaled level operator, [2] = 1
- * when the cycle ends on this level, [3] / [4] = smoothing degree / ratio (interval [lmax / ratio, lmax]), [5] / [6] = degree /
- * ratio of the polynomial solve that ends the cycle, [7] = s of the caller's hierarchy S_{l+1}(k) = s P^T S_l(k) P (0 for an
- * internal hierarchy), [8] = ratio_M and [9] = degree of the l1-scaled Chebyshev polynomial of the M-block (lmax 1),
- * [10] = 0: the caller's hierarchy (P of the level structs), 1: an internal aggregation hierarchy, 2: the multiplier
- * hierarchy of a hybridized handle.  Returns the number of V-cycle levels through *nvlevels; vlevel out of range is an error. */
+/* Setup values of level `vlevel` (0 = the first) of the Schur-block (hybridized: multiplier) V-cycle the solves of `level`
+ * run (what a reference of B(k)^-1 cannot derive from the caller's data): info[0] = rows, [1] = lmax of the diagonally scaled
+ * level operator (1 on an internal hierarchy: there the per-realization Gershgorin bound 1.0001 max_i sum_j |S_ij| / |S_ii| is
+ * folded into D^-1), [2] = 1 when the cycle ends on this level, [3] / [4] = smoothing degree / ratio (interval
+ * [lmax / ratio, lmax]), [5] / [6] = degree / ratio of the polynomial solve that ends the cycle, [7] = s of
+ * S_{l+1}(k) = s P^T S_l(k) P (1/2 on the caller's hierarchy, 1 on an internal aggregation hierarchy, 0.5 on the multiplier
+ * hierarchy of a hybridized handle), [8] = ratio_M and [9] = degree of the l1-scaled Chebyshev polynomial of the M-block
+ * (lmax 1), [10] = 0: the caller's hierarchy (P of the level structs), 1: an internal aggregation hierarchy, 2: the
+ * multiplier hierarchy of a hybridized handle.  Returns the number of V-cycle levels through *nvlevels; vlevel out of range
+ * is an error. */
 int pmc_darcy_vcycle_level(const pmc_darcy* d, int level, int vlevel, int* nvlevels, double info[11]);
+/* The prolongator P from V-cycle level vlevel + 1 to vlevel (0 <= vlevel < nvlevels - 1) of that cycle as CSR, for every
+ * hierarchy kind (the caller's P on the caller's hierarchy).  Sizes and errors as pmc_sampler_vcycle_prolongator: call with
+ * rowptr, colind and vals NULL for *nrows, *ncols and *nnz, then with arrays of nrows + 1 / nnz / nnz entries and *nnz set to
+ * their capacity.  The rows of vlevel 0 are in the caller's numbering (P0 elements; the multipliers of a hybridized handle:
+ * interior and essential faces in face order); coarser levels are numbered by the library, consistently from one level to the
+ * next.  Reads setup only. */
+int pmc_darcy_vcycle_prolongator(const pmc_darcy* d, int level, int vlevel, int* nrows, int* ncols, int64_t* nnz,
+                                 int32_t* rowptr, int32_t* colind, double* vals);
 
 /* Bayesian observation operator (src/BayesianInverseProblem.cpp:178-186, ComputeG): Gobs is nobs x n_p(level), row i
  * = the observation functional g_obs_i (e.g. the indicator of the cells around an observation point, restricted to the

@@ -11,6 +11,11 @@ Multigrid), not from the kernels.
   (a weakly diagonally dominant M-matrix has spec(D^-1 S) in (0, 2]), pre-smoothing from zero, post-smoothing from the
   corrected iterate, and a Chebyshev polynomial of degree `coarse_degree` on [lmax / coarse_ratio, lmax] on the last level.
 
+DarcyChainPrecondOracle: B(k)^-1 of a Darcy handle on its INTERNAL hierarchy - the smoothed-aggregation chain of a
+saddle-point handle (mg_coarsening) or the multiplier aggregation of a hybridized handle - from the prolongators and setup
+values pmc_darcy_vcycle_prolongator / pmc_darcy_vcycle_level export: S_{v+1} = s P_v^T S_v P_v per realization, and on every
+level the per-realization Gershgorin bound lambda_v = 1.0001 max_i sum_j |S_v,ij| / |S_v,ii| as the smoothers' lmax.
+
 SamplerPrecondOracle: the same for the SPDE sampler's handles (csrc/sampler.hip), whose cycles may also end with an exact
 solve (the dense inverse of the bottom level, or of an inner level for narrow launches), and whose hierarchies are either the
 caller's levels, each rediscretized, or internal Galerkin hierarchies over a prolongator the library exports.
@@ -25,6 +30,16 @@ from .darcy_oracle import DarcyOracle
 
 GALERKIN_SCALE = 0.5            # S_{l+1} = 1/2 P^T S_l P on the caller's hierarchy
 LMAX_SCHUR = 2.0 * 1.0001       # Gershgorin bound of D^-1 S with a 1e-4 margin
+# pmc_sampler_vcycle_level: role of a level in a cycle; pmc_sampler_ / pmc_darcy_vcycle_level: the kinds of hierarchy
+ROLE_DESCEND, ROLE_POLY, ROLE_EXACT, ROLE_UNREACHED = 0, 1, 2, 3
+KIND_CALLER, KIND_SA, KIND_HYBRID = 0, 1, 2
+GERSH_MARGIN = 1.0001          # internal hierarchies: lmax of every level and realization = this times its Gershgorin bound
+
+
+def gershgorin_lmax(S):
+    """1.0001 max_i sum_j |S_ij| / |S_ii|: an upper bound of spec(D^-1 S) with a 1e-4 margin"""
+    S = S.tocsr()
+    return GERSH_MARGIN * float((np.asarray(abs(S).sum(axis=1)).ravel() / np.abs(S.diagonal())).max())
 
 
 def cheb2_coefficients(lmax, ratio):
@@ -104,12 +119,16 @@ class DarcyPrecondOracle:
         A = self.do.assemble(level, np.asarray(k, dtype=np.float64))[0].tocsr()
         return A[:L.n_u, :L.n_u].tocsr(), L.ess_mask.astype(bool)
 
-    def schur_levels(self, level, k):
-        """[(S_l, lmax, P_l)] from `level` down to the last level of the problem"""
+    def schur(self, level, k):
+        """S_0(k) = B diag(M(k))^-1 B^T of `level`, the essential u-dofs eliminated"""
         L = self.p.levels[level]
         M, ess = self.mass(level, k)
         Bk = (L.B @ sp.diags((~ess).astype(np.float64))).tocsr()
-        S = (Bk @ sp.diags(1.0 / M.diagonal()) @ Bk.T).tocsr()
+        return (Bk @ sp.diags(1.0 / M.diagonal()) @ Bk.T).tocsr()
+
+    def schur_levels(self, level, k):
+        """[(S_l, lmax, P_l)] from `level` down to the last level of the problem"""
+        S = self.schur(level, k)
         out = []
         for l in range(level, len(self.p.levels)):
             P = self.p.levels[l].P if l + 1 < len(self.p.levels) else None
@@ -118,18 +137,76 @@ class DarcyPrecondOracle:
                 S = (GALERKIN_SCALE * (P.T @ S @ P)).tocsr()
         return out
 
-    def apply(self, level, k, r, ratio_M, degree_M):
-        L = self.p.levels[level]
+    def mblock(self, level, k, r_u, ratio_M, degree_M):
+        """p_M(D_l1^-1 M(k)) D_l1^-1 r_u"""
         M, _ = self.mass(level, k)
         l1inv = 1.0 / np.asarray(abs(M).sum(axis=1)).ravel()
-        zu = chebyshev(M, l1inv, r[:L.n_u], degree_M, 1.0, ratio_M)
+        return chebyshev(M, l1inv, r_u, degree_M, 1.0, ratio_M)
+
+    def apply(self, level, k, r, ratio_M, degree_M):
+        L = self.p.levels[level]
+        zu = self.mblock(level, k, r[:L.n_u], ratio_M, degree_M)
         zp = vcycle(self.schur_levels(level, k), r[L.n_u:], *self.smooth)
         return np.concatenate([zu, zp])
 
 
-# pmc_sampler_vcycle_level: role of a level in a cycle, and the kinds of hierarchy
-ROLE_DESCEND, ROLE_POLY, ROLE_EXACT, ROLE_UNREACHED = 0, 1, 2, 3
-KIND_CALLER, KIND_SA, KIND_HYBRID = 0, 1, 2
+class DarcyChainPrecondOracle:
+    """B(k)^-1 of ONE Monte Carlo level of a Darcy handle whose cycle runs on an internal hierarchy, one realization at a
+    time, from the problem, the setup values of pmc_darcy_vcycle_level (`setup`: CAPI DarcySolver.vcycle_levels) and the
+    prolongators of pmc_darcy_vcycle_prolongator (`prolongators[v]`: vlevel v + 1 -> v).
+
+    - kind 1 (smoothed aggregation of a saddle-point handle): diag(p_M(D_l1^-1 M(k)) D_l1^-1, V(S(k))) with
+      S_0(k) = B diag(M(k))^-1 B^T as on the caller's hierarchy (DarcyPrecondOracle.schur) and the M-block unchanged;
+    - kind 2 (hybridized handle): V(H(kappa)) alone, S_0 = H(kappa) of `hybrid_level` (fe/darcy_hybrid.py:DarcyHybridLevel),
+      kappa = k when M(k) divides by k, else 1 / k;
+    - S_{v+1} = s P_v^T S_v P_v with the exported s; every level smooths with Jacobi-scaled Chebyshev of smooth_degree on
+      [lambda_v / smooth_ratio, lambda_v], lambda_v = gershgorin_lmax(S_v) of this realization; the last level runs the
+      polynomial of (last_degree, last_ratio) on [lambda / last_ratio, lambda]."""
+
+    def __init__(self, problem, level, setup, prolongators, hybrid_level=None):
+        self.p, self.level, self.setup, self.P = problem, level, setup, prolongators
+        self.kind = int(setup[0]["hierarchy"])
+        assert self.kind in (KIND_SA, KIND_HYBRID) and (hybrid_level is not None) == (self.kind == KIND_HYBRID)
+        assert len(prolongators) == len(setup) - 1
+        self.hl = hybrid_level
+        self.base = DarcyPrecondOracle(problem)
+
+    def operators(self, k):
+        """[S_v(k)] of every level of the cycle"""
+        k = np.asarray(k, dtype=np.float64)
+        if self.kind == KIND_HYBRID:
+            S = [self.hl.operator(k if self.p.k_divides else 1.0 / k).tocsr()]
+        else:
+            S = [self.base.schur(self.level, k)]
+        for v in range(len(self.setup) - 1):
+            S.append((self.setup[v]["galerkin_scale"] * (self.P[v].T @ S[v] @ self.P[v])).tocsr())
+        return S
+
+    def levels(self, k):
+        """[(S_v, lambda_v, P_v, bottom_v)] for vcycle"""
+        out = []
+        S = self.operators(k)
+        for v, (Sv, m) in enumerate(zip(S, self.setup)):
+            lam = gershgorin_lmax(Sv)
+            if v + 1 < len(S):
+                out.append((Sv, lam, self.P[v], None))
+            else:
+                out.append((Sv, lam, None, bottom_polynomial(Sv, lam, int(m["last_degree"]), m["last_ratio"])))
+        return out
+
+    def vcycle(self, k, r):
+        m = self.setup[0]
+        return vcycle(self.levels(k), r, int(m["smooth_degree"]), m["smooth_ratio"])
+
+    def apply(self, k, r):
+        if self.kind == KIND_HYBRID:
+            return self.vcycle(k, r)
+        L = self.p.levels[self.level]
+        m = self.setup[0]
+        zu = self.base.mblock(self.level, k, r[:L.n_u], m["ratio_M"], int(m["degree_M"]))
+        return np.concatenate([zu, self.vcycle(k, r[L.n_u:])])
+
+
 
 
 def sampler_schur(level, alpha, schur_scale):

@@ -179,6 +179,9 @@ SYMBOLS = {
     "pmc_darcy_apply_preconditioner": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
     "pmc_darcy_apply_operator": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
     "pmc_darcy_vcycle_level": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "pmc_darcy_vcycle_prolongator": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_double)]),
     "pmc_darcy_set_observations": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_csr)]),
     "pmc_darcy_num_observations": (C.c_int, [_VP, C.c_int]),
     "pmc_darcy_compute_G": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -1014,6 +1017,22 @@ class DarcySolver:
             v += 1
             if v >= nv.value:
                 return out
+
+    def vcycle_prolongator(self, level, vlevel):
+        """P from V-cycle level vlevel + 1 to vlevel of `level` (pmc_darcy_vcycle_prolongator) as a scipy CSR matrix; the
+        rows of vlevel 0 in the caller's numbering"""
+        import scipy.sparse as sp
+        nr, nc, nnz = C.c_int(0), C.c_int(0), C.c_int64(0)
+        _check(self.ctx.lib.pmc_darcy_vcycle_prolongator(self.h, level, vlevel, C.byref(nr), C.byref(nc), C.byref(nnz),
+                                                         None, None, None))
+        rp = np.empty(nr.value + 1, dtype=np.int32)
+        ci = np.empty(nnz.value, dtype=np.int32)
+        va = np.empty(nnz.value, dtype=np.float64)
+        _check(self.ctx.lib.pmc_darcy_vcycle_prolongator(self.h, level, vlevel, C.byref(nr), C.byref(nc), C.byref(nnz),
+                                                         rp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         ci.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         va.ctypes.data_as(C.POINTER(C.c_double))))
+        return sp.csr_matrix((va, ci, rp), shape=(nr.value, nc.value))
 
     def SetObservations(self, level, Gobs):
         """Gobs: scipy sparse (nobs, n_p): rows are the observation functionals g_obs_i of the level."""

@@ -762,6 +762,24 @@ int pmc_darcy_vcycle_level(const pmc_darcy* d, int level, int vlevel, int* nvlev
         d->impl.vcycle_level(level, vlevel, nvlevels, info);
     });
 }
+int pmc_darcy_vcycle_prolongator(const pmc_darcy* d, int level, int vlevel, int* nrows, int* ncols, int64_t* nnz,
+                                 int32_t* rowptr, int32_t* colind, double* vals) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr && nrows != nullptr && ncols != nullptr && nnz != nullptr,
+                    "pmc_darcy_vcycle_prolongator: NULL argument");
+        const HostCsr& P = d->impl.vcycle_prolongator(level, vlevel);
+        const int64_t cap = *nnz;
+        *nrows = P.nrows;
+        *ncols = P.ncols;
+        *nnz = (int64_t)P.colind.size();
+        if (rowptr == nullptr && colind == nullptr && vals == nullptr) return;   // size query
+        PMC_REQUIRE(rowptr != nullptr && colind != nullptr && vals != nullptr && cap >= *nnz,
+                    "pmc_darcy_vcycle_prolongator: arrays missing or smaller than nnz");
+        std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
+        std::copy(P.colind.begin(), P.colind.end(), colind);
+        std::copy(P.vals.begin(), P.vals.end(), vals);
+    });
+}
 int pmc_darcy_set_observations(pmc_darcy* d, int level, const pmc_csr* Gobs) {
     return guarded([&] {
         PMC_REQUIRE(d != nullptr, "darcy is NULL");

@@ -126,6 +126,7 @@ std::unique_ptr<DarcyChain> build_chain(const Symbolic& own, const HostCsr& K1, 
     SetupClock clk;
     clk.lap("  sa_hierarchy", (int)lvh.size());
     std::unique_ptr<DarcyChain> ch(new DarcyChain());
+    ch->galerkin_scale = galerkin_scale;
     Multigrid& mg = ch->mg;
     mg.smooth_degree = o.mg_smooth_degree;
     mg.smooth_ratio = ratio_scale * o.mg_smooth_ratio;
@@ -158,6 +159,7 @@ std::unique_ptr<DarcyChain> build_chain(const Symbolic& own, const HostCsr& K1, 
         if (j + 1 == nl) break;
         const HostCsr& P = lvh[j].P;
         PMC_REQUIRE(P.nrows == m.n, "darcy: aggregation prolongator of the wrong height");
+        m.P_host = P;
         sell_build(m.P, P, true, false, st);
         sell_build(m.Pt, csr_transpose(P), true, false, st);
         // S_{j+1} = P^T S_j P as lists over the SELL slots of S_j
@@ -1242,10 +1244,24 @@ void Darcy::vcycle_level(int level, int vlevel, int* nvlevels, double* info) con
     info[4] = g.smooth_ratio;
     info[5] = m.is_last ? m.last_degree : g.coarse_degree;
     info[6] = m.is_last ? m.last_ratio : g.coarse_ratio;
-    info[7] = own ? 0.0 : galerkin_scale;
+    info[7] = own ? (hybrid ? hyb[level]->chain->galerkin_scale : chains[level]->galerkin_scale) : galerkin_scale;
     info[8] = lv[level].ratio_M;
     info[9] = opts.cheb_degree_M > 0 ? opts.cheb_degree_M : 2;
     info[10] = hybrid ? 2.0 : own ? 1.0 : 0.0;
+}
+
+// P from vlevel + 1 to vlevel of the V-cycle of `level` (pmc_darcy_vcycle_prolongator).  The Darcy handle does not renumber
+// the rows of its internal hierarchies: vlevel 0 is in the caller's numbering (P0 elements; the multipliers of a hybridized
+// handle in the order of fe/darcy_hybrid.py).
+const HostCsr& Darcy::vcycle_prolongator(int level, int vlevel) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_vcycle_prolongator: level out of range");
+    const bool own = hybrid || (level < (int)chains.size() && chains[level]);
+    const Multigrid& g = hybrid ? hyb[level]->chain->mg : own ? chains[level]->mg : mg;
+    const int first = own ? 0 : level;
+    PMC_REQUIRE(vlevel >= 0 && first + vlevel + 1 < (int)g.L.size(), "pmc_darcy_vcycle_prolongator: vlevel out of range");
+    const HostCsr& P = own ? g.L[(size_t)vlevel].P_host : P_host[(size_t)(first + vlevel)];
+    PMC_REQUIRE(P.nrows == g.L[(size_t)(first + vlevel)].n, "pmc_darcy_vcycle_prolongator: no prolongator kept");
+    return P;
 }
 
 }  // namespace pmc

@@ -207,6 +207,7 @@ struct DarcyChainLevel {
 struct DarcyChain {
     Multigrid mg;
     std::vector<DarcyChainLevel> cl;
+    double galerkin_scale = 1.0;       // S_{j+1}(k) = galerkin_scale P_j^T S_j(k) P_j (folded into the refresh weights)
 };
 
 // Hybridized form of one Monte Carlo level (pmc_darcy_create_hybrid: the reference's "Hybridization" branch of DarcySolver,
@@ -215,7 +216,7 @@ struct DarcyChain {
 //     u = kappa_owner (U_0 - U_L lambda) + u_g,     p = P_0 - P_L lambda - z_g / kappa.
 // chain: level 0 holds H(kappa) on its fixed pattern through contribution lists over the coefficient table, the coarser
 // levels the OVER-CORRECTED Galerkin products s P^T H P of a plain-aggregation hierarchy frozen at kappa == 1 (LAB_NOTES
-// 10.15: s = 0.45 makes the iteration count nearly level-independent), all refreshed per realization.
+// 10.15: s = 0.5 makes the iteration count nearly level-independent), all refreshed per realization.
 struct DarcyHybrid {
     int n_lambda = 0;
     std::unique_ptr<DarcyChain> chain;
@@ -271,6 +272,9 @@ struct Darcy {
     void apply_operator(int level, int nbatch, const double* k, const double* x, double* y, int memspace);
     // setup values of one level of the V-cycle `level`'s solves run (pmc_darcy_vcycle_level)
     void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
+    // P from V-cycle level vlevel + 1 to vlevel of that cycle (pmc_darcy_vcycle_prolongator), rows of vlevel 0 in the caller's
+    // numbering
+    const HostCsr& vcycle_prolongator(int level, int vlevel) const;
     // caller's hierarchy: S_{l+1}(k) = galerkin_scale P^T S_l(k) P
     double galerkin_scale = 0.5;
     // the pressure prolongators P_l (n_p(l) x n_p(l + 1)) as handed over, for the level accumulators (level_fields.hip)

@@ -79,7 +79,8 @@ struct MgLevel {
     int last_degree = 12;
     double last_ratio = 100.0;
     Sell P, Pt;                  // to/from the next coarser level (absent on the last)
-    HostCsr P_host;              // internal hierarchies (sampler build_chain): P as uploaded, for pmc_sampler_vcycle_prolongator
+    HostCsr P_host;              // internal hierarchies (build_chain of the sampler and of the Darcy handle): P as uploaded,
+                                 // for pmc_sampler_vcycle_prolongator / pmc_darcy_vcycle_prolongator
     // Injection-type prolongators (one unit entry per row: P0 on nested meshes) with shared values: the coarse
     // correction never materialises on this level.  SP = S P lets the post-smoothing residual be formed from the
     // pre-restriction one, r - S (x + P xc) = res - SP xc, and `parent` adds xc[parent[i]] inside the smoother pass.

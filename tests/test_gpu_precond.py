@@ -21,8 +21,11 @@ vc_prolong8_32, vc_residual32_bv and vc_postsmooth32_bv_z, with PMC_STORAGE_FP64
 residual_restrict8.  The sampler's preconditioner (every hierarchy kind, both width regimes) is compared with a reference in
 test_gpu_sampler_precond.py.
 
-Not covered by this file: a reference of B^-1 on the Darcy internal hierarchies (mg_coarsening and the hybridized Darcy
-handle); the preconditioner inside mini_sampler_kernel (covered indirectly by
+The Darcy internal hierarchies (mg_coarsening and the hybridized Darcy handle) are compared with a reference in
+test_gpu_darcy_internal_precond.py; here hex-sa (mg_coarsening = 1) and spe10-hybrid join the width-consistency and
+column-independence tests.
+
+Not covered by this file: the preconditioner inside mini_sampler_kernel (covered indirectly by
 test_persistent_small_level_solver_equals_the_batched_kernels) and the r32_top input of the hybridized sampler's cycle, which
 only the MINRES loop provides.
 
@@ -36,7 +39,8 @@ Measured on the MI355X (the printed lines), widths 1 .. 256 on every level:
   storages, except the
   materialised M-block (cheb_degree_M = 3), where the polynomial's rounding depends on the width: 1.5e-16 (fp64) and 2.5e-16
   (fp32 storage);
-- every bitwise column-independence check held on every path, both storages.
+- every bitwise column-independence check held on every path, both storages;
+- hex-sa and spe10-hybrid (the internal hierarchies): bit for bit equal to the column alone at every width, both storages.
 """
 import dataclasses
 
@@ -79,6 +83,10 @@ def problems(hex_hierarchy):
     # 32^3 hexahedra, one MC level: a per-realization level above 8 192 rows (outside the LDS tail)
     h32 = build_hierarchy(box_mesh([4, 4, 4], [2, 2, 2], "hex"), 3)
     out["hex32"] = (h32, build_darcy_problem(h32, [0, 1, 1, 1, 1, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 1], n_mc_levels=1))
+    # the hex problem on the internal smoothed-aggregation hierarchy (EXTRA_OPTS), and SPE10-shaped cells hybridized
+    out["hex-sa"] = out["hex"]
+    hs = build_hierarchy(box_mesh([7, 27, 10], [1200.0, 2200.0, 170.0], "hex"), 1)
+    out["spe10"] = (hs, build_darcy_problem(hs, [1, 0, 1, 0, 1, 1], [0, 1, 0, 0, 0, 0], [0, 0, 0, 1, 0, 0], n_mc_levels=1))
     return out
 
 
@@ -88,15 +96,20 @@ HANDLE_IDS = ["hex-saddle", "tet-saddle-eg", "tet-saddle-noeg", "hex-hybrid", "t
 # ... and the saddle-point handle whose finest level (32^3: 32 768 rows) runs the per-realization V-cycle kernels outside the
 # LDS tail: fp32 storage vc_presmooth32_bv / vc_restrict8_32_bv / vc_prolong8_32 / vc_residual32_bv / vc_postsmooth32_bv_z,
 # fp64 storage the bv Chebyshev polynomial and residual_restrict8
-PRECOND_HANDLES = HANDLES + [("hex32", False, 0)]
-PRECOND_IDS = HANDLE_IDS + ["hex32-saddle"]
+# ... and the internal hierarchies: smoothed aggregation of the Schur block (mg_coarsening = 1, every MC level its own chain)
+# and the hybridized handle's multiplier aggregation on SPE10-shaped cells (tests/test_gpu_darcy_internal_precond.py)
+PRECOND_HANDLES = HANDLES + [("hex32", False, 0), ("hex-sa", False, 0), ("spe10", True, 0)]
+PRECOND_IDS = HANDLE_IDS + ["hex32-saddle", "hex-sa", "spe10-hybrid"]
+# solver options of a problem name beyond the storage and cheb_degree_M
+EXTRA_OPTS = {"hex-sa": dict(mg_coarsening=1)}
 
 
 def _solver(ctx, problems, name, hybrid, degM, storage="fp32"):
     from parelagmc_amd import capi
     h, dp = problems[name]
     st = capi.PMC_STORAGE_FP64 if storage == "fp64" else capi.PMC_STORAGE_FP32
-    return capi.DarcySolver(ctx, dp, capi.solver_opts(precond_storage=st, cheb_degree_M=degM), hybrid=hybrid)
+    return capi.DarcySolver(ctx, dp, capi.solver_opts(precond_storage=st, cheb_degree_M=degM, **EXTRA_OPTS.get(name, {})),
+                            hybrid=hybrid)
 
 
 def _rows(problems, name, hybrid, lvl):

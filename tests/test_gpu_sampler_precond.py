@@ -32,7 +32,7 @@ The handles (MC level 0 of each; n_mc_levels = 1):
   aggregate restriction after agg_pack_rows), level 1 row-split (S_split, SP_split) for narrow launches.
 
 Not covered here: mini_sampler_kernel (test_persistent_small_level_solver_equals_the_batched_kernels), the r32_top input of the
-hybridized cycle (only the MINRES loop provides it), the Darcy internal hierarchies.
+hybridized cycle (only the MINRES loop provides it).  The Darcy internal hierarchies: test_gpu_darcy_internal_precond.py.
 
 Tolerances: REF_TOL / WIDTH_TOL of test_gpu_precond.py.  Outside the tail the fp32 storage keeps the level's iterate and
 residuals in fp32 (the matrix values of these shared-value levels stay fp64): 1e-5 holds with more than two orders of margin.

@@ -210,3 +210,136 @@ def test_vcycle_on_an_aggregation_hierarchy_is_spd_and_contracting(hybrid_small,
     assert ev.min() > 0 and ev.max() < 2
     # the polynomial bottom's interval contains the spectrum of its level
     assert ev2[-1] <= lmax[2] and ev2[0] >= lmax[2] / setup[2]["last_ratio"]
+
+
+# ---- internal hierarchies of the Darcy handle (DarcyChainPrecondOracle) ----
+
+@pytest.fixture(scope="module")
+def darcy_hybrid_small(hex_hierarchy_small, darcy_small):
+    from parelagmc_amd.fe.darcy_hybrid import darcy_hybrid_level
+    return darcy_hybrid_level(hex_hierarchy_small.spaces[0], darcy_small.levels[0])
+
+
+def _chain_setup(kind, nlev, smooth_ratio, scale, degree=2, last=(12, 100.0)):
+    """pmc_darcy_vcycle_level's dicts of an internal hierarchy (lmax 1: the Gershgorin bound is folded into D^-1)"""
+    return [dict(hierarchy=kind, lmax=1.0, bottom=float(v == nlev - 1), smooth_degree=degree, smooth_ratio=smooth_ratio,
+                 last_degree=last[0], last_ratio=last[1], galerkin_scale=scale, ratio_M=4.0, degree_M=2)
+            for v in range(nlev)]
+
+
+def _kappa(dp, k):
+    return k if dp.k_divides else 1.0 / k
+
+
+@pytest.mark.parametrize("degree", [1, 2, 3, 5])
+@pytest.mark.parametrize("ratio", [8.0, 16.0])
+def test_gershgorin_folded_chebyshev_is_the_scaled_interval(darcy_small, darcy_hybrid_small, degree, ratio):
+    """what an internal hierarchy runs - D^-1 / lambda as the diagonal, lmax 1 - is chebyshev(S, 1 / diag S, r, d, lambda,
+    ratio), the form the oracle uses; and lambda bounds spec(D^-1 S) on the Schur level and on H(kappa)"""
+    from oracle.precond_oracle import gershgorin_lmax
+    rng = np.random.default_rng(degree)
+    k = np.exp(1.5 * rng.standard_normal(darcy_small.levels[0].n_p))
+    for S in (DarcyPrecondOracle(darcy_small).schur(0, k), darcy_hybrid_small.operator(_kappa(darcy_small, k))):
+        lam = gershgorin_lmax(S)
+        d = S.diagonal()
+        dinv = 1.0 / d
+        ref = (np.asarray(abs(S).sum(axis=1)).ravel() / d).max() * 1.0001
+        assert lam == pytest.approx(ref, rel=1e-15)
+        r = rng.standard_normal(S.shape[0])
+        a = chebyshev(S, dinv / lam, r, degree, 1.0, ratio)
+        b = chebyshev(S, dinv, r, degree, lam, ratio)
+        assert np.linalg.norm(a - b) <= 1e-13 * np.linalg.norm(b)
+        if degree == 2:   # ... and the one-pass closed form the element-grouped finest level runs
+            c0, c1 = cheb2_coefficients(1.0, ratio)
+            dl = dinv / lam
+            assert np.linalg.norm(dl * (c0 * r - c1 * (S @ (dl * r))) - b) <= 1e-13 * np.linalg.norm(b)
+
+
+def test_gershgorin_bound_holds_on_every_level_of_an_internal_hierarchy(darcy_small, darcy_hybrid_small):
+    """lambda_v >= lambda_max(D^-1 S_v) (eigsh) on every level of both internal hierarchy kinds, for k == 1 and a
+    high-contrast k"""
+    from scipy.sparse.linalg import eigsh
+    from oracle.precond_oracle import DarcyChainPrecondOracle, KIND_HYBRID, KIND_SA, gershgorin_lmax
+    n_p = darcy_small.levels[0].n_p
+    H1 = darcy_hybrid_small.operator(np.ones(n_p))
+    Pa = _aggregate(H1)
+    Pb = _aggregate((Pa.T @ H1 @ Pa).tocsr())
+    S1 = DarcyPrecondOracle(darcy_small).schur(0, np.ones(n_p))
+    Ps = _aggregate(S1)
+    Ps = (sp.eye(n_p) - 0.5 * sp.diags(1.0 / S1.diagonal()) @ S1) @ Ps          # a smoothed (non-injection) prolongator
+    cases = [(KIND_SA, [Ps.tocsr()], 1.0, None), (KIND_HYBRID, [Pa, Pb], 0.5, darcy_hybrid_small)]
+    rng = np.random.default_rng(11)
+    for kind, P, s, hl in cases:
+        po = DarcyChainPrecondOracle(darcy_small, 0, _chain_setup(kind, len(P) + 1, 8.0, s), P, hl)
+        for k in (np.ones(n_p), np.where(rng.random(n_p) < 0.3, 1e3, 1.0)):
+            for v, (Sv, lam, _, _) in enumerate(po.levels(k)):
+                d = 1.0 / np.sqrt(Sv.diagonal())
+                A = (sp.diags(d) @ Sv @ sp.diags(d)).tocsr()
+                hi = eigsh(A, k=1, which="LA", return_eigenvectors=False, tol=1e-10)[0]
+                assert lam == gershgorin_lmax(Sv) and hi <= lam, (kind, v, hi, lam)
+                if v > 0:
+                    Sg = s * (P[v - 1].T @ po.operators(k)[v - 1] @ P[v - 1])
+                    assert abs(Sv - Sg).max() <= 1e-14 * abs(Sg).max()
+
+
+def test_element_grouped_cycle_is_the_oracle_vcycle(darcy_small, darcy_hybrid_small):
+    """the finest level of a hybridized handle with degree-2 smoothing written out the way Darcy::hybrid_ops sequences it -
+    x = p2(H) r;  x += P V_1(P^T (r - H x));  x += p2(H)(r - H x),  p2 the one-pass polynomial with (c0, c1) of
+    cheb2_coefficients(1, 2 mg_smooth_ratio) on D^-1 / lambda_0 - equals the oracle's V(1,1) cycle to rounding"""
+    from oracle.precond_oracle import DarcyChainPrecondOracle, KIND_HYBRID
+    n_p = darcy_small.levels[0].n_p
+    H1 = darcy_hybrid_small.operator(np.ones(n_p))
+    P0 = _aggregate(H1)
+    P1 = _aggregate((P0.T @ H1 @ P0).tocsr())
+    ratio = 2 * 8.0
+    po = DarcyChainPrecondOracle(darcy_small, 0, _chain_setup(KIND_HYBRID, 3, ratio, 0.5), [P0, P1], darcy_hybrid_small)
+    rng = np.random.default_rng(12)
+    c0, c1 = cheb2_coefficients(1.0, ratio)
+    for k in (np.ones(n_p), np.exp(2.0 * rng.standard_normal(n_p))):
+        levels = po.levels(k)
+        H, lam0 = levels[0][0], levels[0][1]
+        dl = 1.0 / (lam0 * H.diagonal())
+        p2 = lambda v: dl * (c0 * v - c1 * (H @ (dl * v)))
+        r = rng.standard_normal(H.shape[0])
+        x = p2(r)
+        x = x + P0 @ vcycle(levels, P0.T @ (r - H @ x), 2, ratio, l=1)
+        x = x + p2(r - H @ x)
+        ref = po.apply(k, r)
+        assert np.linalg.norm(x - ref) <= 1e-13 * np.linalg.norm(ref)
+
+
+def test_hybrid_chain_with_over_corrected_coarse_levels_is_spd_and_contracting(darcy_small, darcy_hybrid_small):
+    """a three-level multiplier hierarchy as the hybridized handle builds it - indicator aggregations, S_{v+1} = 0.5 P^T S_v P,
+    smoothing on [lambda_v / 16, lambda_v] - is SPD and spec(V H) lies in (0, 2) for a log-normal kappa"""
+    from oracle.precond_oracle import DarcyChainPrecondOracle, KIND_HYBRID
+    n_p = darcy_small.levels[0].n_p
+    H1 = darcy_hybrid_small.operator(np.ones(n_p))
+    P0 = _aggregate(H1)
+    P1 = _aggregate((P0.T @ H1 @ P0).tocsr())
+    for P in (P0, P1):
+        assert np.array_equal(np.diff(P.indptr), np.ones(P.shape[0])) and np.all(P.data == 1.0)
+    po = DarcyChainPrecondOracle(darcy_small, 0, _chain_setup(KIND_HYBRID, 3, 16.0, 0.5), [P0, P1], darcy_hybrid_small)
+    k = np.exp(np.random.default_rng(13).standard_normal(n_p))
+    H = po.operators(k)[0].toarray()
+    V = _matrix(lambda e: po.apply(k, e), H.shape[0])
+    assert np.abs(V - V.T).max() <= 1e-12 * np.abs(V).max()
+    assert np.linalg.eigvalsh(0.5 * (V + V.T)).min() > 0
+    ev = np.linalg.eigvals(V @ H).real
+    assert ev.min() > 0 and ev.max() < 2
+
+
+def test_chain_oracle_of_a_saddle_point_handle_keeps_the_m_block(darcy_small):
+    """kind 1: the u-rows are DarcyPrecondOracle's M-block polynomial, the p-rows the cycle on S_0(k) of the same level"""
+    from oracle.precond_oracle import DarcyChainPrecondOracle, KIND_SA
+    L = darcy_small.levels[0]
+    S1 = DarcyPrecondOracle(darcy_small).schur(0, np.ones(L.n_p))
+    P = _aggregate(S1)
+    po = DarcyChainPrecondOracle(darcy_small, 0, _chain_setup(KIND_SA, 2, 8.0, 1.0), [P])
+    rng = np.random.default_rng(14)
+    k = np.exp(rng.standard_normal(L.n_p))
+    r = rng.standard_normal(L.n_u + L.n_p)
+    z = po.apply(k, r)
+    base = DarcyPrecondOracle(darcy_small)
+    assert np.array_equal(z[:L.n_u], base.mblock(0, k, r[:L.n_u], 4.0, 2))
+    assert np.array_equal(z[L.n_u:], po.vcycle(k, r[L.n_u:]))
+    assert abs(po.operators(k)[0] - base.schur(0, k)).max() == 0.0
