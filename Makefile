@@ -90,3 +90,10 @@ $(ABIBIN)/pressure_stats_smoke: tests/c/pressure_stats_smoke.c tests/c/prob_io.h
 	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/pressure_stats_smoke.c -Lparelagmc_amd/lib -lpmc_host -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-pressure-stats: $(ABIBIN)/pressure_stats_smoke
 .PHONY: test-pressure-stats
+
+# the posterior field estimates of the ratio managers from C (tests/test_gpu_posterior_fields.py builds and runs it)
+$(ABIBIN)/posterior_fields_smoke: tests/c/posterior_fields_smoke.c tests/c/prob_io.h include/pmc.h include/pmc_host.h | $(HOSTLIB)
+	@mkdir -p $(ABIBIN)
+	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/posterior_fields_smoke.c -Lparelagmc_amd/lib -lpmc_host -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-posterior-fields: $(ABIBIN)/posterior_fields_smoke
+.PHONY: test-posterior-fields

@@ -483,6 +483,14 @@ int pmc_level_fields_reset(pmc_level_fields* f);
  * nbatch x n_p(level + 1) (NULL iff !coupled); realizations in ascending id */
 int pmc_level_fields_accumulate(pmc_level_fields* f, int nbatch, const double* p_fine, const double* p_coarse,
                                 int memspace);
+/* The weighted form (the ratio managers' posterior field estimates): per realization b the terms
+ * a = w_fine[b] x_fine, c = w_coarse[b] x_coarse[parent] and the sums of a - c, (a - c)^2 and a x_fine - c x_coarse[parent]
+ * in the same six pairs, products rounded before they are summed.  w_fine, w_coarse: HOST arrays of nbatch, read before
+ * the call returns (w_coarse NULL iff !coupled).  With every weight 1.0 the sums equal pmc_level_fields_accumulate's bit for
+ * bit; they are bit-identical however the realizations are split into calls.  The same refusals as
+ * pmc_level_fields_accumulate, and NULL weights where they are required. */
+int pmc_level_fields_accumulate_weighted(pmc_level_fields* f, int nbatch, const double* x_fine, const double* w_fine,
+                                         const double* x_coarse, const double* w_coarse, int memspace);
 /* the raw accumulators, 6 x n_p(level) doubles [sum d | comp | sum d^2 | comp | sum p^2 - p_c^2 | comp] (sum + comp is the
  * compensated sum), and the number of realizations accumulated */
 int pmc_level_fields_read_sums(const pmc_level_fields* f, double* sums, int64_t* count, int memspace);

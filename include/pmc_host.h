@@ -167,6 +167,29 @@ int pmc_ratio_set_splitting(pmc_ratio* m, int on);
 int pmc_ratio_run(pmc_ratio* m);
 int pmc_ratio_init_run(pmc_ratio* m, const int32_t* nsamples);
 int pmc_ratio_result_get(pmc_ratio* m, pmc_ratio_result* out);
+/* Posterior field estimates.  Opt-in, on managers from pmc_ratio_create only: from now on every
+ * level also accumulates on the device (pmc_level_fields_accumulate_weighted, on ctx's stream - the one the sampler's Eval
+ * writes on) the sums of d_l = w k_l - w_c k_{l+1}[parent], d_l^2 and w k_l^2 - w_c k_{l+1}[parent]^2, where k is the R-draw's
+ * prior field (Eval's output on the Darcy level: n_p(l) entries) and w, w_c the likelihoods of its evaluations on l and l+1
+ * (plain), or those divided by the Z-draw's likelihoods (splitting); w_c = 0 on the coarsest level.  parent() comes from the
+ * Darcy handle's pressure prolongator, which must be a 0/1 injection.  The scalar sums are unchanged.  Call before the first
+ * InitRun or after Reset; w0: the level-0 P0 mass, n_p(0) entries > 0 in `memspace`.  Refused (PMC_ERR_INVALID): a callbacks
+ * manager, a manager that holds samples, a bad w0, a prior field that is not on the Darcy mesh, a prolongator that is not an
+ * injection. */
+int pmc_ratio_enable_field_stats(pmc_ratio* m, const double* w0, int memspace);
+/* Level-0 maps, n_p(0) entries each in `memspace` (each may be NULL), with N_l = level_nsamples[l], I_l the injection along
+ * the parent chain to level 0, Zhat = Z_estimate, V_Z = estimator_variance_Z and s = Zhat (plain) or 1 (splitting):
+ *   mean               = sum_l I_l mean_l(d_l) / s                           the posterior mean of k
+ *   second_moment      = sum_l I_l mean_l(w k^2 - w_c k_c^2) / s             about zero: Var_post k = second_moment - mean^2
+ *   estimator_variance = (V_R + mean^2 V_Z) / Zhat^2 (plain), V_R (splitting), V_R = sum_l I_l var_l(d_l) / N_l
+ * and per level (nlevels entries in `memspace`, may be NULL) l2_mean_corr = ||mean_l(d_l) / s||_L2 and int_var_corr =
+ * int var_l(d_l) / (N_l s^2), with the weights (P chain)^T w0.  Outputs not requested are not computed.  The raw sums are
+ * reduced once through the farm's reduction: a collective every rank calls.  Refused (PMC_ERR_INVALID): not enabled, a
+ * level whose accumulated count differs from level_nsamples, a level without realizations, estimator_variance or
+ * int_var_corr with some N_l < 2, sums accumulated in a mode other than the current one (pmc_ratio_set_splitting while
+ * samples were held), a plain-mode read with Zhat 0 or not finite. */
+int pmc_ratio_field_stats(pmc_ratio* m, double* mean, double* second_moment, double* estimator_variance,
+                          double* l2_mean_corr, double* int_var_corr, int memspace);
 
 /* ---- P0 x P0 mortar matrix between two NON-MATCHING meshes:  G[i,j] = | A_i  n  B_j |  (setup side, host only).
  * Replaces ParMortarAssembler::Assemble (src/transfer/ParMortarAssembler.cpp:1127-1144) as used for Gt by

@@ -173,6 +173,7 @@ SYMBOLS = {
     "pmc_level_fields_destroy": (None, [_VP]),
     "pmc_level_fields_reset": (C.c_int, [_VP]),
     "pmc_level_fields_accumulate": (C.c_int, [_VP, C.c_int, _DP, _DP, C.c_int]),
+    "pmc_level_fields_accumulate_weighted": (C.c_int, [_VP, C.c_int, _DP, _DP, _DP, _DP, C.c_int]),
     "pmc_level_fields_read_sums": (C.c_int, [_VP, _DP, C.POINTER(C.c_int64), C.c_int]),
     "pmc_level_fields_size": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pmc_level_fields_parents": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
@@ -842,6 +843,22 @@ class LevelFields:
             raise PmcError(-1, "pressure blocks do not match the level sizes")
         _check(self.ctx.lib.pmc_level_fields_accumulate(self.h, pf.shape[0], pf.ctypes.data,
                                                         None if pc is None else pc.ctypes.data, PMC_MEM_HOST))
+        return self
+
+    def accumulate_weighted(self, x_fine, w_fine, x_coarse=None, w_coarse=None):
+        """add (nbatch, n) fields weighted per realization: d = w_fine[b] x_fine - w_coarse[b] x_coarse[parent], d^2 and
+        w_fine[b] x_fine^2 - w_coarse[b] x_coarse[parent]^2 (pmc_level_fields_accumulate_weighted)"""
+        xf = _f64(np.atleast_2d(x_fine))
+        xc = None if x_coarse is None else _f64(np.atleast_2d(x_coarse))
+        wf = _f64(np.atleast_1d(w_fine))
+        wc = None if w_coarse is None else _f64(np.atleast_1d(w_coarse))
+        nb = xf.shape[0]
+        if xf.shape[1] != self.n or wf.shape != (nb,) or (xc is not None and (xc.shape != (nb, self.nc))) or \
+                (wc is not None and wc.shape != (nb,)):
+            raise PmcError(-1, "fields / weights do not match the level sizes")
+        addr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        _check(self.ctx.lib.pmc_level_fields_accumulate_weighted(self.h, nb, addr(xf), addr(wf), addr(xc), addr(wc),
+                                                                 PMC_MEM_HOST))
         return self
 
     def reset(self):

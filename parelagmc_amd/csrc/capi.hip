@@ -720,6 +720,13 @@ int pmc_level_fields_accumulate(pmc_level_fields* f, int nbatch, const double* p
         f->impl.accumulate(nbatch, p_fine, p_coarse, memspace);
     });
 }
+int pmc_level_fields_accumulate_weighted(pmc_level_fields* f, int nbatch, const double* x_fine, const double* w_fine,
+                                         const double* x_coarse, const double* w_coarse, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(f != nullptr, "level fields is NULL");
+        f->impl.accumulate_weighted(nbatch, x_fine, w_fine, x_coarse, w_coarse, memspace);
+    });
+}
 int pmc_level_fields_read_sums(const pmc_level_fields* f, double* sums, int64_t* count, int memspace) {
     return guarded([&] {
         PMC_REQUIRE(f != nullptr, "level fields is NULL");

@@ -148,10 +148,14 @@ struct LevelFields {
     LevelFields(Ctx& c, const Darcy& d, int level, bool coupled);
     void reset();
     void accumulate(int nbatch, const double* p_fine, const double* p_coarse, int memspace);
+    // per-column weights (host arrays of nbatch): w_fine[b] p_fine - w_coarse[b] p_coarse[parent]
+    void accumulate_weighted(int nbatch, const double* p_fine, const double* w_fine, const double* p_coarse,
+                             const double* w_coarse, int memspace);
     void read_sums(double* sums, int64_t* count, int memspace);
 
   private:
     void accumulate_device(int nbatch, const double* pf, const double* pc);
+    void accumulate_weighted_device(int nbatch, const double* pf, const double* wf, const double* pc, const double* wc);
 };
 
 // kl.hip: s[b n + i] = sum_k phi[k n + i] xi[b n_xi + k] (exp() if lognormal, the Gaussian value to emb when non-NULL) for

@@ -980,10 +980,12 @@ ML_BayesRatio_Manager::ML_BayesRatio_Manager(pmc_ctx* ctx, int memspace, int nle
       init_nsamples_(p.init_nsamples),
       batch_(p.batch),
       max_rounds_(p.max_rounds),
+      ctx_(ctx),
       zxi(ctx, memspace),
       xi(ctx, memspace),
       zparam(ctx, memspace),
-      sparam(ctx, memspace) {
+      sparam(ctx, memspace),
+      sparam_c(ctx, memspace) {
     if (nlevels < 1) throw std::invalid_argument("ML_BayesRatio_Manager: nlevels < 1");
     if (batch_ < 1 || batch_ > 256) throw std::invalid_argument("ML_BayesRatio_Manager: batch must be in 1..256");
     if (!(ratio > 0.0 && ratio < 1.0)) throw std::invalid_argument("ML_BayesRatio_Manager: ratio must be in (0,1)");
@@ -1000,7 +1002,11 @@ void ML_BayesRatio_Manager::SetFarm(int nranks, int rank, std::function<void(dou
     reduce_ = std::move(reduce);
 }
 
+ML_BayesRatio_Manager::~ML_BayesRatio_Manager() { release_field_stats(); }
+
 void ML_BayesRatio_Manager::Reset() {
+    for (pmc_level_fields* f : ffields_) check(pmc_level_fields_reset(f), "ML_BayesRatio_Manager::Reset (field statistics)");
+    fields_mode_ = -1;
     auto z = [&](std::vector<double>& v) { v.assign(nlevels, 0.0); };
     sums.assign((size_t)nlevels * NVAR, 0.0);
     z(eR); z(varR); z(eYR); z(varYR); z(eABS_YR); z(eZ); z(varZ); z(eYZ); z(varYZ); z(eABS_YZ); z(eC); z(cost);
@@ -1024,6 +1030,157 @@ int ML_BayesRatio_Manager::level_batch(int ilevel, int nsamples) const {
     return std::max(1, std::min(b, share));
 }
 
+void ML_BayesRatio_Manager::release_field_stats() {
+    for (pmc_level_fields* f : ffields_) pmc_level_fields_destroy(f);
+    ffields_.clear();
+    fparents_.clear();
+    fweights_.clear();
+    fields_mode_ = -1;
+}
+
+void ML_BayesRatio_Manager::EnableFieldStatistics(const Vector& w0) {
+    pmc_darcy* d = problem.DarcyHandle();
+    if (!d || !ctx_)
+        throw std::invalid_argument("EnableFieldStatistics: device-handle managers only (pmc_ratio_create); the fields of a "
+                                    "callbacks manager never reach the device");
+    for (int l = 0; l < nlevels; ++l)
+        if (level_nsamples[l] != 0)
+            throw std::invalid_argument("EnableFieldStatistics: the manager already holds samples - enable before the first "
+                                        "InitRun or after Reset");
+    const int n0 = pmc_darcy_num_pressure_dofs(d, 0);
+    if (n0 < 1 || w0.Size() != n0 || w0.Batch() != 1 || !w0.GetData())
+        throw std::invalid_argument("EnableFieldStatistics: w0 must hold the n_p(0) = " + std::to_string(n0) +
+                                    " level-0 P0 masses");
+    if (w0.MemSpace() != PMC_MEM_HOST && w0.MemSpace() != PMC_MEM_DEVICE)
+        throw std::invalid_argument("EnableFieldStatistics: bad memspace");
+    std::vector<double> w(w0.GetData(), w0.GetData() + (w0.MemSpace() == PMC_MEM_HOST ? n0 : 0));
+    if (w0.MemSpace() == PMC_MEM_DEVICE) {
+        w.resize(n0);
+        check(pmc_memcpy_d2h(ctx_, w.data(), w0.GetData(), sizeof(double) * n0), "EnableFieldStatistics");
+    }
+    for (int i = 0; i < n0; ++i)
+        if (!(std::isfinite(w[i]) && w[i] > 0.0))
+            throw std::invalid_argument("EnableFieldStatistics: w0[" + std::to_string(i) + "] is not a positive mass");
+    for (int l = 0; l < nlevels; ++l) {
+        const int np = pmc_darcy_num_pressure_dofs(d, l), ns = problem.PriorFieldSize(l);
+        if (ns != np)
+            throw std::invalid_argument("EnableFieldStatistics: the prior's field on level " + std::to_string(l) + " has " +
+                                        std::to_string(ns) + " entries, the Darcy level n_p = " + std::to_string(np) +
+                                        " (the maps need k on the Darcy mesh)");
+    }
+    release_field_stats();
+    try {
+        fparents_.assign(nlevels, {});
+        fweights_.assign(1, std::move(w));
+        for (int l = 0; l < nlevels; ++l) {
+            const bool coupled = l + 1 < nlevels;
+            pmc_level_fields* f = nullptr;
+            check_arg(pmc_level_fields_create(ctx_, d, l, coupled ? 1 : 0, &f), "EnableFieldStatistics");
+            ffields_.push_back(f);
+            int nf = 0, nc = 0;
+            check(pmc_level_fields_size(f, &nf, &nc), "EnableFieldStatistics");
+            if (nf != (int)fweights_[l].size())
+                throw std::invalid_argument("EnableFieldStatistics: level sizes do not chain");
+            if (!coupled) break;
+            fparents_[l].resize(nf);
+            check(pmc_level_fields_parents(f, fparents_[l].data()), "EnableFieldStatistics");
+            std::vector<double> wc(nc, 0.0);   // w_{l+1} = P_l^T w_l
+            for (int i = 0; i < nf; ++i) wc[fparents_[l][i]] += fweights_[l][i];
+            fweights_.push_back(std::move(wc));
+        }
+    } catch (...) {
+        release_field_stats();
+        throw;
+    }
+}
+
+void ML_BayesRatio_Manager::FieldStatistics(Vector* mean, Vector* second_moment, Vector* estimator_variance,
+                                            double* l2_mean_corr, double* int_var_corr) {
+    if (ffields_.empty())
+        throw std::invalid_argument("FieldStatistics: field statistics are not enabled (EnableFieldStatistics)");
+    const int n0 = (int)fweights_[0].size();
+    for (Vector* v : {mean, second_moment, estimator_variance})
+        if (v && (v->Size() != n0 || v->Batch() != 1 || !v->GetData() ||
+                  (v->MemSpace() != PMC_MEM_HOST && v->MemSpace() != PMC_MEM_DEVICE)))
+            throw std::invalid_argument("FieldStatistics: a map must hold the n_p(0) = " + std::to_string(n0) + " entries");
+    // the raw pairs and the count of every level in one buffer: one reduction across the farm's ranks
+    std::vector<size_t> off(nlevels + 1, 0);
+    for (int l = 0; l < nlevels; ++l) off[l + 1] = off[l] + 6 * fweights_[l].size() + 1;
+    std::vector<double> buf(off[nlevels]);
+    for (int l = 0; l < nlevels; ++l) {
+        int64_t cnt = 0;
+        check(pmc_level_fields_read_sums(ffields_[l], buf.data() + off[l], &cnt, PMC_MEM_HOST), "FieldStatistics");
+        buf[off[l + 1] - 1] = (double)cnt;
+    }
+    if (nranks_ > 1) reduce_(buf.data(), (int)buf.size());
+    const bool need_var = estimator_variance || int_var_corr;
+    for (int l = 0; l < nlevels; ++l) {
+        const double N = buf[off[l + 1] - 1];
+        if (N != (double)level_nsamples[l])
+            throw std::invalid_argument("FieldStatistics: level " + std::to_string(l) + " accumulated " +
+                                        std::to_string((int64_t)N) + " fields, the manager counts " +
+                                        std::to_string(level_nsamples[l]) + " realizations (Reset and run again)");
+        if (N < 1.0) throw std::invalid_argument("FieldStatistics: level " + std::to_string(l) + " has no realizations");
+        if (need_var && N < 2.0)
+            throw std::invalid_argument("FieldStatistics: estimator_variance / int_var_corr need N_l >= 2 on level " +
+                                        std::to_string(l));
+    }
+    if (fields_mode_ != (splitting ? 1 : 0))
+        throw std::invalid_argument(std::string("FieldStatistics: the sums were accumulated ") +
+                                    (fields_mode_ == 2 ? "in both modes" : fields_mode_ == 1 ? "in splitting mode" : "in plain mode") +
+                                    " but the manager is now in " + (splitting ? "splitting" : "plain") +
+                                    " mode (pmc_ratio_set_splitting while samples were held; Reset and run again)");
+    const bool plain = !splitting;
+    double zhat = 0.0;
+    for (double x : eYZ) zhat += x;   // Z_estimate
+    if (plain && !(std::isfinite(zhat) && zhat != 0.0))
+        throw std::invalid_argument("FieldStatistics: the evidence estimate Z_estimate is 0 or not finite - the posterior "
+                                    "maps of the plain ratio manager divide by it");
+    const double scale = plain ? zhat : 1.0;
+    std::vector<double> m0(n0, 0.0), s0(n0, 0.0), v0(n0, 0.0);
+    std::vector<int32_t> map(n0);   // level-0 element -> its ancestor on level l
+    for (int i = 0; i < n0; ++i) map[i] = i;
+    for (int l = 0; l < nlevels; ++l) {
+        const int n = (int)fweights_[l].size();
+        const double* a = buf.data() + off[l];
+        const double N = buf[off[l + 1] - 1];
+        std::vector<double> md(n), e2(n), var(n, 0.0);
+        double l2 = 0.0, iv = 0.0;
+        for (int j = 0; j < n; ++j) {
+            md[j] = (a[j] + a[n + j]) / N;
+            e2[j] = (a[4 * n + j] + a[5 * n + j]) / N;
+            if (need_var) var[j] = ((a[2 * n + j] + a[3 * n + j]) / N - md[j] * md[j]) * (N / (N - 1.0));
+            const double mc = md[j] / scale;
+            l2 += fweights_[l][j] * mc * mc;
+            iv += fweights_[l][j] * var[j];
+        }
+        if (l2_mean_corr) l2_mean_corr[l] = std::sqrt(l2);
+        if (int_var_corr) int_var_corr[l] = iv / N / (scale * scale);
+        for (int i = 0; i < n0; ++i) {
+            const int j = map[i];
+            m0[i] += md[j];
+            s0[i] += e2[j];
+            v0[i] += var[j] / N;
+        }
+        if (l + 1 < nlevels)
+            for (int i = 0; i < n0; ++i) map[i] = fparents_[l][map[i]];
+    }
+    for (int i = 0; i < n0; ++i) {
+        m0[i] /= scale;
+        s0[i] /= scale;
+        // delta method for A / Zhat with independent R and Z draws: (V_R + (A / Zhat)^2 V_Z) / Zhat^2
+        if (plain) v0[i] = (v0[i] + m0[i] * m0[i] * ml_estimator_variance_Z) / (zhat * zhat);
+    }
+    auto put = [&](Vector* v, const std::vector<double>& x) {
+        if (!v) return;
+        if (v->MemSpace() == PMC_MEM_HOST) std::copy(x.begin(), x.end(), v->GetData());
+        else check(pmc_memcpy_h2d(ctx_, v->GetData(), x.data(), sizeof(double) * n0), "FieldStatistics");
+    };
+    put(mean, m0);
+    put(second_moment, s0);
+    put(estimator_variance, v0);
+}
+
 void ML_BayesRatio_Manager::run_level(int ilevel, int nsamples) {
     const uint64_t base = (uint64_t)level_nsamples[ilevel];
     double* psum = pending_.data() + (size_t)ilevel * NVAR;
@@ -1031,6 +1188,14 @@ void ML_BayesRatio_Manager::run_level(int ilevel, int nsamples) {
     std::vector<double> z(lb), r(lb), zc(lb), rc(lb), c(lb), ctot(lb), tmp(lb);
     const int nblocks = (nsamples + lb - 1) / lb;
     const bool coarsest = (ilevel == nlevels - 1);
+    // field statistics: the R-draws' likelihoods (lr, lrc) are kept, the coarse field goes to sparam_c so that the fine one
+    // survives, and one weighted accumulate per block follows both evaluations on ctx_'s stream
+    const bool fs = !ffields_.empty();
+    std::vector<double> lr(fs ? lb : 0), lrc(fs ? lb : 0), wf(fs ? lb : 0), wc(fs ? lb : 0);
+    if (fs) {
+        const int mode = splitting ? 1 : 0;
+        fields_mode_ = fields_mode_ < 0 || fields_mode_ == mode ? mode : 2;
+    }
     const double t0 = now_s();
     for (int blk = rank_; blk < nblocks; blk += nranks_) {
         const int first = blk * lb;
@@ -1047,15 +1212,28 @@ void ML_BayesRatio_Manager::run_level(int ilevel, int nsamples) {
         for (int b = 0; b < m; ++b) ctot[b] += c[b];
         problem.SamplePrior(ilevel, xi, id0, m);
         problem.EvalPrior(ilevel, xi, sparam);
-        problem.ComputeLikelihoodAndR(ilevel, sparam, tmp.data(), r.data(), c.data());
+        problem.ComputeLikelihoodAndR(ilevel, sparam, fs ? lr.data() : tmp.data(), r.data(), c.data());
         for (int b = 0; b < m; ++b) ctot[b] += c[b];
         if (!coarsest) {
             problem.EvalPrior(ilevel + 1, zxi, zparam);
             problem.ComputeLikelihoodAndR(ilevel + 1, zparam, zc.data(), tmp.data(), c.data());
             for (int b = 0; b < m; ++b) ctot[b] += c[b];
-            problem.EvalPrior(ilevel + 1, xi, sparam);
-            problem.ComputeLikelihoodAndR(ilevel + 1, sparam, tmp.data(), rc.data(), c.data());
+            Vector& sc = fs ? sparam_c : sparam;
+            problem.EvalPrior(ilevel + 1, xi, sc);
+            problem.ComputeLikelihoodAndR(ilevel + 1, sc, fs ? lrc.data() : tmp.data(), rc.data(), c.data());
             for (int b = 0; b < m; ++b) ctot[b] += c[b];
+        }
+        if (fs) {
+            // w = L (plain) or L / Z (splitting, the field counterpart of q = r / z below); the weights are consumed at
+            // launch, and the next block's Eval into sparam / sparam_c queues behind the accumulate on the same stream
+            for (int b = 0; b < m; ++b) {
+                wf[b] = splitting ? lr[b] / z[b] : lr[b];
+                if (!coarsest) wc[b] = splitting ? lrc[b] / zc[b] : lrc[b];
+            }
+            check(pmc_level_fields_accumulate_weighted(ffields_[ilevel], m, sparam.GetData(), wf.data(),
+                                                       coarsest ? nullptr : sparam_c.GetData(),
+                                                       coarsest ? nullptr : wc.data(), sparam.MemSpace()),
+                  "ML_BayesRatio_Manager: field statistics");
         }
         for (int b = 0; b < m; ++b) {
             const double y_r = coarsest ? r[b] : r[b] - rc[b];
@@ -1218,6 +1396,8 @@ class DeviceBayesRatioProblem : public BayesRatioProblem {
     int PreferredBatch(int level) const override {
         return std::min(sampler_.PreferredBatch(level), pmc_darcy_batch_width(solver_, level));
     }
+    pmc_darcy* DarcyHandle() const override { return solver_; }
+    int PriorFieldSize(int level) const override { return sampler_.SampleSize(level); }
 
   private:
     PDESampler sampler_;
@@ -1628,6 +1808,43 @@ int pmc_ratio_result_get(pmc_ratio* m, pmc_ratio_result* r) {
         r->sums = g.sums.data();
         r->nsamples = g.level_nsamples.data();
         r->nsamples_missing = g.level_nsamples_missing.data();
+    });
+}
+
+int pmc_ratio_enable_field_stats(pmc_ratio* m, const double* w0, int memspace) {
+    return hguard([&] {
+        if (!m || !w0) throw std::invalid_argument("pmc_ratio_enable_field_stats: NULL argument");
+        if (!m->ctx || !m->problem->DarcyHandle())
+            throw std::invalid_argument("pmc_ratio_enable_field_stats: device-handle managers only (pmc_ratio_create); "
+                                        "the fields of a callbacks manager never reach the device");
+        if (memspace != PMC_MEM_HOST && memspace != PMC_MEM_DEVICE)
+            throw std::invalid_argument("pmc_ratio_enable_field_stats: bad memspace");
+        const int n0 = pmc_darcy_num_pressure_dofs(m->problem->DarcyHandle(), 0);
+        BatchView v(const_cast<double*>(w0), n0, memspace);
+        m->mgr->EnableFieldStatistics(v);
+    });
+}
+int pmc_ratio_field_stats(pmc_ratio* m, double* mean, double* second_moment, double* estimator_variance,
+                          double* l2_mean_corr, double* int_var_corr, int memspace) {
+    return hguard([&] {
+        if (!m) throw std::invalid_argument("manager is NULL");
+        if (memspace != PMC_MEM_HOST && memspace != PMC_MEM_DEVICE)
+            throw std::invalid_argument("pmc_ratio_field_stats: bad memspace");
+        if (!m->mgr->FieldStatisticsEnabled())
+            throw std::invalid_argument("pmc_ratio_field_stats: field statistics are not enabled "
+                                        "(pmc_ratio_enable_field_stats)");
+        const int n0 = pmc_darcy_num_pressure_dofs(m->problem->DarcyHandle(), 0);
+        BatchView vm(mean, n0, memspace), vs(second_moment, n0, memspace), ve(estimator_variance, n0, memspace);
+        std::vector<double> l2(m->mgr->nlevels), iv(m->mgr->nlevels);
+        m->mgr->FieldStatistics(mean ? &vm : nullptr, second_moment ? &vs : nullptr, estimator_variance ? &ve : nullptr,
+                                l2_mean_corr ? l2.data() : nullptr, int_var_corr ? iv.data() : nullptr);
+        auto put = [&](double* dst, const std::vector<double>& x) {
+            if (!dst) return;
+            if (memspace == PMC_MEM_HOST) std::copy(x.begin(), x.end(), dst);
+            else check(pmc_memcpy_h2d(m->ctx, dst, x.data(), sizeof(double) * x.size()), "pmc_ratio_field_stats");
+        };
+        put(l2_mean_corr, l2);
+        put(int_var_corr, iv);
     });
 }
 

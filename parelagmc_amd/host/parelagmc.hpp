@@ -396,6 +396,10 @@ class BayesRatioProblem {
     virtual int GetGlobalNumberOfDofs(int level) const = 0;
     /// realizations of `level` one launch of the device plugins carries (0: no preference), see MLSampler::PreferredBatch
     virtual int PreferredBatch(int /*level*/) const { return 0; }
+    /// for the posterior field estimates: the device forward-problem handle and the entries of EvalPrior's output on
+    /// `level` (nullptr / -1: the prior's fields never reach the device)
+    virtual pmc_darcy* DarcyHandle() const { return nullptr; }
+    virtual int PriorFieldSize(int /*level*/) const { return -1; }
 };
 
 /// Multilevel (nlevels > 1) / single-level (nlevels == 1) ratio estimator, src/ML_BayesRatio_Manager.hpp.
@@ -415,6 +419,19 @@ class ML_BayesRatio_Manager {
     void Run();
     void InitRun(std::vector<int>& level_nsamples_init);
     void Reset();
+    /// Posterior field estimates: from now on every level also accumulates, on the device, the
+    /// likelihood-weighted sums of the R-draws' prior field k (w k - w_c k_c[parent] with w = L, or L / Z when splitting).
+    /// The scalar sums are unchanged.  Device-handle managers only, before the first InitRun or after Reset.  w0: the
+    /// level-0 P0 mass, n_p(0) entries > 0 (host or device).
+    void EnableFieldStatistics(const Vector& w0);
+    bool FieldStatisticsEnabled() const { return !ffields_.empty(); }
+    /// Level-0 maps (each may be NULL, else n_p(0) entries in its own memory space) of the posterior mean of k, its second
+    /// moment about zero and the estimator variance of the mean; per level (host arrays of nlevels, may be NULL) the level's
+    /// contribution to the mean in the L2 norm and the integral of its variance term, with the weights (P chain)^T w0.
+    /// The maps follow the mode (plain / splitting) the sums were accumulated in.  Collective when the farm has several ranks.
+    void FieldStatistics(Vector* mean, Vector* second_moment, Vector* estimator_variance, double* l2_mean_corr,
+                         double* int_var_corr);
+    ~ML_BayesRatio_Manager();
 
     bool wallTime;
     bool splitting = false;
@@ -439,7 +456,17 @@ class ML_BayesRatio_Manager {
     int nranks_ = 1, rank_ = 0;
     std::function<void(double*, int)> reduce_;
     std::vector<double> pending_;
+    pmc_ctx* ctx_;
     Vector zxi, xi, zparam, sparam;
+    // posterior field estimates: one accumulator per level on ctx_'s stream, the parent maps of the coupled levels, the
+    // weights (P chain)^T w0 per level, the coarse R-draw field (the fine one stays in sparam) and the mode the sums were
+    // accumulated in (-1 none yet, 0 plain, 1 splitting, 2 both)
+    std::vector<pmc_level_fields*> ffields_;
+    std::vector<std::vector<int32_t>> fparents_;
+    std::vector<std::vector<double>> fweights_;
+    Vector sparam_c;
+    int fields_mode_ = -1;
+    void release_field_stats();
 };
 
 /// Single-level Monte Carlo manager (src/MC_Manager.hpp): the nlevels == 1 case of the above.

@@ -79,6 +79,8 @@ HOST_SYMBOLS = {
     "pmc_ratio_run": (C.c_int, [_VP]),
     "pmc_ratio_init_run": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "pmc_ratio_result_get": (C.c_int, [_VP, _VP]),
+    "pmc_ratio_enable_field_stats": (C.c_int, [_VP, _VP, C.c_int]),
+    "pmc_ratio_field_stats": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int]),
     "pmc_host_last_error": (C.c_char_p, []),
     "pmc_mortar_assemble": (C.c_int, [_VP, _VP, C.c_double, C.POINTER(_VP)]),
     "pmc_mortar_nnz": (C.c_int64, [_VP]),
@@ -220,8 +222,10 @@ class RatioManager:
         else:
             g = np.ascontiguousarray(G_obs, np.float64)
             self._keep += [sampler, solver, g]
+            self._darcy = solver
             _hcheck(self.lib.pmc_ratio_create(sampler.ctx.h, sampler.h, solver.h, nlevels, g.ctypes.data_as(_DPTR), len(g),
                                               float(noise), C.byref(p), C.byref(h)))
+            sampler.ctx._adopt(self)    # the manager's device buffers and accumulators die before the context does
         self.h = h
         if splitting:
             _hcheck(self.lib.pmc_ratio_set_splitting(self.h, 1))
@@ -248,6 +252,33 @@ class RatioManager:
     def Run(self):
         _hcheck(self.lib.pmc_ratio_run(self.h))
         return self.result()
+
+    def enable_field_stats(self, w0):
+        """Posterior field estimates from now on (device-handle managers, before the first InitRun or after Reset).
+        w0: the level-0 P0 mass (for the fe hierarchies h.spaces[0].vol)."""
+        w = np.ascontiguousarray(w0, np.float64).ravel()
+        d = getattr(self, "_darcy", None)
+        if d is not None:
+            n0 = d.ctx.lib.pmc_darcy_num_pressure_dofs(d.h, 0)
+            if w.size != n0:
+                raise capi.PmcError(-1, f"enable_field_stats: w0 must hold the n_p(0) = {n0} level-0 P0 masses")
+        self._keep.append(w)
+        _hcheck(self.lib.pmc_ratio_enable_field_stats(self.h, w.ctypes.data, 0))
+        self._n_p0 = w.size
+        return self
+
+    def field_stats(self, variance: bool = True) -> dict:
+        """Level-0 maps of the posterior "mean" of k, its "second_moment" (about zero) and, with variance (needs N_l >= 2
+        on every level), the "estimator_variance" of the mean, plus the per-level "l2_mean_corr" (and "int_var_corr") as
+        numpy arrays (pmc_ratio_field_stats; collective in a farm)."""
+        n0 = getattr(self, "_n_p0", 0)
+        out = {"mean": np.empty(n0), "second_moment": np.empty(n0), "l2_mean_corr": np.empty(self.nlevels)}
+        if variance:
+            out["estimator_variance"], out["int_var_corr"] = np.empty(n0), np.empty(self.nlevels)
+        addr = lambda k: out[k].ctypes.data if k in out else None   # noqa: E731
+        _hcheck(self.lib.pmc_ratio_field_stats(self.h, addr("mean"), addr("second_moment"), addr("estimator_variance"),
+                                               addr("l2_mean_corr"), addr("int_var_corr"), 0))
+        return out
 
     def result(self):
         r = pmc_ratio_result()
