@@ -617,16 +617,19 @@ __device__ __forceinline__ SliceWalk slice_walk(int nslices) {
 // a fixed xor tree over the lanes of a row step, and the separate restriction kernel (13 us of dependent latency for a
 // few MB) disappears from the V-cycle.
 // XT: storage type of x and dot_with (fp32 or fp64 for the preconditioned Krylov vectors, zvec)
-template <int NB, int BV, int MODE, bool DOT, int TAG, bool NT = false, bool R8 = false, bool DL = false, typename XT = double>
+// YT: storage type of y (fp32: the coarse right-hand side of a V-cycle level with fp32 inter-level vectors, plain products only)
+template <int NB, int BV, int MODE, bool DOT, int TAG, bool NT = false, bool R8 = false, bool DL = false, typename XT = double,
+          typename YT = double>
 __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3 : 1)) void sell_spmm_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                            const int* __restrict__ sched,
                                                            const int* __restrict__ cols,
                                                            const double* __restrict__ vals,
-                                                           const XT* __restrict__ x, double* __restrict__ y,
+                                                           const XT* __restrict__ x, typename ident<YT>::type* __restrict__ y,
                                                            const double* __restrict__ r,
                                                            const typename ident<XT>::type* __restrict__ dot_with,
                                                            double* __restrict__ partial, int ld) {
     static_assert(!R8 || (MODE == 2 && !DOT), "fused restriction goes with the residual");
+    static_assert(sizeof(YT) == 8 || (MODE == 0 && !DOT && !NT), "fp32 result: plain products only");
     const int LD = row_ld<NB>(ld);
     {
         const int c0 = col0<NB>();   // this group's columns of every interleaved operand
@@ -680,7 +683,8 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
 #pragma unroll
                     for (int c = 0; c < C; ++c) acc[rs][c] = rv[c] - acc[rs][c];
                 }
-                store_c_stream<NT, C>(y + at, acc[rs]);
+                if constexpr (sizeof(YT) == 8) store_c_stream<NT, C>(y + at, acc[rs]);
+                else store_v<C>(y + at, acc[rs]);
                 if constexpr (LEAN_DL) {
                 } else if constexpr (DL) {
 #pragma unroll
@@ -1050,14 +1054,16 @@ __device__ __forceinline__ void split_row_sums(double (&acc)[T][C], int sl) {
 // GIB (launches of 64 realizations = two column groups): ONE workgroup sweeps a slice for both groups back to back - the slice's
 // (index, value) pairs come from L1 / L2 the second time instead of being fetched again by another workgroup at another time
 // (what `traffic` showed as 1.34 x the algorithmic bytes) - gridDim.y is 1 and the partial sums keep their layout.
+// PT: storage type of padd_x (the coarse correction: fp64, or fp32 with fp32 inter-level vectors), widened on load
 template <int NB, typename XT, typename OT, typename AT, bool DOT, bool NT = false, int BV = 0, int DEEP = 1, bool SPL = false,
-          bool GIB = false>
+          bool GIB = false, typename PT = double>
 __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc_poly2_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                           const int* __restrict__ cols, const double* __restrict__ vals_scaled,
                                                           const double* __restrict__ dinv, const XT* __restrict__ r, OT* xout,
                                                           double c0, double c1, double* __restrict__ partial, const AT* xadd,
                                                           const double* __restrict__ dot_with,
-                                                          const int* __restrict__ padd_idx, const double* __restrict__ padd_x,
+                                                          const int* __restrict__ padd_idx,
+                                                          const typename ident<PT>::type* __restrict__ padd_x,
                                                           int ld, int sl = 0) {
     static_assert(!SPL || (NB <= 8 && BV == 0 && DEEP == 1), "row-split instantiations: narrow launches, shared values");
     static_assert(!GIB || (NB == kGroup && BV == 0 && DEEP == 1 && !SPL), "both column groups in one workgroup: 64 wide, shared values");
@@ -1085,7 +1091,7 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
       OT* xg = xout + go;
       const AT* xa = xadd ? xadd + go : nullptr;
       const double* dw = dot_with ? dot_with + go : nullptr;
-      const double* px = padd_x ? padd_x + go : nullptr;
+      const PT* px = padd_x ? padd_x + go : nullptr;
       double p[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) p[c] = 0.0;
@@ -1126,7 +1132,7 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
             }
             if (padd_idx) {
 #pragma unroll
-                for (int u = 0; u < H; ++u) load_c<C>(px + (size_t)par[u] * LD + t * C, pc[u]);
+                for (int u = 0; u < H; ++u) load_v<C>(px + (size_t)par[u] * LD + t * C, pc[u]);
             }
 #pragma unroll
             for (int u = 0; u < H; ++u) {
@@ -1167,12 +1173,14 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
 // in increasing row order: coarse[cid] = sum of the rows of segment (cid, first row, rows).  No other wavefront touches those
 // coarse rows: deterministic, no atomics, and the separate product with P^T (one more pass over the residual) is gone.
 // SPL: rows stored in 2^sl pieces, see vc_poly2_kernel
+// CT: storage type of `coarse` (fp64, or fp32 with fp32 inter-level vectors: the fp64 sums are rounded once, on store)
+// TAG only names the instantiation: 1 = res - (S P) xc (in place), so that profiles show that pass on a row of its own
 template <int NB, typename XT, typename RT, typename YT, bool R8, int BV = 0, bool STORE = true, int DEEP = 1, bool RAGG = false,
-          bool SPL = false>
+          bool SPL = false, typename CT = double, int TAG = 0>
 __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                              const int* __restrict__ cols, const double* __restrict__ vals,
                                                              const XT* __restrict__ x, const RT* r, YT* y,
-                                                             double* __restrict__ coarse, int ld,
+                                                             typename ident<CT>::type* __restrict__ coarse, int ld,
                                                              const int* __restrict__ seg_ptr = nullptr,
                                                              const int* __restrict__ seg_cid = nullptr,
                                                              const int* __restrict__ seg_pos = nullptr, int sl = 0) {
@@ -1236,7 +1244,7 @@ __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nsli
                     v += __shfl_xor(v, 4 * T, kWave);
                     s[c] = v;
                 }
-                if ((g & 7) == 0 && row < nrows) store_c<C>(coarse + (size_t)(row >> 3) * LD + t * C, s);
+                if ((g & 7) == 0 && row < nrows) store_v<C>(coarse + (size_t)(row >> 3) * LD + t * C, s);
             }
         }
         if constexpr (RAGG) {
@@ -1253,7 +1261,7 @@ __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nsli
                 for (int q = 0; q < len; ++q)
 #pragma unroll
                     for (int c = 0; c < C; ++c) sum[c] += (double)tile[(first + q) * NB + t * C + c];
-                store_c<C>(coarse + (size_t)seg_cid[sg] * LD + t * C, sum);
+                store_v<C>(coarse + (size_t)seg_cid[sg] * LD + t * C, sum);
             }
             __builtin_amdgcn_wave_barrier();    // the next slice overwrites the tile
         }
@@ -2666,10 +2674,11 @@ PMC_TAIL_INLINE void tail_vcycle_lds(const TailParams& P, int nb, int k, double*
     }
 }
 
-// out32: xout points at fp32 storage (the preconditioned Krylov vectors in fp32 storage)
+// out32: xout points at fp32 storage (the preconditioned Krylov vectors in fp32 storage, or the coarse correction of a cycle
+// with fp32 inter-level vectors); in32: so does rin (the coarse right-hand side of such a cycle)
 __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailParams* __restrict__ pp, int nb,
                                                                const double* __restrict__ rin, double* __restrict__ xout,
-                                                               double* __restrict__ partial, int out32) {
+                                                               double* __restrict__ partial, int out32, int in32) {
     extern __shared__ __align__(16) double lds[];
     __shared__ double red[kTailThreads / kWave];
     const TailParams& P = *pp;
@@ -2677,7 +2686,12 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailParams*
     const TailLevelDev& L0 = P.lev[0];
     {
         double* r0 = lds + L0.lds_off;
-        for (int i = threadIdx.x; i < L0.n; i += kTailThreads) r0[i] = rin[(size_t)i * nb + k];
+        if (in32) {
+            const float* rf = reinterpret_cast<const float*>(rin);
+            for (int i = threadIdx.x; i < L0.n; i += kTailThreads) r0[i] = (double)rf[(size_t)i * nb + k];
+        } else {
+            for (int i = threadIdx.x; i < L0.n; i += kTailThreads) r0[i] = rin[(size_t)i * nb + k];
+        }
     }
     __syncthreads();
     tail_vcycle_lds(P, nb, k, lds);
@@ -3183,146 +3197,142 @@ static inline bool deep_level(const SellView& A, int nb) {
     return nb >= kGroup && !A.bv && (long)A.nslices * (nb / kGroup) <= limit;
 }
 
-void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const double* r, float* xout, double c0,
-                    double c1) {
+// the launchers below take the right-hand side and the inter-level vectors (coarse right-hand side, coarse correction) of a
+// shared-value level in either storage: T names the element type inside the braces
+#define PMC_DISPATCH_F32(is_f32, T, ...)                \
+    if (is_f32) { using T = float; __VA_ARGS__; }       \
+    else { using T = double; __VA_ARGS__; }
+
+// r in fp32: the copy of the Lanczos vector the MINRES loop keeps for the top level of a cycle (k::lincomb3) - gathered, and
+// read at the own row, as 128-byte rows instead of 256-byte ones - or the coarse right-hand side the level above wrote
+template <typename RT>
+static void vc_presmooth32_t(hipStream_t st, int nb, const SellView& As, const double* dinv, const RT* r, float* xout, double c0,
+                             double c1) {
     check_offsets32(As, nb);
     if (As.nrows == 0) return;
     if (As.bv) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32: shared values expected");
     const dim3 g = grid_slices(As.nslices);
     if (As.split_log2) {
         PMC_DISPATCH_NARROW(nb, {
-            vc_poly2_kernel<NB, double, float, float, false, false, 0, 1, true><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb, As.split_log2);
+            vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, true><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb, As.split_log2);
         });
         check_launch();
         return;
     }
     if (deep_level(As, nb)) {
-        vc_poly2_kernel<kGroup, double, float, float, false, false, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+        vc_poly2_kernel<kGroup, RT, float, float, false, false, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
         check_launch();
         return;
     }
     PMC_DISPATCH_NB(nb, {
         if (nt_poly(As, NB))
-            vc_poly2_kernel<NB, double, float, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+            vc_poly2_kernel<NB, RT, float, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
         else
-            vc_poly2_kernel<NB, double, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+            vc_poly2_kernel<NB, RT, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
     });
     check_launch();
 }
-
-// the same from the fp32 copy of the right-hand side (the top level of a cycle inside the MINRES loop: the Lanczos update
-// writes that copy, k::lincomb3): r is gathered - and read at the own row - as 128-byte fp32 rows instead of 256-byte fp64 ones
-void vc_presmooth32_r32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* r32, float* xout,
-                        double c0, double c1) {
-    check_offsets32(As, nb);
-    if (As.nrows == 0) return;
-    if (As.bv) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32_r32: shared values expected");
-    const dim3 g = grid_slices(As.nslices);
-    PMC_DISPATCH_NB(nb, {
-        if (nt_poly(As, NB))
-            vc_poly2_kernel<NB, float, float, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r32, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
-        else
-            vc_poly2_kernel<NB, float, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r32, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
-    });
-    check_launch();
+void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, zvec r, float* xout, double c0, double c1) {
+    PMC_DISPATCH_F32(r.f32, RT, vc_presmooth32_t<RT>(st, nb, As, dinv, r.as<RT>(), xout, c0, c1));
 }
 
-void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out,
-                              double* coarse) {
+void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse) {
     check_offsets32(A, nb);
     if (A.nrows == 0) return;
     if (A.bv || A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict8_32: shared values and groups of 8 rows expected");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, double, float, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, coarse, nb);
-    });
+    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, RT, float, true, 0, true, 1, false, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb);
+    })));
     check_launch();
 }
 
-void vc_residual32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out) {
+template <typename RT>
+static void vc_residual32_t(hipStream_t st, int nb, const SellView& A, const RT* r, const float* x, float* out) {
     check_offsets32(A, nb);
     if (A.nrows == 0) return;
     if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual32: shared values expected");
     const dim3 g = grid_slices(A.nslices);
     if (A.split_log2) {
         PMC_DISPATCH_NARROW(nb, {
-            vc_residual_kernel<NB, float, double, float, false, 0, true, 1, false, true><<<g, kBlock, 0, st>>>(A.nrows >> A.split_log2, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb, nullptr, nullptr, nullptr, A.split_log2);
+            vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, false, true><<<g, kBlock, 0, st>>>(A.nrows >> A.split_log2, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb, nullptr, nullptr, nullptr, A.split_log2);
         });
         check_launch();
         return;
     }
     if (deep_level(A, nb)) {
-        vc_residual_kernel<kGroup, float, double, float, false, 0, true, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
+        vc_residual_kernel<kGroup, float, RT, float, false, 0, true, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
         check_launch();
         return;
     }
     PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, double, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
+        vc_residual_kernel<NB, float, RT, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
     });
     check_launch();
 }
+void vc_residual32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out) {
+    PMC_DISPATCH_F32(r.f32, RT, vc_residual32_t<RT>(st, nb, A, r.as<RT>(), x, out));
+}
 
-void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out,
-                                double* coarse, const int* seg_ptr, const int* seg_cid, const int* seg_pos) {
+void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse,
+                                const int* seg_ptr, const int* seg_cid, const int* seg_pos) {
     check_offsets32(A, nb);
     if (A.nrows == 0) return;
     if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict_agg32: shared values expected");
     const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, true, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb, seg_ptr, seg_cid, seg_pos);
+    })));
+    check_launch();
+}
+
+// coarse = Pt res (the restriction of a level without a fused one): fp64 through the product every caller uses, fp32 through
+// the same kernel with a typed result
+void vc_restrict32(hipStream_t st, int nb, const SellView& Pt, const float* res, zvec coarse) {
+    if (!coarse.f32) {
+        spmm_z(st, nb, Pt, zvec(const_cast<float*>(res), true), coarse.as<double>(), nullptr, zvec());
+        return;
+    }
+    check_offsets32(Pt, nb);
+    if (Pt.nrows == 0) return;
+    if (Pt.bv) throw Error(PMC_ERR_INTERNAL, "vc_restrict32: shared values expected");
+    const dim3 g = grid_slices(Pt.nslices);
     PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, double, float, false, 0, true, 1, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, coarse, nb, seg_ptr, seg_cid, seg_pos);
+        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, float, float><<<groups_xcd(g, nb), kBlock, 0, st>>>(Pt.nrows, Pt.nslices, Pt.slice_off, Pt.sched, Pt.cols, Pt.vals, res, coarse.as<float>(), nullptr, nullptr, nullptr, nb);
     });
     check_launch();
 }
 
-void vc_residual_restrict_agg32_r32(hipStream_t st, int nb, const SellView& A, const float* r32, const float* x, float* out,
-                                    double* coarse, const int* seg_ptr, const int* seg_cid, const int* seg_pos) {
-    check_offsets32(A, nb);
-    if (A.nrows == 0) return;
-    if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict_agg32_r32: shared values expected");
-    const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, float, float, false, 0, true, 1, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r32, out, coarse, nb, seg_ptr, seg_cid, seg_pos);
-    });
-    check_launch();
-}
-
-void vc_residual32_r32(hipStream_t st, int nb, const SellView& A, const float* r32, const float* x, float* out) {
-    check_offsets32(A, nb);
-    if (A.nrows == 0) return;
-    if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual32_r32: shared values expected");
-    const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r32, out, nullptr, nb);
-    });
-    check_launch();
-}
-
-void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, const double* xc) {
+template <typename XT>
+static void vc_residual_coarse32_t(hipStream_t st, int nb, const SellView& SP, float* res, const XT* xc) {
     check_offsets32(SP, nb);
     if (SP.nrows == 0) return;
     if (SP.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_coarse32: shared values expected");
     const dim3 g = grid_slices(SP.nslices);
     if (SP.split_log2) {
         PMC_DISPATCH_NARROW(nb, {
-            vc_residual_kernel<NB, double, float, float, false, 0, true, 1, false, true><<<g, kBlock, 0, st>>>(SP.nrows >> SP.split_log2, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb, nullptr, nullptr, nullptr, SP.split_log2);
+            vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, true, double, 1><<<g, kBlock, 0, st>>>(SP.nrows >> SP.split_log2, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb, nullptr, nullptr, nullptr, SP.split_log2);
         });
         check_launch();
         return;
     }
     if (deep_level(SP, nb)) {
-        vc_residual_kernel<kGroup, double, float, float, false, 0, true, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
+        vc_residual_kernel<kGroup, XT, float, float, false, 0, true, 2, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
         check_launch();
         return;
     }
     PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, double, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
+        vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
     });
     check_launch();
 }
+void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, zvec xc) {
+    PMC_DISPATCH_F32(xc.f32, XT, vc_residual_coarse32_t<XT>(st, nb, SP, res, xc.as<XT>()));
+}
 
-template <typename OT>
+template <typename OT, typename PT>
 static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                             OT* xout, double c0, double c1, const double* r, const int* parent, const double* xc,
+                             OT* xout, double c0, double c1, const double* r, const int* parent, const PT* xc,
                              double* dot_partial) {
     check_offsets32(As, nb);
     if (As.nrows == 0) return 0;
@@ -3331,16 +3341,16 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     if (As.split_log2) {
         if (dot_partial) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: the row-split form serves inner levels (no fused dot)");
         PMC_DISPATCH_NARROW(nb, {
-            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, true><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb, As.split_log2);
+            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, true, false, PT><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb, As.split_log2);
         });
         check_launch();
         return 0;
     }
     if (deep_level(As, nb)) {
         if (dot_partial)
-            vc_poly2_kernel<kGroup, float, OT, float, true, false, 0, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+            vc_poly2_kernel<kGroup, float, OT, float, true, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
         else
-            vc_poly2_kernel<kGroup, float, OT, float, false, false, 0, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+            vc_poly2_kernel<kGroup, float, OT, float, false, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
         check_launch();
         return dot_partial ? dot_blocks(g, nb) : 0;
     }
@@ -3349,35 +3359,38 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     static const bool gib = [] { const char* e = lab_env("PMC_GIB"); return e && atoi(e) != 0; }();
     if (gib && nb == 2 * kGroup && nt_poly(As, kGroup) && !xcd_layout(g, nb)) {
         if (dot_partial)
-            vc_poly2_kernel<kGroup, float, OT, float, true, true, 0, 1, false, true><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+            vc_poly2_kernel<kGroup, float, OT, float, true, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
         else
-            vc_poly2_kernel<kGroup, float, OT, float, false, true, 0, 1, false, true><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+            vc_poly2_kernel<kGroup, float, OT, float, false, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
         check_launch();
         return dot_partial ? (int)g.x : 0;
     }
     PMC_DISPATCH_NB(nb, {
         if (nt_poly(As, NB)) {
             if (dot_partial)
-                vc_poly2_kernel<NB, float, OT, float, true, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+                vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
             else
-                vc_poly2_kernel<NB, float, OT, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+                vc_poly2_kernel<NB, float, OT, float, false, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
         } else if (dot_partial)
-            vc_poly2_kernel<NB, float, OT, float, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+            vc_poly2_kernel<NB, float, OT, float, true, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
         else
-            vc_poly2_kernel<NB, float, OT, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
     });
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
 
-int vc_postsmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                    double* xout, double c0, double c1, const double* r, const int* parent, const double* xc, double* dot_partial) {
-    return vc_postsmooth32_t<double>(st, nb, As, dinv, res, x, xout, c0, c1, r, parent, xc, dot_partial);
-}
 int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                      zvec xout, double c0, double c1, const double* r, const int* parent, const double* xc, double* dot_partial) {
-    if (xout.f32) return vc_postsmooth32_t<float>(st, nb, As, dinv, res, x, xout.as<float>(), c0, c1, r, parent, xc, dot_partial);
-    return vc_postsmooth32_t<double>(st, nb, As, dinv, res, x, xout.as<double>(), c0, c1, r, parent, xc, dot_partial);
+                      zvec xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial) {
+    int nblk = 0;
+    PMC_DISPATCH_F32(xout.f32, OT, PMC_DISPATCH_F32(xc.f32, PT, {
+        nblk = vc_postsmooth32_t<OT, PT>(st, nb, As, dinv, res, x, xout.as<OT>(), c0, c1, r, parent, xc.as<PT>(), dot_partial);
+    }));
+    return nblk;
+}
+int vc_postsmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                    double* xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial) {
+    return vc_postsmooth32_z(st, nb, As, dinv, res, x, zvec(xout, false), c0, c1, r, parent, xc, dot_partial);
 }
 
 // ---- the same level with per-realization fp32 values (Darcy; SellView::f32) and per-realization diagonals
@@ -3888,8 +3901,10 @@ void darcy_backsub_p(hipStream_t st, int nb, int n_p, const double* kappa, const
 // x[i][k] = sum_j ainv[i][j] r[j][k] for a launch of at most 8 realizations: one wavefront per row, lanes over the columns of the
 // (symmetric, row-major) dense inverse, so the matrix is read once, coalesced, by n wavefronts spread over the chip - the exact
 // solve of a level of a few hundred rows that a narrow launch would otherwise cycle through in ONE workgroup's LDS tail
+// VT: storage of r and x (fp32 inside a cycle with fp32 inter-level vectors; the sums are fp64, rounded once on store)
+template <typename VT>
 __global__ __launch_bounds__(kBlock) void dense_apply_kernel(int n, int nb, const double* __restrict__ ainv,
-                                                              const double* __restrict__ r, double* __restrict__ x) {
+                                                              const VT* __restrict__ r, VT* __restrict__ x) {
     const int lane = threadIdx.x & (kWave - 1);
     const int i = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (i >= n) return;
@@ -3899,10 +3914,10 @@ __global__ __launch_bounds__(kBlock) void dense_apply_kernel(int n, int nb, cons
     const double* row = ainv + (size_t)i * n;
     for (int j = lane; j < n; j += kWave) {
         const double a = row[j];
-        const double* rj = r + (size_t)j * nb;
+        const VT* rj = r + (size_t)j * nb;
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            if (k < nb) acc[k] = fma(a, rj[k], acc[k]);
+            if (k < nb) acc[k] = fma(a, (double)rj[k], acc[k]);
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -3910,20 +3925,23 @@ __global__ __launch_bounds__(kBlock) void dense_apply_kernel(int n, int nb, cons
         double v = acc[k];
 #pragma unroll
         for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-        if (lane == 0) x[(size_t)i * nb + k] = v;
+        if (lane == 0) x[(size_t)i * nb + k] = (VT)v;
     }
 }
 
-void dense_apply(hipStream_t st, int nb, int n, const double* ainv, const double* r, double* x) {
+void dense_apply(hipStream_t st, int nb, int n, const double* ainv, zvec r, zvec x) {
+    if (r.f32 != x.f32) throw Error(PMC_ERR_INTERNAL, "dense_apply: right-hand side and result in different storage");
     if (nb < 1 || nb > 8) throw Error(PMC_ERR_INTERNAL, "dense_apply: serves launches of at most 8 realizations");
     if (n <= 0) return;
     const int rows_per_block = kBlock / kWave;
-    dense_apply_kernel<<<(n + rows_per_block - 1) / rows_per_block, kBlock, 0, st>>>(n, nb, ainv, r, x);
+    const unsigned g = (unsigned)((n + rows_per_block - 1) / rows_per_block);
+    if (r.f32) dense_apply_kernel<float><<<g, kBlock, 0, st>>>(n, nb, ainv, r.as<float>(), x.as<float>());
+    else dense_apply_kernel<double><<<g, kBlock, 0, st>>>(n, nb, ainv, r.as<double>(), x.as<double>());
     check_launch();
 }
 
 int mg_tail(hipStream_t st, int nb, const TailParams* dev_params, size_t lds_doubles, const double* r, double* xout,
-            double* dot_partial, bool out32) {
+            double* dot_partial, bool out32, bool in32) {
     const size_t bytes = lds_doubles * sizeof(double);
     if (bytes > kTailLdsBytes) throw Error(PMC_ERR_INTERNAL, "mg_tail: LDS request too large");
     // the dynamic-LDS limit is a per-device function attribute: raise it once per device (idempotent if two lanes race)
@@ -3935,7 +3953,7 @@ int mg_tail(hipStream_t st, int nb, const TailParams* dev_params, size_t lds_dou
                                     (int)kTailLdsBytes));
         attr_mask.fetch_or(1ull << (dev & 63));
     }
-    mg_tail_kernel<<<nb, kTailThreads, bytes, st>>>(dev_params, nb, r, xout, dot_partial, out32 ? 1 : 0);
+    mg_tail_kernel<<<nb, kTailThreads, bytes, st>>>(dev_params, nb, r, xout, dot_partial, out32 ? 1 : 0, in32 ? 1 : 0);
     check_launch();
     return dot_partial ? 1 : 0;
 }

@@ -24,6 +24,11 @@ struct zvec {
     template <typename T>
     T* as() const { return static_cast<T*>(p); }
 };
+// The same pair (pointer, storage) also names the vectors that live only inside one application of a V-cycle: the right-hand
+// side a level receives and the coarse correction it returns (fp32 between the levels of the fp32-intermediate path of a
+// shared-value hierarchy, fp64 everywhere else).  zconst wraps a read-only operand.
+inline zvec zconst(const double* p) { return zvec(const_cast<double*>(p), false); }
+inline zvec zconst(const float* p) { return zvec(const_cast<float*>(p), true); }
 // device buffer behind a zvec: `count` entries in either storage
 struct ZBuf {
     DevBuf<float> b;
@@ -144,27 +149,25 @@ int poly2_z(hipStream_t st, int nb, const SellView& As, const double* dinv, bool
             double c0, double c1, double* dot_partial = nullptr, const double* xadd = nullptr,
             const double* dot_with = nullptr, const int* padd_idx = nullptr, const double* padd_x = nullptr);
 // V-cycle level with fp32 intermediates (shared values; see vc_poly2_kernel): pre-smoothing from zero into an fp32 iterate,
-// residual + restriction over groups of 8 rows from it (fp32 residual, fp64 coarse right-hand side), res -= (S P) xc, and the
-// post-smoothing x + xc[parent] + p2(res) -> fp64 result with the fused <r, result>
-void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const double* r, float* xout, double c0,
-                    double c1);
-void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out,
-                              double* coarse);
-void vc_residual32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out);   // no restriction
-// the V-cycle's first two kernels of a level from the fp32 copy of its right-hand side (written by k::lincomb3)
-void vc_presmooth32_r32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* r32, float* xout,
-                        double c0, double c1);
-void vc_residual32_r32(hipStream_t st, int nb, const SellView& A, const float* r32, const float* x, float* out);
-void vc_residual_restrict_agg32_r32(hipStream_t st, int nb, const SellView& A, const float* r32, const float* x, float* out,
-                                    double* coarse, const int* seg_ptr, const int* seg_cid, const int* seg_pos);
+// residual + restriction from it (fp32 residual), res -= (S P) xc, and the post-smoothing x + xc[parent] + p2(res) -> result
+// with the fused <r, result>.  The level's right-hand side r (fp64 Lanczos vector, its fp32 copy written by k::lincomb3, or the
+// coarse right-hand side the level above wrote), the coarse right-hand side it writes and the coarse correction xc it
+// gathers come in either storage (zvec): fp32 ones are widened on load and rounded once on store, all arithmetic is fp64.
+void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, zvec r, float* xout, double c0, double c1);
+// restriction over groups of 8 consecutive rows fused into the residual
+void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse);
+void vc_residual32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out);   // no restriction
 // residual + restriction of an aggregation level renumbered by agg_pack_rows (segments per slice: seg_ptr / seg_cid / seg_pos)
-void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out,
-                                double* coarse, const int* seg_ptr, const int* seg_cid, const int* seg_pos);
-void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, const double* xc);
+void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse,
+                                const int* seg_ptr, const int* seg_cid, const int* seg_pos);
+// coarse = Pt res: the separate restriction of a level without a fused one
+void vc_restrict32(hipStream_t st, int nb, const SellView& Pt, const float* res, zvec coarse);
+void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, zvec xc);
+// r is the operand of the fused dot only (top level of a cycle: fp64)
 int vc_postsmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                    double* xout, double c0, double c1, const double* r, const int* parent, const double* xc, double* dot_partial);
+                    double* xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial);
 int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                      zvec xout, double c0, double c1, const double* r, const int* parent, const double* xc, double* dot_partial);
+                      zvec xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial);
 // ... and for a level with per-realization fp32 values and diagonals (Darcy; no S P: the coarse correction is added to the
 // fp32 iterate, then residual and post-smoothing): the fine residual of the restriction is never stored
 void vc_presmooth32_bv(hipStream_t st, int nb, const SellView& As, const double* dinv, const double* r, float* xout, double c0,
@@ -321,14 +324,16 @@ void mini_sampler_solve(hipStream_t st, int nb, const MiniSamplerParams& P, size
                         bool zero_guess, double* scratch, pmc_stats* stats);
 // One workgroup per batch column runs the whole V-cycle over the tail levels in LDS.  r, xout: interleaved
 // vectors of the first tail level.  dot_partial != nullptr: writes <r, xout> per column as ONE partial block.
+// out32 / in32: xout / r point at fp32 storage
 int mg_tail(hipStream_t st, int nb, const TailParams* dev_params, size_t lds_doubles, const double* r, double* xout,
-            double* dot_partial, bool out32 = false);
+            double* dot_partial, bool out32 = false, bool in32 = false);
 inline int mg_tail_z(hipStream_t st, int nb, const TailParams* dev_params, size_t lds_doubles, const double* r, zvec xout,
                      double* dot_partial) {
     return mg_tail(st, nb, dev_params, lds_doubles, r, xout.as<double>(), dot_partial, xout.f32);
 }
-// x = ainv r, ainv dense n x n row-major (symmetric), r / x interleaved [row][nb], nb <= 8 (see dense_apply_kernel)
-void dense_apply(hipStream_t st, int nb, int n, const double* ainv, const double* r, double* x);
+// x = ainv r, ainv dense n x n row-major (symmetric), r / x interleaved [row][nb] in the same storage, nb <= 8 (see
+// dense_apply_kernel)
+void dense_apply(hipStream_t st, int nb, int n, const double* ainv, zvec r, zvec x);
 // out[k][i] = in[i][k]: per-realization values of a small level re-laid column-major for the tail kernel, whose
 // workgroup k then streams only its own realization's values
 void transpose_bv(hipStream_t st, int nb, size_t count, const double* in, double* out);

@@ -741,12 +741,13 @@ PrecFn Sampler::preconditioner(int level, int nb, int degM, Multigrid* mgp, int 
 
 // post-smoothing of the finest V-cycle level: shared matrix (scaled values + column indices), 1 / diagonal and parent index
 // per row; per realization res (fp32), the pre-smoothed iterate (fp32) and r (fp64, for the fused <r, z>) read, z written,
-// and the coarse correction (fp64) gathered once per coarse row
+// and the coarse correction (in the storage level 1 returns it in: Multigrid::inner_f32) gathered once per coarse row
 double Sampler::smoother_bytes(int level, int nb) const {
     if (!hybrid || level < 0 || level >= n_mc || !amg[level] || amg[level]->L.size() < 2) return 0.0;
     const MgLevel& m = amg[level]->L[0];
     const double zb = opts.precond_storage == PMC_STORAGE_FP64 ? 8.0 : 4.0;
-    return 12.0 * (double)m.S.nnz + 12.0 * m.n + (double)nb * ((4.0 + 4.0 + 8.0 + zb) * m.n + 8.0 * amg[level]->L[1].n);
+    const double cb = amg[level]->inner_f32(1, 0, nb) ? 4.0 : 8.0;
+    return 12.0 * (double)m.S.nnz + 12.0 * m.n + (double)nb * ((4.0 + 4.0 + 8.0 + zb) * m.n + cb * amg[level]->L[1].n);
 }
 
 void Sampler::apply_preconditioner(int level, int nbatch, const double* r_in, double* z_out, int memspace) {

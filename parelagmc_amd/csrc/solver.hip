@@ -188,31 +188,64 @@ void Multigrid::build_tails(hipStream_t st) {
     }
 }
 
-double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r, double* target, zvec ztarget,
-                         double* dot_partial, int* dot_blocks, const std::function<void()>* side) {
+// PMC_COARSE_F32=0 (laboratory builds): the vectors between the levels of the fp32-intermediate path stay fp64 (A/B switch)
+static bool coarse_f32_on() {
+    static const bool v = [] {
+        const char* e = lab_env("PMC_COARSE_F32");
+        return !e || atoi(e) != 0;
+    }();
+    return v;
+}
+
+Multigrid::LevelPath Multigrid::level_path(int l, int l0, int nb) const {
+    const MgLevel& lv = L[(size_t)l];
+    LevelPath p;
+    p.last = (l == (int)L.size() - 1) || lv.is_last;
+    p.dense = l > l0 && nb <= dense_nb && lv.dense_inv.p;
+    if (p.dense) return p;
+    const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && !p.last && l + 1 < (int)tail.size() && tail[(size_t)l + 1].p;
+    p.tail_here = use_tail && l < (int)tail.size() && tail[(size_t)l].p && !tail_later;
+    if (p.tail_here) return p;
+    p.f32_shared = !p.last && !lv.bv && lv.has_sp && (lv.p_oct || f32_any_injection) && smooth_degree == 2 &&
+                   lv.vals_scaled.p && f32_intermediates;
+    p.f32_bv = !p.last && lv.bv && lv.f32 && lv.p_oct && smooth_degree == 2 && lv.scaled32.p && f32_intermediates;
+    return p;
+}
+
+bool Multigrid::inner_f32(int l, int l0, int nb) const {
+    if (!f32_intermediates || !coarse_f32_on() || l <= l0 || l >= (int)L.size() || L[(size_t)l].bv) return false;
+    const LevelPath p = level_path(l, l0, nb);
+    return p.dense || p.tail_here || p.f32_shared;
+}
+
+zvec Multigrid::cycle(hipStream_t st, int nb, int l, int l0, zvec rz, double* target, zvec ztarget, double* dot_partial,
+                      int* dot_blocks, const std::function<void()>* side) {
     MgLevel& lv = L[l];
     lv.ensure(nb);
-    const bool last = (l == (int)L.size() - 1) || lv.is_last;
     struct ClearR32 {   // whatever path the top level takes, a copy offered for THIS cycle is not seen by the next one
         Multigrid* m; bool top;
         ~ClearR32() { if (top) m->r32_top = nullptr; }
     } clear_r32{this, l == l0};
+    const LevelPath path = level_path(l, l0, nb);
+    const bool last = path.last;
+    // r in fp32: an inner level whose parent found inner_f32() true - the result goes back in fp32 too (the buffer xa holds it)
+    const bool io32 = rz.f32;
+    if (io32 && !(l > l0 && inner_f32(l, l0, nb) && !target && !ztarget && !dot_partial))
+        throw Error(PMC_ERR_INTERNAL, "V-cycle: fp32 right-hand side on a level that does not take one");
+    const double* r = io32 ? nullptr : rz.as<double>();   // every path but the two fp32 ones below reads this
     // A launch of few realizations (the drop-in path: one per call) runs the LDS tail on as many compute units as it has
     // realizations, and a tail that starts at a level of several thousand rows with 17-27 entries each is bound by ONE
     // unit's L2 port (LAB_NOTES 9.16: 142 us per cycle - half of a one-realization Eval of the hybridized sampler).  Such
     // a level runs as kernels then and the tail starts one level further down.
     // ... and it ends on the first level that carries a dense inverse: x = A^-1 r by n wavefronts (k::dense_apply) instead of
     // one workgroup cycling through the remaining levels (573 rows at 400 k multipliers: 25 -> 4 us per cycle)
-    if (l > l0 && nb <= dense_nb && lv.dense_inv.p && !target && !ztarget && !dot_partial) {
+    if (path.dense && !target && !ztarget && !dot_partial) {
         if (side && *side) (*side)();
-        k::dense_apply(st, nb, lv.n, lv.dense_inv.p, r, lv.xa.p);
-        return lv.xa.p;
+        const zvec x(lv.xa.p, io32);
+        k::dense_apply(st, nb, lv.n, lv.dense_inv.p, rz, x);
+        return x;
     }
-    const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && !last && l + 1 < (int)tail.size() && tail[l + 1].p;
-    const bool tail_here = use_tail && l < (int)tail.size() && tail[l].p && !tail_later;
-    const bool f32_shared = !last && !lv.bv && lv.has_sp && (lv.p_oct || f32_any_injection) && smooth_degree == 2 &&
-                            lv.vals_scaled.p && f32_intermediates;
-    const bool f32_bv = !last && lv.bv && lv.f32 && lv.p_oct && smooth_degree == 2 && lv.scaled32.p && f32_intermediates;
+    const bool tail_here = path.tail_here, f32_shared = path.f32_shared, f32_bv = path.f32_bv;
     if (ztarget && target) throw Error(PMC_ERR_INTERNAL, "V-cycle: two result buffers");
     const bool ends_here = tail_here || last;
     if (side && *side && ends_here) (*side)();   // beside the bottom of the V: the least parallel kernels of the cycle
@@ -220,18 +253,20 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
         if (ztarget) {
             const int nblk = k::mg_tail_z(st, nb, tail[l].p, tail_lds[l], r, ztarget, dot_partial);
             if (dot_blocks) *dot_blocks = nblk;
-            return nullptr;
+            return zvec();
         }
         double* out = target ? target : lv.xa.p;
-        const int nblk = k::mg_tail(st, nb, tail[l].p, tail_lds[l], r, out, dot_partial);
+        const int nblk = k::mg_tail(st, nb, tail[l].p, tail_lds[l], rz.as<double>(), out, dot_partial, io32, io32);
         if (dot_blocks) *dot_blocks = nblk;
-        return out;
+        return zvec(out, io32);
     }
     const SellView A = lv.sview();
-    // Shared-value level with an injection prolongator over groups of 8 (uniform refinement) and the one-pass degree-2
-    // smoothers: the iterate and the residuals of the level - vectors that live only inside this application of the
-    // preconditioner - are kept in fp32 (k::vc_* kernels; the buffers xb / res hold them).  Input, output, coarse vectors and
-    // all arithmetic stay fp64.
+    // Shared-value level with an injection prolongator (over groups of 8: uniform refinement; or over aggregates) and the
+    // one-pass degree-2 smoothers: the iterate and the residuals of the level - vectors that live only inside this application
+    // of the preconditioner - are kept in fp32 (k::vc_* kernels; the buffers xb / res hold them).  So are the vectors BETWEEN
+    // such levels (inner_f32): the coarse right-hand side (buffer r of the next level) and the coarse correction it returns
+    // (its buffer xa) - the correction is the only thing `res - (S P) xc` gathers.  The cycle's own input and output and all
+    // arithmetic stay fp64.
     if (f32_shared) {
         double c0, c1;
         cheb2_coefficients(lv.lmax, smooth_ratio, &c0, &c1);
@@ -239,53 +274,47 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
         As.vals = lv.vals_scaled.p;
         float* xf = reinterpret_cast<float*>(lv.xb.p);
         float* resf = reinterpret_cast<float*>(lv.res.p);
-        double* out = target ? target : lv.xa.p;
+        const zvec out = ztarget ? ztarget : zvec(target ? target : lv.xa.p, io32);
         // top level of a cycle inside the MINRES loop of an aggregation hierarchy: the fp32 copy of r, if the caller has one
         const float* r32 = (l == l0 && !lv.p_oct) ? r32_top : nullptr;
         if (l == l0) r32_top = nullptr;
+        const zvec rin = r32 ? zconst(r32) : rz;
+        MgLevel& lc = L[l + 1];
+        lc.ensure(nb);
+        const zvec rc(lc.r.p, inner_f32(l + 1, l0, nb));
         // inner level of a launch of at most 8 realizations: the row-split forms of the four kernels (MgLevel::S_split)
         if (l > l0 && nb <= dense_nb && lv.split_log2 > 0 && !lv.p_oct && !lv.p_agg && !dot_partial) {
             const SellView Asp = view_split(lv.S_split, lv.split_log2);
             SellView Assp = Asp;
             Assp.vals = lv.scaled_split.p;
             const SellView SPv = lv.sp_split_log2 > 0 ? view_split(lv.SP_split, lv.sp_split_log2) : view(lv.SP);
-            k::vc_presmooth32(st, nb, Assp, lv.dinv.p, r, xf, c0, c1);
-            MgLevel& lcs = L[l + 1];
-            lcs.ensure(nb);
-            k::vc_residual32(st, nb, Asp, r, xf, resf);
-            k::spmm_z(st, nb, view(lv.Pt), zvec(resf, true), lcs.r.p, nullptr, zvec());
-            double* xcs = cycle(st, nb, l + 1, l0, lcs.r.p, nullptr, zvec(), nullptr, nullptr, side);
+            k::vc_presmooth32(st, nb, Assp, lv.dinv.p, rz, xf, c0, c1);
+            k::vc_residual32(st, nb, Asp, rz, xf, resf);
+            k::vc_restrict32(st, nb, view(lv.Pt), resf, rc);
+            const zvec xcs = cycle(st, nb, l + 1, l0, rc, nullptr, zvec(), nullptr, nullptr, side);
             k::vc_residual_coarse32(st, nb, SPv, resf, xcs);
-            if (ztarget) k::vc_postsmooth32_z(st, nb, Assp, lv.dinv.p, resf, xf, ztarget, c0, c1, r, lv.parent.p, xcs, nullptr);
-            else k::vc_postsmooth32(st, nb, Assp, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xcs, nullptr);
+            k::vc_postsmooth32_z(st, nb, Assp, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xcs, nullptr);
             if (dot_blocks) *dot_blocks = 0;
-            return ztarget ? nullptr : out;
+            return ztarget ? zvec() : out;
         }
-        if (r32) k::vc_presmooth32_r32(st, nb, As, lv.dinv.p, r32, xf, c0, c1);
-        else k::vc_presmooth32(st, nb, As, lv.dinv.p, r, xf, c0, c1);
-        MgLevel& lc = L[l + 1];
-        lc.ensure(nb);
+        k::vc_presmooth32(st, nb, As, lv.dinv.p, rin, xf, c0, c1);
         if (lv.p_oct) {
-            k::vc_residual_restrict8_32(st, nb, A, r, xf, resf, lc.r.p);
+            k::vc_residual_restrict8_32(st, nb, A, rz, xf, resf, rc);
         } else if (lv.p_agg) {
-            if (r32) k::vc_residual_restrict_agg32_r32(st, nb, A, r32, xf, resf, lc.r.p, lv.seg_ptr.p, lv.seg_cid.p, lv.seg_pos.p);
-            else k::vc_residual_restrict_agg32(st, nb, A, r, xf, resf, lc.r.p, lv.seg_ptr.p, lv.seg_cid.p, lv.seg_pos.p);
-        } else if (r32) {
-            k::vc_residual32_r32(st, nb, A, r32, xf, resf);
-            k::spmm_z(st, nb, view(lv.Pt), zvec(resf, true), lc.r.p, nullptr, zvec());
+            k::vc_residual_restrict_agg32(st, nb, A, rin, xf, resf, rc, lv.seg_ptr.p, lv.seg_cid.p, lv.seg_pos.p);
         } else {
-            k::vc_residual32(st, nb, A, r, xf, resf);
-            k::spmm_z(st, nb, view(lv.Pt), zvec(resf, true), lc.r.p, nullptr, zvec());
+            k::vc_residual32(st, nb, A, rin, xf, resf);
+            k::vc_restrict32(st, nb, view(lv.Pt), resf, rc);
         }
-        double* xc = cycle(st, nb, l + 1, l0, lc.r.p, nullptr, zvec(), nullptr, nullptr, side);
+        const zvec xc = cycle(st, nb, l + 1, l0, rc, nullptr, zvec(), nullptr, nullptr, side);
         k::vc_residual_coarse32(st, nb, view(lv.SP), resf, xc);
         const bool timed = smooth_timer && smooth_timer->on && l == l0;
         if (timed) smooth_timer->begin(st);
-        const int nblk = ztarget ? k::vc_postsmooth32_z(st, nb, As, lv.dinv.p, resf, xf, ztarget, c0, c1, r, lv.parent.p, xc, dot_partial)
-                                 : k::vc_postsmooth32(st, nb, As, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xc, dot_partial);
+        // (r is the operand of the fused dot only: top level, fp64)
+        const int nblk = k::vc_postsmooth32_z(st, nb, As, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xc, dot_partial);
         if (timed) smooth_timer->end(st);
         if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? nullptr : out;
+        return ztarget ? zvec() : out;
     }
     // The same for a per-realization level with fp32 values (Darcy): pre-smoothing into an fp32 iterate, restriction of its
     // residual without storing the fine residual (nothing reads it: there is no S P for per-realization values), the coarse
@@ -302,13 +331,13 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
         MgLevel& lc = L[l + 1];
         lc.ensure(nb);
         k::vc_restrict8_32_bv(st, nb, A, r, xf, lc.r.p);
-        double* xc = cycle(st, nb, l + 1, l0, lc.r.p, nullptr, zvec(), nullptr, nullptr, side);
+        double* xc = cycle(st, nb, l + 1, l0, zvec(lc.r.p, false), nullptr, zvec(), nullptr, nullptr, side).as<double>();
         k::vc_prolong8_32(st, nb, lv.n, xf, xc);
         k::vc_residual32_bv(st, nb, A, r, xf, df);
         const int nblk = ztarget ? k::vc_postsmooth32_bv_z(st, nb, As, lv.dinv.p, df, xf, ztarget, c0, c1, r, dot_partial)
                                  : k::vc_postsmooth32_bv(st, nb, As, lv.dinv.p, df, xf, out, c0, c1, r, dot_partial);
         if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? nullptr : out;
+        return ztarget ? zvec() : zvec(out, false);
     }
     const int last_deg = lv.is_last ? lv.last_degree : coarse_degree;
     const double last_rat = lv.is_last ? lv.last_ratio : coarse_ratio;
@@ -323,7 +352,7 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
     }
     if (last) {
         const ChebParams& cp = cp_last;
-        return cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, start, other, lv.d.p, true, dot_partial, dot_blocks, ztarget);
+        return zvec(cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, start, other, lv.d.p, true, dot_partial, dot_blocks, ztarget), false);
     }
     const ChebParams& cp = cp_smooth;
     double* x = cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, start, other, lv.d.p, true);
@@ -336,17 +365,17 @@ double* Multigrid::cycle(hipStream_t st, int nb, int l, int l0, const double* r,
         k::residual(st, nb, A, r, x, lv.res.p);
         k::spmm(st, nb, view(lv.Pt), lv.res.p, lc.r.p, false, nullptr, nullptr);
     }
-    double* xc = cycle(st, nb, l + 1, l0, lc.r.p, nullptr, zvec(), nullptr, nullptr, side);
+    double* xc = cycle(st, nb, l + 1, l0, zvec(lc.r.p, false), nullptr, zvec(), nullptr, nullptr, side).as<double>();
     if (lv.has_sp && !lv.bv && cheb_fused(cp, false)) {
         // r - S (x + P xc) = res - (S P) xc, in place; then x <- x + P xc + p2(that residual) in one pass
         k::residual(st, nb, view(lv.SP), lv.res.p, xc, lv.res.p);
         const int nblk = cheb_post_from_residual(st, nb, A, lv.dinv.p, lv.bv, cp, r, lv.res.p, x, lv.parent.p, xc,
                                                  dot_partial, ztarget);
         if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? nullptr : x;
+        return ztarget ? zvec() : zvec(x, false);
     }
     k::spmm(st, nb, view(lv.P), xc, x, true, nullptr, nullptr);
-    return cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, x, oth, lv.d.p, false, dot_partial, dot_blocks, ztarget);
+    return zvec(cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, x, oth, lv.d.p, false, dot_partial, dot_blocks, ztarget), false);
 }
 
 int Multigrid::cycle_role(int l0, int nb, int l, bool* in_tail) const {
@@ -377,15 +406,15 @@ int Multigrid::cycle_role(int l0, int nb, int l, bool* in_tail) const {
 int Multigrid::vcycle(hipStream_t st, int nb, int l0, const double* r, double* xout, double* dot_partial,
                       const std::function<void()>& side) {
     int nblk = 0;
-    double* res = cycle(st, nb, l0, l0, r, xout, zvec(), dot_partial, &nblk, side ? &side : nullptr);
-    if (res != xout) throw Error(PMC_ERR_INTERNAL, "V-cycle result landed in the wrong buffer");
+    const zvec res = cycle(st, nb, l0, l0, zconst(r), xout, zvec(), dot_partial, &nblk, side ? &side : nullptr);
+    if (res.p != xout || res.f32) throw Error(PMC_ERR_INTERNAL, "V-cycle result landed in the wrong buffer");
     return nblk;
 }
 
 int Multigrid::vcycle_z(hipStream_t st, int nb, int l0, const double* r, zvec zout, double* dot_partial,
                         const std::function<void()>& side) {
     int nblk = 0;
-    cycle(st, nb, l0, l0, r, nullptr, zout, dot_partial, &nblk, side ? &side : nullptr);
+    cycle(st, nb, l0, l0, zconst(r), nullptr, zout, dot_partial, &nblk, side ? &side : nullptr);
     return nblk;
 }
 

@@ -94,6 +94,8 @@ struct MgLevel {
     // slice): the restriction is fused into the residual kernel through per-slice segment tables
     bool p_agg = false;
     DevBuf<int> seg_ptr, seg_cid, seg_pos;
+    // work vectors, n*nb doubles each.  xb and res hold the fp32 iterate and residual of the fp32-intermediate branches; r and
+    // xa hold fp32 data on a level for which Multigrid::inner_f32() is true
     DevBuf<double> r, xa, xb, d, res;
     DevBuf<double> ainv;         // last level of a small shared-value hierarchy: dense inverse (see TailLevelDev::ainv)
     // an inner level of a few hundred rows: dense inverse for launches of at most Multigrid::dense_nb realizations, which
@@ -179,10 +181,23 @@ struct Multigrid {
     int vcycle_z(hipStream_t st, int nb, int l0, const double* r, zvec zout, double* dot_partial = nullptr,
                  const std::function<void()>& side = nullptr);
 
+    // what cycle() does on level l of a cycle from level l0 at width nb: ends with the dense inverse (narrow launches), runs the
+    // LDS tail from here on, or one of the fp32-intermediate branches (none of them: the generic fp64 path)
+    struct LevelPath {
+        bool last = false, dense = false, tail_here = false, f32_shared = false, f32_bv = false;
+    };
+    LevelPath level_path(int l, int l0, int nb) const;
+    // does level l > l0 take its right-hand side and return its correction in fp32?  The vectors between two levels of the
+    // fp32-intermediate path of a shared-value hierarchy live only inside one application of the preconditioner, like the
+    // levels' iterates and residuals: such a level (f32_shared branch, LDS tail, dense inverse) reads MgLevel::r and writes
+    // MgLevel::xa as fp32.  False with PMC_STORAGE_FP64, for per-realization (Darcy) levels and for levels on the generic path.
+    bool inner_f32(int l, int l0, int nb) const;
+
   private:
+    // rz: the level's right-hand side; fp32 only where inner_f32() says so, and then the result is fp32 too.
     // ztarget non-null (top level of vcycle_z only): the result goes there and the return value is null
-    double* cycle(hipStream_t st, int nb, int l, int l0, const double* r, double* target, zvec ztarget, double* dot_partial,
-                  int* dot_blocks, const std::function<void()>* side);
+    zvec cycle(hipStream_t st, int nb, int l, int l0, zvec rz, double* target, zvec ztarget, double* dot_partial,
+               int* dot_blocks, const std::function<void()>* side);
 };
 
 // Abstract pieces MINRES needs.

@@ -40,8 +40,13 @@ def main():
         zb = smp.z_bytes()
         nb = smp.BatchWidth(0)    # what `bench.py --streams 1` hands over per call (64 = two column groups of 32 per launch)
     ngroups = max(1, nb // 32)
+    # the vectors between the V-cycle levels (coarse right-hand side, coarse correction) are fp32 when the `res - (S P) xc` pass
+    # (the vc_residual_kernel instantiation tagged 1) gathers fp32 rows, fp64 otherwise (PMC_STORAGE_FP64, PMC_COARSE_F32=0)
+    sp_pass = lambda name: "vc_residual_kernel<32, " in name and ", 1>(" in name   # noqa: E731
+    c32 = any(sp_pass(r["kernel"]) and "vc_residual_kernel<32, float, " in r["kernel"] for r in stats)
     n = [l["rows"] for l in lv]
     V, F = 8.0 * nb, 4.0 * nb
+    CV = F if c32 else V          # one row of an inter-level vector
 
     def level_of(grid):           # slice kernels: grid = rows rounded up to a multiple of 256 threads (x column groups when
         for i, r in enumerate(n):  # the profiler reports the total grid)
@@ -57,7 +62,7 @@ def main():
             passes = 4.0          # pre-smoothing, residual, two products of the post-smoothing on every tail level but the last
             l2 = sum(12.0 * x["slots"] * passes for x in lv[t:-1]) + 12.0 * lv[-1]["slots"]
             return (f"LDS tail (levels of {[x['rows'] for x in lv[t:]]} rows, one workgroup per realization)",
-                    2 * V * n[t], {"l2_to_cu_bytes_per_workgroup_estimate": l2, "l2_to_cu_bytes_per_launch_estimate": l2 * nb,
+                    2 * (CV if t > 0 else V) * n[t], {"l2_to_cu_bytes_per_workgroup_estimate": l2, "l2_to_cu_bytes_per_launch_estimate": l2 * nb,
                                    "note": "every workgroup re-reads the tail levels' (index, value) pairs from L2 in each of its "
                                            "passes; the HBM bytes are the level's right-hand side in and correction out"})
         if "lincomb3_kernel" in name:
@@ -71,26 +76,30 @@ def main():
             return ("K5 on H with the fused <u, Hu>", 12.0 * lv[0]["nnz"] + 4.0 * n[0] + (zb * nb + V) * n[0], None)
         if "vc_poly2_kernel<32, double, float, float, false" in name:
             return (f"pre-smoothing, V-cycle level {l}", 12.0 * lv[l]["nnz"] + 12.0 * n[l] + (V + F) * n[l], None)
+        # fp32 right-hand side below the top: the post-smoothing of such a level has the same leading arguments and gathers an
+        # fp32 coarse correction (last template argument float), the pre-smoothing gathers none (default: double)
+        if "vc_poly2_kernel<32, float, float, float, false" in name and l > 0 and c32 and not name.split("(")[0].endswith(", float>"):
+            return (f"pre-smoothing (fp32 coarse right-hand side), V-cycle level {l}", 12.0 * lv[l]["nnz"] + 12.0 * n[l] + 2 * F * n[l], None)
         if "vc_poly2_kernel<32, float, float, float, false" in name and l == 0:
             return ("pre-smoothing from the fp32 copy of r, V-cycle level 0", 12.0 * lv[0]["nnz"] + 12.0 * n[0] + 2 * F * n[0], None)
+        if sp_pass(name) or "vc_residual_kernel<32, double, float, float, false" in name:
+            return (f"res - (S P) xc, V-cycle level {l}", 12.0 * lv[l]["sp_nnz"] + 4.0 * n[l] + 2 * F * n[l] + CV * nxt, None)
         if "vc_residual_kernel<32, float, double, float, false" in name or "vc_residual_kernel<32, float, float, float, false" in name:
             fused = bool(lv[l]["fused_restriction"])
             rin = F if "float, float, float" in name else V
-            b = 12.0 * lv[l]["nnz"] + 4.0 * n[l] + (rin + 2 * F) * n[l] + ((8.0 + V) * nxt if fused else 0.0)
+            b = 12.0 * lv[l]["nnz"] + 4.0 * n[l] + (rin + 2 * F) * n[l] + ((8.0 + CV) * nxt if fused else 0.0)
             return (f"residual{' + fused restriction' if fused else ''}{' (fp32 r)' if rin == F else ''}, V-cycle level {l}", b, None)
-        if "vc_residual_kernel<32, double, float, float, false" in name:
-            return (f"res - (S P) xc, V-cycle level {l}", 12.0 * lv[l]["sp_nnz"] + 4.0 * n[l] + 2 * F * n[l] + V * nxt, None)
         if "vc_poly2_kernel<32, float, " in name:     # (DOT variants on level 0, the level-1 post-smoothing: gathers fp32 residuals)
-            out = zb * nb if l == 0 else V
+            out = zb * nb if l == 0 else CV
             return (f"post-smoothing + coarse correction{' + fused <r, z>' if l == 0 else ''}, V-cycle level {l}",
-                    12.0 * lv[l]["nnz"] + 12.0 * n[l] + (2 * F + V + out) * n[l] + V * nxt, None)
+                    12.0 * lv[l]["nnz"] + 12.0 * n[l] + (2 * F + V + out) * n[l] + CV * nxt, None)
         return None
 
     def price_restriction(grid):
         # the separate restriction's grid follows its COARSE rows: P^T of level l has n[l + 1] rows
         for i in range(len(n) - 1):
             if (n[i + 1] + 255) // 256 * 256 in (grid, grid // ngroups):
-                return (f"restriction P^T res (separate product), V-cycle level {i}", 12.0 * n[i] + 4.0 * n[i + 1] + F * n[i] + V * n[i + 1])
+                return (f"restriction P^T res (separate product), V-cycle level {i}", 12.0 * n[i] + 4.0 * n[i + 1] + F * n[i] + CV * n[i + 1])
         return None
 
     def counter(rows, name, grid):
