@@ -1799,9 +1799,22 @@ __global__ __launch_bounds__(kBlock) void minres_wx_kernel(size_t nflat, const d
     store_c_nt<NT, C>(x + e, xv);
 }
 
-// The w / x updates of B.cnt <= kWxDefer iterations in one pass (see kWxDefer): the u vectors of all pending iterations are
-// requested first, the recurrences then run in registers in iteration order - the same operations in the same order as
-// cnt successive minres_wx launches.
+// a flat vector entry in its storage type (fp32-stored vectors are widened only where they are consumed)
+template <bool NT, typename UT, int C>
+__device__ __forceinline__ void load_raw_nt(const UT* __restrict__ p, RawVec<UT, C>& r) {
+    if constexpr (NT) {
+#pragma unroll
+        for (int i = 0; i < C; ++i) r.v[i] = __builtin_nontemporal_load(p + i);
+    } else {
+        load_raw<C>(p, r);
+    }
+}
+
+// The w / x updates of B.cnt <= kWxWindow iterations in one pass (see kWxWindow): the pending iterations are walked in
+// trips of kWxDefer - the u vectors of a trip are requested first (and stay in their storage type until their FMA), the
+// recurrences then run in registers in iteration order, w0 / w1 / x stay in registers from trip to trip - the same
+// operations in the same order as cnt successive minres_wx launches.  B.first: w0 and w1 are zero, and with B.x_zero so
+// is x: they start as literal zeros (the same bits as a loaded +0.0); B.last: w0 / w1 are never read again and not stored.
 template <int NB, bool NT, typename UT>
 __global__ __launch_bounds__(kBlock) void minres_wx_deferred_kernel(size_t nflat, k::WxDeferred B,
                                                                     const double* __restrict__ cW, double* __restrict__ w0,
@@ -1811,28 +1824,43 @@ __global__ __launch_bounds__(kBlock) void minres_wx_deferred_kernel(size_t nflat
     if (i >= nflat) return;
     const size_t e = i * C;
     const int k0 = (int)(e % row_ld<NB>(ld));
-    double uv[k::kWxDefer][C], a[C], b[C], xv[C];
+    double a[C], b[C], xv[C];
+    if (B.first) {
 #pragma unroll
-    for (int j = 0; j < k::kWxDefer; ++j)
-        if (j < B.cnt) load_v_nt<NT, C>(static_cast<const UT*>(B.u[j]) + e, uv[j]);
-    load_c_nt<NT, C>(w0 + e, a);
-    load_c_nt<NT, C>(w1 + e, b);
-    load_c_nt<NT, C>(x + e, xv);
+        for (int c = 0; c < C; ++c) a[c] = b[c] = 0.0;
+    } else {
+        load_c_nt<NT, C>(w0 + e, a);
+        load_c_nt<NT, C>(w1 + e, b);
+    }
+    if (B.first && B.x_zero) {
 #pragma unroll
-    for (int j = 0; j < k::kWxDefer; ++j) {
-        if (j < B.cnt) {
-            const double* cj = cW + (size_t)B.slot[j] * 4 * kMaxBatch + k0;
+        for (int c = 0; c < C; ++c) xv[c] = 0.0;
+    } else {
+        load_c_nt<NT, C>(x + e, xv);
+    }
+    for (int t = 0; t < B.cnt; t += k::kWxDefer) {
+        RawVec<UT, C> uv[k::kWxDefer];
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const double wn = cj[c] * uv[j][c] + cj[kMaxBatch + c] * a[c] + cj[2 * kMaxBatch + c] * b[c];
-                xv[c] += cj[3 * kMaxBatch + c] * wn;
-                a[c] = b[c];
-                b[c] = wn;
+        for (int j = 0; j < k::kWxDefer; ++j)
+            if (t + j < B.cnt) load_raw_nt<NT>(static_cast<const UT*>(B.u[t + j]) + e, uv[j]);
+#pragma unroll
+        for (int j = 0; j < k::kWxDefer; ++j) {
+            if (t + j < B.cnt) {
+                const double* cj = cW + (size_t)B.slot[t + j] * 4 * kMaxBatch + k0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const double wn = cj[c] * (double)uv[j].v[c] + cj[kMaxBatch + c] * a[c] + cj[2 * kMaxBatch + c] * b[c];
+                    xv[c] += cj[3 * kMaxBatch + c] * wn;
+                    a[c] = b[c];
+                    b[c] = wn;
+                }
             }
         }
     }
-    store_c_nt<NT, C>(w0 + e, a);
-    store_c_nt<NT, C>(w1 + e, b);
+    if (!B.last) {
+        store_c_nt<NT, C>(w0 + e, a);
+        store_c_nt<NT, C>(w1 + e, b);
+    }
     store_c_nt<NT, C>(x + e, xv);
 }
 
@@ -3681,7 +3709,7 @@ void minres_wx(hipStream_t st, int nb, int n, const double* c0, zvec u, const do
 void minres_wx_deferred(hipStream_t st, int nb, int n, const MinresState* s, const WxDeferred& B, double* w0, double* w1,
                         double* x) {
     if (n == 0 || B.cnt == 0) return;
-    if (B.cnt < 0 || B.cnt > kWxDefer) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: bad count");
+    if (B.cnt < 0 || B.cnt > kWxWindow) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: bad count");
     const double* cW = reinterpret_cast<const double*>(reinterpret_cast<const char*>(s) + offsetof(MinresState, cW));
     const bool nt = nt_flat((size_t)n * nb);
     PMC_DISPATCH_NB(nb, {

@@ -91,20 +91,29 @@ void count_kernel_launches(int n);
 
 namespace k {
 
-// The w / x updates of up to kWxDefer consecutive MINRES iterations are applied in ONE pass over the vectors
+// The w / x updates of up to kWxWindow consecutive MINRES iterations are applied in ONE pass over the vectors
 // (minres_wx_deferred): nothing reads w or x before the solve ends, and every update needs only its own iteration's
-// coefficients and preconditioned vector.  One pass costs (kWxDefer + 5) vector streams instead of 6 kWxDefer.
-// (round 5: 8 instead of 4 - per iteration (8 x 4 + 6 x 8) / 8 = 10 bytes per entry instead of 16 with fp32-stored u; the ring
-// of preconditioned vectors grows from 5 to 9)
+// coefficients and preconditioned vector.  A pass over c iterations costs c streams of the preconditioned vectors plus
+// the w0 / w1 / x it carries from the pass before to the pass after - so the window is as long as memory allows
+// (minres_solve picks it per solve, 8 ... kWxWindow): a solve that fits into one window reads every preconditioned vector
+// once and writes x once, nothing else (the first pass starts from literal zeros instead of loading w0 / w1 / x, the last
+// pass does not store w0 / w1).  With fp32-stored u, 20 iterations: 4 x 21 + 8 = 92 bytes per entry and solve; with the
+// window of 8 of round 5 it was 228 plus 24 of fills.
+// kWxDefer is the number of preconditioned vectors ONE TRIP of the kernel has in flight: a pass walks its window in trips
+// of kWxDefer, w0 / w1 / x stay in registers across the trips (round 5: 8 instead of 4).
 #ifndef PMC_WX_DEFER_N
 #define PMC_WX_DEFER_N 8
 #endif
 static constexpr int kWxDefer = PMC_WX_DEFER_N;
+static constexpr int kWxWindow = 32;
 struct WxDeferred {
-    const void* u[kWxDefer];    // preconditioned vectors of the pending iterations (rows of the maintained block), oldest first
-    int slot[kWxDefer];          // coefficient set (MinresState::cW ring) of each
+    const void* u[kWxWindow];   // preconditioned vectors of the pending iterations (rows of the maintained block), oldest first
+    int slot[kWxWindow];         // coefficient set (MinresState::cW ring) of each
     int cnt;
     bool f32;                    // storage of the u vectors
+    bool first;                  // nothing applied yet in this solve: w0 = w1 = 0, not loaded
+    bool x_zero;                 // ... and the initial guess is zero: x not loaded either
+    bool last;                   // nothing follows in this solve: w0 / w1 not stored
 };
 
 // Device-resident MINRES scalars, one entry per batch column.
@@ -113,12 +122,14 @@ struct MinresState {
     double gamma0[kMaxBatch], gamma1[kMaxBatch], sigma0[kMaxBatch], sigma1[kMaxBatch];
     double goal[kMaxBatch], alpha[kMaxBatch], delta[kMaxBatch], rho2[kMaxBatch], rho3[kMaxBatch];
     double cV[3][kMaxBatch];  // v_new = cV0*q + cV1*v1 + cV2*v0
-    // w_new = cW0*u1 + cW1*w0 + cW2*w1 ; x += cW3*w_new.  Iteration i (0-based) writes set i % ring: ring == 1 when the
-    // update follows its iteration at once, kWxDefer when updates are deferred
-    double cW[kWxDefer][4][kMaxBatch];
     int active[kMaxBatch], iters[kMaxBatch], flag[kMaxBatch];
     int n_active, it, ring;
+    // w_new = cW0*u1 + cW1*w0 + cW2*w1 ; x += cW3*w_new.  Iteration i (0-based) writes set i % ring: ring == 1 when the
+    // update follows its iteration at once, the solve's window when updates are deferred.  LAST member: the host reads
+    // only what precedes it (kMinresHeadBytes) at the end of a solve.
+    double cW[kWxWindow][4][kMaxBatch];
 };
+static constexpr size_t kMinresHeadBytes = offsetof(MinresState, cW);
 
 // y = A x (accumulate=false) or y += A x.  If dot_partial != nullptr (accumulate must be false) also
 // writes per-block partial sums of <dot_with, A x>; returns the number of partial blocks written.
@@ -222,7 +233,8 @@ struct DotParts {
 };
 void minres_init(hipStream_t st, int nb, MinresState* s, const DotParts& d, double rel_tol, double abs_tol, int ring = 1);
 // the pending w / x updates of B.cnt iterations on n rows: for j < cnt  w = cW0 u_j + cW1 w0 + cW2 w1; x += cW3 w;
-// (w0, w1) <- (w1, w).  w0 is the OLDER direction on entry and on return (no role swap by the caller).
+// (w0, w1) <- (w1, w).  w0 is the OLDER direction on entry and on return (no role swap by the caller).  B.first: w0 / w1
+// (with B.x_zero also x) hold nothing yet and count as zeros; B.last: w0 / w1 are left as they are.
 void minres_wx_deferred(hipStream_t st, int nb, int n, const MinresState* s, const WxDeferred& B, double* w0, double* w1,
                         double* x);
 void minres_scal1(hipStream_t st, int nb, MinresState* s, const DotParts& d);

@@ -505,6 +505,26 @@ static size_t sampler_wide_rows(int device) {
     return v;
 }
 
+// Bytes one solve may spend on the ring of preconditioned vectors behind the deferred w / x update: 1/128 of the device's
+// TOTAL memory (deterministic, see above; 2.4 GB of 309).  The ring holds window + 1 vectors, and only as many as the solve
+// has iterations: config 2 (0.4 M multipliers x 64, fp32: 103 MB per vector) gets a window of 22 and needs 2.2 GB for the 21
+// vectors of its 20 iterations.  Levels with vectors of 0.4 GB (r = 6; config 5's 6.46 M-row level, which fills the device
+// with four lanes - 1/16 of the memory, a window of 32, ran r = 6 and ran config 5 out of memory) stay at the window of 8
+// they had.  Unknown total: 0, i.e. the shortest window.
+static size_t wx_ring_budget(int device) {
+    static std::atomic<size_t> cache[64];
+    const int slot = device & 63;
+    size_t v = cache[slot].load(std::memory_order_relaxed);
+    if (v == 0) {
+        size_t total_b = 0;
+        hipDevice_t dev;
+        if (hipDeviceGet(&dev, device) != hipSuccess || hipDeviceTotalMem(&total_b, dev) != hipSuccess) total_b = 0;
+        v = total_b / 128 + 1;
+        cache[slot].store(v, std::memory_order_relaxed);
+    }
+    return v - 1;
+}
+
 int batch_width(size_t rows, bool darcy, int device) {
     static const auto lim = [](const char* name, size_t dflt) {
         const char* e = lab_env(name);
@@ -543,6 +563,18 @@ static bool wx_defer_on() {
     return v;
 }
 
+// Iterations whose w / x updates one pass applies in a solve with vectors of `vec_bytes`: as many as the ring budget holds,
+// at least 8 (round 5's window) and at most k::kWxWindow.  PMC_WX_WINDOW=n (laboratory builds): n, 1 ... kWxWindow.
+static int wx_window(int device, size_t vec_bytes) {
+    static const int lab = [] {
+        const char* e = lab_env("PMC_WX_WINDOW");
+        return e ? std::min(std::max(atoi(e), 1), k::kWxWindow) : 0;
+    }();
+    if (lab) return lab;
+    const size_t fit = wx_ring_budget(device) / std::max<size_t>(vec_bytes, 1);
+    return (int)std::min<size_t>(std::max<size_t>(fit, 9) - 1, (size_t)k::kWxWindow);
+}
+
 // PMC_LATE_WX=0 keeps the w / x update inside its own iteration also on two streams (A/B switch)
 static bool late_wx() {
     static const bool v = [] {
@@ -573,16 +605,29 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     // v1 = b - A x0
     if (x_rows && !zero_guess) throw Error(PMC_ERR_INTERNAL, "minres: compact solution needs a zero initial guess");
     if (!A.apply_z || (!zero_guess && !A.apply)) throw Error(PMC_ERR_INTERNAL, "minres: operator closures missing");
+    if (x_row0 < 0 || x_nrows < 0 || (!x_rows && x_row0 + x_nrows > n))
+        throw Error(PMC_ERR_INTERNAL, "minres: bad solution row range");
+    const size_t xoff = (size_t)x_row0 * nb;
+    const int every = o.check_every > 0 ? o.check_every : 1;
+    const bool graphs = hint.key != 0 && o.use_graph != 0 && every == 2;
+    const bool late = L.split && !graphs && A.n0 > 0 && A.n0 < n && late_wx();
+    // w / x updates of a whole window of iterations in one pass (see k::minres_wx_deferred): whenever the update is a plain
+    // vector kernel on this stream - not the compact index-list update of the Darcy solves (a few rows), not the two-stream
+    // schedule (its update already runs beside other work) and not inside a captured graph.  Its first pass starts w0, w1
+    // and (zero guess) the maintained rows of x from literal zeros, so none of the three is filled here.
+    const bool defer = !graphs && !late && !x_rows && wx_defer_on();
     if (zero_guess) {
-        k::fill(st, x_rows ? (size_t)x_nrows * nb : len, x, 0.0);
+        if (defer) {   // only the rows the update never writes
+            k::fill(st, xoff, x, 0.0);
+            k::fill(st, len - xoff - (size_t)x_nrows * nb, x + xoff + (size_t)x_nrows * nb, 0.0);
+        } else {
+            k::fill(st, x_rows ? (size_t)x_nrows * nb : len, x, 0.0);
+        }
         k::copy(st, len, b, v1);
     } else {
         A.apply(L, nb, x, v1, nullptr, nullptr);
         axpby(st, len, 1.0, b, -1.0, v1);
     }
-    if (x_row0 < 0 || x_nrows < 0 || (!x_rows && x_row0 + x_nrows > n))
-        throw Error(PMC_ERR_INTERNAL, "minres: bad solution row range");
-    const size_t xoff = (size_t)x_row0 * nb;
     const size_t seg2 = (size_t)dot_capacity(n, nb) * nb;
     const bool r32 = w.want_r32 && z32;
     if (r32) {
@@ -592,17 +637,13 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     }
     k::DotParts dp = prec(L, nb, v1, u1, w.partial.p, w.partial.p + seg2);
     if (dp.total() == 0) dp = k::DotParts{w.partial.p, k::dot_z(st, nb, n, v1, u1, w.partial.p)};
-    const int every = o.check_every > 0 ? o.check_every : 1;
-    const bool graphs = hint.key != 0 && o.use_graph != 0 && every == 2;
-    const bool late = L.split && !graphs && A.n0 > 0 && A.n0 < n && late_wx();
-    // w / x updates of kWxDefer iterations in one pass (see k::minres_wx_deferred): whenever the update is a plain vector
-    // kernel on this stream - not the compact index-list update of the Darcy solves (a few rows), not the two-stream
-    // schedule (its update already runs beside other work) and not inside a captured graph
-    const bool defer = !graphs && !late && !x_rows && wx_defer_on();
-    k::minres_init(st, nb, S, dp, o.rel_tol, o.abs_tol, defer ? k::kWxDefer : 1);
+    const int window = defer ? wx_window(ctx.device, len * (z32 ? sizeof(float) : sizeof(double))) : 1;
+    k::minres_init(st, nb, S, dp, o.rel_tol, o.abs_tol, window);
     k::fill(st, len, v0, 0.0);
-    k::fill(st, len, w0, 0.0);
-    k::fill(st, len, w1, 0.0);
+    if (!defer) {
+        k::fill(st, len, w0, 0.0);
+        k::fill(st, len, w1, 0.0);
+    }
 
     auto coef = [&](size_t off) { return reinterpret_cast<const double*>(reinterpret_cast<const char*>(S) + off); };
     const double* cV0 = coef(offsetof(k::MinresState, cV));
@@ -750,34 +791,47 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
             n_active = poll();
         }
     } else if (defer) {
-        // ring of kWxDefer + 1 preconditioned vectors: the pending iterations' z stay alive until their updates are flushed
-        constexpr int R = k::kWxDefer + 1;
-        if ((int)w.ring.size() < R - 2) w.ring.resize(R - 2);
-        zvec ub[R];
+        // up to window + 1 preconditioned vectors: the pending iterations' z stay alive until their updates are flushed.
+        // ub[c] holds the preconditioned vector of the current Lanczos vector, the iteration writes the next one to
+        // ub[c + 1]; a flush frees all but that one, which moves to the front.  Buffers beyond u0 / u1 are allocated when
+        // an iteration first reaches them: a solve of 20 iterations owns 21 vectors, whatever the window.
+        zvec ub[k::kWxWindow + 1];
         ub[0] = u1;
         ub[1] = u0;
-        for (int j = 2; j < R; ++j) {
-            w.ring[(size_t)j - 2].ensure(len, z32);
-            ub[j] = w.ring[(size_t)j - 2].v(z32);
-        }
-        int c = 0;                                   // ub[c] holds the preconditioned vector of the current Lanczos vector
+        int have = 2, c = 0;
         k::WxDeferred pending{};
         pending.f32 = z32;
-        auto flush = [&]() {
+        pending.first = true;
+        pending.x_zero = zero_guess;
+        auto flush = [&](bool last) {
+            if (pending.cnt == 0) return;
+            pending.last = last;
             k::minres_wx_deferred(st, nb, x_nrows, S, pending, w0, w1, x + xoff);
             pending.cnt = 0;
+            pending.first = false;
+            std::swap(ub[0], ub[c]);
+            c = 0;
         };
         while (n_active > 0 && it < o.max_iter) {
             ++it;
-            iteration(ub[(c + 1) % R], ub[c], v0, v1, w0, w1, it == o.max_iter);
+            if (c + 1 == have) {
+                if (w.ring.size() < (size_t)have - 1) w.ring.resize((size_t)have - 1);
+                w.ring[(size_t)have - 2].ensure(len, z32);
+                ub[have] = w.ring[(size_t)have - 2].v(z32);
+                ++have;
+            }
+            iteration(ub[c + 1], ub[c], v0, v1, w0, w1, it == o.max_iter);
             pending.u[pending.cnt] = (ub[c] + xoff).p;
-            pending.slot[pending.cnt] = (it - 1) % k::kWxDefer;
-            if (++pending.cnt == k::kWxDefer) flush();
-            c = (c + 1) % R;
+            pending.slot[pending.cnt] = (it - 1) % window;
+            ++pending.cnt;
+            ++c;
+            if (pending.cnt == window) flush(it == o.max_iter);
             std::swap(v0, v1);
             if ((it % every == 0 && (it >= first_poll || it == mid_poll)) || it == o.max_iter) n_active = poll();
         }
-        flush();
+        flush(true);
+        // no iteration at all (zero right-hand side, max_iter == 0): nothing has written the maintained rows of x
+        if (pending.first && zero_guess) k::fill(st, (size_t)x_nrows * nb, x + xoff, 0.0);
     } else {
         while (n_active > 0 && it < o.max_iter) {
             ++it;
@@ -799,12 +853,12 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         flush_wx(st);
     }
     out.iterations = it;
-    static_assert(sizeof(k::MinresState) <= Ctx::kHostScratch * sizeof(double), "pinned scratch too small");
-    PMC_HIP(hipMemcpyAsync(ctx.h_scal, S, sizeof(k::MinresState), hipMemcpyDeviceToHost, st));
+    // the scalars only: the coefficient ring behind them (k::MinresState::cW, 256 KB) stays on the device
+    static_assert(k::kMinresHeadBytes <= Ctx::kHostScratch * sizeof(double), "pinned scratch too small");
+    PMC_HIP(hipMemcpyAsync(ctx.h_scal, S, k::kMinresHeadBytes, hipMemcpyDeviceToHost, st));
     PMC_HIP(hipStreamSynchronize(st));
     if (timing) w.op_timer.harvest();
-    k::MinresState hs;
-    std::memcpy(&hs, ctx.h_scal, sizeof(hs));
+    const k::MinresState& hs = *reinterpret_cast<const k::MinresState*>(ctx.h_scal);   // members before cW only
     int max_it = 0;
     for (int kcol = 0; kcol < nb; ++kcol) {
         pmc_stats& s = out.col[kcol];

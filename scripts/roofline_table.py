@@ -48,6 +48,9 @@ def main():
     V, F = 8.0 * nb, 4.0 * nb
     CV = F if c32 else V          # one row of an inter-level vector
 
+    calls = lambda key: sum(int(r["calls"]) for r in stats if key in r["kernel"] and "<32, " in r["kernel"])   # noqa: E731
+    wx_iters = calls("lincomb3_kernel") / max(1, calls("minres_wx_deferred_kernel"))
+
     def level_of(grid):           # slice kernels: grid = rows rounded up to a multiple of 256 threads (x column groups when
         for i, r in enumerate(n):  # the profiler reports the total grid)
             if (r + 255) // 256 * 256 in (grid, grid // ngroups):
@@ -68,7 +71,11 @@ def main():
         if "lincomb3_kernel" in name:
             return ("Lanczos update v = c0 q + c1 v1 + c2 v0 (+ the fp32 copy the V-cycle reads)", (4 * V + (F if zb == 4 else 0)) * n[0], None)
         if "minres_wx_deferred_kernel" in name:
-            return ("w / x update, eight iterations per launch", (8 * zb * nb + 6 * V) * n[0], None)
+            # priced by the iterations a pass carried (Lanczos updates per w / x launch of this profile): a pass that carries
+            # less than the full window of 32 is the only one of its solve - it reads the preconditioned vectors and writes x,
+            # nothing else; full windows also carry w0 / w1 / x in and out
+            c = wx_iters
+            return (f"w / x update, {c:.0f} iterations per launch", (c * zb * nb + (V if c < 32 else 6 * V)) * n[0], None)
         if l is None:
             return None
         nxt = n[l + 1] if l + 1 < len(n) else 0
