@@ -260,7 +260,7 @@ typedef struct pmc_kl_level {
     pmc_csr P;            /* n_s(level) x n_s(level+1); ignored (may be zeroed) on the last level */
 } pmc_kl_level;
 /* KLSampler over what CovarianceFunction::Eigenvalues() / Eigenvectors() hold after SolveEigenvalue() (the caller runs its
- * own eigensolver on the host, as the reference does): evals (nmodes, each finite and >= 0) and evect0 (n_s(0) x nmodes,
+ * own eigensolver on the host, as the reference does, or pmc_kl_matern_eigs below): evals (nmodes, each finite and >= 0) and evect0 (n_s(0) x nmodes,
  * column-major = mfem::DenseMatrix::Data()).  The handle projects Phi to the coarser levels itself at create,
  * Phi_{l+1} = D^-1 P^T W_l Phi_l, without renormalising the coarse columns (KLSampler::BuildHierarchy).  Every level is a
  * Monte Carlo level.  nmodes > n_s of a level is refused: the reference reads past xi there (Sample draws n_s normals,
@@ -274,6 +274,44 @@ typedef struct pmc_kl_level {
 int pmc_sampler_create_kl(pmc_ctx* ctx, int nlevels, const pmc_kl_level* levels, int nmodes, const double* evals,
                           const double* evect0, int lognormal, pmc_sampler** out);
 int pmc_sampler_is_kl(const pmc_sampler* s);
+/* ---- MaternCovariance::SolveEigenvalue on the device (src/MaternCovariance.cpp:357-420) -------------------------- */
+/* The top m = min(nmodes, n) eigenpairs of A v = lambda W v, A = W C W, W = diag(w_diag), C_ij = c(|x_i - x_j|) at the element
+ * centres, c(r) = exp(-r / corlen) (the 3D Matern kernel with nu = 1/2; c = 1 where r / corlen < 1e-10), without ever
+ * storing C: with y = W^1/2 v the problem is K y = lambda y, K = W^1/2 C W^1/2, and every product with K evaluates its entries
+ * on the fly (fp64 MFMA; O(n (m + guard)) memory).  Chebyshev-filtered subspace iteration on a block of m + guard columns
+ * (at most 512), filter degree `degree` on [0, smallest Ritz value], Rayleigh-Ritz after every filter; it stops when
+ * max_k ||K y_k - theta_k y_k||_2 <= tol theta_1 over the m wanted columns, or after max_iter filters.  The start block comes
+ * from the library's Philox generator with `seed`: the same seed, device and options give bitwise the same output.
+ * Output as pmc_sampler_create_kl takes it: evals ascending (m), evect0 n x m column-major with V^T W V = I, the entry of
+ * largest magnitude of every column (the first one on ties) positive.
+ * Not converged after max_iter is NOT an error: the call returns PMC_OK with the best pairs, info.converged = 0 and the
+ * residual reached, so pass `info` and read it.  gap_rel = (lambda_m - lambda_{m+1}) / lambda_1 from the guard Ritz values
+ * (0 when guard = 0 or m = n): near zero means the truncation cuts through a cluster and the last modes are an arbitrary
+ * rotation inside it.
+ * PMC_ERR_INVALID: dim != 3 (the 2D kernel needs the Bessel function K1; 2D meshes fit a dense host solve), w_diag not
+ * positive, coordinates not finite, corlen <= 0, nmodes < 1, m + guard > 512, a NULL pointer. */
+typedef struct pmc_kl_eigs_opts {
+    double tol;       /* 1e-8                                                        */
+    int32_t max_iter; /* 100 filter applications                                     */
+    int32_t guard;    /* 16 extra columns of the block                               */
+    int32_t degree;   /* 8, degree of the Chebyshev filter; keep it modest           */
+    uint64_t seed;    /* 0, seed of the start block                                  */
+} pmc_kl_eigs_opts;
+typedef struct pmc_kl_eigs_info {
+    int32_t iterations;      /* filters applied                                      */
+    int32_t block_products;  /* products of K with the whole block                   */
+    int32_t converged;       /* 1: the stop rule was met                             */
+    double max_residual_rel; /* max_k ||K y_k - theta_k y_k||_2 / theta_1, k < m      */
+    double gap_rel;          /* (lambda_m - lambda_{m+1}) / lambda_1                 */
+    double seconds;          /* wall time of the call                                */
+} pmc_kl_eigs_info;
+void pmc_kl_eigs_opts_default(pmc_kl_eigs_opts* opts);
+/* Y = K X: X and Y n x ncols column-major HOST arrays, centroids n x dim row-major, 1 <= ncols <= 512 (tests, benchmarks) */
+int pmc_kl_matern_apply(pmc_ctx* ctx, int dim, int n, const double* centroids, const double* w_diag, double corlen,
+                        int ncols, const double* X, double* Y);
+int pmc_kl_matern_eigs(pmc_ctx* ctx, int dim, int n, const double* centroids, const double* w_diag, double corlen,
+                       int nmodes, const pmc_kl_eigs_opts* opts /* NULL = defaults */, double* evals /* m */,
+                       double* evect0 /* n x m */, pmc_kl_eigs_info* info /* may be NULL */);
 void pmc_sampler_destroy(pmc_sampler* s);
 /* Output map of the embedded variants.  PMC_PROJ_GATHER: s = sbar[gather_idx]
  * (src/EmbeddedPDESampler.cpp:552-556); PMC_PROJ_L2: s = inv_w_orig .* (Gt sbar)

@@ -68,6 +68,16 @@ class pmc_kl_level(C.Structure):
     _fields_ = [("n_s", C.c_int32), ("w_diag", C.POINTER(C.c_double)), ("P", pmc_csr)]
 
 
+class pmc_kl_eigs_opts(C.Structure):
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("guard", C.c_int32), ("degree", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class pmc_kl_eigs_info(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("block_products", C.c_int32), ("converged", C.c_int32),
+                ("max_residual_rel", C.c_double), ("gap_rel", C.c_double), ("seconds", C.c_double)]
+
+
 class pmc_darcy_level(C.Structure):
     _fields_ = [("n_u", C.c_int32), ("n_p", C.c_int32), ("M_pattern", pmc_csr), ("c_ptr", C.POINTER(C.c_int32)),
                 ("c_elem", C.POINTER(C.c_int32)), ("c_val", C.POINTER(C.c_double)), ("B", pmc_csr),
@@ -109,6 +119,12 @@ SYMBOLS = {
     "pmc_sampler_create_kl": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_kl_level), C.c_int, C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.c_int, C.POINTER(_VP)]),
     "pmc_sampler_is_kl": (C.c_int, [_VP]),
+    "pmc_kl_eigs_opts_default": (None, [C.POINTER(pmc_kl_eigs_opts)]),
+    "pmc_kl_matern_apply": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pmc_kl_matern_eigs": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                     C.POINTER(pmc_kl_eigs_opts), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(pmc_kl_eigs_info)]),
     "pmc_hybrid_build": (C.c_int, [C.POINTER(pmc_hybrid_elements), C.c_double, C.POINTER(_VP)]),
     "pmc_hybrid_system_level": (C.c_int, [_VP, C.POINTER(pmc_hybrid_level)]),
     "pmc_hybrid_system_destroy": (None, [_VP]),
@@ -887,6 +903,42 @@ class LevelFields:
             self.close()
         except Exception:
             pass
+
+
+def kl_matern_apply(ctx, centroids, w_diag, corlen, X) -> np.ndarray:
+    """Y = K X on the device (pmc_kl_matern_apply): K = W^1/2 C W^1/2 of the 3D Matern kernel exp(-r / corlen), never stored.
+    centroids (n, dim), X (n,) or (n, ncols); returns Y of X's shape."""
+    x = _f64(centroids)
+    w = _f64(w_diag)
+    n, dim = x.shape
+    X = np.asarray(X, dtype=np.float64)
+    Xc = np.asfortranarray(X.reshape(n, -1))
+    Y = np.empty_like(Xc, order="F")
+    _check(ctx.lib.pmc_kl_matern_apply(ctx.h, dim, n, _ptr(x, C.c_double), _ptr(w, C.c_double), float(corlen), Xc.shape[1],
+                                       Xc.ctypes.data_as(C.POINTER(C.c_double)), Y.ctypes.data_as(C.POINTER(C.c_double))))
+    return np.ascontiguousarray(Y).reshape(X.shape)
+
+
+def kl_matern_eigs(ctx, centroids, w_diag, corlen, nmodes, tol=None, max_iter=None, guard=None, degree=None, seed=None):
+    """The top min(nmodes, n) eigenpairs of the Matern covariance on the device (pmc_kl_matern_eigs).  Returns
+    (evals ascending (m,), evect0 (n, m) with V^T W V = I, info dict of pmc_kl_eigs_info).  info["converged"] == 0 is not an
+    error: the pairs are the best reached after max_iter."""
+    x = _f64(centroids)
+    w = _f64(w_diag)
+    n, dim = x.shape
+    o = pmc_kl_eigs_opts()
+    ctx.lib.pmc_kl_eigs_opts_default(C.byref(o))
+    for name, val in (("tol", tol), ("max_iter", max_iter), ("guard", guard), ("degree", degree), ("seed", seed)):
+        if val is not None:
+            setattr(o, name, val)
+    m = max(1, min(int(nmodes), n))
+    evals = np.empty(m)
+    V = np.empty((n, m), order="F")
+    info = pmc_kl_eigs_info()
+    _check(ctx.lib.pmc_kl_matern_eigs(ctx.h, dim, n, _ptr(x, C.c_double), _ptr(w, C.c_double), float(corlen), int(nmodes),
+                                      C.byref(o), _ptr(evals, C.c_double), V.ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.byref(info)))
+    return evals, np.ascontiguousarray(V), {f: getattr(info, f) for f, _ in pmc_kl_eigs_info._fields_}
 
 
 class KLSampler(PDESampler):

@@ -336,6 +336,22 @@ int pmc_sampler_create_kl(pmc_ctx* c, int nlevels, const pmc_kl_level* levels, i
     });
 }
 int pmc_sampler_is_kl(const pmc_sampler* s) { return s ? (s->impl.kl ? 1 : 0) : PMC_ERR_INVALID; }
+void pmc_kl_eigs_opts_default(pmc_kl_eigs_opts* o) {
+    if (!o) return;
+    o->tol = 1e-8;
+    o->max_iter = 100;
+    o->guard = 16;
+    o->degree = 8;
+    o->seed = 0;
+}
+int pmc_kl_matern_apply(pmc_ctx* c, int dim, int n, const double* centroids, const double* w_diag, double corlen, int ncols,
+                        const double* X, double* Y) {
+    return guarded([&] { kl_matern_apply(c, dim, n, centroids, w_diag, corlen, ncols, X, Y); });
+}
+int pmc_kl_matern_eigs(pmc_ctx* c, int dim, int n, const double* centroids, const double* w_diag, double corlen, int nmodes,
+                       const pmc_kl_eigs_opts* opts, double* evals, double* evect0, pmc_kl_eigs_info* info) {
+    return guarded([&] { kl_matern_eigs(c, dim, n, centroids, w_diag, corlen, nmodes, opts, evals, evect0, info); });
+}
 // entry points that act on the linear system of an SPDE sampler: a KL handle has none
 static void refuse_kl(const pmc_sampler* s, const char* what) {
     PMC_REQUIRE(!s->impl.kl, std::string(what) + " is not defined on a KL sampler handle (pmc_sampler_create_kl)");

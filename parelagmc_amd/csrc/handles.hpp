@@ -158,6 +158,14 @@ struct LevelFields {
     void accumulate_weighted_device(int nbatch, const double* pf, const double* wf, const double* pc, const double* wc);
 };
 
+// kl_eigs.hip: the Matern covariance operator K = W^1/2 C W^1/2 applied matrix-free (Y = K X, host pointers, column-major
+// n x ncols) and its top eigenpairs by Chebyshev-filtered subspace iteration (pmc_kl_matern_apply / pmc_kl_matern_eigs).
+// Both validate their arguments themselves and throw Error.
+void kl_matern_apply(pmc_ctx* c, int dim, int n, const double* centroids, const double* w_diag, double corlen, int ncols,
+                     const double* X, double* Y);
+void kl_matern_eigs(pmc_ctx* c, int dim, int n, const double* centroids, const double* w_diag, double corlen, int nmodes,
+                    const pmc_kl_eigs_opts* opts, double* evals, double* evect0, pmc_kl_eigs_info* info);
+
 // kl.hip: s[b n + i] = sum_k phi[k n + i] xi[b n_xi + k] (exp() if lognormal, the Gaussian value to emb when non-NULL) for
 // b < nb, i < n, k < m, in fp64 (MFMA for nb > 4, a bandwidth GEMV below); phi column-major n x m.
 void kl_eval(hipStream_t st, int n, int m, int nb, const double* phi, const double* xi, int n_xi, double* s, double* emb,

@@ -145,19 +145,145 @@ def matern_covariance(h: Hierarchy, corlen: float) -> np.ndarray:
     return C
 
 
-def matern_eigs(h: Hierarchy, corlen: float, nmodes: int):
-    """(lambda, Phi0) of MaternCovariance with the dense symmetric solver: the top m = min(nmodes, NE) eigenpairs of the
-    generalised problem A v = lambda W v, A = W C W, W = diag(P0 mass), in LAPACK's ascending order (dsygvx, RANGE='I',
-    indices n - m + 1 .. n) and with V^T W V = I.  Dense O(NE^2) memory and O(NE^3) work: meant for NE up to about 16k."""
+def matern_eigs(h: Hierarchy, corlen: float, nmodes: int, eigensolver: str = "dense", ctx=None, **solver_opts):
+    """(lambda, Phi0) of MaternCovariance: the top m = min(nmodes, NE) eigenpairs of the generalised problem
+    A v = lambda W v, A = W C W, W = diag(P0 mass), in ascending order and with V^T W V = I.
+      eigensolver="dense"     LAPACK (dsygvx, RANGE='I', indices n - m + 1 .. n).  Dense O(NE^2) memory and O(NE^3) work:
+                              meant for NE up to about 16k.
+      eigensolver="filtered"  matern_eigs_filtered, the numpy twin of the device solver (O(NE (m + guard)) memory).
+      eigensolver="device"    pmc_kl_matern_eigs on the device of `ctx` (capi.Context): matrix-free, 3D only.
+    solver_opts (filtered / device): tol, max_iter, guard, degree, seed."""
     sp0 = h.spaces[0]
     n = sp0.n_s
     m = min(int(nmodes), n)
     w = sp0.vol
+    if eigensolver == "filtered":
+        lam, V, _ = matern_eigs_filtered(element_centroids(sp0.mesh), w, corlen, m, **solver_opts)
+        return lam, V
+    if eigensolver == "device":
+        if ctx is None:
+            raise ValueError("matern_eigs: eigensolver='device' needs ctx (a capi.Context)")
+        from .. import capi
+        lam, V, _ = capi.kl_matern_eigs(ctx, element_centroids(sp0.mesh), w, corlen, m, **solver_opts)
+        return lam, V
+    if eigensolver != "dense":
+        raise ValueError(f"unknown eigensolver {eigensolver!r} (dense | filtered | device)")
+    if solver_opts:
+        raise ValueError("matern_eigs: the dense solver takes no options")
     A = matern_covariance(h, corlen)
     A *= w[:, None]
     A *= w[None, :]
     lam, V = sla.eigh(A, np.diag(w), subset_by_index=[n - m, n - 1], driver="gvx")
     return lam, np.ascontiguousarray(V)
+
+
+def matern_apply_blocked(x: np.ndarray, w: np.ndarray, corlen: float, X: np.ndarray, rows: int = 1024) -> np.ndarray:
+    """Y = K X with K = W^1/2 C W^1/2, K_ij = sqrt(w_i) c(|x_i - x_j|) sqrt(w_j), K_ii = w_i, in row blocks of `rows`: never
+    holds more than rows x n entries of K.  Distances from sum (x_i - x_j)^2, as the device kernel takes them."""
+    x = np.asarray(x, dtype=np.float64)
+    n, dim = x.shape
+    sw = np.sqrt(w)
+    X = np.asarray(X, dtype=np.float64).reshape(n, -1)
+    Y = np.empty_like(X)
+    swX = sw[:, None] * X
+    for r0 in range(0, n, rows):
+        r1 = min(n, r0 + rows)
+        d2 = np.zeros((r1 - r0, n))
+        for d in range(dim):
+            diff = x[r0:r1, d:d + 1] - x[None, :, d]
+            d2 += diff * diff
+        C = matern_kernel(np.sqrt(d2), corlen, dim)
+        C[np.arange(r1 - r0), np.arange(r0, r1)] = 1.0
+        Y[r0:r1] = sw[r0:r1, None] * (C @ swX)
+    return Y
+
+
+def normalise_signs(V: np.ndarray) -> np.ndarray:
+    """the entry of largest magnitude of every column (the first one on ties) made positive"""
+    idx = np.argmax(np.abs(V), axis=0)
+    s = np.where(V[idx, np.arange(V.shape[1])] < 0.0, -1.0, 1.0)
+    return V * s[None, :]
+
+
+def _cholqr(X: np.ndarray) -> np.ndarray:
+    """unit columns, then Cholesky-QR until two passes ran without a shift"""
+    clean = 0
+    b = X.shape[1]
+    for _ in range(6):
+        X = X / np.sqrt((X * X).sum(0))[None, :]
+        G = X.T @ X
+        G = 0.5 * (G + G.T)
+        shifted = False
+        try:
+            L = np.linalg.cholesky(G)
+        except np.linalg.LinAlgError:
+            shifted = True
+            shift = 1e-13 * b
+            while True:
+                try:
+                    L = np.linalg.cholesky(G + shift * np.eye(b))
+                    break
+                except np.linalg.LinAlgError:
+                    shift *= 100.0
+        X = sla.solve_triangular(L, X.T, lower=True).T
+        clean += not shifted
+        if clean >= 2:
+            return X
+    raise RuntimeError("matern_eigs_filtered: the block could not be orthonormalised")
+
+
+def matern_eigs_filtered(x: np.ndarray, w: np.ndarray, corlen: float, nmodes: int, tol: float = 1e-8, max_iter: int = 100,
+                         guard: int = 16, degree: int = 8, seed: int = 0, rows: int = 1024):
+    """numpy twin of pmc_kl_matern_eigs: Chebyshev-filtered subspace iteration on K y = lambda y (y = W^1/2 v) with a block
+    of m + guard columns, filter of `degree` on [0, smallest Ritz value] scaled to 1 at the largest, Cholesky-QR twice and
+    Rayleigh-Ritz after every filter; stops when max_k ||K y_k - theta_k y_k|| <= tol theta_1 over the m wanted columns.
+    K is applied in row blocks (matern_apply_blocked).  Returns (lambda ascending (m), V (n, m) with V^T W V = I and the
+    sign rule of normalise_signs, info dict as pmc_kl_eigs_info).  The start block is numpy's Philox stream of `seed`, not the
+    device's: the two solvers agree to the tolerance, not bitwise."""
+    x = np.asarray(x, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    n = x.shape[0]
+    if x.shape[1] != 3:
+        raise ValueError("matern_eigs_filtered: 3D only (as the device solver)")
+    m = min(int(nmodes), n)
+    if m + guard > 512:
+        raise ValueError("matern_eigs_filtered: m + guard exceeds 512")
+    b = min(m + guard, n)
+    products = 0
+
+    def apply(X):
+        nonlocal products
+        products += 1
+        return matern_apply_blocked(x, w, corlen, X, rows)
+
+    def ritz(X):
+        Y = apply(X)
+        H = X.T @ Y
+        th, S = np.linalg.eigh(0.5 * (H + H.T))
+        th, S = th[::-1], S[:, ::-1]
+        return X @ S, Y @ S, th
+
+    X = np.random.Generator(np.random.Philox(seed)).standard_normal((n, b))
+    X, Y, th = ritz(_cholqr(X))
+    res = np.sqrt(((Y - X * th[None, :])[:, :m] ** 2).sum(0)).max() / th[0]
+    it = 0
+    while res > tol and it < max_iter:
+        it += 1
+        lo = max(th[-1], 1e-14 * th[0])
+        e = c = 0.5 * lo
+        sigma = e / (th[0] - c)
+        tau = 2.0 / sigma
+        P0, P1 = X, (Y - c * X) * (sigma / e)
+        for _ in range(2, degree + 1):
+            sigma2 = 1.0 / (tau - sigma)
+            P0, P1 = P1, (apply(P1) - c * P1) * (2.0 * sigma2 / e) - (sigma * sigma2) * P0
+            sigma = sigma2
+        X, Y, th = ritz(_cholqr(P1))
+        res = np.sqrt(((Y - X * th[None, :])[:, :m] ** 2).sum(0)).max() / th[0]
+    V = normalise_signs(np.ascontiguousarray((X[:, :m] / np.sqrt(w)[:, None])[:, ::-1]))
+    info = dict(iterations=it, block_products=products, converged=int(res <= tol), max_residual_rel=float(res),
+                gap_rel=float((th[m - 1] - th[m]) / th[0]) if b > m else 0.0)
+    return np.ascontiguousarray(th[:m][::-1]), V, info
 
 
 def kl_projector(P: sp.csr_matrix, w_fine: np.ndarray) -> sp.csr_matrix:
@@ -204,10 +330,12 @@ class KLProblem:
 
 
 def build_kl_sampler_problem(h: Hierarchy, covariance: str = "analytic", nmodes=None, domain_lengths=None, corlen=0.1,
-                             lognormal: bool = False, n_mc_levels: Optional[int] = None) -> KLProblem:
+                             lognormal: bool = False, n_mc_levels: Optional[int] = None, eigensolver: str = "dense",
+                             ctx=None, **solver_opts) -> KLProblem:
     """Everything pmc_sampler_create_kl takes.  analytic: nmodes = modes per axis (default 4 per axis, the
     CreateSamplerParameterList default), domain_lengths = the box (default: the finest mesh's extent from the origin);
-    matern: nmodes = total number of modes (default 64).  n_mc_levels defaults to the levels with at least m elements
+    matern: nmodes = total number of modes (default 64), eigensolver / ctx / solver_opts as matern_eigs takes them
+    ("device": the matrix-free solver on the GPU of ctx).  n_mc_levels defaults to the levels with at least m elements
     (the reference would read past xi on a level with fewer)."""
     dim = h.spaces[0].mesh.dim
     if covariance == "analytic":
@@ -215,7 +343,8 @@ def build_kl_sampler_problem(h: Hierarchy, covariance: str = "analytic", nmodes=
         dl = list(h.spaces[0].mesh.verts.max(axis=0)) if domain_lengths is None else list(domain_lengths)
         lam, phi0 = analytic_exponential_eigs(h, nm, dl, corlen)
     elif covariance == "matern":
-        lam, phi0 = matern_eigs(h, corlen, 64 if nmodes is None else int(nmodes))
+        lam, phi0 = matern_eigs(h, corlen, 64 if nmodes is None else int(nmodes), eigensolver=eigensolver, ctx=ctx,
+                                **solver_opts)
     else:
         raise ValueError(f"unknown covariance {covariance!r} (analytic | matern)")
     m = lam.size

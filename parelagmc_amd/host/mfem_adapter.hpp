@@ -261,6 +261,45 @@ class DeviceKLSampler : public DevicePDESampler {
           }) {}
 };
 
+/// MaternCovariance::SolveEigenvalue on the device for an MFEM caller: centroids n x 3 (row-major mfem::Vector of 3 n
+/// entries), the P0 mass diagonal; Eigenvalues() / Eigenvectors() feed DeviceKLSampler(device_id, cov.Eigenvalues(),
+/// cov.Eigenvectors(), n, levels, lognormal) unchanged.  Owns a context on `device_id` for the duration of the solve.
+class DeviceMaternCovariance {
+  public:
+    DeviceMaternCovariance(int device_id, const mfem::Vector& centroids, const mfem::Vector& w_diag, double corlen, int nmodes)
+        : device_(device_id), x_(centroids), w_(w_diag), corlen_(corlen), nmodes_(nmodes) {
+        if (centroids.Size() != 3 * w_diag.Size()) throw std::runtime_error("DeviceMaternCovariance: centroids must hold 3 n entries");
+        pmc_kl_eigs_opts_default(&opts_);
+    }
+    pmc_kl_eigs_opts& Options() { return opts_; }
+    void SolveEigenvalue() {
+        pmc_ctx* ctx = nullptr;
+        check(pmc_ctx_create(device_, &ctx), "pmc_ctx_create");
+        const int n = w_.Size(), m = nmodes_ < n ? nmodes_ : n;
+        evals_.SetSize(m);
+        evect_.assign((size_t)n * m, 0.0);
+        const int rc = pmc_kl_matern_eigs(ctx, 3, n, x_.GetData(), w_.GetData(), corlen_, m, &opts_, evals_.GetData(),
+                                          evect_.data(), &info_);
+        const std::string msg = rc == PMC_OK ? "" : pmc_last_error();
+        pmc_ctx_destroy(ctx);
+        if (rc != PMC_OK) throw std::runtime_error("pmc_kl_matern_eigs: " + msg);
+    }
+    const mfem::Vector& Eigenvalues() const { return evals_; }
+    const double* Eigenvectors() const { return evect_.data(); }   ///< n x Eigenvalues().Size(), column-major
+    const pmc_kl_eigs_info& Info() const { return info_; }
+
+  private:
+    int device_;
+    const mfem::Vector& x_;
+    const mfem::Vector& w_;
+    double corlen_;
+    int nmodes_;
+    pmc_kl_eigs_opts opts_;
+    pmc_kl_eigs_info info_{};
+    mfem::Vector evals_;
+    std::vector<double> evect_;
+};
+
 /// What DarcySolver precomputes on one level (src/DarcySolver.cpp:194-227,297-319,360-414) plus the element
 /// decomposition of ComputeMassOperator(uform, k): M(k)[p] = sum_t coef(k[c_elem[t]]) c_val[t], t in c_ptr[p]..c_ptr[p+1]
 struct DarcyLevelOps {

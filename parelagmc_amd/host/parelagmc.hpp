@@ -7,6 +7,7 @@
 //   NormalDistributionSampler src/NormalDistributionSampler.hpp:27-64
 //   PDESampler                src/PDESampler.hpp (Sample/Eval/SampleSize/GetNNZ)
 //   KLSampler                 src/KLSampler.hpp (the same methods over a pmc_sampler_create_kl handle)
+//   MaternCovariance          src/MaternCovariance.hpp (SolveEigenvalue / Eigenvalues / Eigenvectors over pmc_kl_matern_eigs)
 //   DarcySolver               src/DarcySolver.hpp (SolveFwd/GetNumberOfDofs/GetNNZ)
 //   MLMC_Manager              src/MLMC_Manager.hpp:24-181
 //   MC_Manager                src/MC_Manager.hpp
@@ -184,6 +185,41 @@ class PDESampler : public MLSampler {
 class KLSampler : public PDESampler {
   public:
     using PDESampler::PDESampler;
+};
+
+/// MaternCovariance on the finest level, solved on the device without storing the covariance matrix (pmc_kl_matern_eigs;
+/// 3D only).  centroids: n x 3 row-major element centres, w_diag: the P0 mass diagonal; both are read by SolveEigenvalue()
+/// and must live until then.  Eigenvalues() ascend, Eigenvectors() is n x NumberOfModes() column-major with V^T W V = I:
+/// what pmc_sampler_create_kl (KLSampler) and mfem_adapter::DeviceKLSampler take.  Not converged within max_iter is not
+/// an exception: read Info().converged.
+class MaternCovariance {
+  public:
+    MaternCovariance(pmc_ctx* ctx, int n, const double* centroids, const double* w_diag, double corlen, int nmodes)
+        : ctx_(ctx), n_(n), x_(centroids), w_(w_diag), corlen_(corlen), m_(nmodes < n ? nmodes : n) {
+        pmc_kl_eigs_opts_default(&opts_);
+    }
+    pmc_kl_eigs_opts& Options() { return opts_; }
+    void SolveEigenvalue() {
+        if (m_ < 1) throw std::runtime_error("MaternCovariance: need at least one mode");
+        evals_.assign((size_t)m_, 0.0);
+        evect_.assign((size_t)n_ * m_, 0.0);
+        if (pmc_kl_matern_eigs(ctx_, 3, n_, x_, w_, corlen_, m_, &opts_, evals_.data(), evect_.data(), &info_) != PMC_OK)
+            throw std::runtime_error(std::string("MaternCovariance::SolveEigenvalue: ") + pmc_last_error());
+    }
+    int NumberOfModes() const { return m_; }
+    const std::vector<double>& Eigenvalues() const { return evals_; }
+    const std::vector<double>& Eigenvectors() const { return evect_; }
+    const pmc_kl_eigs_info& Info() const { return info_; }
+
+  private:
+    pmc_ctx* ctx_;
+    int n_;
+    const double *x_, *w_;
+    double corlen_;
+    int m_;
+    pmc_kl_eigs_opts opts_;
+    pmc_kl_eigs_info info_{};
+    std::vector<double> evals_, evect_;
 };
 
 /// The drivers' per-level statistics (PDESamplerTest.cpp:205-274) on the device: an owning wrapper of pmc_field_stats.
