@@ -597,7 +597,12 @@ void kl_matern_eigs(pmc_ctx* c, int dim, int n, const double* centroids, const d
     while (!converged && it < o.max_iter) {
         ++it;
         // Chebyshev filter of degree d on [0, theta_b], scaled to 1 at theta_1 (three-term form: no power of K is formed)
-        const double lo = std::max(theta[(size_t)b - 1], 1e-14 * theta[0]);
+        // Without a guard column (b == m < n) theta_b is a wanted value: at the edge of the damped interval it would be
+        // scaled by exactly 1 while the unwanted values inside reach 1 at the extrema of the polynomial, and column m would
+        // never separate.  The interval ends at 0.9 theta_b then: theta_m lies outside, where the polynomial grows
+        // monotonically, so it gains on every smaller eigenvalue whatever the true gap is.
+        const double top = (b == m && b < n) ? 0.9 * theta[(size_t)b - 1] : theta[(size_t)b - 1];
+        const double lo = std::max(top, 1e-14 * theta[0]);
         const double e = 0.5 * lo, cc = 0.5 * lo;
         double sigma = e / (theta[0] - cc);
         const double tau = 2.0 / sigma;

@@ -235,8 +235,8 @@ def _cholqr(X: np.ndarray) -> np.ndarray:
 def matern_eigs_filtered(x: np.ndarray, w: np.ndarray, corlen: float, nmodes: int, tol: float = 1e-8, max_iter: int = 100,
                          guard: int = 16, degree: int = 8, seed: int = 0, rows: int = 1024):
     """numpy twin of pmc_kl_matern_eigs: Chebyshev-filtered subspace iteration on K y = lambda y (y = W^1/2 v) with a block
-    of m + guard columns, filter of `degree` on [0, smallest Ritz value] scaled to 1 at the largest, Cholesky-QR twice and
-    Rayleigh-Ritz after every filter; stops when max_k ||K y_k - theta_k y_k|| <= tol theta_1 over the m wanted columns.
+    of m + guard columns, filter of `degree` on [0, smallest Ritz value] (0.9 of it when guard = 0) scaled to 1 at the
+    largest, Cholesky-QR twice and Rayleigh-Ritz after every filter; stops when max_k ||K y_k - theta_k y_k|| <= tol theta_1 over the m wanted columns.
     K is applied in row blocks (matern_apply_blocked).  Returns (lambda ascending (m), V (n, m) with V^T W V = I and the
     sign rule of normalise_signs, info dict as pmc_kl_eigs_info).  The start block is numpy's Philox stream of `seed`, not the
     device's: the two solvers agree to the tolerance, not bitwise."""
@@ -269,7 +269,8 @@ def matern_eigs_filtered(x: np.ndarray, w: np.ndarray, corlen: float, nmodes: in
     it = 0
     while res > tol and it < max_iter:
         it += 1
-        lo = max(th[-1], 1e-14 * th[0])
+        # no guard column (b == m < n): th[-1] is a wanted value and must lie outside the damped interval (see kl_eigs.hip)
+        lo = max((0.9 if b == m and b < n else 1.0) * th[-1], 1e-14 * th[0])
         e = c = 0.5 * lo
         sigma = e / (th[0] - c)
         tau = 2.0 / sigma

@@ -101,6 +101,70 @@ def test_filtered_twin_matches_the_dense_solve(name, corlen, m):
     cases.check_against_dense(name, corlen, m, lam, V, info["gap_rel"])
 
 
+def test_filtered_twin_with_a_wide_block():
+    """m = 120 on hex16 (b = 136): the narrowest of cases.WIDE_CASES; the wider ones run on the device only"""
+    from parelagmc_amd.fe.kl import matern_eigs_filtered
+    name, corlen, m, guard = cases.WIDE_CASES[0]
+    assert (name, corlen, m, guard) == ("hex16", 0.1, 120, 16)
+    x, w = cases.points(name)
+    lam, V, info = matern_eigs_filtered(x, w, corlen, m, tol=cases.TOL, guard=guard)
+    print(info)
+    assert info["converged"] == 1 and info["max_residual_rel"] <= cases.TOL
+    cases.check_against_dense(name, corlen, m, lam, V, info["gap_rel"])
+
+
+@pytest.mark.parametrize("name,corlen,nmodes", cases.SMALL_CASES)
+def test_filtered_twin_on_small_problems(name, corlen, nmodes):
+    """b = n (hex4) and m = n (the others): the block spans the whole space, so the twin stops without a filter step"""
+    from parelagmc_amd.fe.kl import matern_eigs_filtered
+    x, w = cases.points(name)
+    lam, V, info = matern_eigs_filtered(x, w, corlen, nmodes, tol=cases.TOL)
+    print(info)
+    assert info["converged"] == 1 and info["iterations"] == 0
+    cases.check_small_against_dense(name, corlen, nmodes, lam, V)
+
+
+@pytest.mark.parametrize("opts", [dict(guard=0), dict(degree=1), dict(degree=2)], ids=["guard0", "degree1", "degree2"])
+def test_filtered_twin_option_extremes(opts):
+    """cube_tet_embed, m = 24 (gap 0.0221), default max_iter = 100.  guard = 0: b == m, so the smallest Ritz value of the
+    block is a wanted one; with the filter interval ending there the twin stopped at residual 4.8e-5 after 100 filters."""
+    from parelagmc_amd.fe.kl import matern_eigs_filtered
+    x, w = cases.points("cube_tet_embed")
+    lam, V, info = matern_eigs_filtered(x, w, 0.1, 24, tol=cases.TOL, **opts)
+    print(info)
+    assert info["converged"] == 1 and info["iterations"] <= 100
+    if "guard" in opts:
+        assert info["gap_rel"] == 0.0
+        cases.check_against_dense("cube_tet_embed", 0.1, 24, lam, V)
+    else:
+        cases.check_against_dense("cube_tet_embed", 0.1, 24, lam, V, info["gap_rel"])
+
+
+@pytest.mark.parametrize("n", [1, 33, 1000, 4100])
+def test_integer_fixture_through_the_twin(n):
+    """cases.integer_clusters fed to matern_apply_blocked returns the int64 product exactly: the fixture is what its
+    docstring says, and the twin has the device's conventions (c = 1 where kr < 1e-10, exp underflowing to 0, K_ii = w_i;
+    DESIGN section 10)"""
+    from parelagmc_amd.fe.kl import matern_apply_blocked
+    x, w, cl, s = cases.integer_clusters(n)
+    assert np.array_equal(np.sqrt(w), s) and s.min() >= 1 and s.max() <= 8
+    assert np.all((x == 0.0) | (x == 1000.0 * cases.INT_CORLEN)) and np.all((x != 0.0).sum(1) <= 1)
+    for p in (4, 16, 32, 128):
+        if n >= 8 * p:
+            assert not np.array_equal(cl[:-p], cl[p:]) and not np.array_equal(s[:-p], s[p:]), f"periodic in {p}"
+    if n >= 1000:
+        assert np.bincount(cl, minlength=4).min() >= n // 8 and np.bincount(s, minlength=9)[1:].min() >= n // 16
+    X = cases.integer_block(n, 129)
+    assert np.abs(X).max() <= 3 and (n < 4 or np.unique(X, axis=1).shape[1] == 129)
+    ref = cases.integer_product(cl, s, X)
+    if n <= 1000:
+        K = cases.integer_k(cl, s)
+        assert np.array_equal(np.diag(K), (s * s)) and np.array_equal(K @ X, ref)
+        assert np.array_equal(cases.dense_k(x, w, cases.INT_CORLEN), K)
+    Y = matern_apply_blocked(x, w, cases.INT_CORLEN, X.astype(np.float64))
+    assert np.array_equal(Y, ref)
+
+
 def test_eigensolver_keyword():
     """default stays dense; "filtered" goes through the twin; unknown names and a device solve without ctx are refused"""
     from parelagmc_amd.fe import box_mesh, build_hierarchy, build_kl_sampler_problem
