@@ -185,6 +185,10 @@ int pmc_sampler_krylov_z_bytes(const pmc_sampler* s);
 int pmc_darcy_krylov_z_bytes(const pmc_darcy* d);
 /* kernels launched by this process through the library so far (all handles, all host threads): launch-rate diagnostics */
 uint64_t pmc_kernel_launches(void);
+/* MINRES solves of this process that ran the operator twice per iteration and never stored q = A u (the hybridized multiplier
+ * solve in its eager loop; DESIGN.md section 3, paragraph "The multiplier solve without q"): path diagnostics, as
+ * pmc_kernel_launches */
+uint64_t pmc_fused_lanczos_solves(void);
 const char* pmc_last_error(void);
 void pmc_solver_opts_default(pmc_solver_opts* opts);
 

@@ -97,6 +97,7 @@ SYMBOLS = {
     "pmc_sampler_krylov_z_bytes": (C.c_int, [_VP]),
     "pmc_darcy_krylov_z_bytes": (C.c_int, [_VP]),
     "pmc_kernel_launches": (C.c_uint64, []),
+    "pmc_fused_lanczos_solves": (C.c_uint64, []),
     "pmc_ctx_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_create_abi": (C.c_int, [C.c_int, C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_destroy": (None, [_VP]),

@@ -291,6 +291,17 @@ __device__ __forceinline__ double load_stream(const double* __restrict__ p) {
     else return *p;
 }
 
+// The Lanczos update y = c0 a + c1 b + c2 y of MINRES, columns k0 .. k0 + C - 1: ONE expression for the flat kernel
+// (lincomb3_kernel) and for the operator pass that forms the vector in its epilogue (sell_spmm_kernel, LZ >= 2), so that
+// both contract to the same instructions and give the same bits.
+template <int C>
+__device__ __forceinline__ void lanczos_combine(const double* __restrict__ c0, const double* __restrict__ c1,
+                                                const double* __restrict__ c2, int k0, const double (&a)[C],
+                                                const double (&b)[C], double (&y)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) y[c] = c0[k0 + c] * a[c] + c1[k0 + c] * b[c] + c2[k0 + c] * y[c];
+}
+
 template <bool NT, int C>
 __device__ __forceinline__ void store_v_stream(double* __restrict__ p, const double (&v)[C]) { store_c_stream<NT, C>(p, v); }
 template <bool NT, int C>
@@ -618,8 +629,15 @@ __device__ __forceinline__ SliceWalk slice_walk(int nslices) {
 // few MB) disappears from the V-cycle.
 // XT: storage type of x and dot_with (fp32 or fp64 for the preconditioned Krylov vectors, zvec)
 // YT: storage type of y (fp32: the coarse right-hand side of a V-cycle level with fp32 inter-level vectors, plain products only)
+// LZ: the two operator passes of a MINRES iteration that never stores q = A u (shared values, MODE 0; k::LanczosUpdate):
+//   1 = the product is not stored, only the fused dot leaves the kernel (alpha = <u, Au>: the same partials, bit for bit,
+//       as the storing form);
+//   2 = no dot; the epilogue forms the next Lanczos vector from the row sums (the same bits as the stored q) and the own
+//       rows of v1 (lz.v1) and v0 (y): y = c0 (A x) + c1 v1 + c2 y, written over v0 together with its fp32 copy lz.y32;
+//   3 = as 2 in the first iteration, where v0 is zero: y is not read (the c2 term is kept with a literal +0.0, so even the
+//       sign of a zero result is that of the flat kernel)
 template <int NB, int BV, int MODE, bool DOT, int TAG, bool NT = false, bool R8 = false, bool DL = false, typename XT = double,
-          typename YT = double>
+          typename YT = double, int LZ = 0>
 __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3 : 1)) void sell_spmm_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                            const int* __restrict__ sched,
                                                            const int* __restrict__ cols,
@@ -627,18 +645,25 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
                                                            const XT* __restrict__ x, typename ident<YT>::type* __restrict__ y,
                                                            const double* __restrict__ r,
                                                            const typename ident<XT>::type* __restrict__ dot_with,
-                                                           double* __restrict__ partial, int ld) {
+                                                           double* __restrict__ partial, int ld,
+                                                           k::LanczosUpdate lz = k::LanczosUpdate{}) {
     static_assert(!R8 || (MODE == 2 && !DOT), "fused restriction goes with the residual");
+    static_assert(LZ == 0 || (BV == 0 && MODE == 0 && !R8 && sizeof(YT) == 8 && DOT == (LZ == 1)),
+                  "Lanczos passes: shared values, plain product; the dot-only pass has the dot, the update passes none");
     static_assert(sizeof(YT) == 8 || (MODE == 0 && !DOT && !NT), "fp32 result: plain products only");
     const int LD = row_ld<NB>(ld);
     {
         const int c0 = col0<NB>();   // this group's columns of every interleaved operand
         x += c0;
-        y += c0;
+        if constexpr (LZ != 1) y += c0;   // (the dot-only pass has no y)
         if constexpr (BV) vals = shift_bv<BV>(vals, c0);
         if constexpr (MODE == 2) r += c0;
         if constexpr (DOT && !DL) dot_with += c0;
         if constexpr (DOT || R8) partial += c0;
+        if constexpr (LZ >= 2) {
+            lz.v1 += c0; lz.y32 += c0;
+            lz.c0 += c0; lz.c1 += c0; lz.c2 += c0;
+        }
     }
     static_assert(!DL || (DOT && !BV && Lay<NB>::T > 1), "diagonal-last serves the fused <x, Ax> of shared-value operators");
     constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
@@ -683,7 +708,20 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
 #pragma unroll
                     for (int c = 0; c < C; ++c) acc[rs][c] = rv[c] - acc[rs][c];
                 }
-                if constexpr (sizeof(YT) == 8) store_c_stream<NT, C>(y + at, acc[rs]);
+                if constexpr (LZ >= 2) {
+                    double bv[C], yv[C];
+                    load_c_nt<NT, C>(lz.v1 + at, bv);
+                    if constexpr (LZ == 2) {
+                        load_c_nt<NT, C>(y + at, yv);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) yv[c] = 0.0;
+                    }
+                    lanczos_combine<C>(lz.c0, lz.c1, lz.c2, t * C, acc[rs], bv, yv);
+                    store_c<C>(y + at, yv);          // gathered by the next kernels
+                    store_v<C>(lz.y32 + at, yv);
+                } else if constexpr (LZ == 1) {      // the product only feeds the dot
+                } else if constexpr (sizeof(YT) == 8) store_c_stream<NT, C>(y + at, acc[rs]);
                 else store_v<C>(y + at, acc[rs]);
                 if constexpr (LEAN_DL) {
                 } else if constexpr (DL) {
@@ -1753,6 +1791,19 @@ __global__ __launch_bounds__(kBlock) void convert_dot_kernel(size_t nflat, const
     if constexpr (DOT) reduce_flat_store<NB>(p, partial, row_ld<NB>(ld));
 }
 
+// out = in and out32 = its fp32 copy in one pass (the first Lanczos vector of a solve from a zero guess: k::copy + k::convert_z)
+template <int NB>
+__global__ __launch_bounds__(kBlock) void copy_r32_kernel(size_t nflat, const double* __restrict__ in,
+                                                          double* __restrict__ out, float* __restrict__ out32) {
+    constexpr int C = Lay<NB>::C;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < nflat; i += (size_t)gridDim.x * kBlock) {
+        double v[C];
+        load_c<C>(in + i * C, v);
+        store_c<C>(out + i * C, v);
+        store_v<C>(out32 + i * C, v);
+    }
+}
+
 // y32 (optional): the result is also written in fp32 - the copy the V-cycle's first two kernels gather and read (k::vc_*_r32)
 template <int NB, bool NT = false>
 __global__ __launch_bounds__(kBlock) void lincomb3_kernel(size_t nflat, const double* __restrict__ c0,
@@ -1768,8 +1819,7 @@ __global__ __launch_bounds__(kBlock) void lincomb3_kernel(size_t nflat, const do
     load_c_nt<NT, C>(a + e, av);   // the three inputs are read once; the result is gathered by the next kernels
     load_c_nt<NT, C>(b + e, bv);
     load_c_nt<NT, C>(y + e, yv);
-#pragma unroll
-    for (int c = 0; c < C; ++c) yv[c] = c0[k0 + c] * av[c] + c1[k0 + c] * bv[c] + c2[k0 + c] * yv[c];
+    lanczos_combine<C>(c0, c1, c2, k0, av, bv, yv);
     store_c<C>(y + e, yv);
     if (y32) store_v<C>(y32 + e, yv);
 }
@@ -2994,14 +3044,35 @@ static inline bool nt_poly(const SellView& A, int nb) {
     return limit > 0.0 && bytes > limit;
 }
 
+// one Lanczos pass of the operator (sell_spmm_kernel's LZ forms) with the matrix streams and the dot of the in-loop product
+#define PMC_SPMM_LZ(NTF, DLF, LZF)                                                                                          \
+    sell_spmm_kernel<NB, false, 0, (LZF) == 1, TAG, NTF, false, DLF, XT, double, LZF><<<groups_xcd(g, nb), kBlock, 0, st>>>( \
+        A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb, *lz)
+
 template <int NB, int TAG, typename XT>
 static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const XT* x, double* y, bool accumulate,
-                        double* dot_partial, const XT* dot_with) {
+                        double* dot_partial, const XT* dot_with, int lz_mode = 0, const LanczosUpdate* lz = nullptr) {
     // <x, Ax> with a diagonal-last matrix: x_i is what the row's last slice column gathers
     const bool dl = TAG == 1 && Lay<NB>::T > 1 && A.diag_last && dot_with == x;
     if constexpr (!std::is_same<XT, double>::value) {
         // fp32-stored input (the preconditioned Krylov vectors): the operator products of the solver loop only
         if (A.bv || accumulate) throw Error(PMC_ERR_INTERNAL, "spmm: fp32 input with per-realization values / accumulation");
+        if constexpr (TAG == 1) {
+            if (lz_mode) {
+                // the matrix streams of both passes are those of the in-loop product (its launch carries the dot)
+                const bool ntl = nt_streams(A, NB, true);
+                constexpr bool kDl = Lay<NB>::T > 1;
+                if (lz_mode == 1) {
+                    if (ntl) { if (dl) PMC_SPMM_LZ(true, kDl, 1); else PMC_SPMM_LZ(true, false, 1); }
+                    else { if (dl) PMC_SPMM_LZ(false, kDl, 1); else PMC_SPMM_LZ(false, false, 1); }
+                } else if (lz_mode == 2) {
+                    if (ntl) PMC_SPMM_LZ(true, false, 2); else PMC_SPMM_LZ(false, false, 2);
+                } else {
+                    if (ntl) PMC_SPMM_LZ(true, false, 3); else PMC_SPMM_LZ(false, false, 3);
+                }
+                return;
+            }
+        }
         const bool nt = TAG != 0 && nt_streams(A, NB, dot_partial != nullptr);
         if (nt) {
             if (dot_partial && dl)
@@ -3057,7 +3128,7 @@ static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const
 
 template <typename XT>
 static int spmm_t(hipStream_t st, int nb, const SellView& A, const XT* x, double* y, bool accumulate, double* dot_partial,
-                  const XT* dot_with) {
+                  const XT* dot_with, int lz_mode = 0, const LanczosUpdate* lz = nullptr) {
     check_offsets32(A, nb);
     if (A.nrows == 0) return 0;
     if (dot_partial && !dot_with) throw Error(PMC_ERR_INTERNAL, "spmm: fused dot without its second vector");
@@ -3072,7 +3143,7 @@ static int spmm_t(hipStream_t st, int nb, const SellView& A, const XT* x, double
         kernel_partial = dot_partial + (size_t)kCompressBlocks * nb;
     }
     PMC_DISPATCH_NB(nb, {
-        if (A.tag == 1) spmm_launch<NB, 1, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
+        if (A.tag == 1) spmm_launch<NB, 1, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with, lz_mode, lz);
         else if (A.tag == 2) spmm_launch<NB, 2, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
         else spmm_launch<NB, 0, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
     });
@@ -3091,6 +3162,22 @@ int spmm(hipStream_t st, int nb, const SellView& A, const double* x, double* y, 
 int spmm_z(hipStream_t st, int nb, const SellView& A, zvec x, double* y, double* dot_partial, zvec dot_with) {
     if (x.f32) return spmm_t<float>(st, nb, A, x.as<float>(), y, false, dot_partial, dot_with.as<float>());
     return spmm_t<double>(st, nb, A, x.as<double>(), y, false, dot_partial, dot_with.as<double>());
+}
+
+static void check_lanczos_pass(const SellView& A, zvec x) {
+    if (!x.f32 || A.bv || A.tag != 1)
+        throw Error(PMC_ERR_INTERNAL, "Lanczos operator passes: shared values, fp32-stored input, the solver's operator");
+}
+int spmm_z_dot(hipStream_t st, int nb, const SellView& A, zvec x, double* dot_partial) {
+    check_lanczos_pass(A, x);
+    const LanczosUpdate none{};
+    return spmm_t<float>(st, nb, A, x.as<float>(), nullptr, false, dot_partial, x.as<float>(), 1, &none);
+}
+void spmm_z_update(hipStream_t st, int nb, const SellView& A, zvec x, const LanczosUpdate& lz, double* v, bool v_zero) {
+    check_lanczos_pass(A, x);
+    if (!lz.c0 || !lz.c1 || !lz.c2 || !lz.v1 || !lz.y32 || !v)
+        throw Error(PMC_ERR_INTERNAL, "Lanczos update pass: operand missing");
+    spmm_t<float>(st, nb, A, x.as<float>(), v, false, nullptr, nullptr, v_zero ? 3 : 2, &lz);
 }
 
 void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, double* out,
@@ -3664,6 +3751,12 @@ int convert_z(hipStream_t st, int nb, int n, const double* in, zvec out, const d
     });
     check_launch();
     return dot_partial ? (int)g.x : 0;
+}
+
+void copy_r32(hipStream_t st, int nb, int n, const double* in, double* out, float* out32) {
+    if (n == 0) return;
+    PMC_DISPATCH_NB(nb, { copy_r32_kernel<NB><<<grid_dot(n, nb), kBlock, 0, st>>>(flat_count(n, nb), in, out, out32); });
+    check_launch();
 }
 
 int wdot(hipStream_t st, int nb, int n, const double* w, const double* x, double* partial) {

@@ -137,6 +137,20 @@ int spmm(hipStream_t st, int nb, const SellView& A, const double* x, double* y, 
           double* dot_partial, const double* dot_with);
 // the same product from a vector in zvec storage (shared values, no accumulation): the operator products of the solver loop
 int spmm_z(hipStream_t st, int nb, const SellView& A, zvec x, double* y, double* dot_partial, zvec dot_with);
+// A MINRES iteration that never stores q = A u runs the operator twice (shared values, fp32-stored u, the operator tagged
+// 1): spmm_z_dot leaves only the partials of <u, A u> - the very partials of spmm_z(.., dot_with = x) - and, once the scalar
+// step has turned them into the Lanczos coefficients, spmm_z_update recomputes the row sums (the same bits) and writes
+// v = c0 (A u) + c1 v1 + c2 v over v (the vector before last) together with its fp32 copy y32: what lincomb3 computes from
+// a stored q.  v_zero: v is zero and not read (first iteration).  c0, c1, c2: per-column coefficients on the device.
+struct LanczosUpdate {
+    const double* __restrict__ c0 = nullptr;
+    const double* __restrict__ c1 = nullptr;
+    const double* __restrict__ c2 = nullptr;
+    const double* __restrict__ v1 = nullptr;
+    float* __restrict__ y32 = nullptr;
+};
+int spmm_z_dot(hipStream_t st, int nb, const SellView& A, zvec x, double* dot_partial);
+void spmm_z_update(hipStream_t st, int nb, const SellView& A, zvec x, const LanczosUpdate& lz, double* v, bool v_zero);
 // out = r - A x and coarse[i] = sum of out over the rows 8 i .. 8 i + 7 (restriction with the transpose of an
 // "8 consecutive children, unit weights" prolongator); A.nrows must be a multiple of 8
 void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, double* out,
@@ -213,6 +227,8 @@ int wdot(hipStream_t st, int nb, int n, const double* w, const double* x, double
 int dot_z(hipStream_t st, int nb, int n, const double* a, zvec b, double* partial);
 // out = in rounded to zvec storage; dot_partial != nullptr: partials of <r, out>.  Returns the partial-block count.
 int convert_z(hipStream_t st, int nb, int n, const double* in, zvec out, const double* r, double* dot_partial);
+// out = in and out32 = in rounded to fp32, one pass (copy + convert_z of the same vector)
+void copy_r32(hipStream_t st, int nb, int n, const double* in, double* out, float* out32);
 void reduce_final(hipStream_t st, int nb, int nblocks, const double* partial, double* out);
 void lincomb3(hipStream_t st, int nb, int n, const double* c0, const double* a, const double* c1, const double* b,
               const double* c2, double* y, float* y32 = nullptr);

@@ -682,6 +682,14 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
     A.apply_z = [Av](const Lanes& L, int nb_, zvec x, double* y, double* partial, double*) {
         return k::DotParts{partial, k::spmm_z(L.main, nb_, Av, x, y, partial, x)};
     };
+    if (hybrid && !Av.bv) {   // the multiplier solve may run the operator twice per iteration and never store q (minres_solve)
+        A.apply_z_dot = [Av](const Lanes& L, int nb_, zvec x, double* partial, double*) {
+            return k::DotParts{partial, k::spmm_z_dot(L.main, nb_, Av, x, partial)};
+        };
+        A.apply_z_update = [Av](const Lanes& L, int nb_, zvec x, const k::LanczosUpdate& lz, double* v, bool v_zero) {
+            k::spmm_z_update(L.main, nb_, Av, x, lz, v, v_zero);
+        };
+    }
     PrecFn prec = preconditioner(level, nb, degM, mgp, mg_l0);
     // hybridized solver: the Lanczos update also writes the fp32 copy the cycle's first two kernels read (LAB_NOTES 10.9)
     work.want_r32 = hybrid && opts.precond_storage != PMC_STORAGE_FP64 && mgp->top_reads_r32(mg_l0, nb);

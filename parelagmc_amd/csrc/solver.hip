@@ -439,10 +439,11 @@ uint64_t Multigrid::signature(int l0) const {
     return h;
 }
 
-void MinresWork::ensure(int n, int nb, bool z32) {
+void MinresWork::ensure(int n, int nb, bool z32, bool need_q) {
     const size_t need = (size_t)n * nb;
     v0.ensure(need); v1.ensure(need); u0.ensure(need, z32); u1.ensure(need, z32);
-    w0.ensure(need); w1.ensure(need); q.ensure(need);
+    w0.ensure(need); w1.ensure(need);
+    if (need_q) q.ensure(need);
     // two segments each (see k::DotParts): [0, cap) and [cap, 2 cap)
     partial.ensure((size_t)2 * dot_capacity(n, nb) * nb);
     partial_op.ensure((size_t)2 * dot_capacity(n, nb) * nb);
@@ -575,6 +576,19 @@ static int wx_window(int device, size_t vec_bytes) {
     return (int)std::min<size_t>(std::max<size_t>(fit, 9) - 1, (size_t)k::kWxWindow);
 }
 
+// PMC_FUSED_LANCZOS=0: every solve stores q = A u and forms the Lanczos vector with k::lincomb3 (A/B switch for the two
+// operator passes of minres_solve, LAB_NOTES 10.26)
+static std::atomic<uint64_t> g_fused_solves{0};
+uint64_t fused_lanczos_solve_count() { return g_fused_solves.load(std::memory_order_relaxed); }
+
+static bool fused_lanczos_on() {
+    static const bool v = [] {
+        const char* e = lab_env("PMC_FUSED_LANCZOS");
+        return !e || atoi(e) != 0;
+    }();
+    return v;
+}
+
 // PMC_LATE_WX=0 keeps the w / x update inside its own iteration also on two streams (A/B switch)
 static bool late_wx() {
     static const bool v = [] {
@@ -597,7 +611,17 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
                                               Ctx::contexts_on_device(ctx.device) == 1);
     const Lanes L = ctx.lanes(split);
     const bool z32 = o.precond_storage != PMC_STORAGE_FP64;
-    w.ensure(n, nb, z32);
+    const int every = o.check_every > 0 ? o.check_every : 1;
+    const bool graphs = hint.key != 0 && o.use_graph != 0 && every == 2;
+    const bool late = L.split && !graphs && A.n0 > 0 && A.n0 < n && late_wx();
+    const bool r32 = w.want_r32 && z32;
+    const bool timing = w.op_timer.on && !(hint.key != 0 && o.use_graph != 0);
+    // q = A u never stored (the operator runs twice per iteration, see `iteration` below): the plain eager loop of a solve
+    // that keeps the fp32 copy of its Lanczos vectors.  Not inside a captured graph, not on the two-stream schedule, and not
+    // while the operator is being timed - the bracket then measures the storing product; the two paths give the same bits.
+    const bool fused = A.apply_z_dot && A.apply_z_update && !graphs && !late && r32 && !timing && fused_lanczos_on();
+    w.ensure(n, nb, z32, !fused);
+    if (r32) w.r32.ensure(len);
     k::MinresState* S = w.state.p;
     double* v0 = w.v0.p; double* v1 = w.v1.p; zvec u0 = w.u0.v(z32); zvec u1 = w.u1.v(z32);
     double* w0 = w.w0.p; double* w1 = w.w1.p; double* q = w.q.p;
@@ -607,10 +631,8 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     if (!A.apply_z || (!zero_guess && !A.apply)) throw Error(PMC_ERR_INTERNAL, "minres: operator closures missing");
     if (x_row0 < 0 || x_nrows < 0 || (!x_rows && x_row0 + x_nrows > n))
         throw Error(PMC_ERR_INTERNAL, "minres: bad solution row range");
+    if (fused) g_fused_solves.fetch_add(1, std::memory_order_relaxed);   // counted once the arguments have passed
     const size_t xoff = (size_t)x_row0 * nb;
-    const int every = o.check_every > 0 ? o.check_every : 1;
-    const bool graphs = hint.key != 0 && o.use_graph != 0 && every == 2;
-    const bool late = L.split && !graphs && A.n0 > 0 && A.n0 < n && late_wx();
     // w / x updates of a whole window of iterations in one pass (see k::minres_wx_deferred): whenever the update is a plain
     // vector kernel on this stream - not the compact index-list update of the Darcy solves (a few rows), not the two-stream
     // schedule (its update already runs beside other work) and not inside a captured graph.  Its first pass starts w0, w1
@@ -623,23 +645,20 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         } else {
             k::fill(st, x_rows ? (size_t)x_nrows * nb : len, x, 0.0);
         }
-        k::copy(st, len, b, v1);
+        if (r32) k::copy_r32(st, nb, n, b, v1, w.r32.p);   // v1 and its fp32 copy from one read of b
+        else k::copy(st, len, b, v1);
     } else {
         A.apply(L, nb, x, v1, nullptr, nullptr);
         axpby(st, len, 1.0, b, -1.0, v1);
+        if (r32) k::convert_z(st, nb, n, v1, zvec(reinterpret_cast<double*>(w.r32.p), true), nullptr, nullptr);
     }
     const size_t seg2 = (size_t)dot_capacity(n, nb) * nb;
-    const bool r32 = w.want_r32 && z32;
-    if (r32) {
-        w.r32.ensure(len);
-        k::convert_z(st, nb, n, v1, zvec(reinterpret_cast<double*>(w.r32.p), true), nullptr, nullptr);
-        w.r32_valid = true;
-    }
+    w.r32_valid = r32;
     k::DotParts dp = prec(L, nb, v1, u1, w.partial.p, w.partial.p + seg2);
     if (dp.total() == 0) dp = k::DotParts{w.partial.p, k::dot_z(st, nb, n, v1, u1, w.partial.p)};
     const int window = defer ? wx_window(ctx.device, len * (z32 ? sizeof(float) : sizeof(double))) : 1;
     k::minres_init(st, nb, S, dp, o.rel_tol, o.abs_tol, window);
-    k::fill(st, len, v0, 0.0);
+    if (!fused) k::fill(st, len, v0, 0.0);   // (the first update pass of a fused solve does not read v0)
     if (!defer) {
         k::fill(st, len, w0, 0.0);
         k::fill(st, len, w1, 0.0);
@@ -667,12 +686,15 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         w.u2.ensure(len, z32);
         u2 = w.u2.v(z32);
     }
-    const bool timing = w.op_timer.on && !(hint.key != 0 && o.use_graph != 0);
     // q = A u, d1 = <u, A u>.  The product for iteration i+1 is issued right after the preconditioner of iteration i has
     // written u (both blocks of u are then the most recently written data on the chip), before the scalar recurrences
     // and the w / x update of iteration i, which do not depend on it.
     k::DotParts dp_op;
     auto apply_op = [&](zvec u) {
+        if (fused) {   // alpha only; the update pass of the next iteration recomputes the product
+            dp_op = A.apply_z_dot(L, nb, u, w.partial_op.p, w.partial_op.p + seg2);
+            return;
+        }
         if (timing) w.op_timer.begin(st);
         dp_op = A.apply_z(L, nb, u, q, w.partial_op.p, w.partial_op.p + seg2);
         if (timing) w.op_timer.end(st);   // + an empty bracket: what one event record costs on this stream
@@ -695,8 +717,17 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         if (pend.u) wx(s, pend.u, pend.w0, pend.w1);
         pend.u = zvec();
     };
+    int it = 0;   // iterations issued so far, the current one included
     auto iteration = [&](zvec u0_, zvec u1_, double* v0_, double* v1_, double* w0_, double* w1_, bool last) {
-        if (late) {
+        if (fused) {
+            // v0_ = cV0 (A u1_) + cV1 v1_ + cV2 v0_ and its fp32 copy from a second pass over the operator
+            k::LanczosUpdate lz;
+            lz.c0 = cV0; lz.c1 = cV1; lz.c2 = cV2;
+            lz.v1 = v1_;
+            lz.y32 = w.r32.p;
+            A.apply_z_update(L, nb, u1_, lz, v0_, it == 1);
+            w.r32_valid = true;
+        } else if (late) {
             const size_t off = (size_t)A.n0 * nb;
             L.fork();
             k::lincomb3(L.aux, nb, A.n0, cV0, q, cV1, v1_, cV2, v0_);
@@ -723,7 +754,6 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         iteration(u0, u1, v0, v1, w0, w1, false);
         iteration(u1, u0, v1, v0, w1, w0, false);
     };
-    int it = 0;
     int n_active = poll();
     // Convergence polls drain the stream; iteration counts of one configuration barely move between batches, so the polls
     // start a few iterations before the count the previous solve of this configuration needed.  Converged columns are

@@ -214,6 +214,11 @@ struct LinOp {
     // the same product from a preconditioned vector (zvec storage): every product inside the MINRES loop
     std::function<k::DotParts(const Lanes& L, int nb, zvec x, double* y, double* dot_partial,
                               double* dot_partial2)> apply_z;
+    // optional pair (both or neither; fp32-stored x): the two passes of an iteration that never stores q = A u.
+    // apply_z_dot: the partials of <x, A x> exactly as apply_z leaves them, without the product itself;
+    // apply_z_update: v = c0 (A x) + c1 v1 + c2 v in place and its fp32 copy (k::LanczosUpdate), v_zero: v is zero, not read
+    std::function<k::DotParts(const Lanes& L, int nb, zvec x, double* dot_partial, double* dot_partial2)> apply_z_dot;
+    std::function<void(const Lanes& L, int nb, zvec x, const k::LanczosUpdate& lz, double* v, bool v_zero)> apply_z_update;
 };
 // z = B^-1 r.  When dot_partial != nullptr the preconditioner may fuse <r, z> into its last kernels and
 // return the number of partial blocks it wrote (0 = not computed, the solver then runs a separate dot).
@@ -304,8 +309,11 @@ struct MinresWork {
     MinresWork(const MinresWork&) = delete;
     MinresWork& operator=(const MinresWork&) = delete;
     ~MinresWork();
-    void ensure(int n, int nb, bool z32);
+    void ensure(int n, int nb, bool z32, bool need_q = true);   // need_q = false: a solve that never stores q = A u
 };
+
+// solves of this process that took the two operator passes of minres_solve instead of storing q = A u (all handles, all threads)
+uint64_t fused_lanczos_solve_count();
 
 struct MinresResult {
     pmc_stats col[kMaxBatch];

@@ -59,8 +59,8 @@ def per_kernel(path):
     return acc
 
 
-def mean(d, key):
-    v = [x for k, vals in d.items() if key in k for x in vals]
+def mean(d, key, tail=""):
+    v = [x for k, vals in d.items() if key in k and tail in k for x in vals]
     return (sum(v) / len(v), len(v)) if v else (None, 0)
 
 
@@ -74,9 +74,9 @@ def dump(name, acc, suffix):
             f.write(f"\"{k}\",{len(v)},{sum(v) / len(v):.3f}\n")
 
 
-def entry(fetch, write, kern, what):
-    fr, n = mean(fetch, kern)
-    wr, _ = mean(write, kern)
+def entry(fetch, write, kern, what, tail=""):
+    fr, n = mean(fetch, kern, tail)
+    wr, _ = mean(write, kern, tail)
     if fr is None or wr is None:
         return None
     return {"kernel": f"pmc::{kern} ...> {what}", "FETCH_SIZE_KB_raw": fr, "WRITE_SIZE_KB_raw": wr,
@@ -129,10 +129,16 @@ for refine, nvec, nlam in ((5, 595968, 399360), (6, 4743168, 3170304)):
     dump("fetch_size", fetch, f"r{refine}")
     dump("write_size", write, f"r{refine}")
     nbh = batch_of(f"pmc_fetch_r{refine}.log")
-    for key, kern, what in ((f"r{refine}_hyb_post_nb{nbh}_inloop", "vc_poly2_kernel<32, float, float, float, true, true, 0>",
-                             "post-smoothing of the finest level of the multiplier V-cycle, in the MINRES loop"),
-                            (f"r{refine}_hyb_k5_nb{nbh}_inloop", "sell_spmm_kernel<32, 0, 0, true, 1,", "K5 on H, in the MINRES loop")):
-        e = entry(fetch, write, kern.rstrip(">") if kern.endswith(">") else kern, what)
+    # K5 on H: the storing form (`, double, 0>`: the timed solves of --full) and the two passes of the solves that never store q (`, double, 1>`: dot only, `, double, 2>`: update)
+    for key, kern, what, tail in ((f"r{refine}_hyb_post_nb{nbh}_inloop", "vc_poly2_kernel<32, float, float, float, true, true, 0>",
+                                   "post-smoothing of the finest level of the multiplier V-cycle, in the MINRES loop", ""),
+                                  (f"r{refine}_hyb_k5_nb{nbh}_inloop", "sell_spmm_kernel<32, 0, 0, true, 1,",
+                                   "K5 on H storing q, in the MINRES loop of a timed solve", ", double, 0>("),
+                                  (f"r{refine}_hyb_k5_dot_nb{nbh}_inloop", "sell_spmm_kernel<32, 0, 0, true, 1,",
+                                   "K5 on H, dot-only pass, in the MINRES loop", ", double, 1>("),
+                                  (f"r{refine}_hyb_k5_update_nb{nbh}_inloop", "sell_spmm_kernel<32, 0, 0, false, 1,",
+                                   "K5 on H, update pass (forms v and its fp32 copy), in the MINRES loop", ", double, 2>(")):
+        e = entry(fetch, write, kern.rstrip(">") if kern.endswith(">") else kern, what, tail)
         if e:
             out[key] = e
     lv = [x for k, vals in fetch.items() if "lincomb3_kernel<32" in k for x in vals]

@@ -49,7 +49,11 @@ def main():
     CV = F if c32 else V          # one row of an inter-level vector
 
     calls = lambda key: sum(int(r["calls"]) for r in stats if key in r["kernel"] and "<32, " in r["kernel"])   # noqa: E731
-    wx_iters = calls("lincomb3_kernel") / max(1, calls("minres_wx_deferred_kernel"))
+    # Lanczos updates of the profile: lincomb3 launches (timed solves, which store q) and update passes of the operator
+    # (the solves that never store it: one `, 3>` launch for the first iteration, `, 2>` for the others)
+    lz_pass = lambda name, form: "sell_spmm_kernel<32, 0, 0, " in name and f", double, {form}>(" in name   # noqa: E731
+    updates = calls("lincomb3_kernel") + sum(int(r["calls"]) for r in stats if lz_pass(r["kernel"], 2) or lz_pass(r["kernel"], 3))
+    wx_iters = updates / max(1, calls("minres_wx_deferred_kernel"))
 
     def level_of(grid):           # slice kernels: grid = rows rounded up to a multiple of 256 threads (x column groups when
         for i, r in enumerate(n):  # the profiler reports the total grid)
@@ -79,8 +83,15 @@ def main():
         if l is None:
             return None
         nxt = n[l + 1] if l + 1 < len(n) else 0
+        if lz_pass(name, 1):
+            return ("pass A: H u for <u, Hu> only, nothing stored", 12.0 * lv[0]["nnz"] + 4.0 * n[0] + zb * nb * n[0], None)
+        if lz_pass(name, 2):
+            return ("pass B: H u again, v = c0 Hu + c1 v1 + c2 v0 and its fp32 copy in the epilogue",
+                    12.0 * lv[0]["nnz"] + 4.0 * n[0] + (zb * nb + 3 * V + F) * n[0], None)
+        if lz_pass(name, 3):
+            return ("pass B of the first iteration (no v0)", 12.0 * lv[0]["nnz"] + 4.0 * n[0] + (zb * nb + 2 * V + F) * n[0], None)
         if "sell_spmm_kernel<32, 0, 0, true, 1," in name:
-            return ("K5 on H with the fused <u, Hu>", 12.0 * lv[0]["nnz"] + 4.0 * n[0] + (zb * nb + V) * n[0], None)
+            return ("K5 on H with the fused <u, Hu>, q stored (timed solves)", 12.0 * lv[0]["nnz"] + 4.0 * n[0] + (zb * nb + V) * n[0], None)
         if "vc_poly2_kernel<32, double, float, float, false" in name:
             return (f"pre-smoothing, V-cycle level {l}", 12.0 * lv[l]["nnz"] + 12.0 * n[l] + (V + F) * n[l], None)
         # fp32 right-hand side below the top: the post-smoothing of such a level has the same leading arguments and gathers an
