@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip
+SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -104,3 +104,10 @@ $(ABIBIN)/kl_matern_smoke: tests/c/kl_matern_smoke.c include/pmc.h | $(LIB)
 	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/kl_matern_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-kl-matern: $(ABIBIN)/kl_matern_smoke
 .PHONY: test-kl-matern
+
+# conditioning on observed field values from C (tests/test_gpu_condition.py builds and runs it)
+$(ABIBIN)/condition_smoke: tests/c/condition_smoke.c tests/c/kl_io.h include/pmc.h | $(LIB)
+	@mkdir -p $(ABIBIN)
+	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/condition_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-condition: $(ABIBIN)/condition_smoke
+.PHONY: test-condition

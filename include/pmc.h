@@ -393,6 +393,46 @@ int pmc_sampler_max_error(pmc_sampler* s, int level, int nbatch, const double* c
  * (sample_size(0) entries, > 0).  Copied; nlevels in [1, number of Monte Carlo levels]. */
 int pmc_sampler_set_output_hierarchy(pmc_sampler* s, int nlevels, const pmc_csr* P_orig, const double* w0_orig);
 
+/* ---- Conditioning on observed field values (an extension of this project; nothing in the reference
+ *      does this) ---------------------------------------------------------------------------------------------------------- */
+/* Kriging / Matheron's rule for LINEAR observations of the Gaussian field: with C_l the covariance of the Gaussian field Eval
+ * produces on level l, H_l the observation operator (H_{l+1} = H_l P_l) and R = diag(sigma2),
+ *     g_c = g + K_l A_l^-1 (y + R^1/2 zeta - H_l g),   K_l = C_l H_l^T,   A_l = 1/2 (H_l K_l + (H_l K_l)^T) + R,
+ * is a draw of the field conditioned on the data whenever g is a prior draw and zeta ~ N(0, I) is independent of it.
+ * pmc_conditioner_create does everything expensive once per handle and Monte Carlo level: K_l by two applications of the
+ * handle's own Eval per observation (a KL handle: from its device modes), A_l^-1 by a host Cholesky.  H0: nobs x n_s(0), point
+ * values or averages, every row non-empty; y: nobs values; sigma2: nobs values >= 0, NULL = exact data.
+ * PMC_ERR_INVALID: a handle with a projection set (pmc_sampler_set_projection), nobs < 1 or nobs > 512, an empty row or a
+ * wrong column count of H0, a non-finite y / sigma2 / entry of H0, a negative sigma2, an A_l that is not positive definite (a
+ * Cholesky pivot below 1e-12 of its diagonal entry; with exact data: two observations inside one element of a coarse level -
+ * the message names the level). */
+typedef struct pmc_conditioner pmc_conditioner;
+int pmc_conditioner_create(pmc_sampler* s, int nobs, const pmc_csr* H0, const double* y,
+                           const double* sigma2 /* NULL = exact */, pmc_conditioner** out);
+void pmc_conditioner_destroy(pmc_conditioner* c);   /* before the sampler it was created on; detaches itself */
+int pmc_conditioner_num_obs(const pmc_conditioner* c);
+/* Setup export (tests): *n = n_s(level), *nnz = entries of H_level; K: n x nobs column-major; A: nobs x nobs as inverted;
+ * rowptr (nobs + 1) / colind (nnz) / vals (nnz): H_level in CSR, columns ascending.  Every pointer may be NULL: call once for
+ * the sizes, then with arrays.  Host arrays. */
+int pmc_conditioner_level(const pmc_conditioner* c, int level, int* n, int64_t* nnz, double* K, double* A, int32_t* rowptr,
+                          int32_t* colind, double* vals);
+/* out = f(g + K_l A_l^-1 (y + sqrt(sigma2) zeta - H_l g)) for nbatch >= 1 Gaussian fields g (nbatch x n_s(level), sample-major)
+ * in `memspace`; zeta: nbatch x nobs standard normals in the same memspace, NULL iff the data are exact (every sigma2 == 0),
+ * e.g. from pmc_normal_fill on a stream of the caller's own; f = exp when apply_exp != 0, else the identity; out may alias g.
+ * Every sum has a fixed order: a realization's result does not depend on how its call was split and two identical calls agree
+ * bit for bit.  Calls of more than 4 realizations run the fp64 MFMA kernel, narrower ones a VALU kernel: a column's bits may
+ * differ between the two (as for pmc_sampler_create_kl handles).  PMC_ERR_INVALID: zeta == NULL with some sigma2 > 0 (and zeta
+ * given for exact data), a level out of range, nbatch < 1, a NULL g / out. */
+int pmc_conditioner_apply(pmc_conditioner* c, int level, int nbatch, const double* g, const double* zeta, double* out,
+                          int apply_exp, int memspace);
+/* Eval hook: with a conditioner set, pmc_sampler_eval (and with it the managers, pmc_field_stats_run and the farm) returns
+ * conditional fields - exp() AFTER conditioning on a lognormal handle; embed_s_out keeps the PRIOR Gaussian field (it is the
+ * finer level's warm start).  NULL detaches; without a conditioner Eval takes exactly the path it took before.
+ * PMC_ERR_INVALID: a conditioner with any sigma2 > 0 (Eval receives no realization id, so it has no independent noise to
+ * draw: such callers use pmc_conditioner_apply), a conditioner created on another handle.  While one is attached
+ * pmc_sampler_set_projection is refused. */
+int pmc_sampler_set_conditioner(pmc_sampler* s, pmc_conditioner* c);
+
 /* invA[level]->Mult(rhs, sol) (src/PDESampler.cpp:397,521), the narrowest seam of the reference: the whole linear solve
  * A [u; s] = rhs on FULL vectors of n_u + n_s entries per realization (sample-major), every row of the solution maintained.
  * use_sol_as_guess != 0 = mfem::Solver::iterative_mode (:510): sol holds the initial guess on entry.  pmc_sampler_eval is this

@@ -163,6 +163,15 @@ SYMBOLS = {
     "pmc_sampler_set_operator_timing": (C.c_int, [_VP, C.c_int]),
     "pmc_sampler_operator_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pmc_sampler_operator_event_overhead": (C.c_int, [_VP, C.POINTER(C.c_double)]),
+    "pmc_conditioner_create": (C.c_int, [_VP, C.c_int, C.POINTER(pmc_csr), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(_VP)]),
+    "pmc_conditioner_destroy": (None, [_VP]),
+    "pmc_conditioner_num_obs": (C.c_int, [_VP]),
+    "pmc_conditioner_level": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_double)]),
+    "pmc_conditioner_apply": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.c_int]),
+    "pmc_sampler_set_conditioner": (C.c_int, [_VP, _VP]),
     "pmc_field_stats_create": (C.c_int, [_VP, C.c_int, _DP, C.c_int, C.POINTER(_VP)]),
     "pmc_field_stats_destroy": (None, [_VP]),
     "pmc_field_stats_reset": (C.c_int, [_VP]),
@@ -738,9 +747,15 @@ class PDESampler:
             return sol, [(t.iterations, t.converged, t.initial_norm, t.final_norm) for t in st]
         return sol
 
+    def SetConditioner(self, conditioner):
+        """Eval returns fields conditioned on the data of `conditioner` (a Conditioner created on this handle with exact
+        data); None detaches (pmc_sampler_set_conditioner)"""
+        _check(self.ctx.lib.pmc_sampler_set_conditioner(self.h, None if conditioner is None else conditioner.h))
+        self._conditioner = conditioner
+
     def close(self):
         if getattr(self, "h", None):
-            for ref in getattr(self, "_stats", []):     # FieldStatistics of this handle die first
+            for ref in getattr(self, "_stats", []):     # FieldStatistics and Conditioners of this handle die first
                 obj = ref()
                 if obj is not None:
                     obj.close()
@@ -828,6 +843,76 @@ class FieldStatistics:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.pmc_field_stats_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Conditioner:
+    """Conditioning of a sampler's Gaussian fields on linear observations H0 g (+ noise of variance sigma2) = y
+    (pmc_conditioner_*; fe.condition is its numpy twin).  H0: scipy sparse nobs x n_s(0); sigma2 None = exact data."""
+
+    def __init__(self, sampler: PDESampler, H0, y, sigma2=None):
+        self.sampler, self.ctx = sampler, sampler.ctx
+        keep = _Keep()
+        H = keep.csr(H0)
+        y = _f64(y).ravel()
+        self.nobs = int(H.nrows)
+        if y.size != self.nobs or (sigma2 is not None and np.size(sigma2) != self.nobs):
+            raise PmcError(-1, "Conditioner: y / sigma2 must hold one value per row of H0")
+        self.noisy = sigma2 is not None and bool(np.any(np.asarray(sigma2) > 0.0))
+        h = _VP()
+        _check(self.ctx.lib.pmc_conditioner_create(sampler.h, self.nobs, C.byref(H), keep.f64(y),
+                                                   None if sigma2 is None else keep.f64(np.ravel(sigma2)), C.byref(h)))
+        self.h = h
+        if not hasattr(sampler, "_stats"):
+            sampler._stats = []
+        sampler._stats.append(weakref.ref(self))
+
+    def level(self, level):
+        """(K (n_s(level), nobs), A (nobs, nobs), H_level scipy CSR) of the device setup"""
+        import scipy.sparse as sp
+        lib = self.ctx.lib
+        n, nnz = C.c_int(0), C.c_int64(0)
+        _check(lib.pmc_conditioner_level(self.h, level, C.byref(n), C.byref(nnz), None, None, None, None, None))
+        K = np.empty((self.nobs, n.value))      # column-major n x nobs
+        A = np.empty((self.nobs, self.nobs))
+        rp, ci, va = np.empty(self.nobs + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value)
+        _check(lib.pmc_conditioner_level(self.h, level, None, None, _ptr(K, C.c_double), _ptr(A, C.c_double),
+                                         _ptr(rp, C.c_int32), _ptr(ci, C.c_int32), _ptr(va, C.c_double)))
+        return np.ascontiguousarray(K.T), A, sp.csr_matrix((va, ci, rp), shape=(self.nobs, n.value))
+
+    def apply(self, level, g, zeta=None, exp=False, out=None):
+        """g + K A^-1 (y + sqrt(sigma2) zeta - H g) (exp() of it with exp=True) for (nbatch, n_s(level)) numpy fields, or for
+        a DeviceArray / torch tensor g (zeta and out of the same kind; out defaults to g itself: in place)"""
+        if isinstance(g, np.ndarray):
+            g = _f64(np.atleast_2d(g))
+            nbatch = g.shape[0]
+            if zeta is not None:
+                zeta = _f64(np.atleast_2d(zeta))
+                if zeta.shape != (nbatch, self.nobs):
+                    raise PmcError(-1, "Conditioner.apply: zeta must be (nbatch, nobs)")
+            if out is None:
+                out = np.empty_like(g)
+        else:
+            nbatch = _batch_of(g, self.sampler.xi_size(level))
+            if out is None:
+                out = g
+        pg, ms = _addr(g)
+        pz, _ = _addr(zeta)
+        po, _ = _addr(out)
+        _check(self.ctx.lib.pmc_conditioner_apply(self.h, level, nbatch, pg, pz, po, 1 if exp else 0, ms))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.sampler, "_conditioner", None) is self:
+                self.sampler._conditioner = None
+            self.ctx.lib.pmc_conditioner_destroy(self.h)      # detaches itself from the sampler
             self.h = None
 
     def __del__(self):

@@ -435,6 +435,49 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
     });
 }
 
+int pmc_conditioner_create(pmc_sampler* s, int nobs, const pmc_csr* H0, const double* y, const double* sigma2,
+                           pmc_conditioner** out) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr && out != nullptr, "pmc_conditioner_create: NULL argument");
+        *out = nullptr;
+        *out = new pmc_conditioner(s->impl, nobs, H0, y, sigma2);
+    });
+}
+void pmc_conditioner_destroy(pmc_conditioner* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->impl.smp.ctx.device);
+    (void)hipStreamSynchronize(c->impl.smp.ctx.stream);
+    delete c;
+}
+int pmc_conditioner_num_obs(const pmc_conditioner* c) { return c ? c->impl.nobs : PMC_ERR_INVALID; }
+int pmc_conditioner_level(const pmc_conditioner* c, int level, int* n, int64_t* nnz, double* K, double* A, int32_t* rowptr,
+                          int32_t* colind, double* vals) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr, "conditioner is NULL");
+        c->impl.export_level(level, n, nnz, K, A, rowptr, colind, vals);
+    });
+}
+int pmc_conditioner_apply(pmc_conditioner* c, int level, int nbatch, const double* g, const double* zeta, double* out,
+                          int apply_exp, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr, "conditioner is NULL");
+        c->impl.apply(level, nbatch, g, zeta, out, apply_exp != 0, memspace);
+    });
+}
+int pmc_sampler_set_conditioner(pmc_sampler* s, pmc_conditioner* c) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        if (c) {
+            PMC_REQUIRE(&c->impl.smp == &s->impl, "pmc_sampler_set_conditioner: the conditioner was created on another handle");
+            PMC_REQUIRE(!c->impl.noisy, "pmc_sampler_set_conditioner: the conditioner has sigma2 > 0; Eval receives no realization "
+                                        "id to draw independent noise from - use pmc_conditioner_apply with pmc_normal_fill");
+            for (int l = 0; l < s->impl.n_mc; ++l)
+                PMC_REQUIRE(s->impl.lv[l].proj == PMC_PROJ_NONE, "pmc_sampler_set_conditioner: the handle has a projection set");
+        }
+        s->impl.cond = c ? &c->impl : nullptr;
+    });
+}
+
 int pmc_field_stats_create(pmc_sampler* s, int level, const double* chi, int memspace, pmc_field_stats** out) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr && out != nullptr, "pmc_field_stats_create: NULL argument");

@@ -9,6 +9,11 @@ HostCsr schur_host(const HostCsr& B, const HostCsr& Bt, const std::vector<double
 std::unique_ptr<Multigrid> build_sa_chain(const HostCsr& K, const std::vector<double>& w, const pmc_solver_opts& o,
                                           hipStream_t st);
 
+// inv = S^-1 (dense, row-major, exactly symmetric) of a small SPD operator by Cholesky; false when S is not numerically SPD
+bool spd_dense_inverse(const HostCsr& S, std::vector<double>& inv);
+
+struct Conditioner;
+
 struct SamplerLevel {
     double ratio_M = 8.0;            // Chebyshev interval lambda_max/lambda_min of the l1-scaled M-block
     int n_u = 0, n_s = 0;
@@ -51,6 +56,9 @@ struct Sampler {
     bool kl = false;
     int kl_m = 0;
     std::vector<DevBuf<double>> kl_phi;
+    // pmc_sampler_set_conditioner (condition.hip): when set, Eval conditions its Gaussian field before the output map (the
+    // exp() of a lognormal handle then happens in the conditioner's store); embed_s_out keeps the prior field
+    Conditioner* cond = nullptr;
     // ComputeL2Error / ComputeMaxError (field_stats.hip): diag(W) of level 0 as handed over, and the hierarchy of the output
     // space of the embedded / L2-projected variants (pmc_sampler_set_output_hierarchy: out_P[l] maps sample_size(l + 1) ->
     // sample_size(l), out_w0 the P0 mass of the original mesh's level 0; empty = not set)
@@ -110,6 +118,37 @@ struct Sampler {
     // Eval of a KL handle: every realization in one launch
     void eval_kl(int level, int xi_level, int nbatch, const double* xi, double* s_out, double* emb_out, int memspace,
                  pmc_stats* stats);
+};
+
+// Conditioning on linear observations of the Gaussian field (condition.hip, pmc_conditioner_*): per
+// Monte Carlo level H_l (CSR), K_l = C_l H_l^T and A_l^-1 on the device.  K_l is column-major with leading dimension ld (n
+// rounded up to 16) and mp columns (nobs rounded up to 16, the padding zero).
+constexpr int kCondMaxObs = 512;
+struct Conditioner {
+    Sampler& smp;
+    int nobs, mp;
+    bool noisy = false;               // some sigma2 > 0: apply needs zeta
+    struct Level {
+        int n = 0, ld = 0;
+        HostCsr H;
+        DevBuf<int> hrp, hci;
+        DevBuf<double> hv, K, Ainv;
+        std::vector<double> A;        // nobs x nobs, as inverted
+    };
+    std::vector<Level> lv;
+    DevBuf<double> y, sqrt_sigma2, coef, stage_g, stage_z;
+    Conditioner(Sampler& s, int nobs, const pmc_csr* H0, const double* y, const double* sigma2);
+    ~Conditioner() { if (smp.cond == this) smp.cond = nullptr; }
+    // out = f(g + K_l A_l^-1 (y + sqrt(sigma2) zeta - H_l g)), f = exp or the identity; out may alias g
+    void apply(int level, int nbatch, const double* g, const double* zeta, double* out, bool apply_exp, int memspace);
+    // the same on device arrays, enqueued on the handle's stream (the Eval hook)
+    void apply_device(int level, int nbatch, const double* g_d, const double* zeta_d, double* out_d, bool apply_exp);
+    void export_level(int level, int* n, int64_t* nnz, double* K, double* A, int32_t* rowptr, int32_t* colind,
+                      double* vals) const;
+
+  private:
+    void build_K_solves(int level);
+    void build_K_kl(int level);
 };
 
 // Accumulators of one sampler level's output (field_stats.hip, pmc_field_stats_*): (sum, compensation) pairs of s, s^2 and
@@ -312,6 +351,7 @@ struct Darcy {
 }  // namespace pmc
 
 struct pmc_sampler { pmc::Sampler impl; template <class... A> explicit pmc_sampler(A&&... a) : impl(std::forward<A>(a)...) {} };
+struct pmc_conditioner { pmc::Conditioner impl; template <class... A> explicit pmc_conditioner(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_field_stats { pmc::FieldStats impl; template <class... A> explicit pmc_field_stats(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_level_fields { pmc::LevelFields impl; template <class... A> explicit pmc_level_fields(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_darcy { pmc::Darcy impl; template <class... A> explicit pmc_darcy(A&&... a) : impl(std::forward<A>(a)...) {} };

@@ -52,7 +52,7 @@ struct AggSegments {   // agg_pack_rows' tables of the finest level (empty: the 
     std::vector<int> ptr, cid, pos;
 };
 // inv = S^-1 (dense, row-major, exactly symmetric) of a small SPD operator by Cholesky; false when S is not numerically SPD
-static bool spd_dense_inverse(const HostCsr& S, std::vector<double>& inv) {
+bool spd_dense_inverse(const HostCsr& S, std::vector<double>& inv) {
     const int n = S.nrows;
     std::vector<double> a((size_t)n * n, 0.0);
     inv.assign((size_t)n * n, 0.0);
@@ -480,6 +480,7 @@ Sampler::Sampler(Ctx& c, int nlevels_, const pmc_hybrid_level* in, double alpha_
 void Sampler::set_projection(int level, int kind, const pmc_csr* Gt, const int32_t* idx, const double* inv_w,
                              int orig_size) {
     PMC_REQUIRE(level >= 0 && level < n_mc, "set_projection: level out of range");
+    PMC_REQUIRE(cond == nullptr, "set_projection: a conditioner is attached (pmc_sampler_set_conditioner); detach it first");
     SamplerLevel& d = lv[level];
     ctx.activate();
     hipStream_t st = ctx.stream;
@@ -614,7 +615,9 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
     // outputs (:526-533 and the embedded variants' maps)
     const double* sol_s = sol.p + (size_t)n_u * nb;
     if (d.proj == PMC_PROJ_NONE) {
-        k::deinterleave(st, nb, n_s, sol_s, nullptr, nullptr, lognormal, s_d);
+        // with a conditioner the Gaussian field lands in s_d and is updated in place, exp() fused into that kernel's store
+        k::deinterleave(st, nb, n_s, sol_s, nullptr, nullptr, lognormal && !cond, s_d);
+        if (cond) cond->apply_device(level, nb, s_d, nullptr, s_d, lognormal);
     } else if (d.proj == PMC_PROJ_GATHER) {
         k::deinterleave(st, nb, d.out_size, sol_s, d.gather.p, nullptr, lognormal, s_d);
     } else {

@@ -171,6 +171,8 @@ void PDESampler::ComputeMaxError(int level, const Vector& coeff, double exact, d
     pmc_free(ctx_, d);
     check(rc, "PDESampler::ComputeMaxError");
 }
+void PDESampler::SetConditioner(pmc_conditioner* c) { check_arg(pmc_sampler_set_conditioner(h_, c), "PDESampler::SetConditioner"); }
+
 double PDESampler::ComputeL2Error(int level, const Vector& coeff, double exact) const {
     if (coeff.Batch() != 1) throw std::invalid_argument("PDESampler::ComputeL2Error: one field expected");
     double e = 0.0;

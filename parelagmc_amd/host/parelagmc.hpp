@@ -165,6 +165,9 @@ class PDESampler : public MLSampler {
     /// the batched forms: err[c] of each of coeff.Batch() fields (err: coeff.Batch() host doubles)
     void ComputeL2Error(int level, const Vector& coeff, double exact, double* err) const;
     void ComputeMaxError(int level, const Vector& coeff, double exact, double* err) const;
+    /// Eval returns fields conditioned on the data of `c` (pmc_conditioner_create on this handle, exact data); nullptr
+    /// detaches (pmc_sampler_set_conditioner).  The caller keeps ownership of `c`.
+    void SetConditioner(pmc_conditioner* c);
     pmc_sampler* Handle() const { return h_; }
 
   private:
