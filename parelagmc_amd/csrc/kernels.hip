@@ -9,7 +9,7 @@
 //   normal_fill                                : K1 NormalDistributionSampler
 //   interleave / deinterleave                  : K2 white-noise RHS scaling, K9 exp, K10 gather (fused with the layout change)
 //   darcy_*                                    : K12-K15 per-sample M(k), BC elimination, Schur refresh, QoI
-#include "kernels.hpp"
+#include "sell_rows.hpp"
 
 #include <cstddef>
 #include <cstdlib>
@@ -18,30 +18,6 @@
 #include <atomic>
 
 namespace pmc {
-
-#ifndef PMC_KBLOCK
-#define PMC_KBLOCK 256
-#endif
-static constexpr int kBlock = PMC_KBLOCK;   // workgroup size of the streaming / SpMM kernels (tuning builds may override)
-static constexpr int kWave = 64;
-#ifndef PMC_LEAN_GATHER
-#define PMC_LEAN_GATHER 1
-#endif
-static constexpr bool kLeanGather = PMC_LEAN_GATHER != 0;   // see sell_row_part: fp32 gathers without column scaling
-#ifndef PMC_LEAN_CS
-#define PMC_LEAN_CS 1
-#endif
-static constexpr bool kLeanCs = PMC_LEAN_CS != 0;           // ... fp64 gathers / column scaling (eg_poly2_kernel)
-#ifndef PMC_EG_LATE_COEF
-#define PMC_EG_LATE_COEF 1
-#endif
-static constexpr bool kEgLateCoef = PMC_EG_LATE_COEF != 0;  // see eg_row_product
-#ifndef PMC_LEAN_RANGE_MIN_NB
-#define PMC_LEAN_RANGE_MIN_NB 32
-#endif
-// sell_row_range takes the lean gather loop (see sell_row_part) from this batch width on: at NB = 32 the one-column loop
-// needs 170-184 registers (two waves per SIMD), the lean one fits three; at NB = 16 (four waves either way) it changed nothing
-static constexpr int kLeanRangeMinNb = PMC_LEAN_RANGE_MIN_NB;
 
 static unsigned dot_grid_bound();
 int dot_capacity(int nrows, int nb) {
@@ -54,537 +30,6 @@ int dot_capacity(int nrows, int nb) {
     return (int)std::max<size_t>(bounded, 256 + slice_blocks) + 2;
 }
 
-// Batch layout helper.  A row of NB interleaved values is handled by T lanes, C = 2 doubles (one 16 B
-// access) each, so a group of T lanes touches NB*8 contiguous bytes and a wavefront G = 64/T rows.
-template <int NB>
-struct Lay {
-    static constexpr int C = NB >= 32 ? 4 : (NB >= 2 ? 2 : 1);   // NB = 32: two 16 B accesses per lane, still 8 lanes per row
-    static constexpr int T = NB / C;
-    static constexpr int G = kWave / T;
-};
-
-// Column groups (super-batches).  A batch wider than kGroup realizations is ONE interleaved vector with row stride
-// ld = nb doubles, worked on as nb / kGroup groups of kGroup columns: group g owns the columns [g kGroup, (g + 1) kGroup) of
-// every row, blockIdx.y names the group, and every launch carries all groups - a level too small to fill the chip with 32
-// realizations is solved 64 ... 256 at a time.  Only the widest instantiation (NB == kGroup) is group-capable; the
-// narrower ones keep the compile-time row stride NB (ld is ignored, gridDim.y == 1).
-template <int NB>
-__device__ __forceinline__ int row_ld(int ld) {
-    if constexpr (NB == kGroup) return ld;
-    else return NB;
-}
-template <int NB>
-__device__ __forceinline__ int col0() {
-    if constexpr (NB == kGroup) return (int)blockIdx.y * NB;
-    else return 0;
-}
-
-template <int C>
-__device__ __forceinline__ void load_c(const double* __restrict__ p, double (&v)[C]) {
-    if constexpr (C == 1) {
-        v[0] = p[0];
-    } else {
-#pragma unroll
-        for (int i = 0; i < C / 2; ++i) {
-            const double2 t = reinterpret_cast<const double2*>(p)[i];
-            v[2 * i] = t.x;
-            v[2 * i + 1] = t.y;
-        }
-    }
-}
-template <int C>
-__device__ __forceinline__ void store_c(double* __restrict__ p, const double (&v)[C]) {
-    if constexpr (C == 1) {
-        p[0] = v[0];
-    } else {
-#pragma unroll
-        for (int i = 0; i < C / 2; ++i) reinterpret_cast<double2*>(p)[i] = make_double2(v[2 * i], v[2 * i + 1]);
-    }
-}
-
-// Per-realization matrix values of the PRECONDITIONER (Darcy: the Schur-complement hierarchy S(k)) may be stored in fp32
-// (BV == 2; BV == 1: fp64): the preconditioner stays a fixed symmetric linear operator - MINRES converges to the same
-// solution at the same tolerance - while the dominant stream of its kernels halves.  Arithmetic stays fp64.
-template <int C>
-__device__ __forceinline__ void load_cf(const float* __restrict__ p, double (&v)[C]) {
-    if constexpr (C == 1) {
-        v[0] = (double)p[0];
-    } else if constexpr (C == 2) {
-        const float2 t = *reinterpret_cast<const float2*>(p);
-        v[0] = (double)t.x;
-        v[1] = (double)t.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < C / 4; ++i) {
-            const float4 t = reinterpret_cast<const float4*>(p)[i];
-            v[4 * i] = (double)t.x;
-            v[4 * i + 1] = (double)t.y;
-            v[4 * i + 2] = (double)t.z;
-            v[4 * i + 3] = (double)t.w;
-        }
-    }
-}
-// values of batched matrix entry `idx` (in units of one value): fp64 or fp32 storage
-template <int BV, int C>
-__device__ __forceinline__ void load_bv(const double* __restrict__ vals, size_t idx, double (&v)[C]) {
-    if constexpr (BV == 2) load_cf<C>(reinterpret_cast<const float*>(vals) + idx, v);
-    else load_c<C>(vals + idx, v);
-}
-// advance a batched-value pointer by c columns
-template <int BV>
-__device__ __forceinline__ const double* shift_bv(const double* vals, int c) {
-    if constexpr (BV == 2) return reinterpret_cast<const double*>(reinterpret_cast<const float*>(vals) + c);
-    else return vals + c;
-}
-
-// typed vector accesses: fp64 or fp32 storage, fp64 in registers
-template <typename T>
-struct ident { using type = T; };   // keeps a parameter out of template argument deduction (nullptr arguments)
-template <int C>
-__device__ __forceinline__ void load_v(const double* __restrict__ p, double (&v)[C]) { load_c<C>(p, v); }
-template <int C>
-__device__ __forceinline__ void load_v(const float* __restrict__ p, double (&v)[C]) { load_cf<C>(p, v); }
-template <int C>
-__device__ __forceinline__ void store_v(double* __restrict__ p, const double (&v)[C]) { store_c<C>(p, v); }
-template <int C>
-__device__ __forceinline__ void store_v(float* __restrict__ p, const double (&v)[C]) {
-    if constexpr (C == 1) {
-        p[0] = (float)v[0];
-    } else if constexpr (C == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2((float)v[0], (float)v[1]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < C / 4; ++i)
-            reinterpret_cast<float4*>(p)[i] = make_float4((float)v[4 * i], (float)v[4 * i + 1], (float)v[4 * i + 2], (float)v[4 * i + 3]);
-    }
-}
-// values an fp32 store will keep: rounding BEFORE a fused dot keeps <., out> consistent with what is stored
-template <typename T, int C>
-__device__ __forceinline__ void round_to(double (&v)[C]) {
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) v[i] = (double)(float)v[i];
-    }
-}
-
-// What a gather leaves in registers until its FMA: fp32-stored vectors stay fp32 (half the registers per gather in flight)
-// and are widened only when they are consumed.
-template <typename XT, int C>
-struct RawVec {
-    XT v[C];
-};
-template <int C>
-__device__ __forceinline__ void load_raw(const double* __restrict__ p, RawVec<double, C>& r) { load_c<C>(p, r.v); }
-template <int C>
-__device__ __forceinline__ void load_raw(const float* __restrict__ p, RawVec<float, C>& r) {
-    if constexpr (C == 1) {
-        r.v[0] = p[0];
-    } else if constexpr (C == 2) {
-        const float2 t = *reinterpret_cast<const float2*>(p);
-        r.v[0] = t.x;
-        r.v[1] = t.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < C / 4; ++i) {
-            const float4 t = reinterpret_cast<const float4*>(p)[i];
-            r.v[4 * i] = t.x;
-            r.v[4 * i + 1] = t.y;
-            r.v[4 * i + 2] = t.z;
-            r.v[4 * i + 3] = t.w;
-        }
-    }
-}
-
-// The T = 8 gathers of one slice column (fp32 rows, four columns per lane) as ONE point of use.  hipcc sinks loads from
-// __restrict__ pointers past __builtin_amdgcn_sched_barrier (they carry no ordering against it) down to their first use; in
-// the kernels whose gathered fp32 values die in their own FMA group that turned "eight gathers in flight" into load - wait -
-// convert - fma, eight times per slice column (ISA of vc_residual_kernel<32, float, ...> and vc_poly2_kernel<32, float, ...>,
-// round 4: a level of 44 k rows took 67-74 us per launch where the fp64-gather kernel on the same matrix took 30).  An empty
-// asm that takes all eight results as operands cannot be split: every load is issued before it.
-typedef float pmc_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void pin_gathers(RawVec<float, 4> (&xr)[8]) {
-    pmc_f4 q0 = {xr[0].v[0], xr[0].v[1], xr[0].v[2], xr[0].v[3]}, q1 = {xr[1].v[0], xr[1].v[1], xr[1].v[2], xr[1].v[3]};
-    pmc_f4 q2 = {xr[2].v[0], xr[2].v[1], xr[2].v[2], xr[2].v[3]}, q3 = {xr[3].v[0], xr[3].v[1], xr[3].v[2], xr[3].v[3]};
-    pmc_f4 q4 = {xr[4].v[0], xr[4].v[1], xr[4].v[2], xr[4].v[3]}, q5 = {xr[5].v[0], xr[5].v[1], xr[5].v[2], xr[5].v[3]};
-    pmc_f4 q6 = {xr[6].v[0], xr[6].v[1], xr[6].v[2], xr[6].v[3]}, q7 = {xr[7].v[0], xr[7].v[1], xr[7].v[2], xr[7].v[3]};
-    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5), "+v"(q6), "+v"(q7));
-    const pmc_f4 q[8] = {q0, q1, q2, q3, q4, q5, q6, q7};
-#pragma unroll
-    for (int rs = 0; rs < 8; ++rs)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) xr[rs].v[c] = q[rs][c];
-}
-template <typename XT, int C, int T>
-__device__ __forceinline__ void pin_gathers(RawVec<XT, C> (&)[T]) {}
-// the same for sixteen widened values (8 row steps x 2 columns or 4 x 4): the own-row reads of an epilogue, issued together
-template <int R, int C>
-__device__ __forceinline__ void pin_block(double (&a)[R][C]) {
-    if constexpr (R == 8 && C == 2)
-        asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]),
-                     "+v"(a[3][1]), "+v"(a[4][0]), "+v"(a[4][1]), "+v"(a[5][0]), "+v"(a[5][1]), "+v"(a[6][0]), "+v"(a[6][1]),
-                     "+v"(a[7][0]), "+v"(a[7][1]));
-    else if constexpr (R == 4 && C == 4)
-        asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]),
-                     "+v"(a[1][3]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[2][2]), "+v"(a[2][3]), "+v"(a[3][0]), "+v"(a[3][1]),
-                     "+v"(a[3][2]), "+v"(a[3][3]));
-    else if constexpr (R == 2 && C == 4)
-        asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]),
-                     "+v"(a[1][3]));
-}
-
-// Vector streams without reuse inside the iteration (MINRES w / x updates of large levels): non-temporal variants, so that a
-// flat kernel running beside a gather kernel (second stream, other lanes) does not sweep that kernel's rows out of L2.
-// Measured at 0.6 M rows x 16: one lane 1096 -> 1112, four lanes 1446 -> 1454 samples/s; small levels keep the cached
-// accesses (their vectors live in the caches from one iteration to the next).
-template <bool NT, int C>
-__device__ __forceinline__ void load_c_nt(const double* __restrict__ p, double (&v)[C]) {
-    if constexpr (NT) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) v[i] = __builtin_nontemporal_load(p + i);
-    } else {
-        load_c<C>(p, v);
-    }
-}
-template <bool NT, int C>
-__device__ __forceinline__ void load_v_nt(const double* __restrict__ p, double (&v)[C]) { load_c_nt<NT, C>(p, v); }
-template <bool NT, int C>
-__device__ __forceinline__ void load_v_nt(const float* __restrict__ p, double (&v)[C]) {
-    if constexpr (NT) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) v[i] = (double)__builtin_nontemporal_load(p + i);
-    } else {
-        load_cf<C>(p, v);
-    }
-}
-template <bool NT, int C>
-__device__ __forceinline__ void store_c_nt(double* __restrict__ p, const double (&v)[C]) {
-    if constexpr (NT) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) __builtin_nontemporal_store(v[i], p + i);
-    } else {
-        store_c<C>(p, v);
-    }
-}
-
-// Streaming accesses (matrix values / indices read once, result rows written once) with NT = true are non-temporal, so
-// that they do not displace the gathered x rows - the only data with reuse - from the XCD's L2.  Worth it only when the
-// operands exceed the 256 MiB Infinity Cache, which non-temporal accesses bypass: measured on the block operator at
-// 4.7 M rows (1.65 GB per launch) 460-475 -> 435-448 us inside the solver loop; at 0.6 M rows (206 MB, cache-resident when
-// launched back to back) 43 -> 55 us, and no change inside the loop.  The launcher picks NT by operand size.
-template <bool NT, int C>
-__device__ __forceinline__ void store_c_stream(double* __restrict__ p, const double (&v)[C]) {
-    if constexpr (NT) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) __builtin_nontemporal_store(v[i], p + i);
-    } else {
-        store_c<C>(p, v);
-    }
-}
-template <bool NT>
-__device__ __forceinline__ int load_stream(const int* __restrict__ p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <bool NT>
-__device__ __forceinline__ double load_stream(const double* __restrict__ p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-
-// The Lanczos update y = c0 a + c1 b + c2 y of MINRES, columns k0 .. k0 + C - 1: ONE expression for the flat kernel
-// (lincomb3_kernel) and for the operator pass that forms the vector in its epilogue (sell_spmm_kernel, LZ >= 2), so that
-// both contract to the same instructions and give the same bits.
-template <int C>
-__device__ __forceinline__ void lanczos_combine(const double* __restrict__ c0, const double* __restrict__ c1,
-                                                const double* __restrict__ c2, int k0, const double (&a)[C],
-                                                const double (&b)[C], double (&y)[C]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) y[c] = c0[k0 + c] * a[c] + c1[k0 + c] * b[c] + c2[k0 + c] * y[c];
-}
-
-template <bool NT, int C>
-__device__ __forceinline__ void store_v_stream(double* __restrict__ p, const double (&v)[C]) { store_c_stream<NT, C>(p, v); }
-template <bool NT, int C>
-__device__ __forceinline__ void store_v_stream(float* __restrict__ p, const double (&v)[C]) {
-    if constexpr (NT) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) __builtin_nontemporal_store((float)v[i], p + i);
-    } else {
-        store_v<C>(p, v);
-    }
-}
-
-template <int NB>
-__device__ __forceinline__ void load_row(const double* __restrict__ p, double (&v)[NB]) {
-    if constexpr (NB == 1) {
-        v[0] = p[0];
-    } else {
-        const double2* q = reinterpret_cast<const double2*>(p);
-#pragma unroll
-        for (int i = 0; i < NB / 2; ++i) {
-            double2 t = q[i];
-            v[2 * i] = t.x;
-            v[2 * i + 1] = t.y;
-        }
-    }
-}
-template <int NB>
-__device__ __forceinline__ void store_row(double* __restrict__ p, const double (&v)[NB]) {
-    if constexpr (NB == 1) {
-        p[0] = v[0];
-    } else {
-        double2* q = reinterpret_cast<double2*>(p);
-#pragma unroll
-        for (int i = 0; i < NB / 2; ++i) q[i] = make_double2(v[2 * i], v[2 * i + 1]);
-    }
-}
-
-// Column-wise block reduction.  Every lane holds partial sums p[0..C) for columns (lane % T)*C + c.
-// Deterministic: fixed xor tree over the lanes that share a column, fixed order over the 4 wavefronts.
-// Virtual block index / grid extent of the slice kernels.  A launch of several column groups (nb > kGroup) is laid out as
-// dim3(8, groups, chunks) (groups_xcd): the hardware deals workgroups to the 8 XCDs by their linear id x + 8 y + 8 groups z, so
-// the blocks (x, 0, z) and (x, 1, z) - the SAME slices for column group 0 and 1 - run on the same XCD right after each other and
-// the second one finds the slices' (index, value) pairs in that XCD's L2 instead of reading the matrix from HBM once more.
-// Ordinary launches are dim3(blocks, groups, 1): vblock() == blockIdx.x.
-__device__ __forceinline__ int vblock() { return (int)(blockIdx.z * gridDim.x + blockIdx.x); }
-__device__ __forceinline__ int vgrid() { return (int)(gridDim.z * gridDim.x); }
-
-// Writes partial[vblock()*LD + k] (partial already points at the group's first column).
-template <int NB>
-__device__ __forceinline__ void reduce_cols_store(double (&p)[Lay<NB>::C], double* __restrict__ partial, int LD = NB) {
-    constexpr int C = Lay<NB>::C, T = Lay<NB>::T;
-    __shared__ double lds[kBlock / kWave][NB];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        double v = p[c];
-#pragma unroll
-        for (int off = kWave / 2; off >= T; off >>= 1) v += __shfl_xor(v, off, kWave);
-        p[c] = v;
-    }
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane < T) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) lds[wave][lane * C + c] = p[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < NB) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) s += lds[w][threadIdx.x];
-        partial[(size_t)vblock() * LD + threadIdx.x] = s;
-    }
-}
-
-// The same for the flat kernels on a batch of W = ld > kGroup columns (runtime width, W divides 4 * kBlock): thread t owns the
-// columns (4 t) % W + c of the rows it visits; LDS holds every thread's four sums, thread j < W adds the 4 kBlock / W
-// entries of column j in index order (deterministic).  Writes partial[blockIdx.x * W + j].
-__device__ __forceinline__ void reduce_cols_store_wide(const double (&p)[4], double* __restrict__ partial, int W) {
-    __shared__ double lds[kBlock * 4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) lds[threadIdx.x * 4 + c] = p[c];
-    __syncthreads();
-    if ((int)threadIdx.x < W) {
-        double s = 0.0;
-        for (int m = threadIdx.x; m < kBlock * 4; m += W) s += lds[m];
-        partial[(size_t)blockIdx.x * W + threadIdx.x] = s;
-    }
-}
-template <int NB>
-__device__ __forceinline__ void reduce_flat_store(double (&p)[Lay<NB>::C], double* __restrict__ partial, int W) {
-    if constexpr (NB == kGroup) {
-        if (W > NB) {
-            reduce_cols_store_wide(p, partial, W);
-            return;
-        }
-    }
-    reduce_cols_store<NB>(p, partial);
-}
-
-// ------------------------------------------------------------------------------------------
-// SELL-64 sparse matrix times interleaved multi-vector.  One wavefront per 64-row slice.  Every lane
-// loads the value / column of "its" row for slice column j (one fully coalesced 512 B + 256 B access
-// per wavefront), then the wavefront sweeps the slice in T steps of G rows: lane (g, t) takes row
-// rs*G+g and the 16 B column pair t, fetching that row's value / column index with a cross-lane
-// shuffle, so each x gather and each y store is one contiguous NB*8-byte segment per row.
-// sell_row_range works on `width` slice columns starting at slot `off`.  CS: every gathered x[col] is multiplied by a
-// second gathered per-realization vector cs[col] (column scaling A D^-1 without stored scaled values).  ZERO: acc is
-// cleared first, otherwise accumulated into.
-// xlast (optional): receives the x rows gathered by the LAST slice column.  A matrix built diagonal-last (Sell::diag_last:
-// every row ends with its diagonal entry and is padded with zero-weight copies of it) gathers x[row] there, so a fused
-// <x, Ax> needs no second read of x - which by the end of a slice has long left the L2 (measured at 0.6 M rows: 25 MB of
-// 280 MB per launch).
-template <int NB>
-__device__ __forceinline__ constexpr bool lean_range() {
-    return Lay<NB>::T > 1 && NB >= kLeanRangeMinNb;
-}
-template <int NB, int BV, bool CS, bool ZERO, bool NT = false, typename XT = double>
-__device__ __forceinline__ void sell_row_range(const int* __restrict__ cols, const double* __restrict__ vals,
-                                               const XT* __restrict__ x, const double* __restrict__ cs, int off,
-                                               int width, int lane, int LD, double (&acc)[Lay<NB>::T][Lay<NB>::C],
-                                               double (*xlast)[Lay<NB>::C] = nullptr, double* pdot = nullptr) {
-    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
-    const int g = lane / T, t = lane % T;
-    if constexpr (ZERO) {
-#pragma unroll
-        for (int rs = 0; rs < T; ++rs)
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[rs][c] = 0.0;
-    }
-    int slot = off + lane;
-
-    if constexpr (T == 1) {
-        // one lane per row (NB = 1, 2): take JU slice columns at a time so that JU (index, value) pairs and then
-        // JU gathers are in flight together instead of one dependent chain per column
-        constexpr int JU = 4;
-        for (int j = 0; j < width; j += JU, slot += JU * kWave) {
-            int cc[JU];
-            double aa[JU];
-#pragma unroll
-            for (int u = 0; u < JU; ++u) {
-                const bool ok = j + u < width;
-                const int at = ok ? slot + u * kWave : slot;   // out-of-range columns re-read column j, weight 0
-                cc[u] = cols[at];
-                if constexpr (BV) aa[u] = ok ? 1.0 : 0.0;
-                else aa[u] = ok ? vals[at] : 0.0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            double xv[JU][C], av[JU][C], sv[JU][C];
-#pragma unroll
-            for (int u = 0; u < JU; ++u) {
-                load_v<C>(x + (size_t)cc[u] * LD, xv[u]);
-                if constexpr (CS) load_c<C>(cs + (size_t)cc[u] * LD, sv[u]);
-                if constexpr (BV) load_bv<BV, C>(vals, (size_t)(j + u < width ? slot + u * kWave : slot) * LD, av[u]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < JU; ++u)
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if constexpr (CS) xv[u][c] *= sv[u][c];
-                    if constexpr (BV) acc[0][c] = fma(aa[u] * av[u][c], xv[u][c], acc[0][c]);
-                    else acc[0][c] = fma(aa[u], xv[u][c], acc[0][c]);
-                }
-        }
-        return;
-    }
-
-    int cj = 0;
-    double vj = 0.0;
-    if (width > 0) {
-        cj = load_stream<NT>(cols + slot);
-        if constexpr (!BV) vj = load_stream<NT>(vals + slot);
-    }
-    if constexpr (lean_range<NB>()) {
-        // lean loop (as sell_row_part): 32-bit element offsets, gathered rows and fp32 per-realization values stay in their
-        // storage type until the FMA, shared values are fetched across lanes after the gathers have been issued; with pdot
-        // the fused <x, A x> of a diagonal-last matrix is taken right at the row's last column (rows past the end carry
-        // zero values)
-        for (int j = 0; j < width; ++j, slot += kWave) {
-            int cn = cj;
-            double vn = vj;
-            if (j + 1 < width) {
-                cn = load_stream<NT>(cols + slot + kWave);
-                if constexpr (!BV) vn = load_stream<NT>(vals + slot + kWave);
-            }
-            unsigned at[T];
-#pragma unroll
-            for (int rs = 0; rs < T; ++rs) at[rs] = (unsigned)__shfl(cj, rs * G + g, kWave) * (unsigned)LD + (unsigned)(t * C);
-            RawVec<XT, C> xr[T];
-            RawVec<float, C> avf[BV == 2 ? T : 1];
-            double avd[BV == 1 ? T : 1][C];
-            double sv[CS ? T : 1][C];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rs = 0; rs < T; ++rs) {
-                load_raw<C>(x + at[rs], xr[rs]);
-                if constexpr (CS) load_c<C>(cs + at[rs], sv[rs]);
-                if constexpr (BV == 2)
-                    load_raw<C>(reinterpret_cast<const float*>(vals) + ((size_t)(slot - lane + rs * G + g) * LD + t * C), avf[rs]);
-                if constexpr (BV == 1) load_c<C>(vals + ((size_t)(slot - lane + rs * G + g) * LD + t * C), avd[rs]);
-            }
-            if (!pdot && !xlast) pin_gathers(xr);   // (with pdot / xlast the values live past the FMAs and stay grouped)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rs = 0; rs < T; ++rs) {
-                double a = 0.0;
-                if constexpr (!BV) a = __shfl(vj, rs * G + g, kWave);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    double xv = (double)xr[rs].v[c];
-                    if constexpr (CS) xv *= sv[rs][c];
-                    if constexpr (BV == 2) acc[rs][c] = fma((double)avf[rs].v[c], xv, acc[rs][c]);
-                    else if constexpr (BV == 1) acc[rs][c] = fma(avd[rs][c], xv, acc[rs][c]);
-                    else acc[rs][c] = fma(a, xv, acc[rs][c]);
-                }
-            }
-            if (j + 1 == width) {
-                if (pdot) {
-#pragma unroll
-                    for (int rs = 0; rs < T; ++rs)
-#pragma unroll
-                        for (int c = 0; c < C; ++c) pdot[c] = fma((double)xr[rs].v[c], acc[rs][c], pdot[c]);
-                } else if (xlast) {
-#pragma unroll
-                    for (int rs = 0; rs < T; ++rs)
-#pragma unroll
-                        for (int c = 0; c < C; ++c) xlast[rs][c] = (double)xr[rs].v[c];
-                }
-            }
-            cj = cn;
-            vj = vn;
-        }
-        return;
-    }
-    for (int j = 0; j < width; ++j, slot += kWave) {
-        // software pipeline: the next slice column's (value, index) pair is requested before this
-        // column's gathers, so its latency overlaps them
-        int cn = cj;
-        double vn = vj;
-        if (j + 1 < width) {
-            cn = load_stream<NT>(cols + slot + kWave);
-            if constexpr (!BV) vn = load_stream<NT>(vals + slot + kWave);
-        }
-        // phase 1: all cross-lane fetches, phase 2: all gathers (independent registers, so the T loads of a
-        // slice column are in flight together), phase 3: FMAs
-        int cc[T];
-        double aa[T];
-#pragma unroll
-        for (int rs = 0; rs < T; ++rs) {
-            const int src = rs * G + g;
-            cc[rs] = (T == 1) ? cj : __shfl(cj, src, kWave);
-            if constexpr (!BV) aa[rs] = (T == 1) ? vj : __shfl(vj, src, kWave);
-        }
-        double xv[T][C];
-        double av[T][C];
-        double sv[T][C];
-        if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise re-serialises load -> wait -> fma
-#pragma unroll
-        for (int rs = 0; rs < T; ++rs) {
-            load_v<C>(x + (size_t)cc[rs] * LD + t * C, xv[rs]);
-            if constexpr (CS) load_c<C>(cs + (size_t)cc[rs] * LD + t * C, sv[rs]);
-            if constexpr (BV) load_bv<BV, C>(vals, (size_t)(slot - lane + rs * G + g) * LD + t * C, av[rs]);
-        }
-        if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int rs = 0; rs < T; ++rs) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if constexpr (CS) xv[rs][c] *= sv[rs][c];
-                if constexpr (BV) acc[rs][c] = fma(av[rs][c], xv[rs][c], acc[rs][c]);
-                else acc[rs][c] = fma(aa[rs], xv[rs][c], acc[rs][c]);
-            }
-        }
-        if (xlast && j + 1 == width) {
-#pragma unroll
-            for (int rs = 0; rs < T; ++rs)
-#pragma unroll
-                for (int c = 0; c < C; ++c) xlast[rs][c] = xv[rs][c];
-        }
-        cj = cn;
-        vj = vn;
-    }
-}
-
 template <int NB, int BV, typename XT = double>
 __device__ __forceinline__ void sell_row_product(const int* __restrict__ slice_off, const int* __restrict__ cols,
                                                  const double* __restrict__ vals, const XT* __restrict__ x,
@@ -592,29 +37,6 @@ __device__ __forceinline__ void sell_row_product(const int* __restrict__ slice_o
     const int off = slice_off[slice];
     const int width = (slice_off[slice + 1] - off) >> 6;
     sell_row_range<NB, BV, false, true, false, XT>(cols, vals, x, nullptr, off, width, lane, LD, acc);
-}
-
-// XCD-aware slice assignment.  The dispatcher deals workgroups round-robin over the 8 XCDs (block b runs on XCD b % 8),
-// and each XCD has its own 4 MiB L2.  XCD x owns one CONTIGUOUS eighth of the slices (in processing order), so the x
-// entries its gathers touch (mesh neighbours = nearby indices) stay in that XCD's L2 instead of being fetched by all
-// eight.  Inside the eighth the slices are dealt CYCLICALLY over the XCD's workgroups (block i of the XCD takes the
-// slices 4 i .. 4 i + 3, then those one full round of workgroups further on, ...): whatever the grid size, the slices
-// in flight on an XCD at any time form one compact window of the rows.  (With one contiguous chunk per workgroup - the
-// round-1 layout - a bounded grid of 4096 workgroups at 4.7 M rows had concurrently running workgroups 19 slices apart:
-// the window of x rows in flight was 5x wider than the L2 and x was fetched 3 times, 2.87 GB per launch against
-// 1.65 GB algorithmic.)  Placement only affects speed, never results.
-struct SliceWalk {
-    int begin, end, stride;
-};
-__device__ __forceinline__ SliceWalk slice_walk(int nslices) {
-    constexpr int WPB = kBlock / kWave;                     // wavefronts = slices per workgroup and round
-    const int nblk = vgrid(), bid = vblock(), wave = threadIdx.x / kWave;
-    if (nblk < 8) return SliceWalk{bid * WPB + wave, nslices, nblk * WPB};
-    const int xcd = bid % 8, idx = bid / 8;
-    const int nb_x = nblk / 8 + (xcd < nblk % 8 ? 1 : 0);   // workgroups of this XCD
-    const int per = (nslices + 7) / 8;                      // slices of an XCD (the last one may get fewer)
-    const int lo = min(xcd * per, nslices), hi = min(lo + per, nslices);
-    return SliceWalk{lo + idx * WPB + wave, hi, nb_x * WPB};
 }
 
 // MODE 0: y = Ax   1: y += Ax   2: y = r - Ax ; DOT: partial sums of <dot_with, result>.
@@ -938,129 +360,6 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 ? 3 : 1)) void sell_po
 // consistent - measured (z rounded to fp32 after every application, cube_tet r = 4): identical iteration counts at 1e-6 ...
 // 1e-12 and fields equal to the unrounded run's to 7e-16.  What it saves is 87 MB of the 1 089 MB an iteration moves at r = 5.
 
-// DEEP gather loop for levels too small to fill the chip (NB = 32, shared values): J slice columns - J x 8 gathers per lane -
-// are in flight together.  A launch of a few hundred to a few thousand wavefronts (one per 64-row slice) runs less than one
-// wavefront per SIMD; each walks its slice's columns as a chain of dependent round trips to L2, so the launch lasts
-// `slice width` x latency whatever its size (round 5: the five V-cycle kernels of the 4 964-row level of the hybridized
-// hierarchy - 78 wavefronts, 17-27 columns - took ~38 us each, those of the 43 622-row level ~30 us).  With J columns per
-// trip the chain is J times shorter; registers (J x 32 for the raw fp32 rows) are no concern at that occupancy.  Same FMA
-// order per accumulator as the one-column loop (column after column), out-of-range columns re-read the last column with
-// weight zero: bit-identical results.
-typedef float pmc_f4x __attribute__((ext_vector_type(4)));
-template <int J>
-__device__ __forceinline__ void pin_deep(pmc_f4x (&q)[J][8]) {
-    if constexpr (J == 2)
-        asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[0][2]), "+v"(q[0][3]), "+v"(q[0][4]), "+v"(q[0][5]), "+v"(q[0][6]),
-                     "+v"(q[0][7]), "+v"(q[1][0]), "+v"(q[1][1]), "+v"(q[1][2]), "+v"(q[1][3]), "+v"(q[1][4]), "+v"(q[1][5]),
-                     "+v"(q[1][6]), "+v"(q[1][7]));
-    else if constexpr (J == 4)
-        asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[0][2]), "+v"(q[0][3]), "+v"(q[0][4]), "+v"(q[0][5]), "+v"(q[0][6]),
-                     "+v"(q[0][7]), "+v"(q[1][0]), "+v"(q[1][1]), "+v"(q[1][2]), "+v"(q[1][3]), "+v"(q[1][4]), "+v"(q[1][5]),
-                     "+v"(q[1][6]), "+v"(q[1][7]), "+v"(q[2][0]), "+v"(q[2][1]), "+v"(q[2][2]), "+v"(q[2][3]), "+v"(q[2][4]),
-                     "+v"(q[2][5]), "+v"(q[2][6]), "+v"(q[2][7]), "+v"(q[3][0]), "+v"(q[3][1]), "+v"(q[3][2]), "+v"(q[3][3]),
-                     "+v"(q[3][4]), "+v"(q[3][5]), "+v"(q[3][6]), "+v"(q[3][7]));
-}
-typedef double pmc_d2x __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void pin_deep_d(pmc_d2x (&q)[2][8][2]) {
-    asm volatile("" : "+v"(q[0][0][0]), "+v"(q[0][0][1]), "+v"(q[0][1][0]), "+v"(q[0][1][1]), "+v"(q[0][2][0]), "+v"(q[0][2][1]),
-                 "+v"(q[0][3][0]), "+v"(q[0][3][1]), "+v"(q[0][4][0]), "+v"(q[0][4][1]), "+v"(q[0][5][0]), "+v"(q[0][5][1]),
-                 "+v"(q[0][6][0]), "+v"(q[0][6][1]), "+v"(q[0][7][0]), "+v"(q[0][7][1]), "+v"(q[1][0][0]), "+v"(q[1][0][1]),
-                 "+v"(q[1][1][0]), "+v"(q[1][1][1]), "+v"(q[1][2][0]), "+v"(q[1][2][1]), "+v"(q[1][3][0]), "+v"(q[1][3][1]),
-                 "+v"(q[1][4][0]), "+v"(q[1][4][1]), "+v"(q[1][5][0]), "+v"(q[1][5][1]), "+v"(q[1][6][0]), "+v"(q[1][6][1]),
-                 "+v"(q[1][7][0]), "+v"(q[1][7][1]));
-}
-template <int NB, typename XT, int J>
-__device__ __forceinline__ void sell_row_range_deep(const int* __restrict__ cols, const double* __restrict__ vals,
-                                                    const XT* __restrict__ x, int off, int width, int lane, int LD,
-                                                    double (&acc)[Lay<NB>::T][Lay<NB>::C]) {
-    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
-    static_assert(C == 4 && T == 8, "the deep loop is written for the 32-wide layout");
-    static_assert((sizeof(XT) == 4 && (J == 2 || J == 4)) || (sizeof(XT) == 8 && J == 2), "columns per trip");
-    const int g = lane / T, t = lane % T;
-#pragma unroll
-    for (int rs = 0; rs < T; ++rs)
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[rs][c] = 0.0;
-    int slot = off + lane;
-    int cj[J];
-    double vj[J];
-#pragma unroll
-    for (int u = 0; u < J; ++u) {
-        const bool ok = u < width;
-        const int at = ok ? slot + u * kWave : slot;
-        cj[u] = width > 0 ? cols[at] : 0;
-        vj[u] = (ok && width > 0) ? vals[at] : 0.0;
-    }
-    for (int j = 0; j < width; j += J, slot += J * kWave) {
-        int cn[J];
-        double vn[J];
-#pragma unroll
-        for (int u = 0; u < J; ++u) {   // the next trip's (index, value) pairs: requested before this trip's gathers
-            const bool ok = j + J + u < width;
-            const int at = ok ? slot + (J + u) * kWave : slot;
-            cn[u] = cols[at];
-            vn[u] = ok ? vals[at] : 0.0;
-        }
-        unsigned at[J][T];
-#pragma unroll
-        for (int u = 0; u < J; ++u)
-#pragma unroll
-            for (int rs = 0; rs < T; ++rs) at[u][rs] = (unsigned)__shfl(cj[u], rs * G + g, kWave) * (unsigned)LD + (unsigned)(t * C);
-        if constexpr (sizeof(XT) == 4) {
-            pmc_f4x q[J][8];
-#pragma unroll
-            for (int u = 0; u < J; ++u)
-#pragma unroll
-                for (int rs = 0; rs < T; ++rs) q[u][rs] = *reinterpret_cast<const pmc_f4x*>(x + at[u][rs]);
-            pin_deep<J>(q);
-#pragma unroll
-            for (int u = 0; u < J; ++u)
-#pragma unroll
-                for (int rs = 0; rs < T; ++rs) {
-                    const double a = __shfl(vj[u], rs * G + g, kWave);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) acc[rs][c] = fma(a, (double)q[u][rs][c], acc[rs][c]);
-                }
-        } else {
-            pmc_d2x q[2][8][2];
-#pragma unroll
-            for (int u = 0; u < J; ++u)
-#pragma unroll
-                for (int rs = 0; rs < T; ++rs) {
-                    q[u][rs][0] = reinterpret_cast<const pmc_d2x*>(x + at[u][rs])[0];
-                    q[u][rs][1] = reinterpret_cast<const pmc_d2x*>(x + at[u][rs])[1];
-                }
-            pin_deep_d(q);
-#pragma unroll
-            for (int u = 0; u < J; ++u)
-#pragma unroll
-                for (int rs = 0; rs < T; ++rs) {
-                    const double a = __shfl(vj[u], rs * G + g, kWave);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) acc[rs][c] = fma(a, q[u][rs][c >> 1][c & 1], acc[rs][c]);
-                }
-        }
-#pragma unroll
-        for (int u = 0; u < J; ++u) {
-            cj[u] = cn[u];
-            vj[u] = vn[u];
-        }
-    }
-}
-
-// acc = A x for one slice, shared fp64 values, gathered vector of type XT (the T > 1 schedule of sell_row_range; T == 1
-// walks the slice columns one by one)
-// DEEP > 1 (NB = 32, shared values): sell_row_range_deep with that many slice columns per trip
-template <int NB, typename XT, bool NT = false, int BV = 0, int DEEP = 1>
-__device__ __forceinline__ void sell_row_range_t(const int* __restrict__ cols, const double* __restrict__ vals,
-                                                 const XT* __restrict__ x, int off, int width, int lane, int LD,
-                                                 double (&acc)[Lay<NB>::T][Lay<NB>::C]) {
-    if constexpr (DEEP > 1 && NB == 32 && BV == 0)
-        sell_row_range_deep<NB, XT, DEEP>(cols, vals, x, off, width, lane, LD, acc);
-    else
-        sell_row_range<NB, BV, false, true, NT, XT>(cols, vals, x, nullptr, off, width, lane, LD, acc);
-}
-
 // out = dinv (c0 r - c1 As r) (+ xadd) (+ padd_x[padd_idx]) with r of type XT (gathered and read at the own row), out of
 // type OT, xadd of type AT; DOT: partials of <dot_with, out> (dot_with fp64).  See sell_poly2_kernel.
 #ifndef PMC_VC_MIN_WAVES
@@ -1367,110 +666,6 @@ __global__ __launch_bounds__(kBlock) void sell_pair_spmm_kernel(
         }
     }
     if constexpr (DOT) reduce_cols_store<NB>(p, partial, LD);
-}
-
-// sell_row_range for the TH row steps rs0 .. rs0 + TH - 1 of a slice only (shared values).  A kernel that sweeps a slice in
-// T / TH such passes keeps TH instead of T rows' accumulators, gathers and shuffled slot data alive - the element-grouped
-// kernels below, which carry two accumulators and up to three gathered vectors per row, drop from 206-246 VGPRs (two waves per
-// SIMD) to four waves per SIMD; the (index, value) pairs of the later passes come from L1.
-template <int NB, bool CS, typename XT>
-__device__ __forceinline__ constexpr bool lean_part() {
-    return Lay<NB>::T > 1 && ((!CS && sizeof(XT) == 4) ? kLeanGather : kLeanCs);
-}
-template <int NB, bool CS, bool ZERO, bool NT, int TH, typename XT = double>
-__device__ __forceinline__ void sell_row_part(const int* __restrict__ cols, const double* __restrict__ vals,
-                                              const XT* __restrict__ x, const double* __restrict__ cs, int off, int width,
-                                              int lane, int LD, int rs0, double (&acc)[TH][Lay<NB>::C]) {
-    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
-    const int g = lane / T, t = lane % T;
-    if constexpr (ZERO) {
-#pragma unroll
-        for (int q = 0; q < TH; ++q)
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[q][c] = 0.0;
-    }
-    int slot = off + lane;
-    int cj = 0;
-    double vj = 0.0;
-    if (width > 0) {
-        cj = load_stream<NT>(cols + slot);
-        vj = load_stream<NT>(vals + slot);
-    }
-    if constexpr (lean_part<NB, CS, XT>()) {
-        // Lean loop: 32-bit element offsets address the gathers, gathered rows stay in their storage type until their FMA
-        // (fp32 rows of the preconditioned Krylov vectors: half the registers), and the matrix values are fetched across
-        // lanes only AFTER the gathers have been issued - fewer registers live while the loads are in flight, and the
-        // cross-lane traffic overlaps the gather latency.  Hex 64^3 x 16, rocprofv3 averages: Darcy operator u-rows
-        // 96.9 -> 85.1 us, M-block polynomial 119.5 -> 114.8 us (compiled for three waves per SIMD instead the operator
-        // spills and takes 90.5 us; the same loop in the block operator K5 - 92 instead of 114 registers, five waves - changed
-        // nothing measurable).
-        for (int j = 0; j < width; ++j, slot += kWave) {
-            int cn = cj;
-            double vn = vj;
-            if (j + 1 < width) {
-                cn = load_stream<NT>(cols + slot + kWave);
-                vn = load_stream<NT>(vals + slot + kWave);
-            }
-            unsigned at[TH];
-#pragma unroll
-            for (int q = 0; q < TH; ++q) at[q] = (unsigned)__shfl(cj, (rs0 + q) * G + g, kWave) * (unsigned)LD + (unsigned)(t * C);
-            RawVec<XT, C> xr[TH];
-            double sv[CS ? TH : 1][C];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < TH; ++q) {
-                load_raw<C>(x + at[q], xr[q]);
-                if constexpr (CS) load_c<C>(cs + at[q], sv[q]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < TH; ++q) {
-                const double a = __shfl(vj, (rs0 + q) * G + g, kWave);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    double xv = (double)xr[q].v[c];
-                    if constexpr (CS) xv *= sv[q][c];
-                    acc[q][c] = fma(a, xv, acc[q][c]);
-                }
-            }
-            cj = cn;
-            vj = vn;
-        }
-        return;
-    }
-    for (int j = 0; j < width; ++j, slot += kWave) {
-        int cn = cj;
-        double vn = vj;
-        if (j + 1 < width) {
-            cn = load_stream<NT>(cols + slot + kWave);
-            vn = load_stream<NT>(vals + slot + kWave);
-        }
-        int cc[TH];
-        double aa[TH];
-#pragma unroll
-        for (int q = 0; q < TH; ++q) {
-            const int src = (rs0 + q) * G + g;
-            cc[q] = (T == 1) ? cj : __shfl(cj, src, kWave);
-            aa[q] = (T == 1) ? vj : __shfl(vj, src, kWave);
-        }
-        double xv[TH][C], sv[TH][C];
-        if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < TH; ++q) {
-            load_v<C>(x + (size_t)cc[q] * LD + t * C, xv[q]);
-            if constexpr (CS) load_c<C>(cs + (size_t)cc[q] * LD + t * C, sv[q]);
-        }
-        if constexpr (T > 1) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < TH; ++q)
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if constexpr (CS) xv[q][c] *= sv[q][c];
-                acc[q][c] = fma(aa[q], xv[q][c], acc[q][c]);
-            }
-        cj = cn;
-        vj = vn;
-    }
 }
 
 // row steps per pass of the element-grouped kernels
@@ -3503,10 +2698,6 @@ int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* 
     }));
     return nblk;
 }
-int vc_postsmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                    double* xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial) {
-    return vc_postsmooth32_z(st, nb, As, dinv, res, x, zvec(xout, false), c0, c1, r, parent, xc, dot_partial);
-}
 
 // ---- the same level with per-realization fp32 values (Darcy; SellView::f32) and per-realization diagonals
 void vc_presmooth32_bv(hipStream_t st, int nb, const SellView& As, const double* dinv, const double* r, float* xout, double c0,
@@ -3662,10 +2853,6 @@ static int pair_spmm_t(hipStream_t st, int nb, const SellView& A1, const XT* x1,
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
 
-int pair_spmm(hipStream_t st, int nb, const SellView& A1, const double* x1, const SellView& A2, const double* x2, double* y,
-              double* dot_partial, const double* dot_with) {
-    return pair_spmm_t<double>(st, nb, A1, x1, A2, x2, y, dot_partial, dot_with);
-}
 int pair_spmm_z(hipStream_t st, int nb, const SellView& A1, zvec x1, const SellView& A2, zvec x2, double* y,
                 double* dot_partial, zvec dot_with) {
     if (x1.f32) return pair_spmm_t<float>(st, nb, A1, x1.as<float>(), A2, x2.as<float>(), y, dot_partial, dot_with.as<float>());
@@ -3719,13 +2906,6 @@ int cheb_first(hipStream_t st, int nb, int n, const double* dinv, bool dinv_bv, 
 }
 
 static inline dim3 grid_dot(int n, int nb) { return dim3(std::min(grid_flat(n, nb).x, 1024u)); }
-
-int dot(hipStream_t st, int nb, int n, const double* a, const double* b, double* partial) {
-    const dim3 g = grid_dot(n, nb);
-    PMC_DISPATCH_NB(nb, { dot_kernel<NB><<<g, kBlock, 0, st>>>(flat_count(n, nb), a, b, partial, nb); });
-    check_launch();
-    return (int)g.x;
-}
 
 int dot_z(hipStream_t st, int nb, int n, const double* a, zvec b, double* partial) {
     const dim3 g = grid_dot(n, nb);

@@ -1,4 +1,5 @@
-// Launchers of the CDNA4 kernels (kernels.hip).  All vectors are "interleaved" batches:
+// Launchers of the CDNA4 kernels (kernels.hip, over kdev.hpp: device-side helpers, and sell_rows.hpp: the SELL-64 gather
+// loops; this header is the one interface the rest of the library sees).  All vectors are "interleaved" batches:
 // row i, column (realization) k of a batch of nb lives at v[i*nb + k], nb in {1,2,4,8,16,32} or - as 2, 4, 8 column groups
 // of 32 handled by one launch (gridDim.y) - 64, 128, 256.
 #pragma once
@@ -189,8 +190,6 @@ void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec 
 void vc_restrict32(hipStream_t st, int nb, const SellView& Pt, const float* res, zvec coarse);
 void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, zvec xc);
 // r is the operand of the fused dot only (top level of a cycle: fp64)
-int vc_postsmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
-                    double* xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial);
 int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
                       zvec xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial);
 // ... and for a level with per-realization fp32 values and diagonals (Darcy; no S P: the coarse correction is added to the
@@ -205,8 +204,6 @@ int vc_postsmooth32_bv(hipStream_t st, int nb, const SellView& As, const double*
 int vc_postsmooth32_bv_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
                          zvec xout, double c0, double c1, const double* r, double* dot_partial);
 // y = A1 x1 + A2 x2 (A1 per-realization values, A2 shared values, same rows); optional fused dot
-int pair_spmm(hipStream_t st, int nb, const SellView& A1, const double* x1, const SellView& A2, const double* x2, double* y,
-              double* dot_partial, const double* dot_with);
 int pair_spmm_z(hipStream_t st, int nb, const SellView& A1, zvec x1, const SellView& A2, zvec x2, double* y,
                 double* dot_partial, zvec dot_with);
 // out[slot][k] = vals[slot][k] * colscale[cols[slot]][k]
@@ -222,7 +219,6 @@ void minres_wx_idx(hipStream_t st, int nb, int nsel, const int* rows, const doub
 int cheb_first(hipStream_t st, int nb, int n, const double* dinv, bool dinv_bv, const double* r, double* d,
                double* x, double b, double* dot_partial = nullptr);
 // both return the number of partial blocks written
-int dot(hipStream_t st, int nb, int n, const double* a, const double* b, double* partial);
 int wdot(hipStream_t st, int nb, int n, const double* w, const double* x, double* partial);
 int dot_z(hipStream_t st, int nb, int n, const double* a, zvec b, double* partial);
 // out = in rounded to zvec storage; dot_partial != nullptr: partials of <r, out>.  Returns the partial-block count.
