@@ -189,6 +189,11 @@ uint64_t pmc_kernel_launches(void);
  * solve in its eager loop; DESIGN.md section 3, paragraph "The multiplier solve without q"): path diagnostics, as
  * pmc_kernel_launches */
 uint64_t pmc_fused_lanczos_solves(void);
+/* ... whose right-hand side was written by its producer straight into the first Lanczos vector and its fp32 copy (the
+ * hybridized sampler's G product from a zero guess), and batch evaluations of the hybridized sampler whose back-substitution
+ * wrote the field sample-major itself (identity output map, no embedded copy, no conditioner): path diagnostics */
+uint64_t pmc_adopted_rhs_solves(void);
+uint64_t pmc_fused_field_evals(void);
 const char* pmc_last_error(void);
 void pmc_solver_opts_default(pmc_solver_opts* opts);
 

@@ -98,6 +98,8 @@ SYMBOLS = {
     "pmc_darcy_krylov_z_bytes": (C.c_int, [_VP]),
     "pmc_kernel_launches": (C.c_uint64, []),
     "pmc_fused_lanczos_solves": (C.c_uint64, []),
+    "pmc_adopted_rhs_solves": (C.c_uint64, []),
+    "pmc_fused_field_evals": (C.c_uint64, []),
     "pmc_ctx_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_create_abi": (C.c_int, [C.c_int, C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_destroy": (None, [_VP]),
@@ -219,6 +221,10 @@ SYMBOLS = {
     "pmc_allreduce_sum_f64": (C.c_int, [_VP, C.POINTER(C.c_double), C.c_int]),
 }
 
+# path diagnostics added after the boundary settled: a library built from an older commit (the parent in a same-box A/B,
+# scripts/ab_libs.sh) lacks them and still loads; calling one on such a library raises AttributeError
+_LATE_DIAGNOSTICS = ("pmc_adopted_rhs_solves", "pmc_fused_field_evals")
+
 _lib = None
 
 
@@ -234,6 +240,8 @@ def load_library(path: Optional[str] = None):
         raise PmcError(-2, f"{p} not found - build it with `make` / __graft_entry__.build() (no CPU fallback)")
     lib = C.CDLL(p)
     for name, (res, args) in SYMBOLS.items():
+        if name in _LATE_DIAGNOSTICS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)     # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -106,6 +106,8 @@ int pmc_abi_version(void) { return PMC_ABI_VERSION; }
 int pmc_krylov_z_bytes(void) { return 4; }   // of the default options (PMC_STORAGE_FP32)
 uint64_t pmc_kernel_launches(void) { return kernel_launch_count(); }
 uint64_t pmc_fused_lanczos_solves(void) { return fused_lanczos_solve_count(); }
+uint64_t pmc_adopted_rhs_solves(void) { return adopted_rhs_solve_count(); }
+uint64_t pmc_fused_field_evals(void) { return fused_field_eval_count(); }
 const char* pmc_last_error(void) { return g_last_error.c_str(); }
 
 static void check_abi(const pmc_solver_opts& o) {

@@ -40,6 +40,10 @@ struct SamplerLevel {
     std::vector<int> lam_n2o_host;   // lam_new2old on the host (setup export of the V-cycle's finest prolongator)
 };
 
+// evaluations (launches of one batch) of this process whose back-substitution wrote the field sample-major itself
+// (k::residual_samples) instead of the interleaved field and its k::deinterleave (all handles, all threads)
+uint64_t fused_field_eval_count();
+
 struct Sampler {
     Ctx& ctx;
     int nlevels, n_mc;
@@ -111,7 +115,8 @@ struct Sampler {
 
   private:
     void ensure(int level, int nb);
-    void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats);
+    // rhs (hybridized solver): the kernel that would write the multiplier right-hand side, handed to the solve (RhsFn)
+    void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs = nullptr);
     PrecFn preconditioner(int level, int nb, int degM, Multigrid* mgp, int mg_l0);
     void eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                     int init_level, bool use_init, double* emb_d, pmc_stats* stats);

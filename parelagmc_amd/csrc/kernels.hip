@@ -57,9 +57,14 @@ __device__ __forceinline__ void sell_row_product(const int* __restrict__ slice_o
 //   2 = no dot; the epilogue forms the next Lanczos vector from the row sums (the same bits as the stored q) and the own
 //       rows of v1 (lz.v1) and v0 (y): y = c0 (A x) + c1 v1 + c2 y, written over v0 together with its fp32 copy lz.y32;
 //   3 = as 2 in the first iteration, where v0 is zero: y is not read (the c2 term is kept with a literal +0.0, so even the
-//       sign of a zero result is that of the flat kernel)
+//       sign of a zero result is that of the flat kernel);
+//   4 = a plain product that also leaves the fp32 copy of its result in lz.y32 (k::spmm_store32: the right-hand side a MINRES
+//       solve adopts as its first Lanczos vector - what k::copy_r32 made of the stored product, from the registers)
+// SM (MODE 2, shared values): the result leaves the kernel sample-major, y[k * nrows + row], as k::deinterleave would write it
+//   from the interleaved one (k::residual_samples); 2 = through exp().  Each value is computed as in the interleaved form and
+//   stored once; a wavefront writes, per column, the 64 rows of its slice in T runs of G consecutive rows.
 template <int NB, int BV, int MODE, bool DOT, int TAG, bool NT = false, bool R8 = false, bool DL = false, typename XT = double,
-          typename YT = double, int LZ = 0>
+          typename YT = double, int LZ = 0, int SM = 0>
 __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3 : 1)) void sell_spmm_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                            const int* __restrict__ sched,
                                                            const int* __restrict__ cols,
@@ -73,19 +78,23 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
     static_assert(LZ == 0 || (BV == 0 && MODE == 0 && !R8 && sizeof(YT) == 8 && DOT == (LZ == 1)),
                   "Lanczos passes: shared values, plain product; the dot-only pass has the dot, the update passes none");
     static_assert(sizeof(YT) == 8 || (MODE == 0 && !DOT && !NT), "fp32 result: plain products only");
+    static_assert(SM == 0 || (MODE == 2 && BV == 0 && !DOT && !R8 && LZ == 0 && sizeof(YT) == 8),
+                  "sample-major result: the plain residual of a shared-value matrix");
     const int LD = row_ld<NB>(ld);
     {
         const int c0 = col0<NB>();   // this group's columns of every interleaved operand
         x += c0;
-        if constexpr (LZ != 1) y += c0;   // (the dot-only pass has no y)
+        if constexpr (SM) y += (size_t)c0 * nrows;   // column k of the result starts at k * nrows
+        else if constexpr (LZ != 1) y += c0;         // (the dot-only pass has no y)
         if constexpr (BV) vals = shift_bv<BV>(vals, c0);
         if constexpr (MODE == 2) r += c0;
         if constexpr (DOT && !DL) dot_with += c0;
         if constexpr (DOT || R8) partial += c0;
-        if constexpr (LZ >= 2) {
-            lz.v1 += c0; lz.y32 += c0;
+        if constexpr (LZ == 2 || LZ == 3) {
+            lz.v1 += c0;
             lz.c0 += c0; lz.c1 += c0; lz.c2 += c0;
         }
+        if constexpr (LZ >= 2) lz.y32 += c0;
     }
     static_assert(!DL || (DOT && !BV && Lay<NB>::T > 1), "diagonal-last serves the fused <x, Ax> of shared-value operators");
     constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
@@ -130,7 +139,17 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
 #pragma unroll
                     for (int c = 0; c < C; ++c) acc[rs][c] = rv[c] - acc[rs][c];
                 }
-                if constexpr (LZ >= 2) {
+                if constexpr (LZ == 4) {
+                    store_c<C>(y + at, acc[rs]);
+                    store_v<C>(lz.y32 + at, acc[rs]);
+                } else if constexpr (SM) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        double tv = acc[rs][c];
+                        if constexpr (SM == 2) tv = exp(tv);
+                        y[(size_t)(t * C + c) * nrows + row] = tv;
+                    }
+                } else if constexpr (LZ >= 2) {
                     double bv[C], yv[C];
                     load_c_nt<NT, C>(lz.v1 + at, bv);
                     if constexpr (LZ == 2) {
@@ -1056,57 +1075,93 @@ __device__ __forceinline__ void load_raw_nt(const UT* __restrict__ p, RawVec<UT,
 }
 
 // The w / x updates of B.cnt <= kWxWindow iterations in one pass (see kWxWindow): the pending iterations are walked in
-// trips of kWxDefer - the u vectors of a trip are requested first (and stay in their storage type until their FMA), the
-// recurrences then run in registers in iteration order, w0 / w1 / x stay in registers from trip to trip - the same
-// operations in the same order as cnt successive minres_wx launches.  B.first: w0 and w1 are zero, and with B.x_zero so
-// is x: they start as literal zeros (the same bits as a loaded +0.0); B.last: w0 / w1 are never read again and not stored.
+// trips - the u vectors of a trip are requested first (and stay in their storage type until their FMA), the recurrences
+// then run in registers in iteration order, w0 / w1 / x stay in registers from trip to trip - the same operations in the
+// same order as cnt successive minres_wx launches.  B.first: w0 and w1 are zero, and with B.x_zero so is x: they start as
+// literal zeros (the same bits as a loaded +0.0); B.last: w0 / w1 are never read again and not stored.
+//
+// A thread owns R entries kBlock flat indices apart: kBlock * C is a multiple of every row stride, so the R entries lie in
+// the same columns and one load of an iteration's four coefficient rows serves all of them.  With one entry per thread the
+// coefficient loads - eight 16-byte loads per lane and iteration, against one of u - kept the vector memory pipeline busy
+// six times as long as the payload did, and the pass ran at 0.42 of the HBM rate (LAB_NOTES 10.27).  A workgroup walks
+// R * kBlock consecutive entries; entries past the end alias the thread's first one and are not stored.
+template <typename UT, int C>
+struct WxShape {
+    static constexpr int R = sizeof(UT) == 4 ? 4 : 2;
+    // u values in flight per lane: about 64 registers' worth, at most kWxDefer iterations
+    static constexpr int Dfit = 64 / (R * C * (int)(sizeof(UT) / 4));
+    static constexpr int D = Dfit < 1 ? 1 : (Dfit > k::kWxDefer ? k::kWxDefer : Dfit);
+};
 template <int NB, bool NT, typename UT>
 __global__ __launch_bounds__(kBlock) void minres_wx_deferred_kernel(size_t nflat, k::WxDeferred B,
                                                                     const double* __restrict__ cW, double* __restrict__ w0,
                                                                     double* __restrict__ w1, double* __restrict__ x, int ld) {
     constexpr int C = Lay<NB>::C;
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nflat) return;
-    const size_t e = i * C;
-    const int k0 = (int)(e % row_ld<NB>(ld));
-    double a[C], b[C], xv[C];
-    if (B.first) {
+    constexpr int R = WxShape<UT, C>::R, D = WxShape<UT, C>::D;
+    const size_t i0 = (size_t)blockIdx.x * (R * kBlock) + threadIdx.x;
+    if (i0 >= nflat) return;
+    const int k0 = (int)((i0 * C) % row_ld<NB>(ld));
+    size_t e[R];
+    bool live[R];
 #pragma unroll
-        for (int c = 0; c < C; ++c) a[c] = b[c] = 0.0;
-    } else {
-        load_c_nt<NT, C>(w0 + e, a);
-        load_c_nt<NT, C>(w1 + e, b);
+    for (int r = 0; r < R; ++r) {
+        const size_t i = i0 + (size_t)r * kBlock;
+        live[r] = i < nflat;
+        e[r] = (live[r] ? i : i0) * C;
     }
-    if (B.first && B.x_zero) {
+    double a[R][C], b[R][C], xv[R][C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) xv[c] = 0.0;
-    } else {
-        load_c_nt<NT, C>(x + e, xv);
+    for (int r = 0; r < R; ++r) {
+        if (B.first) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) a[r][c] = b[r][c] = 0.0;
+        } else {
+            load_c_nt<NT, C>(w0 + e[r], a[r]);
+            load_c_nt<NT, C>(w1 + e[r], b[r]);
+        }
+        if (B.first && B.x_zero) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) xv[r][c] = 0.0;
+        } else {
+            load_c_nt<NT, C>(x + e[r], xv[r]);
+        }
     }
-    for (int t = 0; t < B.cnt; t += k::kWxDefer) {
-        RawVec<UT, C> uv[k::kWxDefer];
+    for (int t = 0; t < B.cnt; t += D) {
+        RawVec<UT, C> uv[D][R];
 #pragma unroll
-        for (int j = 0; j < k::kWxDefer; ++j)
-            if (t + j < B.cnt) load_raw_nt<NT>(static_cast<const UT*>(B.u[t + j]) + e, uv[j]);
+        for (int j = 0; j < D; ++j) {
+            if (t + j < B.cnt) {
+                const UT* up = static_cast<const UT*>(B.u[t + j]);
 #pragma unroll
-        for (int j = 0; j < k::kWxDefer; ++j) {
+                for (int r = 0; r < R; ++r) load_raw_nt<NT>(up + e[r], uv[j][r]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
             if (t + j < B.cnt) {
                 const double* cj = cW + (size_t)B.slot[t + j] * 4 * kMaxBatch + k0;
 #pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const double wn = cj[c] * (double)uv[j].v[c] + cj[kMaxBatch + c] * a[c] + cj[2 * kMaxBatch + c] * b[c];
-                    xv[c] += cj[3 * kMaxBatch + c] * wn;
-                    a[c] = b[c];
-                    b[c] = wn;
+                for (int r = 0; r < R; ++r) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const double wn = cj[c] * (double)uv[j][r].v[c] + cj[kMaxBatch + c] * a[r][c] + cj[2 * kMaxBatch + c] * b[r][c];
+                        xv[r][c] += cj[3 * kMaxBatch + c] * wn;
+                        a[r][c] = b[r][c];
+                        b[r][c] = wn;
+                    }
                 }
             }
         }
     }
-    if (!B.last) {
-        store_c_nt<NT, C>(w0 + e, a);
-        store_c_nt<NT, C>(w1 + e, b);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!live[r]) continue;
+        if (!B.last) {
+            store_c_nt<NT, C>(w0 + e[r], a[r]);
+            store_c_nt<NT, C>(w1 + e[r], b[r]);
+        }
+        store_c_nt<NT, C>(x + e[r], xv[r]);
     }
-    store_c_nt<NT, C>(x + e, xv);
 }
 
 // partial sums of <w, x[:,k]> with a shared (non-batched) weight vector w   (K15 QoI)
@@ -2176,6 +2231,11 @@ static inline dim3 grid_rows(int n) { return dim3((unsigned)((n + kBlock - 1) / 
 static inline dim3 grid_slices(int nslices) { return dim3((unsigned)((nslices + kBlock / kWave - 1) / (kBlock / kWave))); }
 static inline int lay_c(int nb) { return nb >= 32 ? 4 : (nb >= 2 ? 2 : 1); }   // = Lay<nb>::C
 static inline size_t flat_count(int n, int nb) { return (size_t)n * nb / lay_c(nb); }
+// workgroups of k::minres_wx_deferred: each walks `rows` * kBlock consecutive flat entries
+static inline unsigned wx_deferred_blocks(size_t nflat, int rows) {
+    const size_t per = (size_t)rows * kBlock;
+    return (unsigned)((nflat + per - 1) / per);
+}
 static inline dim3 grid_flat(int n, int nb) { return dim3((unsigned)((flat_count(n, nb) + kBlock - 1) / kBlock)); }
 static std::atomic<uint64_t> g_kernel_launches{0};
 uint64_t kernel_launch_count() { return g_kernel_launches.load(std::memory_order_relaxed); }
@@ -2388,6 +2448,33 @@ void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double*
             sell_spmm_kernel<NB, true, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
         else
             sell_spmm_kernel<NB, false, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
+    });
+    check_launch();
+}
+
+void spmm_store32(hipStream_t st, int nb, const SellView& A, const double* x, double* y, float* y32) {
+    check_offsets32(A, nb);
+    if (A.bv || A.tag != 0 || !y || !y32) throw Error(PMC_ERR_INTERNAL, "spmm_store32: shared values, an untagged matrix, both results");
+    if (A.nrows == 0) return;
+    const dim3 g = grid_slices(A.nslices);
+    LanczosUpdate lz{};
+    lz.y32 = y32;
+    PMC_DISPATCH_NB(nb, {
+        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, double, double, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb, lz);
+    });
+    check_launch();
+}
+
+void residual_samples(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, bool do_exp, double* out) {
+    check_offsets32(A, nb);
+    if (A.bv) throw Error(PMC_ERR_INTERNAL, "residual_samples: shared values only");
+    if (A.nrows == 0) return;
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        if (do_exp)
+            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
     });
     check_launch();
 }
@@ -2985,13 +3072,18 @@ void minres_wx_deferred(hipStream_t st, int nb, int n, const MinresState* s, con
     if (B.cnt < 0 || B.cnt > kWxWindow) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: bad count");
     const double* cW = reinterpret_cast<const double*>(reinterpret_cast<const char*>(s) + offsetof(MinresState, cW));
     const bool nt = nt_flat((size_t)n * nb);
+    // the entries of one thread share their columns (see the kernel): kBlock * C flat values are whole rows
+    if ((kBlock * lay_c(nb)) % nb != 0) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: row stride does not divide a workgroup's step");
+    const size_t nf = flat_count(n, nb);
     PMC_DISPATCH_NB(nb, {
+        constexpr int C = Lay<NB>::C;
+        const dim3 g32(wx_deferred_blocks(nf, WxShape<float, C>::R)), g64(wx_deferred_blocks(nf, WxShape<double, C>::R));
         if (B.f32) {
-            if (nt) minres_wx_deferred_kernel<NB, true, float><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), B, cW, w0, w1, x, nb);
-            else minres_wx_deferred_kernel<NB, false, float><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), B, cW, w0, w1, x, nb);
+            if (nt) minres_wx_deferred_kernel<NB, true, float><<<g32, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
+            else minres_wx_deferred_kernel<NB, false, float><<<g32, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
         } else {
-            if (nt) minres_wx_deferred_kernel<NB, true, double><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), B, cW, w0, w1, x, nb);
-            else minres_wx_deferred_kernel<NB, false, double><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), B, cW, w0, w1, x, nb);
+            if (nt) minres_wx_deferred_kernel<NB, true, double><<<g64, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
+            else minres_wx_deferred_kernel<NB, false, double><<<g64, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
         }
     });
     check_launch();

@@ -100,8 +100,10 @@ namespace k {
 // once and writes x once, nothing else (the first pass starts from literal zeros instead of loading w0 / w1 / x, the last
 // pass does not store w0 / w1).  With fp32-stored u, 20 iterations: 4 x 21 + 8 = 92 bytes per entry and solve; with the
 // window of 8 of round 5 it was 228 plus 24 of fills.
-// kWxDefer is the number of preconditioned vectors ONE TRIP of the kernel has in flight: a pass walks its window in trips
-// of kWxDefer, w0 / w1 / x stay in registers across the trips (round 5: 8 instead of 4).
+// A pass walks its window in trips: the preconditioned vectors of a trip's iterations are requested together, w0 / w1 / x
+// stay in registers across the trips.  A thread owns several entries in the same columns (one load of an iteration's
+// coefficients serves all of them), so a trip is as many iterations as about 64 registers of u hold - four at four values
+// per thread and four entries - and at most kWxDefer (WxShape in kernels.hip).
 #ifndef PMC_WX_DEFER_N
 #define PMC_WX_DEFER_N 8
 #endif
@@ -158,6 +160,12 @@ void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double*
                         double* coarse);
 // out = r - A x
 void residual(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, double* out);
+// the same values sample-major, out[k * A.nrows + i] = post(r - A x)[i][k], post = exp if do_exp: what deinterleave (identity
+// rows, no scaling) makes of residual's result, without the interleaved vector in between (shared values)
+void residual_samples(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, bool do_exp, double* out);
+// y = A x and y32 = its fp32 copy from one launch (shared values, untagged matrix): spmm followed by copy_r32, without the
+// pass that reads y again
+void spmm_store32(hipStream_t st, int nb, const SellView& A, const double* x, double* y, float* y32);
 // Chebyshev / Jacobi step:  d = a*d + b*dinv.*(r - A xin);  xout = xin + d   (xin != xout).
 // dot_partial != nullptr: also per-block partials of <r, xout>; returns the number of blocks written.
 int cheb_step(hipStream_t st, int nb, const SellView& A, const double* dinv, bool dinv_bv, const double* r,

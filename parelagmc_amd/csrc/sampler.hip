@@ -1,6 +1,7 @@
 // SPDE Matérn sampler on the device: PDESampler / EmbeddedPDESampler / L2ProjectionPDESampler
 // ::Sample and ::Eval (reference: src/PDESampler.cpp:336-535, src/EmbeddedPDESampler.cpp:438-563,
 // src/L2ProjectionPDESampler.cpp:621-757).
+#include <atomic>
 #include <algorithm>
 #include <cmath>
 
@@ -545,6 +546,9 @@ void Sampler::sample(int level, uint64_t first_id, int nbatch, double* xi, int m
     }
 }
 
+static std::atomic<uint64_t> g_fused_field_evals{0};
+uint64_t fused_field_eval_count() { return g_fused_field_evals.load(std::memory_order_relaxed); }
+
 void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                          int init_level, bool use_init, double* emb_d, pmc_stats* stats) {
     hipStream_t st = ctx.stream;
@@ -568,11 +572,27 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
                 std::swap(cur, nxt);
             }
         }
-        k::spmm(st, nb, view(d.Gz), fz, rhs.p, false, nullptr, nullptr);
+        // the product is handed to the solve, which has it write the first Lanczos vector and its fp32 copy where it can
+        // (RhsFn); nothing reads the multiplier rows of rhs after the solve, only fz behind them
+        const SellView Gzv = view(d.Gz);
+        RhsFn make_rhs;
+        make_rhs.store = rhs.p;
+        make_rhs.write = [Gzv, fz](const Lanes& L, int nb_, double* y, float* y32) {
+            if (y32) k::spmm_store32(L.main, nb_, Gzv, fz, y, y32);
+            else k::spmm(L.main, nb_, Gzv, fz, y, false, nullptr, nullptr);
+        };
         if (stats) ctx.phase_mark(1);
-        solve_system(level, nb, true, 0, n_u, stats);
+        solve_system(level, nb, true, 0, n_u, stats, &make_rhs);
+        const SellView Glv = view(d.Gl);
+        // the field as the caller gets it, from the back-substitution itself: identity output map, and neither an embedded
+        // copy nor a conditioner that would want the interleaved field
+        if (d.proj == PMC_PROJ_NONE && !cond && !emb_d && !Glv.bv) {
+            k::residual_samples(st, nb, Glv, fz, sol.p, lognormal, s_d);
+            g_fused_field_evals.fetch_add(1, std::memory_order_relaxed);
+            return;
+        }
         double* field = sol.p + (size_t)n_u * nb;
-        k::residual(st, nb, view(d.Gl), fz, sol.p, field);
+        k::residual(st, nb, Glv, fz, sol.p, field);
     } else {
     // rhs_s = -g W^{1/2} xi on xi_level, restricted with Ps^T (PDESampler.cpp:423-438); rhs_u = 0 (:441-442)
     k::fill(st, (size_t)n_u * nb, rhs.p, 0.0);
@@ -629,7 +649,7 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
 
 // invA[level]->Mult(rhs, sol) (PDESampler.cpp:397,521): preconditioned MINRES on the interleaved member vectors rhs -> sol
 // for nb realizations; rows [x_row0, x_row0 + x_nrows) of the solution are maintained.  The caller has marked phase 1.
-void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats) {
+void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs_fn) {
     hipStream_t st = ctx.stream;
     SamplerLevel& d = lv[level];
     const int n_u = d.n_u, n_s = d.n_s, n = (int)system_rows(level);
@@ -703,7 +723,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
     GraphHint hint;
     hint.key = hash_mix(hash_mix(hash_mix(0x5a, (uint64_t)level + 1), (uint64_t)nb), (uint64_t)x_row0);
     hint.sig = hash_ptr(hash_ptr(hash_ptr(mgp->signature(mg_l0), cx.p), cd.p), cx2.p);
-    MinresResult res = minres_solve(ctx, nb, A, prec, rhs.p, sol.p, zero_guess, opts, work, x_row0, x_nrows, nullptr, hint);
+    MinresResult res = minres_solve(ctx, nb, A, prec, rhs.p, sol.p, zero_guess, opts, work, x_row0, x_nrows, nullptr, hint, rhs_fn);
     if (vc_timer.on) vc_timer.harvest();   // minres_solve has synchronised the stream
     if (stats) {
         ctx.phase_mark(2);

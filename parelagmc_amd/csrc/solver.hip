@@ -589,6 +589,9 @@ static bool fused_lanczos_on() {
     return v;
 }
 
+static std::atomic<uint64_t> g_adopted_rhs_solves{0};
+uint64_t adopted_rhs_solve_count() { return g_adopted_rhs_solves.load(std::memory_order_relaxed); }
+
 // PMC_LATE_WX=0 keeps the w / x update inside its own iteration also on two streams (A/B switch)
 static bool late_wx() {
     static const bool v = [] {
@@ -600,7 +603,7 @@ static bool late_wx() {
 
 MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, const double* b, double* x,
                           bool zero_guess, const pmc_solver_opts& o, MinresWork& w, int x_row0, int x_nrows,
-                          const int* x_rows, GraphHint hint) {
+                          const int* x_rows, GraphHint hint, const RhsFn* rhs) {
     hipStream_t st = ctx.stream;
     const int n = A.n;
     const size_t len = (size_t)n * nb;
@@ -631,7 +634,16 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     if (!A.apply_z || (!zero_guess && !A.apply)) throw Error(PMC_ERR_INTERNAL, "minres: operator closures missing");
     if (x_row0 < 0 || x_nrows < 0 || (!x_rows && x_row0 + x_nrows > n))
         throw Error(PMC_ERR_INTERNAL, "minres: bad solution row range");
+    if (rhs && (!rhs->write || !rhs->store)) throw Error(PMC_ERR_INTERNAL, "minres: right-hand side producer incomplete");
     if (fused) g_fused_solves.fetch_add(1, std::memory_order_relaxed);   // counted once the arguments have passed
+    // the producer writes v1 and its fp32 copy itself (RhsFn): a zero guess on the path that keeps r32, in the plain eager
+    // loop on one stream.  Every other solve has b stored first and copies it as before.
+    const bool adopt = rhs && zero_guess && r32 && !graphs && !L.split;
+    if (rhs && !adopt) {
+        rhs->write(L, nb, rhs->store, nullptr);
+        b = rhs->store;
+    }
+    if (adopt) g_adopted_rhs_solves.fetch_add(1, std::memory_order_relaxed);
     const size_t xoff = (size_t)x_row0 * nb;
     // w / x updates of a whole window of iterations in one pass (see k::minres_wx_deferred): whenever the update is a plain
     // vector kernel on this stream - not the compact index-list update of the Darcy solves (a few rows), not the two-stream
@@ -645,7 +657,8 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
         } else {
             k::fill(st, x_rows ? (size_t)x_nrows * nb : len, x, 0.0);
         }
-        if (r32) k::copy_r32(st, nb, n, b, v1, w.r32.p);   // v1 and its fp32 copy from one read of b
+        if (adopt) rhs->write(L, nb, v1, w.r32.p);
+        else if (r32) k::copy_r32(st, nb, n, b, v1, w.r32.p);   // v1 and its fp32 copy from one read of b
         else k::copy(st, len, b, v1);
     } else {
         A.apply(L, nb, x, v1, nullptr, nullptr);

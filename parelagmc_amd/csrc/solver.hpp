@@ -230,6 +230,16 @@ struct LinOp {
 using PrecFn = std::function<k::DotParts(const Lanes& L, int nb, const double* r, zvec z, double* dot_partial,
                                          double* dot_partial2)>;
 
+// Optional producer of the right-hand side: a caller whose b is the result of one last kernel hands that kernel over
+// instead of b.  A solve that starts from a zero guess and keeps the fp32 copy of its Lanczos vectors (MinresWork::r32) in
+// the plain eager loop ADOPTS it: write(L, nb, v1, r32) stores b straight into the first Lanczos vector and its fp32 copy,
+// and b itself is never stored.  Every other solve calls write(L, nb, store, nullptr) first and proceeds from b = store.
+// Either way v1 == b and r32 == (float) b, bit for bit.
+struct RhsFn {
+    std::function<void(const Lanes& L, int nb, double* y, float* y32)> write;
+    double* store = nullptr;   // n * nb doubles: where b goes when the solve keeps it
+};
+
 // Caller-side identity of one solver configuration for hipGraph reuse: `key` names the configuration (handle, level,
 // batch width, ...), `sig` hashes every device pointer the caller's operator / preconditioner closures use, so a
 // reallocation anywhere invalidates the cached graph.  key == 0: never use graphs.
@@ -314,6 +324,8 @@ struct MinresWork {
 
 // solves of this process that took the two operator passes of minres_solve instead of storing q = A u (all handles, all threads)
 uint64_t fused_lanczos_solve_count();
+// ... that adopted their right-hand side from its producer (RhsFn) instead of copying a stored b
+uint64_t adopted_rhs_solve_count();
 
 struct MinresResult {
     pmc_stats col[kMaxBatch];
@@ -323,12 +335,13 @@ struct MinresResult {
 // Preconditioned MINRES on nb right-hand sides at once.  x holds the initial guess on entry when
 // !zero_guess.  b, x: n*nb interleaved device vectors.
 // Only rows [x_row0, x_row0 + x_nrows) of the solution are updated (the samplers need the s-block only,
-// which saves two thirds of the w / x vector traffic); pass 0, A.n for the full solution.  With x_rows != nullptr
+// which saves two thirds of the w / x vector traffic); pass 0, A.n for the full solution.  rhs != nullptr: b is ignored and
+// comes from the producer (see RhsFn).  With x_rows != nullptr
 // (device index list of x_nrows rows, zero initial guess only) x is a COMPACT [x_nrows][nb] vector holding just those
 // rows of the solution (Darcy: the support of the observation functional).
 MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, const double* b, double* x,
                           bool zero_guess, const pmc_solver_opts& o, MinresWork& w, int x_row0, int x_nrows,
-                          const int* x_rows = nullptr, GraphHint hint = GraphHint());
+                          const int* x_rows = nullptr, GraphHint hint = GraphHint(), const RhsFn* rhs = nullptr);
 
 // Gershgorin bounds of spec(D^-1 A) for D = diag(A) on the host (setup): returns lmax, sets *lmin
 // (may be <= 0 when a row is not strictly diagonally dominant)
