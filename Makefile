@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
+SRCS := $(CSRC)/kernels.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -111,3 +111,10 @@ $(ABIBIN)/condition_smoke: tests/c/condition_smoke.c tests/c/kl_io.h include/pmc
 	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/condition_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-condition: $(ABIBIN)/condition_smoke
 .PHONY: test-condition
+
+# the adjoint gradients through the mirror classes of parelagmc.hpp (tests/test_gpu_darcy_gradient.py builds and runs it)
+$(ABIBIN)/gradient_smoke: tests/c/gradient_smoke.cpp tests/c/prob_io.h parelagmc_amd/host/parelagmc.hpp include/pmc.h include/pmc_host.h | $(HOSTLIB)
+	@mkdir -p $(ABIBIN)
+	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/gradient_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-gradient: $(ABIBIN)/gradient_smoke
+.PHONY: test-gradient

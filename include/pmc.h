@@ -624,6 +624,40 @@ int pmc_darcy_num_observations(const pmc_darcy* d, int level);
 int pmc_darcy_compute_G(pmc_darcy* d, int level, int nbatch, const double* k, double* G, double* C, double* Q,
                         int memspace, pmc_stats* stats);
 
+/* ---- Adjoint gradients with respect to the permeability field (an extension: the reference has none)
+ * The mixed system is symmetric: with A(k) x = rhs_bc (essential rows of x hold the essential data) and A(k) lam = dJ/dx
+ * (essential rows of lam zero), dJ/dc_e = -lam_u^T M_e x_u with M_e the unit-coefficient element matrix of the level's
+ * contribution lists, and dJ/dk_e = c'(k_e) dJ/dc_e, c = 1/k (k_divides) or k.  wrt_log != 0: the gradient with respect to
+ * log k (times k).  k, grad: nbatch x n_p(level); full vectors: nbatch x (n_u + n_p), sample-major; arrays in `memspace`
+ * unless stated.  Column b of every result is the same, bit for bit, however nbatch is split into calls and launches.  All
+ * three functions take the saddle-point path, also on a handle from pmc_darcy_create_hybrid (as pmc_darcy_compute_G does).
+ * Refused with PMC_ERR_INVALID: a level outside [0, n_mc_levels), nbatch < 1, NULL k / grad; non-positive k is the caller's
+ * problem, as in pmc_darcy_solve_fwd. */
+/* In-situ timing of the mass-sensitivity kernel (the one new kernel of a gradient), on the pmc_darcy_set_operator_timing switch
+ * and with the meaning of pmc_darcy_operator_time; ALGORITHMIC bytes of one launch for nbatch realizations: per element n_fe
+ * face indices (4 B) + n_fe^2 matrix entries (8 B) + nbatch x 16 (k read, gradient written), and every row of x_u and lam_u
+ * once (nbatch x 16 n_u).  The bytes call builds the level's gradient data when no gradient has been asked for yet. */
+int pmc_darcy_mass_sensitivity_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms);
+int pmc_darcy_mass_sensitivity_bytes(pmc_darcy* d, int level, int nbatch, double* bytes);
+/* grad[b*n_p + e] = -c'(k) lam_u^T M_e x_u for caller-supplied vectors x, lam.  No solve. */
+int pmc_darcy_mass_sensitivity(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, const double* lam,
+                               int wrt_log, double* grad, int memspace);
+/* Forward solve, adjoint solve, gradient: one per-realization setup serves both solves (same operator, preconditioner and
+ * options; the adjoint solve starts from zero).  adj_rhs: nbatch x (n_u + n_p) = dJ/dx per realization, or NULL = the level's
+ * obs (J = Q); its essential rows are ignored.  Q, C (host, may be NULL) as pmc_darcy_solve_fwd - Q bit-identical to
+ * pmc_darcy_solve_fwd(..., sol_out != NULL) of the same call; sol_out / adj_out (may be NULL): x and lam; stats_fwd /
+ * stats_adj (may be NULL): nbatch entries for the two solves. */
+int pmc_darcy_solve_gradient(pmc_darcy* d, int level, int nbatch, const double* k, const double* adj_rhs, int wrt_log,
+                             double* Q, double* C, double* grad, double* sol_out, double* adj_out, int memspace,
+                             pmc_stats* stats_fwd, pmc_stats* stats_adj);
+/* Gradient of the Gaussian log-likelihood loglik = -|G(k) - data|^2 / (2 noise) of the handle's observation functionals
+ * (pmc_darcy_set_observations; the logarithm of BayesianInverseProblem::ComputeLikelihood, src/BayesianInverseProblem.cpp:196):
+ * forward solve -> G -> adjoint right-hand side -(1/noise) sum_i (G_i - data_i) g_i / sum(g_i) on the p-rows, formed on the
+ * device -> adjoint solve -> gradient.  data: HOST array of nobs; loglik (nbatch), G (nbatch x nobs): host arrays, may be NULL.
+ * Also refused: no observation functionals on the level, noise <= 0, NULL data. */
+int pmc_darcy_loglik_gradient(pmc_darcy* d, int level, int nbatch, const double* k, const double* data, double noise,
+                              int wrt_log, double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj);
+
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */
 int pmc_comm_unique_id(void* id128);                                        /* 128 bytes    */

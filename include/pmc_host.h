@@ -130,6 +130,11 @@ const char* pmc_host_last_error(void);
  * likelihood, C: host arrays of nbatch; Q, R: host arrays or NULL. */
 int pmc_bayes_likelihood(pmc_darcy* solver, int level, int nbatch, const double* k, int memspace, const double* G_obs,
                          int nobs, double noise, double* likelihood, double* C, double* Q, double* R);
+/* BayesianInverseProblem::ComputeGradLogLikelihood (an extension: the reference has no gradients): loglik = log of the
+ * likelihood above and its adjoint gradient with respect to k (wrt_log != 0: log k) for nbatch realizations, through
+ * pmc_darcy_loglik_gradient.  loglik: host array of nbatch or NULL; grad: nbatch x n_p(level) in `memspace`, as k. */
+int pmc_bayes_loglik_gradient(pmc_darcy* solver, int level, int nbatch, const double* k, int memspace, const double* G_obs,
+                              int nobs, double noise, int wrt_log, double* loglik, double* grad);
 
 /* ---- ML_BayesRatio_Manager / SL_BayesRatio_Manager (src/ML_BayesRatio_Manager.hpp:315-728, src/SL_BayesRatio_Manager.hpp)
  * Multilevel ratio estimator E[Q * likelihood] / E[likelihood]: per realization two INDEPENDENT prior draws, one for

@@ -215,6 +215,15 @@ SYMBOLS = {
     "pmc_darcy_num_observations": (C.c_int, [_VP, C.c_int]),
     "pmc_darcy_compute_G": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_darcy_mass_sensitivity_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "pmc_darcy_mass_sensitivity_bytes": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "pmc_darcy_mass_sensitivity": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, _DP, C.c_int]),
+    "pmc_darcy_solve_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats),
+                                           C.POINTER(pmc_stats)]),
+    "pmc_darcy_loglik_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.POINTER(C.c_double), C.c_double, C.c_int,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), _DP, C.c_int,
+                                            C.POINTER(pmc_stats)]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -1230,6 +1239,90 @@ class DarcySolver:
                                                          _ptr(Cc, C.c_double), _ptr(Q, C.c_double),
                                                          1 if compute_Q else 0, PMC_MEM_HOST, stats))
         return P, Cc, (Q if compute_Q else None)
+
+    # ---- adjoint gradients with respect to k --------------------------------------------------
+    def _grad_out(self, level, k, nbatch, grad_out):
+        """(k, nbatch, grad): numpy k -> a new numpy gradient; device k -> grad_out (a DeviceArray / tensor) is required"""
+        if isinstance(k, np.ndarray):
+            k = _f64(np.atleast_2d(k))
+            nbatch = k.shape[0]
+            if grad_out is None:
+                grad_out = np.empty((nbatch, self.problem.levels[level].n_p))
+        assert nbatch is not None and grad_out is not None
+        if _addr(k)[1] != _addr(grad_out)[1]:
+            raise ValueError("k and the gradient must share a memory space")
+        return k, nbatch, grad_out
+
+    def _same_space(self, ms, *arrays):
+        out = []
+        for a in arrays:
+            if isinstance(a, np.ndarray):
+                a = _f64(np.atleast_2d(a))
+            p, m = _addr(a)
+            if a is not None and m != ms:
+                raise ValueError("all arrays of a call must share a memory space")
+            out.append((a, p))
+        return out
+
+    def mass_sensitivity_time(self):
+        """the gradient's mass-sensitivity kernel under set_operator_timing: (bracket ms, launches, empty-bracket ms)"""
+        ms, n, gap = C.c_double(0.0), C.c_int64(0), C.c_double(0.0)
+        _check(self.ctx.lib.pmc_darcy_mass_sensitivity_time(self.h, C.byref(ms), C.byref(n), C.byref(gap)))
+        return ms.value, n.value, gap.value
+
+    def mass_sensitivity_bytes(self, level, nbatch):
+        b = C.c_double(0.0)
+        _check(self.ctx.lib.pmc_darcy_mass_sensitivity_bytes(self.h, level, nbatch, C.byref(b)))
+        return b.value
+
+    def mass_sensitivity(self, level, k, x, lam, wrt_log=False, nbatch=None, grad_out=None):
+        """g[b, e] = -c'(k) lam_u^T M_e x_u for caller-supplied full vectors x, lam (nbatch, n_u + n_p); no solve
+        (pmc_darcy_mass_sensitivity).  numpy arrays, or DeviceArrays / device tensors with nbatch and grad_out."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        (x, px), (lam, pl) = self._same_space(ms, x, lam)
+        _check(self.ctx.lib.pmc_darcy_mass_sensitivity(self.h, level, nbatch, pk, px, pl, 1 if wrt_log else 0,
+                                                       _addr(grad)[0], ms))
+        return grad
+
+    def solve_gradient(self, level, k, adj_rhs=None, wrt_log=False, nbatch=None, grad_out=None, want_solution=False,
+                       sol_out=None, adj_out=None, return_stats=False):
+        """Forward solve, adjoint solve, gradient (pmc_darcy_solve_gradient): returns (Q, C, grad) - plus (x, lam) with
+        want_solution or given sol_out / adj_out, plus the (forward, adjoint) stats lists with return_stats.  adj_rhs None:
+        J = Q (the level's obs)."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        if want_solution and ms == PMC_MEM_HOST:
+            n = self.GetGlobalNumberOfDofs(level)
+            sol_out = np.empty((nbatch, n)) if sol_out is None else sol_out
+            adj_out = np.empty((nbatch, n)) if adj_out is None else adj_out
+        (adj_rhs, pr), (sol_out, ps), (adj_out, pa) = self._same_space(ms, adj_rhs, sol_out, adj_out)
+        Q, Cc = np.empty(nbatch), np.empty(nbatch)
+        sf, sa = (pmc_stats * nbatch)(), (pmc_stats * nbatch)()
+        _check(self.ctx.lib.pmc_darcy_solve_gradient(self.h, level, nbatch, pk, pr, 1 if wrt_log else 0,
+                                                     _ptr(Q, C.c_double), _ptr(Cc, C.c_double), _addr(grad)[0], ps, pa, ms,
+                                                     sf, sa))
+        out = [Q, Cc, grad]
+        if sol_out is not None or adj_out is not None:
+            out += [sol_out, adj_out]
+        if return_stats:
+            out += [[(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in st] for st in (sf, sa)]
+        return tuple(out)
+
+    def loglik_gradient(self, level, k, data, noise, wrt_log=False, nbatch=None, grad_out=None):
+        """Gradient of the Gaussian log-likelihood of the observation functionals set with SetObservations
+        (pmc_darcy_loglik_gradient): returns (loglik (nbatch,), G (nbatch, nobs), grad)."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        nobs = max(self.ctx.lib.pmc_darcy_num_observations(self.h, level), 0)
+        data = _f64(np.asarray(data, dtype=np.float64).ravel())
+        if nobs and data.size != nobs:
+            raise ValueError("data must hold one value per observation functional")
+        ll, G = np.empty(nbatch), np.empty((nbatch, nobs))
+        _check(self.ctx.lib.pmc_darcy_loglik_gradient(self.h, level, nbatch, pk, _ptr(data, C.c_double), float(noise),
+                                                      1 if wrt_log else 0, _ptr(ll, C.c_double), _ptr(G, C.c_double),
+                                                      _addr(grad)[0], ms, None))
+        return ll, G, grad
 
     def close(self):
         if getattr(self, "h", None):

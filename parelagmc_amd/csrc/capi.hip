@@ -696,6 +696,7 @@ int pmc_darcy_set_operator_timing(pmc_darcy* d, int on) {
         PMC_REQUIRE(d != nullptr, "darcy handle is NULL");
         d->impl.op_timer.on = on != 0;
         d->impl.poly_timer.on = on != 0;
+        d->impl.grad_timer.on = on != 0;
     });
 }
 int pmc_darcy_operator_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms) {
@@ -728,6 +729,22 @@ int pmc_darcy_poly_bytes(const pmc_darcy* d, int level, int nbatch, double* byte
         PMC_REQUIRE(d != nullptr && bytes != nullptr && level >= 0 && level < d->impl.nlevels && valid_batch(nbatch),
                     "pmc_darcy_poly_bytes: bad arguments");
         *bytes = d->impl.poly_bytes(level, nbatch);
+    });
+}
+int pmc_darcy_mass_sensitivity_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy handle is NULL");
+        if (total_ms) *total_ms = d->impl.grad_timer.ms;
+        if (launches) *launches = d->impl.grad_timer.launches;
+        if (event_overhead_ms) *event_overhead_ms = d->impl.grad_timer.gap_ms;
+        d->impl.grad_timer.clear();
+    });
+}
+int pmc_darcy_mass_sensitivity_bytes(pmc_darcy* d, int level, int nbatch, double* bytes) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr && bytes != nullptr && level >= 0 && level < d->impl.n_mc && valid_batch(nbatch),
+                    "pmc_darcy_mass_sensitivity_bytes: bad arguments");
+        *bytes = d->impl.mass_sensitivity_bytes(level, nbatch);
     });
 }
 int pmc_darcy_batch_width(const pmc_darcy* d, int level) {
@@ -864,6 +881,32 @@ int pmc_darcy_compute_G(pmc_darcy* d, int level, int nbatch, const double* kf, d
     return guarded([&] {
         PMC_REQUIRE(d != nullptr, "darcy is NULL");
         d->impl.compute_G(level, nbatch, kf, G, C, Q, memspace, stats);
+    });
+}
+int pmc_darcy_mass_sensitivity(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, const double* lam,
+                               int wrt_log, double* grad, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.mass_sensitivity(level, nbatch, k, x, lam, wrt_log != 0, grad, memspace);
+    });
+}
+int pmc_darcy_solve_gradient(pmc_darcy* d, int level, int nbatch, const double* k, const double* adj_rhs, int wrt_log,
+                             double* Q, double* C, double* grad, double* sol_out, double* adj_out, int memspace,
+                             pmc_stats* stats_fwd, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.solve_gradient(level, nbatch, k, adj_rhs, wrt_log != 0, Q, C, grad, sol_out, adj_out, memspace, stats_fwd,
+                               stats_adj);
+    });
+}
+int pmc_darcy_loglik_gradient(pmc_darcy* d, int level, int nbatch, const double* k, const double* data, double noise,
+                              int wrt_log, double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.loglik_gradient(level, nbatch, k, data, noise, wrt_log != 0, loglik, G, grad, memspace, stats_adj);
     });
 }
 

@@ -590,6 +590,8 @@ void Darcy::set_observations(int level, const pmc_csr* Gc) {
     d.g_norm.upload(norm, st);
     d.n_gobs = G.nrows;
     d.n_grows = (int)rows.size();
+    d.Gobs_host = std::move(G);                // kept for the log-likelihood gradient (darcy_gradient.hip)
+    d.has_gt = false;
     PMC_HIP(hipStreamSynchronize(st));
 }
 

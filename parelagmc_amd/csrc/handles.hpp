@@ -251,6 +251,19 @@ struct DarcyLevel {
     Sell Gobs;
     DevBuf<int> g_rows;
     DevBuf<double> g_obs_w, g_norm;
+    // Adjoint gradients (darcy_gradient.hip), built at the first gradient call of the level: per
+    // element its faces and the dense unit-coefficient matrix M_e, element-major in slices of 64 elements, column-major
+    // inside a slice - faces [slice][a][64], M_e [slice][a n_fe + a'][64]
+    bool has_grad = false;
+    int grad_nfe = 0, grad_nslices = 0;
+    DevBuf<int> grad_faces;
+    DevBuf<double> grad_me;
+    // the observation functionals as handed over and, for the log-likelihood gradient, diag(1 / sum g_i) Gobs transposed
+    // (CSR over the elements, uploaded at the first pmc_darcy_loglik_gradient after a set_observations)
+    HostCsr Gobs_host;
+    bool has_gt = false;
+    DevBuf<int> gt_ptr, gt_obs;
+    DevBuf<double> gt_val;
 };
 
 // Internal algebraic hierarchy of one Monte Carlo level (mg_coarsening): smoothed-aggregation prolongators frozen at
@@ -312,7 +325,12 @@ struct Darcy {
     // timed on the same switch, on the main stream instead of beside the V-cycle's bottom
     OpTimer poly_timer;
     double poly_bytes(int level, int nb) const;
+    // ... and of the gradient's mass-sensitivity kernel (darcy_gradient.hip), on the same switch
+    OpTimer grad_timer;
+    double mass_sensitivity_bytes(int level, int nb);   // builds the level's gradient data when it is not there yet
     DevBuf<double> sol, sol_compact, cx, cd, cx2, stage_k, stage_sol, qpartial, qout, gtmp, gout;
+    // adjoint solve (darcy_gradient.hip): right-hand side and second full solution, host staging; allocated at first use
+    DevBuf<double> adj_rhs, adj_sol, stage_adj, stage_grad, obs_data;
     bool use_eg(const DarcyLevel& d) const;
     void set_observations(int level, const pmc_csr* Gobs);
     void compute_G(int level, int nbatch, const double* k, double* G, double* C, double* Q, int memspace, pmc_stats* stats);
@@ -326,6 +344,15 @@ struct Darcy {
     // (pmc_darcy_apply_preconditioner / _apply_operator): the same setup and the same closures as solve_fwd
     void apply_preconditioner(int level, int nbatch, const double* k, const double* r, double* z, int memspace);
     void apply_operator(int level, int nbatch, const double* k, const double* x, double* y, int memspace);
+    // Adjoint gradients with respect to k (pmc_darcy_mass_sensitivity / _solve_gradient / _loglik_gradient,
+    // darcy_gradient.hip).  All three take the saddle-point path, also on a hybridized handle (as compute_G).
+    void mass_sensitivity(int level, int nbatch, const double* k, const double* x, const double* lam, bool wrt_log,
+                          double* grad, int memspace);
+    void solve_gradient(int level, int nbatch, const double* k, const double* adj_rhs, bool wrt_log, double* Q, double* C,
+                        double* grad, double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd,
+                        pmc_stats* stats_adj);
+    void loglik_gradient(int level, int nbatch, const double* k, const double* data, double noise, bool wrt_log,
+                         double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj);
     // setup values of one level of the V-cycle `level`'s solves run (pmc_darcy_vcycle_level)
     void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
     // P from V-cycle level vlevel + 1 to vlevel of that cycle (pmc_darcy_vcycle_prolongator), rows of vlevel 0 in the caller's
@@ -351,6 +378,18 @@ struct Darcy {
     void apply_one(int level, int nb, const double* k, const double* in, double* out, int memspace, bool precond);
     void solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                             int nrows);
+    // darcy_gradient.hip
+    struct AdjointSpec {
+        const double* rhs_d = nullptr;    // caller's dJ/dx, sample-major on the device (NULL with !loglik: obs)
+        bool loglik = false;              // right-hand side of the Gaussian log-likelihood, formed on the device
+        const double* data = nullptr;     // loglik: observed values (host, n_gobs)
+        double noise = 1.0;
+    };
+    void ensure_gradient(int level);
+    void ensure_loglik(int level);
+    void gradient_chunk(int level, int nb, const double* k_d, const AdjointSpec& adj, bool wrt_log, double* Q_host,
+                        double* G_host, double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd,
+                        pmc_stats* stats_adj);
 };
 
 }  // namespace pmc

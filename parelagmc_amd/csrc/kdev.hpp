@@ -400,4 +400,17 @@ __device__ __forceinline__ SliceWalk slice_walk(int nslices) {
     return SliceWalk{lo + idx * WPB + wave, hi, nb_x * WPB};
 }
 
+// Launch-side dispatch on the batch width: the body sees the compile-time interleave NB of a launch of nb realizations
+// (kernels.hip and every other translation unit that starts a batched kernel).
+#define PMC_DISPATCH_NB(nb, ...)                                          \
+    switch (nb) {                                                         \
+        case 1: { constexpr int NB = 1; __VA_ARGS__; } break;             \
+        case 2: { constexpr int NB = 2; __VA_ARGS__; } break;             \
+        case 4: { constexpr int NB = 4; __VA_ARGS__; } break;             \
+        case 8: { constexpr int NB = 8; __VA_ARGS__; } break;             \
+        case 16: { constexpr int NB = 16; __VA_ARGS__; } break;           \
+        case 32: case 64: case 128: case 256: { constexpr int NB = 32; __VA_ARGS__; } break;   /* column groups of 32 */ \
+        default: throw Error(PMC_ERR_INTERNAL, "unsupported batch width"); \
+    }
+
 }  // namespace pmc

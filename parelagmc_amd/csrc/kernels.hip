@@ -2190,17 +2190,6 @@ __global__ __launch_bounds__(kTailThreads) void mini_sampler_kernel(MiniSamplerP
 
 // ==========================================================================================
 // launchers
-#define PMC_DISPATCH_NB(nb, ...)                                          \
-    switch (nb) {                                                         \
-        case 1: { constexpr int NB = 1; __VA_ARGS__; } break;             \
-        case 2: { constexpr int NB = 2; __VA_ARGS__; } break;             \
-        case 4: { constexpr int NB = 4; __VA_ARGS__; } break;             \
-        case 8: { constexpr int NB = 8; __VA_ARGS__; } break;             \
-        case 16: { constexpr int NB = 16; __VA_ARGS__; } break;           \
-        case 32: case 64: case 128: case 256: { constexpr int NB = 32; __VA_ARGS__; } break;   /* column groups of 32 */ \
-        default: throw Error(PMC_ERR_INTERNAL, "unsupported batch width"); \
-    }
-
 // the row-split instantiations (SellView::split_log2) exist for launches of at most 8 realizations
 #define PMC_DISPATCH_NARROW(nb, ...)                                      \
     switch (nb) {                                                         \

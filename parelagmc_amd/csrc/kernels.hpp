@@ -304,6 +304,19 @@ void darcy_backsub_p(hipStream_t st, int nb, int n_p, const double* kappa, const
                      double* out);
 void diag_inv(hipStream_t st, int nb, int n, const int* diag_slot, const double* vals, double* dinv);
 
+// Per-element mass sensitivity (darcy_gradient.hip): out[b n_elem + e] = f(k[b n_elem + e]) sum_a lam[faces_e(a)][b]
+// (sum_a' M_e[a][a'] x[faces_e(a')][b]), f = -c'(k) (+1/k^2 with k_divides, -1 otherwise; times k with wrt_log).  faces / me:
+// element-major in slices of 64 elements, column-major inside a slice ([slice][a][64], [slice][a nfe + a'][64]); x, lam
+// interleaved [row][nb]; kfield and out sample-major.  One fixed summation order per element (a outer, a' inner), no atomics:
+// column b of the result does not depend on nb.
+struct ElemMassView {
+    int n_elem = 0, nslices = 0, nfe = 0;
+    const int* faces = nullptr;
+    const double* me = nullptr;
+};
+void darcy_mass_sensitivity(hipStream_t st, int nb, const ElemMassView& E, const double* kfield, const double* x,
+                            const double* lam, bool k_divides, bool wrt_log, double* out);
+
 }  // namespace k
 }  // namespace pmc
 

@@ -227,6 +227,18 @@ void DarcySolver::SolveFwd_RtnPressure(int ilevel, Vector& k, Vector& P, double*
           "DarcySolver::SolveFwd_RtnPressure");
     record(ilevel, st);
 }
+void DarcySolver::SolveFwd_Gradient(int ilevel, Vector& k, double* Q, double* C, Vector& grad, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::SolveFwd_Gradient: level");
+    if (grad.MemSpace() != k.MemSpace()) throw std::invalid_argument("SolveFwd_Gradient: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    std::vector<pmc_stats> st(k.Batch()), sta(k.Batch());
+    check(pmc_darcy_solve_gradient(h_, ilevel, k.Batch(), k.GetData(), nullptr, wrt_log ? 1 : 0, Q, C, grad.GetData(), nullptr,
+                                   nullptr, k.MemSpace(), st.data(), sta.data()),
+          "DarcySolver::SolveFwd_Gradient");
+    record(ilevel, st);
+    record(ilevel, sta);
+}
 int DarcySolver::GetSizeOfStochasticData(int l) const { return pmc_darcy_num_pressure_dofs(h_, l); }
 int DarcySolver::GetNumberOfDofs(int l) const { return pmc_darcy_num_dofs(h_, l); }
 int DarcySolver::GetGlobalNumberOfDofs(int l) const { return pmc_darcy_num_dofs(h_, l); }
@@ -259,6 +271,18 @@ void BayesianInverseProblem::ComputeLikelihoodAndQ(int ilevel, Vector& k, double
 }
 void BayesianInverseProblem::ComputeLikelihood(int ilevel, Vector& k, double* likelihood, double* C) {
     ComputeLikelihoodAndQ(ilevel, k, likelihood, C, nullptr);
+}
+void BayesianInverseProblem::ComputeGradLogLikelihood(int ilevel, Vector& k, double* loglik, Vector& grad, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(solver_, ilevel);
+    if (np < 0) throw std::out_of_range("BayesianInverseProblem::ComputeGradLogLikelihood: level");
+    const int nobs = pmc_darcy_num_observations(solver_, ilevel);
+    if (nobs != (int)G_obs_.size()) throw std::runtime_error("BayesianInverseProblem: observation count mismatch");
+    if (grad.MemSpace() != k.MemSpace())
+        throw std::invalid_argument("ComputeGradLogLikelihood: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    check(pmc_darcy_loglik_gradient(solver_, ilevel, k.Batch(), k.GetData(), G_obs_.data(), noise_, wrt_log ? 1 : 0, loglik,
+                                    nullptr, grad.GetData(), k.MemSpace(), nullptr),
+          "BayesianInverseProblem::ComputeGradLogLikelihood");
 }
 void BayesianInverseProblem::ComputeR(int ilevel, Vector& k, double* R, double* C) {
     std::vector<double> q(k.Batch());
@@ -1702,6 +1726,23 @@ int pmc_bayes_likelihood(pmc_darcy* solver, int level, int nbatch, const double*
             if (Q) Q[b] = q[b];
             if (R) R[b] = q[b] * likelihood[b];
         }
+    });
+}
+
+int pmc_bayes_loglik_gradient(pmc_darcy* solver, int level, int nbatch, const double* k, int memspace, const double* G_obs,
+                              int nobs, double noise, int wrt_log, double* loglik, double* grad) {
+    return hguard([&] {
+        if (!solver || !k || !G_obs || !grad || nbatch < 1 || nobs < 1 || !(noise > 0.0))
+            throw std::invalid_argument("pmc_bayes_loglik_gradient: bad argument");
+        struct View : Vector {     // non-owning batch views of k and grad
+            View(double* p, int n, int nb, int ms) : Vector(nullptr, ms) { Adopt(p, n, nb); }
+            ~View() { Release(); }
+        };
+        const int n_k = pmc_darcy_num_pressure_dofs(solver, level);
+        if (n_k <= 0) throw std::invalid_argument("pmc_bayes_loglik_gradient: level out of range");
+        BayesianInverseProblem prob(solver, noise, std::vector<double>(G_obs, G_obs + nobs));
+        View kv(const_cast<double*>(k), n_k, nbatch, memspace), gv(grad, n_k, nbatch, memspace);
+        prob.ComputeGradLogLikelihood(level, kv, loglik, gv, wrt_log != 0);
     });
 }
 

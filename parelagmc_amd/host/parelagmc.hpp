@@ -253,6 +253,10 @@ class DarcySolver : public PhysicalMLSolver {
     using PhysicalMLSolver::SolveFwd_RtnPressure;
     void SolveFwd(int ilevel, Vector& k_over_k_ref, double* Q, double* C) override;
     void SolveFwd_RtnPressure(int ilevel, Vector& k_over_k_ref, Vector& P, double* C, double* Q, bool compute_Q) override;
+    /// SolveFwd plus the adjoint gradient dQ/dk (wrt_log: dQ/dlog k) of every realization: grad is sized to
+    /// GetSizeOfStochasticData(ilevel) x k.Batch() in k's memory space (pmc_darcy_solve_gradient; an extension, the
+    /// reference has no gradients).  Q, C: host arrays of k.Batch(), may be NULL.
+    void SolveFwd_Gradient(int ilevel, Vector& k_over_k_ref, double* Q, double* C, Vector& grad, bool wrt_log = false);
     int GetSizeOfStochasticData(int ilevel) const;   // entries of k (src/DarcySolver.hpp:127-130)
     int GetNumberOfDofs(int ilevel) const override;
     int GetGlobalNumberOfDofs(int ilevel) const override;
@@ -311,6 +315,9 @@ class BayesianInverseProblem {
     void ComputeLikelihood(int ilevel, Vector& k_over_k_ref, double* likelihood, double* C);
     void ComputeLikelihoodAndQ(int ilevel, Vector& k_over_k_ref, double* likelihood, double* C, double* Q);
     void ComputeR(int ilevel, Vector& k_over_k_ref, double* R, double* C);
+    /// log of ComputeLikelihood and its adjoint gradient with respect to k (wrt_log: log k) for every realization: loglik
+    /// host array of k.Batch() (may be NULL), grad sized to n_p x k.Batch() in k's memory space (pmc_darcy_loglik_gradient)
+    void ComputeGradLogLikelihood(int ilevel, Vector& k_over_k_ref, double* loglik, Vector& grad, bool wrt_log = false);
     int SizeOfObservationalData() const { return (int)G_obs_.size(); }
 
   private:

@@ -69,6 +69,8 @@ HOST_SYMBOLS = {
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pmc_bayes_likelihood": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double, _DPTR, _DPTR, _DPTR,
                                        _DPTR]),
+    "pmc_bayes_loglik_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double, C.c_int, _DPTR,
+                                            _VP]),
     "pmc_ratio_create": (C.c_int, [_VP, _VP, _VP, C.c_int, _DPTR, C.c_int, C.c_double, C.POINTER(pmc_mlmc_params),
                                    C.POINTER(_VP)]),
     "pmc_ratio_create_callbacks": (C.c_int, [C.c_int, C.POINTER(pmc_plugin_callbacks), _VP, C.POINTER(pmc_mlmc_params),
@@ -165,6 +167,19 @@ def bayes_likelihood(solver, level, k, G_obs, noise):
                                      len(G_obs), float(noise), like.ctypes.data_as(_DPTR), Cc.ctypes.data_as(_DPTR),
                                      Q.ctypes.data_as(_DPTR), R.ctypes.data_as(_DPTR)))
     return like, Cc, Q, R
+
+
+def bayes_loglik_gradient(solver, level, k, G_obs, noise, wrt_log=False):
+    """BayesianInverseProblem::ComputeGradLogLikelihood for a batch: returns (loglik (nbatch,), grad (nbatch, n_p))."""
+    lib = load_host_library()
+    k = np.ascontiguousarray(np.atleast_2d(k), np.float64)
+    G_obs = np.ascontiguousarray(G_obs, np.float64)
+    nb = k.shape[0]
+    ll, grad = np.empty(nb), np.empty_like(k)
+    _hcheck(lib.pmc_bayes_loglik_gradient(solver.h, level, nb, k.ctypes.data, capi.PMC_MEM_HOST, G_obs.ctypes.data_as(_DPTR),
+                                          len(G_obs), float(noise), 1 if wrt_log else 0, ll.ctypes.data_as(_DPTR),
+                                          grad.ctypes.data))
+    return ll, grad
 
 
 CB_LIKE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
