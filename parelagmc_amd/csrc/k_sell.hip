@@ -1,0 +1,1303 @@
+// Kernels in which a wavefront sweeps the slices of a SELL-64 matrix through sell_row_range, with their launchers: the
+// operator products (K5, K3/K4, K11) with their Lanczos forms, residuals with fused restriction / sample-major stores,
+// Chebyshev steps and the one-pass degree-2 polynomial (K7, K8), the V-cycle level kernels with fp32 intermediates, the pair
+// product of the Darcy u-rows, and the first stage of the two-stage dot reduction.  fp64 values, int32 indices, HBM-bound:
+// no MFMA (<= 0.17 flop/byte), 64-wide wavefronts, SELL-64 operators so that every matrix load of a wavefront is one
+// contiguous 512 B (values) / 256 B (columns) segment.
+//
+// Why the V-cycle kernels are not a unit of their own: sell_row_range takes its optional results (xlast, pdot) as run-time
+// pointers, and the compiler specialises a device function for the arguments ALL callers in its translation unit agree on
+// before it inlines it.  The diagonal-last forms of sell_spmm_kernel pass xlast; every other caller of the same
+// specialisations (NB = 4, 8, 16, shared values: sell_cheb / sell_poly2 / sell_pair_spmm / vc_*) passes nullptr and, in a unit
+// without sell_spmm_kernel, comes out with other machine code (measured for the vc_* kernels: 108 of them, LAB_NOTES 10.28).
+// They stay in one unit until those arguments are template parameters.
+#include "klaunch.hpp"
+#include "sell_rows.hpp"
+
+namespace pmc {
+
+template <int NB, int BV, typename XT = double>
+__device__ __forceinline__ void sell_row_product(const int* __restrict__ slice_off, const int* __restrict__ cols,
+                                                 const double* __restrict__ vals, const XT* __restrict__ x,
+                                                 int slice, int lane, int LD, double (&acc)[Lay<NB>::T][Lay<NB>::C]) {
+    const int off = slice_off[slice];
+    const int width = (slice_off[slice + 1] - off) >> 6;
+    sell_row_range<NB, BV, false, true, false, XT>(cols, vals, x, nullptr, off, width, lane, LD, acc);
+}
+
+// MODE 0: y = Ax   1: y += Ax   2: y = r - Ax ; DOT: partial sums of <dot_with, result>.
+// Wavefronts stride over the slices (grid may be smaller than the slice count: bounded partial-sum count).
+// TAG only names the instantiation: 1 = the block saddle-point operator (K5) inside the solver, 2 = the same operator
+// launched by pmc_sampler_apply_operator (the isolated roofline measurement), so that profiles show the
+// hot operator's launches on their own row; 0 = every other matrix (transfers, residuals, ...).
+// R8 (with MODE 2, no DOT): the rows of the result are also summed in groups of 8 consecutive rows into
+// partial[(row / 8) * NB + k] - the restriction P^T res of a prolongator whose parent i has exactly the children
+// 8 i .. 8 i + 7 with unit weights (uniformly refined tetrahedra / hexahedra): a slice holds 8 whole groups, the sum is
+// a fixed xor tree over the lanes of a row step, and the separate restriction kernel (13 us of dependent latency for a
+// few MB) disappears from the V-cycle.
+// XT: storage type of x and dot_with (fp32 or fp64 for the preconditioned Krylov vectors, zvec)
+// YT: storage type of y (fp32: the coarse right-hand side of a V-cycle level with fp32 inter-level vectors, plain products only)
+// LZ: the two operator passes of a MINRES iteration that never stores q = A u (shared values, MODE 0; k::LanczosUpdate):
+//   1 = the product is not stored, only the fused dot leaves the kernel (alpha = <u, Au>: the same partials, bit for bit,
+//       as the storing form);
+//   2 = no dot; the epilogue forms the next Lanczos vector from the row sums (the same bits as the stored q) and the own
+//       rows of v1 (lz.v1) and v0 (y): y = c0 (A x) + c1 v1 + c2 y, written over v0 together with its fp32 copy lz.y32;
+//   3 = as 2 in the first iteration, where v0 is zero: y is not read (the c2 term is kept with a literal +0.0, so even the
+//       sign of a zero result is that of the flat kernel);
+//   4 = a plain product that also leaves the fp32 copy of its result in lz.y32 (k::spmm_store32: the right-hand side a MINRES
+//       solve adopts as its first Lanczos vector - what k::copy_r32 made of the stored product, from the registers)
+// SM (MODE 2, shared values): the result leaves the kernel sample-major, y[k * nrows + row], as k::deinterleave would write it
+//   from the interleaved one (k::residual_samples); 2 = through exp().  Each value is computed as in the interleaved form and
+//   stored once; a wavefront writes, per column, the 64 rows of its slice in T runs of G consecutive rows.
+template <int NB, int BV, int MODE, bool DOT, int TAG, bool NT = false, bool R8 = false, bool DL = false, typename XT = double,
+          typename YT = double, int LZ = 0, int SM = 0>
+__global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3 : 1)) void sell_spmm_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+                                                           const int* __restrict__ sched,
+                                                           const int* __restrict__ cols,
+                                                           const double* __restrict__ vals,
+                                                           const XT* __restrict__ x, typename ident<YT>::type* __restrict__ y,
+                                                           const double* __restrict__ r,
+                                                           const typename ident<XT>::type* __restrict__ dot_with,
+                                                           double* __restrict__ partial, int ld,
+                                                           k::LanczosUpdate lz = k::LanczosUpdate{}) {
+    static_assert(!R8 || (MODE == 2 && !DOT), "fused restriction goes with the residual");
+    static_assert(LZ == 0 || (BV == 0 && MODE == 0 && !R8 && sizeof(YT) == 8 && DOT == (LZ == 1)),
+                  "Lanczos passes: shared values, plain product; the dot-only pass has the dot, the update passes none");
+    static_assert(sizeof(YT) == 8 || (MODE == 0 && !DOT && !NT), "fp32 result: plain products only");
+    static_assert(SM == 0 || (MODE == 2 && BV == 0 && !DOT && !R8 && LZ == 0 && sizeof(YT) == 8),
+                  "sample-major result: the plain residual of a shared-value matrix");
+    const int LD = row_ld<NB>(ld);
+    {
+        const int c0 = col0<NB>();   // this group's columns of every interleaved operand
+        x += c0;
+        if constexpr (SM) y += (size_t)c0 * nrows;   // column k of the result starts at k * nrows
+        else if constexpr (LZ != 1) y += c0;         // (the dot-only pass has no y)
+        if constexpr (BV) vals = shift_bv<BV>(vals, c0);
+        if constexpr (MODE == 2) r += c0;
+        if constexpr (DOT && !DL) dot_with += c0;
+        if constexpr (DOT || R8) partial += c0;
+        if constexpr (LZ == 2 || LZ == 3) {
+            lz.v1 += c0;
+            lz.c0 += c0; lz.c1 += c0; lz.c2 += c0;
+        }
+        if constexpr (LZ >= 2) lz.y32 += c0;
+    }
+    static_assert(!DL || (DOT && !BV && Lay<NB>::T > 1), "diagonal-last serves the fused <x, Ax> of shared-value operators");
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    double p[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] = 0.0;
+    const SliceWalk sw = slice_walk(nslices);
+    for (int si = sw.begin; si < sw.end; si += sw.stride) {
+        const int slice = sched ? sched[si] : si;   // optional processing order (locality), see Sell::sched
+        double acc[T][C];
+        constexpr bool LEAN_DL = DL && lean_range<NB>();   // the dot is taken inside the gather loop
+        double xd[DL && !LEAN_DL ? T : 1][C];
+        if constexpr (LEAN_DL) {
+            const int off = slice_off[slice];
+            sell_row_range<NB, false, false, true, NT, XT>(cols, vals, x, nullptr, off, (slice_off[slice + 1] - off) >> 6,
+                                                             lane, LD, acc, nullptr, p);
+        } else if constexpr (DL) {
+            const int off = slice_off[slice];
+            sell_row_range<NB, false, false, true, NT, XT>(cols, vals, x, nullptr, off, (slice_off[slice + 1] - off) >> 6,
+                                                             lane, LD, acc, xd);
+        } else if constexpr (NT) {
+            const int off = slice_off[slice];
+            sell_row_range<NB, BV, false, true, true, XT>(cols, vals, x, nullptr, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
+        } else {
+            sell_row_product<NB, BV, XT>(slice_off, cols, vals, x, slice, lane, LD, acc);
+        }
+#pragma unroll
+        for (int rs = 0; rs < T; ++rs) {
+            const int row = slice * kWave + rs * G + g;
+            if (row < nrows) {
+                const size_t at = (size_t)row * LD + t * C;
+                if constexpr (MODE == 1) {
+                    double old[C];
+                    load_c<C>(y + at, old);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[rs][c] += old[c];
+                } else if constexpr (MODE == 2) {
+                    double rv[C];
+                    load_c<C>(r + at, rv);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[rs][c] = rv[c] - acc[rs][c];
+                }
+                if constexpr (LZ == 4) {
+                    store_c<C>(y + at, acc[rs]);
+                    store_v<C>(lz.y32 + at, acc[rs]);
+                } else if constexpr (SM) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        double tv = acc[rs][c];
+                        if constexpr (SM == 2) tv = exp(tv);
+                        y[(size_t)(t * C + c) * nrows + row] = tv;
+                    }
+                } else if constexpr (LZ >= 2) {
+                    double bv[C], yv[C];
+                    load_c_nt<NT, C>(lz.v1 + at, bv);
+                    if constexpr (LZ == 2) {
+                        load_c_nt<NT, C>(y + at, yv);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) yv[c] = 0.0;
+                    }
+                    lanczos_combine<C>(lz.c0, lz.c1, lz.c2, t * C, acc[rs], bv, yv);
+                    store_c<C>(y + at, yv);          // gathered by the next kernels
+                    store_v<C>(lz.y32 + at, yv);
+                } else if constexpr (LZ == 1) {      // the product only feeds the dot
+                } else if constexpr (sizeof(YT) == 8) store_c_stream<NT, C>(y + at, acc[rs]);
+                else store_v<C>(y + at, acc[rs]);
+                if constexpr (LEAN_DL) {
+                } else if constexpr (DL) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) p[c] = fma(xd[rs][c], acc[rs][c], p[c]);
+                } else if constexpr (DOT) {
+                    double w[C];
+                    load_v<C>(dot_with + at, w);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) p[c] = fma(w[c], acc[rs][c], p[c]);
+                }
+            } else if constexpr (R8) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[rs][c] = 0.0;     // rows past the end add nothing to their group
+            }
+            if constexpr (R8) {
+                // lanes (g, t): the 8 rows of a group differ in the low three bits of g = lane / T
+                double s[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    double v = acc[rs][c];
+                    v += __shfl_xor(v, T, kWave);
+                    v += __shfl_xor(v, 2 * T, kWave);
+                    v += __shfl_xor(v, 4 * T, kWave);
+                    s[c] = v;
+                }
+                if ((g & 7) == 0 && row < nrows) store_c<C>(partial + (size_t)(row >> 3) * LD + t * C, s);
+            }
+        }
+    }
+    if constexpr (DOT) reduce_cols_store<NB>(p, partial, LD);
+}
+
+// Chebyshev / Jacobi step: d = a d + b dinv (r - A xin); xout = xin + d ; DOT: partials of <r, xout>
+// OT != double: the LAST step of a polynomial whose result is a preconditioned Krylov vector (zvec storage): d is not
+// written back, the iterate is rounded to its storage before the fused dot
+template <int NB, int BV, bool DOT, typename OT = double>
+__global__ __launch_bounds__(kBlock) void sell_cheb_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+                                                           const int* __restrict__ sched,
+                                                           const int* __restrict__ cols,
+                                                           const double* __restrict__ vals,
+                                                           const double* __restrict__ dinv,
+                                                           const double* __restrict__ r,
+                                                           const double* __restrict__ xin, double* __restrict__ d,
+                                                           OT* __restrict__ xout, double a, double b,
+                                                           double* __restrict__ partial, int ld) {
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    const int LD = row_ld<NB>(ld);
+    {
+        const int c0 = col0<NB>();
+        r += c0; xin += c0; d += c0; xout += c0;
+        if constexpr (BV) { vals = shift_bv<BV>(vals, c0); dinv += c0; }
+        if constexpr (DOT) partial += c0;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    double p[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] = 0.0;
+    const SliceWalk sw = slice_walk(nslices);
+    for (int si = sw.begin; si < sw.end; si += sw.stride) {
+        const int slice = sched ? sched[si] : si;
+        double acc[T][C];
+        sell_row_product<NB, BV>(slice_off, cols, vals, xin, slice, lane, LD, acc);
+#pragma unroll
+        for (int rs = 0; rs < T; ++rs) {
+            const int row = slice * kWave + rs * G + g;
+            if (row >= nrows) continue;
+            const size_t at = (size_t)row * LD + t * C;
+            double rv[C], dv[C], xv[C], di[C];
+            load_c<C>(r + at, rv);
+            load_c<C>(xin + at, xv);
+            if (a != 0.0) {
+                load_c<C>(d + at, dv);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) dv[c] = 0.0;
+            }
+            if constexpr (BV) {
+                load_c<C>(dinv + at, di);
+            } else {
+                const double s = dinv[row];
+#pragma unroll
+                for (int c = 0; c < C; ++c) di[c] = s;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                dv[c] = a * dv[c] + b * di[c] * (rv[c] - acc[rs][c]);
+                xv[c] += dv[c];
+            }
+            round_to<OT>(xv);
+            if constexpr (DOT) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) p[c] = fma(rv[c], xv[c], p[c]);
+            }
+            if constexpr (std::is_same<OT, double>::value) store_c<C>(d + at, dv);
+            store_v<C>(xout + at, xv);
+        }
+    }
+    if constexpr (DOT) reduce_cols_store<NB>(p, partial, LD);
+}
+
+// Degree-2 Chebyshev polynomial from a ZERO initial guess in ONE pass.  With t = D^-1 r the two steps
+//   x1 = t/theta ;  x2 = x1 + rho1 rho0 x1 + (2 rho1/delta) D^-1 (r - A x1)
+// collapse to  x2_i = dinv_i (c0 r_i - c1 (A D^-1 r)_i),  so with the column-scaled values As = A D^-1
+// (precomputed at create time) a single SpMM over r gives the result: 1 gather pass instead of the
+// 3 + 5 vector passes of cheb_first + cheb_step.  DOT: partials of <r, x2>.
+// From a NONZERO guess x0 the same polynomial acts on the residual: x2 = x0 + p2(r - A x0); then r is that residual,
+// xadd = x0 (may alias xout: no gathers on it) and the dot is taken with dot_with (the right-hand side).
+template <int NB, int BV, bool DOT, bool NT = false, typename OT = double>
+__global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 ? 3 : 1)) void sell_poly2_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+                                                            const int* __restrict__ sched,
+                                                            const int* __restrict__ cols,
+                                                            const double* __restrict__ vals_scaled,
+                                                            const double* __restrict__ dinv,
+                                                            const double* __restrict__ r, OT* xout,
+                                                            double c0, double c1, double* __restrict__ partial,
+                                                            const double* xadd, const double* __restrict__ dot_with,
+                                                            const int* __restrict__ padd_idx,
+                                                            const double* __restrict__ padd_x, int ld) {
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    const int LD = row_ld<NB>(ld);
+    {
+        const int c0 = col0<NB>();
+        r += c0; xout += c0;
+        if constexpr (BV) { vals_scaled = shift_bv<BV>(vals_scaled, c0); dinv += c0; }
+        if (xadd) xadd += c0;
+        if (dot_with) dot_with += c0;
+        if (padd_x) padd_x += c0;
+        if constexpr (DOT) partial += c0;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    double p[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] = 0.0;
+    const SliceWalk sw = slice_walk(nslices);
+    for (int si = sw.begin; si < sw.end; si += sw.stride) {
+        const int slice = sched ? sched[si] : si;
+        double acc[T][C];
+        if constexpr (NT) {
+            const int off = slice_off[slice];
+            sell_row_range<NB, BV, false, true, true>(cols, vals_scaled, r, nullptr, off, (slice_off[slice + 1] - off) >> 6,
+                                                        lane, LD, acc);
+        } else {
+            sell_row_product<NB, BV>(slice_off, cols, vals_scaled, r, slice, lane, LD, acc);
+        }
+        // own-row reads in batches of H row steps (shared values only: the per-realization instantiations have no registers
+        // to spare); rows past the end re-read the last row and store nothing
+        constexpr int H = (BV == 0 && T >= 4) ? 2 : 1;   // (4 spills in the fp64-output instantiations: 168 registers are the cap)
+        double rvb[H][C], dib[H];
+#pragma unroll
+        for (int rs = 0; rs < T; ++rs) {
+            const int row = slice * kWave + rs * G + g;
+            if constexpr (H > 1) {
+                if (rs % H == 0) {
+#pragma unroll
+                    for (int u = 0; u < H; ++u) {
+                        const int rc = min(row + u * G, nrows - 1);
+                        load_c<C>(r + (size_t)rc * LD + t * C, rvb[u]);
+                        dib[u] = dinv[rc];
+                    }
+                    pin_block(rvb);
+                }
+            }
+            if (row >= nrows) continue;
+            const size_t at = (size_t)row * LD + t * C;
+            double rv[C], xv[C], di[C];
+            if constexpr (H > 1) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) { rv[c] = rvb[rs % H][c]; di[c] = dib[rs % H]; }
+            } else {
+                load_c<C>(r + at, rv);
+                if constexpr (BV) {
+                    load_c<C>(dinv + at, di);
+                } else {
+                    const double s = dinv[row];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) di[c] = s;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) xv[c] = di[c] * (c0 * rv[c] - c1 * acc[rs][c]);
+            if (xadd) {
+                double x0[C];
+                load_c<C>(xadd + at, x0);
+#pragma unroll
+                for (int c = 0; c < C; ++c) xv[c] += x0[c];
+            }
+            if (padd_idx) {   // + (P xc)_row for an injection-type prolongator: xc[parent[row]]
+                double pc[C];
+                load_c<C>(padd_x + (size_t)padd_idx[row] * LD + t * C, pc);
+#pragma unroll
+                for (int c = 0; c < C; ++c) xv[c] += pc[c];
+            }
+            round_to<OT>(xv);
+            if constexpr (DOT) {
+                if (dot_with) load_c<C>(dot_with + at, rv);
+#pragma unroll
+                for (int c = 0; c < C; ++c) p[c] = fma(rv[c], xv[c], p[c]);
+            }
+            store_v_stream<NT, C>(xout + at, xv);
+        }
+    }
+    if constexpr (DOT) reduce_cols_store<NB>(p, partial, LD);
+}
+
+// ------------------------------------------------------------------------------------------
+// V-cycle kernels with fp32 INTERMEDIATES (shared-value hierarchies: the sampler).  The vectors that live only inside one
+// application of the preconditioner - the pre-smoothed iterate and the residuals of a level - are stored in fp32; the
+// preconditioner's input and output, every coarse right-hand side / correction and all arithmetic stay fp64.  A
+// preconditioner whose result carries fp32-sized rounding does not limit what MINRES attains: its search directions are
+// the preconditioned vectors themselves, q = A z is formed from the z actually delivered, so the residual recurrence stays
+// consistent - measured (z rounded to fp32 after every application, cube_tet r = 4): identical iteration counts at 1e-6 ...
+// 1e-12 and fields equal to the unrounded run's to 7e-16.  What it saves is 87 MB of the 1 089 MB an iteration moves at r = 5.
+
+// out = dinv (c0 r - c1 As r) (+ xadd) (+ padd_x[padd_idx]) with r of type XT (gathered and read at the own row), out of
+// type OT, xadd of type AT; DOT: partials of <dot_with, out> (dot_with fp64).  See sell_poly2_kernel.
+#ifndef PMC_VC_MIN_WAVES
+#define PMC_VC_MIN_WAVES 3   // post-smoothing of the 400 k-row multiplier level: 172 -> 168 registers, 83.6 -> 79.7 us (LAB_NOTES 10.3)
+#endif
+#ifndef PMC_VC_MIN_WAVES_D
+#define PMC_VC_MIN_WAVES_D 1
+#endif
+// wavefronts per SIMD the fp32-gather V-cycle kernels of the 32-wide layout are compiled for (laboratory macro)
+template <int NB, typename XT, int BV, int DEEP>
+constexpr int vc_min_waves() {
+    return (NB >= 32 && BV == 0 && DEEP == 1) ? (sizeof(XT) == 4 ? PMC_VC_MIN_WAVES : PMC_VC_MIN_WAVES_D) : 1;
+}
+// SPL (launches of at most 8 realizations on the small levels of an aggregation hierarchy, whose rows hold 20-40 entries): the
+// matrix stores every row as 2^sl consecutive pieces (csr_split_rows), nrows counts the ROWS; the pieces of a row sit in
+// neighbouring lane groups and are added with a shuffle tree, the first piece's lanes finish the row.  A 5 k-row level then
+// runs 2^sl times the wavefronts over slices 2^sl times shorter - these launches are one chain of dependent gathers per slice.
+template <int NB, int C, int T>
+__device__ __forceinline__ void split_row_sums(double (&acc)[T][C], int sl) {
+#pragma unroll
+    for (int rs = 0; rs < T; ++rs)
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            double v = acc[rs][c];
+            for (int o = 0; o < sl; ++o) v += __shfl_xor(v, T << o, kWave);
+            acc[rs][c] = v;
+        }
+}
+// GIB (launches of 64 realizations = two column groups): ONE workgroup sweeps a slice for both groups back to back - the slice's
+// (index, value) pairs come from L1 / L2 the second time instead of being fetched again by another workgroup at another time
+// (what `traffic` showed as 1.34 x the algorithmic bytes) - gridDim.y is 1 and the partial sums keep their layout.
+// PT: storage type of padd_x (the coarse correction: fp64, or fp32 with fp32 inter-level vectors), widened on load
+template <int NB, typename XT, typename OT, typename AT, bool DOT, bool NT = false, int BV = 0, int DEEP = 1, bool SPL = false,
+          bool GIB = false, typename PT = double>
+__global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc_poly2_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+                                                          const int* __restrict__ cols, const double* __restrict__ vals_scaled,
+                                                          const double* __restrict__ dinv, const XT* __restrict__ r, OT* xout,
+                                                          double c0, double c1, double* __restrict__ partial, const AT* xadd,
+                                                          const double* __restrict__ dot_with,
+                                                          const int* __restrict__ padd_idx,
+                                                          const typename ident<PT>::type* __restrict__ padd_x,
+                                                          int ld, int sl = 0) {
+    static_assert(!SPL || (NB <= 8 && BV == 0 && DEEP == 1), "row-split instantiations: narrow launches, shared values");
+    static_assert(!GIB || (NB == kGroup && BV == 0 && DEEP == 1 && !SPL), "both column groups in one workgroup: 64 wide, shared values");
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    constexpr int NG = GIB ? 2 : 1;
+    const int LD = row_ld<NB>(ld);
+    if constexpr (!GIB) {
+        const int g0 = col0<NB>();
+        r += g0; xout += g0;
+        if constexpr (BV != 0) { vals_scaled = shift_bv<BV>(vals_scaled, g0); dinv += g0; }
+        if (xadd) xadd += g0;
+        if (dot_with) dot_with += g0;
+        if (padd_x) padd_x += g0;
+        if constexpr (DOT) partial += g0;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    const SliceWalk sw = slice_walk(nslices);
+    // (the group loop is the OUTER one and not unrolled: inside the slice loop the two groups' gathers interleave and 84-188
+    // registers spill; a workgroup walks one or two slices per wavefront, so the second sweep still finds them in L1 / L2)
+#pragma unroll 1
+    for (int grp = 0; grp < NG; ++grp) {
+      const int go = grp * NB;                         // 0 unless GIB
+      const XT* rg = r + go;
+      OT* xg = xout + go;
+      const AT* xa = xadd ? xadd + go : nullptr;
+      const double* dw = dot_with ? dot_with + go : nullptr;
+      const PT* px = padd_x ? padd_x + go : nullptr;
+      double p[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) p[c] = 0.0;
+      for (int slice = sw.begin; slice < sw.end; slice += sw.stride) {
+        double acc[T][C];
+        const int off = slice_off[slice];
+        sell_row_range_t<NB, XT, NT, BV, DEEP>(cols, vals_scaled, rg, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
+        if constexpr (SPL) split_row_sums<NB, C, T>(acc, sl);
+        // row steps in pairs: the own-row reads of both (and the parent indices of the coarse correction) are issued before
+        // either is consumed - rows past the end re-read the last row and store nothing
+        // (pairs only where the gathers above leave the registers for it - the fp32-gather instantiations; the fp64-gather
+        // ones, with sixteen 16-byte gathers in flight, would drop from three to two waves per SIMD)
+        constexpr int H = (T >= 2 && sizeof(XT) == 4) ? 2 : 1;
+#pragma unroll
+        for (int h0 = 0; h0 < T; h0 += H) {
+            double rv[H][C], di[H][C], x0[H][C], pc[H][C], wv[H][C];
+            size_t at[H];
+            int par[H];
+            bool ok[H];
+#pragma unroll
+            for (int u = 0; u < H; ++u) {
+                const int piece = slice * kWave + (h0 + u) * G + g;
+                const int row = SPL ? piece >> sl : piece;
+                ok[u] = row < nrows && (!SPL || (piece & ((1 << sl) - 1)) == 0);
+                const int rowc = row < nrows ? row : nrows - 1;
+                at[u] = (size_t)rowc * LD + t * C;
+                load_v<C>(rg + at[u], rv[u]);
+                if constexpr (BV != 0) {
+                    load_c<C>(dinv + at[u], di[u]);
+                } else {
+                    const double sdi = dinv[rowc];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) di[u][c] = sdi;
+                }
+                if (xa) load_v<C>(xa + at[u], x0[u]);
+                if (padd_idx) par[u] = padd_idx[rowc];
+                if constexpr (DOT) load_c<C>(dw + at[u], wv[u]);
+            }
+            if (padd_idx) {
+#pragma unroll
+                for (int u = 0; u < H; ++u) load_v<C>(px + (size_t)par[u] * LD + t * C, pc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < H; ++u) {
+                double xv[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) xv[c] = di[u][c] * (c0 * rv[u][c] - c1 * acc[h0 + u][c]);
+                if (xa) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) xv[c] += x0[u][c];
+                }
+                if (padd_idx) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) xv[c] += pc[u][c];
+                }
+                round_to<OT>(xv);
+                if (ok[u]) {
+                    if constexpr (DOT) {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) p[c] = fma(wv[u][c], xv[c], p[c]);
+                    }
+                    store_v_stream<NT, C>(xg + at[u], xv);
+                }
+            }
+        }
+      }
+      if constexpr (DOT) {
+          reduce_cols_store<NB>(p, partial + go, LD);
+          if (grp + 1 < NG) __syncthreads();            // the reduction's LDS scratch is reused by the next group
+      }
+    }
+}
+
+// y = r - A x with x of type XT (gathered), r of type RT, y of type YT; R8: rows also summed in groups of 8 into `coarse`
+// (fp64), see sell_spmm_kernel
+// BV: 0 shared fp64 values, 2 per-realization fp32 values; STORE = false: only the restricted sums are wanted (y unused)
+// RAGG (aggregation levels renumbered by agg_pack_rows: every aggregate a run of consecutive rows inside one slice): the
+// wavefront keeps its 64 x NB residual tile - the fp32 values it has just stored - in LDS and sums its own aggregates from it
+// in increasing row order: coarse[cid] = sum of the rows of segment (cid, first row, rows).  No other wavefront touches those
+// coarse rows: deterministic, no atomics, and the separate product with P^T (one more pass over the residual) is gone.
+// SPL: rows stored in 2^sl pieces, see vc_poly2_kernel
+// CT: storage type of `coarse` (fp64, or fp32 with fp32 inter-level vectors: the fp64 sums are rounded once, on store)
+// TAG only names the instantiation: 1 = res - (S P) xc (in place), so that profiles show that pass on a row of its own
+template <int NB, typename XT, typename RT, typename YT, bool R8, int BV = 0, bool STORE = true, int DEEP = 1, bool RAGG = false,
+          bool SPL = false, typename CT = double, int TAG = 0>
+__global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+                                                             const int* __restrict__ cols, const double* __restrict__ vals,
+                                                             const XT* __restrict__ x, const RT* r, YT* y,
+                                                             typename ident<CT>::type* __restrict__ coarse, int ld,
+                                                             const int* __restrict__ seg_ptr = nullptr,
+                                                             const int* __restrict__ seg_cid = nullptr,
+                                                             const int* __restrict__ seg_pos = nullptr, int sl = 0) {
+    static_assert(!SPL || (NB <= 8 && BV == 0 && DEEP == 1 && !R8 && !RAGG && STORE), "row-split instantiations: narrow launches, plain residual");
+    static_assert(STORE || R8, "a residual that is neither stored nor restricted");
+    static_assert(!RAGG || (!R8 && STORE && BV == 0 && sizeof(YT) == 4), "fused aggregate restriction: shared values, fp32 residual");
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    const int LD = row_ld<NB>(ld);
+    {
+        const int g0 = col0<NB>();
+        x += g0; r += g0;
+        if constexpr (STORE) y += g0;
+        if constexpr (BV != 0) vals = shift_bv<BV>(vals, g0);
+        if constexpr (R8 || RAGG) coarse += g0;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    __shared__ float tile_all[RAGG ? (kBlock / kWave) * kWave * NB : 1];
+    float* tile = tile_all + (RAGG ? (threadIdx.x / kWave) * kWave * NB : 0);
+    const SliceWalk sw = slice_walk(nslices);
+    for (int slice = sw.begin; slice < sw.end; slice += sw.stride) {
+        double acc[T][C];
+        const int off = slice_off[slice];
+        sell_row_range_t<NB, XT, false, BV, DEEP>(cols, vals, x, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
+        if constexpr (SPL) split_row_sums<NB, C, T>(acc, sl);
+        // the own-row reads of H row steps are issued together (rows past the end re-read the last row): one latency per
+        // batch instead of one per row step - these launches are single occupancy rounds of dependent loads
+        constexpr int H = T >= 4 ? 4 : T;
+        double rvb[H][C];
+#pragma unroll
+        for (int rs = 0; rs < T; ++rs) {
+            const int piece = slice * kWave + rs * G + g;
+            const int row = SPL ? piece >> sl : piece;
+            if (rs % H == 0) {
+#pragma unroll
+                for (int u = 0; u < H; ++u) {
+                    const int ru = SPL ? (piece + u * G) >> sl : row + u * G;
+                    load_v<C>(r + (size_t)(ru < nrows ? ru : nrows - 1) * LD + t * C, rvb[u]);
+                }
+            }
+            if (row < nrows && (!SPL || (piece & ((1 << sl) - 1)) == 0)) {
+                const size_t at = (size_t)row * LD + t * C;
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[rs][c] = rvb[rs % H][c] - acc[rs][c];
+                if constexpr (STORE) store_v<C>(y + at, acc[rs]);
+                if constexpr (RAGG) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) tile[(rs * G + g) * NB + t * C + c] = (float)acc[rs][c];
+                }
+            } else if constexpr (R8) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[rs][c] = 0.0;
+            }
+            if constexpr (R8) {
+                double s[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    double v = acc[rs][c];
+                    v += __shfl_xor(v, T, kWave);
+                    v += __shfl_xor(v, 2 * T, kWave);
+                    v += __shfl_xor(v, 4 * T, kWave);
+                    s[c] = v;
+                }
+                if ((g & 7) == 0 && row < nrows) store_v<C>(coarse + (size_t)(row >> 3) * LD + t * C, s);
+            }
+        }
+        if constexpr (RAGG) {
+            // the tile is private to this wavefront: its own LDS writes are complete once the wait below has passed
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int s0 = seg_ptr[slice], s1 = seg_ptr[slice + 1];
+            for (int sg = s0 + g; sg < s1; sg += G) {
+                const int pos = seg_pos[sg], first = pos >> 8, len = pos & 255;
+                double sum[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) sum[c] = 0.0;
+                for (int q = 0; q < len; ++q)
+#pragma unroll
+                    for (int c = 0; c < C; ++c) sum[c] += (double)tile[(first + q) * NB + t * C + c];
+                store_v<C>(coarse + (size_t)seg_cid[sg] * LD + t * C, sum);
+            }
+            __builtin_amdgcn_wave_barrier();    // the next slice overwrites the tile
+        }
+    }
+}
+
+// x (fp32) += xc[row >> 3] (fp64): the coarse correction of a prolongator over groups of 8 consecutive rows
+template <int NB>
+__global__ __launch_bounds__(kBlock) void vc_prolong8_kernel(size_t nflat, float* __restrict__ x, const double* __restrict__ xc,
+                                                             int ld) {
+    constexpr int C = Lay<NB>::C;
+    const int W = row_ld<NB>(ld);
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nflat) return;
+    const size_t e = i * C;
+    const size_t row = e / W;
+    const int k0 = (int)(e % W);
+    double xv[C], cv[C];
+    load_cf<C>(x + e, xv);
+    load_c<C>(xc + (row >> 3) * W + k0, cv);
+#pragma unroll
+    for (int c = 0; c < C; ++c) xv[c] += cv[c];
+    store_v<C>(x + e, xv);
+}
+
+// y = A1 x1 + A2 x2 over the SAME rows: A1 with per-realization values, A2 with shared values (the u-rows
+// [M(k) | B^T] of the Darcy operator in one pass); DOT: partials of <dot_with, y>.
+template <int NB, bool DOT, typename XT = double>
+__global__ __launch_bounds__(kBlock) void sell_pair_spmm_kernel(
+    int nrows, int nslices, const int* __restrict__ off1, const int* __restrict__ cols1, const double* __restrict__ vals1,
+    const int* __restrict__ off2, const int* __restrict__ cols2, const double* __restrict__ vals2,
+    const XT* __restrict__ x1, const typename ident<XT>::type* __restrict__ x2, double* __restrict__ y,
+    const typename ident<XT>::type* __restrict__ dot_with, double* __restrict__ partial, int ld) {
+    constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
+    const int LD = row_ld<NB>(ld);
+    {
+        const int c0 = col0<NB>();
+        vals1 += c0; x1 += c0; x2 += c0; y += c0;
+        if constexpr (DOT) { dot_with += c0; partial += c0; }
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / T, t = lane % T;
+    double p[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) p[c] = 0.0;
+    const SliceWalk sw = slice_walk(nslices);
+    for (int slice = sw.begin; slice < sw.end; slice += sw.stride) {
+        double acc[T][C], acc2[T][C];
+        sell_row_product<NB, true, XT>(off1, cols1, vals1, x1, slice, lane, LD, acc);
+        sell_row_product<NB, false, XT>(off2, cols2, vals2, x2, slice, lane, LD, acc2);
+#pragma unroll
+        for (int rs = 0; rs < T; ++rs) {
+            const int row = slice * kWave + rs * G + g;
+            if (row >= nrows) continue;
+            const size_t at = (size_t)row * LD + t * C;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[rs][c] += acc2[rs][c];
+            store_c<C>(y + at, acc[rs]);
+            if constexpr (DOT) {
+                double w[C];
+                load_v<C>(dot_with + at, w);
+#pragma unroll
+                for (int c = 0; c < C; ++c) p[c] = fma(w[c], acc[rs][c], p[c]);
+            }
+        }
+    }
+    if constexpr (DOT) reduce_cols_store<NB>(p, partial, LD);
+}
+
+// First stage of a two-stage reduction for launches with many partial blocks: block j of kCompressBlocks sums the input
+// blocks j, j + kCompressBlocks, ... (fixed order: deterministic) into out[j][k].
+static constexpr int kCompressBlocks = 256;   // dot_capacity() reserves this many blocks ahead of the uncompressed ones
+__global__ __launch_bounds__(256) void compress_partials_kernel(const double* __restrict__ in, int nblocks, int nb,
+                                                                double* __restrict__ out) {
+    __shared__ double lds[256];
+    const int k = threadIdx.x % nb, q = threadIdx.x / nb, nq = 256 / nb;
+    double s0 = 0.0, s1 = 0.0;
+    int b = blockIdx.x + kCompressBlocks * q;
+    for (; b + kCompressBlocks * nq < nblocks; b += 2 * kCompressBlocks * nq) {
+        s0 += in[(size_t)b * nb + k];
+        s1 += in[(size_t)(b + kCompressBlocks * nq) * nb + k];
+    }
+    if (b < nblocks) s0 += in[(size_t)b * nb + k];
+    lds[threadIdx.x] = s0 + s1;
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+        double t = 0.0;
+        for (int g = 0; g < nq; ++g) t += lds[g * nb + threadIdx.x];
+        out[(size_t)blockIdx.x * nb + threadIdx.x] = t;
+    }
+}
+
+int dot_capacity(int nrows, int nb) {
+    // upper bound on the partial blocks (of nb doubles each) any fused dot over nrows rows of a batch of nb writes: slice
+    // kernels one block per 4 slices, flat kernels one per kBlock threads, both bounded by dot_grid_bound() - except the
+    // block operator's two-stage reduction, which keeps every slice block behind kCompressBlocks compressed ones (k::spmm)
+    const size_t slice_blocks = ((size_t)nrows + 63) / 64 / (kBlock / kWave) + 1;
+    const size_t flat_blocks = ((size_t)nrows * nb / (nb >= 32 ? 4 : (nb >= 2 ? 2 : 1)) + kBlock - 1) / kBlock;
+    const size_t bounded = std::min<size_t>(std::max(slice_blocks, flat_blocks), dot_grid_bound());
+    return (int)std::max<size_t>(bounded, kCompressBlocks + slice_blocks) + 2;
+}
+
+// ==========================================================================================
+// launchers
+namespace k {
+
+// the row-split instantiations (SellView::split_log2) exist for launches of at most 8 realizations
+#define PMC_DISPATCH_NARROW(nb, ...)                                      \
+    switch (nb) {                                                         \
+        case 1: { constexpr int NB = 1; __VA_ARGS__; } break;             \
+        case 2: { constexpr int NB = 2; __VA_ARGS__; } break;             \
+        case 4: { constexpr int NB = 4; __VA_ARGS__; } break;             \
+        case 8: { constexpr int NB = 8; __VA_ARGS__; } break;             \
+        default: throw Error(PMC_ERR_INTERNAL, "row-split level kernels serve launches of 1, 2, 4 or 8 realizations"); \
+    }
+
+// one Lanczos pass of the operator (sell_spmm_kernel's LZ forms) with the matrix streams and the dot of the in-loop product
+#define PMC_SPMM_LZ(NTF, DLF, LZF)                                                                                          \
+    sell_spmm_kernel<NB, false, 0, (LZF) == 1, TAG, NTF, false, DLF, XT, double, LZF><<<groups_xcd(g, nb), kBlock, 0, st>>>( \
+        A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb, *lz)
+
+template <int NB, int TAG, typename XT>
+static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const XT* x, double* y, bool accumulate,
+                        double* dot_partial, const XT* dot_with, int lz_mode = 0, const LanczosUpdate* lz = nullptr) {
+    // <x, Ax> with a diagonal-last matrix: x_i is what the row's last slice column gathers
+    const bool dl = TAG == 1 && Lay<NB>::T > 1 && A.diag_last && dot_with == x;
+    if constexpr (!std::is_same<XT, double>::value) {
+        // fp32-stored input (the preconditioned Krylov vectors): the operator products of the solver loop only
+        if (A.bv || accumulate) throw Error(PMC_ERR_INTERNAL, "spmm: fp32 input with per-realization values / accumulation");
+        if constexpr (TAG == 1) {
+            if (lz_mode) {
+                // the matrix streams of both passes are those of the in-loop product (its launch carries the dot)
+                const bool ntl = nt_streams(A, NB, true);
+                constexpr bool kDl = Lay<NB>::T > 1;
+                if (lz_mode == 1) {
+                    if (ntl) { if (dl) PMC_SPMM_LZ(true, kDl, 1); else PMC_SPMM_LZ(true, false, 1); }
+                    else { if (dl) PMC_SPMM_LZ(false, kDl, 1); else PMC_SPMM_LZ(false, false, 1); }
+                } else if (lz_mode == 2) {
+                    if (ntl) PMC_SPMM_LZ(true, false, 2); else PMC_SPMM_LZ(false, false, 2);
+                } else {
+                    if (ntl) PMC_SPMM_LZ(true, false, 3); else PMC_SPMM_LZ(false, false, 3);
+                }
+                return;
+            }
+        }
+        const bool nt = TAG != 0 && nt_streams(A, NB, dot_partial != nullptr);
+        if (nt) {
+            if (dot_partial && dl)
+                sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1), XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+            else if (dot_partial)
+                sell_spmm_kernel<NB, false, 0, true, TAG, true, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+            else
+                sell_spmm_kernel<NB, false, 0, false, TAG, true, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        } else {
+            if (dot_partial && dl)
+                sell_spmm_kernel<NB, false, 0, true, TAG, false, false, (Lay<NB>::T > 1), XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+            else if (dot_partial)
+                sell_spmm_kernel<NB, false, 0, true, TAG, false, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+            else
+                sell_spmm_kernel<NB, false, 0, false, TAG, false, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        }
+        return;
+    } else
+    if (A.bv && A.f32) {
+        if (dot_partial)
+            sell_spmm_kernel<NB, 2, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (accumulate)
+            sell_spmm_kernel<NB, 2, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, 2, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+    } else if (A.bv) {
+        if (dot_partial)
+            sell_spmm_kernel<NB, true, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (accumulate)
+            sell_spmm_kernel<NB, true, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, true, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+    } else if (TAG != 0 && nt_streams(A, NB, dot_partial != nullptr)) {
+        if (dot_partial && dl)
+            sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1)><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (dot_partial)
+            sell_spmm_kernel<NB, false, 0, true, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (accumulate)
+            sell_spmm_kernel<NB, false, 1, false, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, false, 0, false, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+    } else {
+        if (dot_partial && dl)
+            sell_spmm_kernel<NB, false, 0, true, TAG, false, false, (Lay<NB>::T > 1)><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (dot_partial)
+            sell_spmm_kernel<NB, false, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
+        else if (accumulate)
+            sell_spmm_kernel<NB, false, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, false, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
+    }
+}
+
+template <typename XT>
+static int spmm_t(hipStream_t st, int nb, const SellView& A, const XT* x, double* y, bool accumulate, double* dot_partial,
+                  const XT* dot_with, int lz_mode = 0, const LanczosUpdate* lz = nullptr) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return 0;
+    if (dot_partial && !dot_with) throw Error(PMC_ERR_INTERNAL, "spmm: fused dot without its second vector");
+    dim3 g = grid_bounded(grid_slices(A.nslices), dot_partial != nullptr);
+    // The block operator keeps one slice per wavefront also with a fused dot (a bounded grid of looping workgroups cost
+    // 22 us of 450 at 4.7 M rows); its partial blocks - more than the single-block consumers should read - are first
+    // compressed to kCompressBlocks.  They are written behind the compressed ones: dot_capacity() leaves the room.
+    const bool two_stage = dot_partial && A.tag != 0 && !A.bv && grid_slices(A.nslices).x > g.x;
+    double* kernel_partial = dot_partial;
+    if (two_stage) {
+        g = grid_slices(A.nslices);
+        kernel_partial = dot_partial + (size_t)kCompressBlocks * nb;
+    }
+    PMC_DISPATCH_NB(nb, {
+        if (A.tag == 1) spmm_launch<NB, 1, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with, lz_mode, lz);
+        else if (A.tag == 2) spmm_launch<NB, 2, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
+        else spmm_launch<NB, 0, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
+    });
+    check_launch();
+    if (two_stage) {
+        compress_partials_kernel<<<kCompressBlocks, 256, 0, st>>>(kernel_partial, dot_blocks(g, nb), nb, dot_partial);
+        check_launch();
+        return kCompressBlocks;
+    }
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+int spmm(hipStream_t st, int nb, const SellView& A, const double* x, double* y, bool accumulate, double* dot_partial,
+         const double* dot_with) {
+    return spmm_t<double>(st, nb, A, x, y, accumulate, dot_partial, dot_with);
+}
+int spmm_z(hipStream_t st, int nb, const SellView& A, zvec x, double* y, double* dot_partial, zvec dot_with) {
+    if (x.f32) return spmm_t<float>(st, nb, A, x.as<float>(), y, false, dot_partial, dot_with.as<float>());
+    return spmm_t<double>(st, nb, A, x.as<double>(), y, false, dot_partial, dot_with.as<double>());
+}
+
+static void check_lanczos_pass(const SellView& A, zvec x) {
+    if (!x.f32 || A.bv || A.tag != 1)
+        throw Error(PMC_ERR_INTERNAL, "Lanczos operator passes: shared values, fp32-stored input, the solver's operator");
+}
+int spmm_z_dot(hipStream_t st, int nb, const SellView& A, zvec x, double* dot_partial) {
+    check_lanczos_pass(A, x);
+    const LanczosUpdate none{};
+    return spmm_t<float>(st, nb, A, x.as<float>(), nullptr, false, dot_partial, x.as<float>(), 1, &none);
+}
+void spmm_z_update(hipStream_t st, int nb, const SellView& A, zvec x, const LanczosUpdate& lz, double* v, bool v_zero) {
+    check_lanczos_pass(A, x);
+    if (!lz.c0 || !lz.c1 || !lz.c2 || !lz.v1 || !lz.y32 || !v)
+        throw Error(PMC_ERR_INTERNAL, "Lanczos update pass: operand missing");
+    spmm_t<float>(st, nb, A, x.as<float>(), v, false, nullptr, nullptr, v_zero ? 3 : 2, &lz);
+}
+
+void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, double* out,
+                        double* coarse) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "residual_restrict8: rows are not groups of 8");
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        if (A.bv && A.f32)
+            sell_spmm_kernel<NB, 2, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
+        else if (A.bv)
+            sell_spmm_kernel<NB, true, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
+        else
+            sell_spmm_kernel<NB, false, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
+    });
+    check_launch();
+}
+
+void spmm_store32(hipStream_t st, int nb, const SellView& A, const double* x, double* y, float* y32) {
+    check_offsets32(A, nb);
+    if (A.bv || A.tag != 0 || !y || !y32) throw Error(PMC_ERR_INTERNAL, "spmm_store32: shared values, an untagged matrix, both results");
+    if (A.nrows == 0) return;
+    const dim3 g = grid_slices(A.nslices);
+    LanczosUpdate lz{};
+    lz.y32 = y32;
+    PMC_DISPATCH_NB(nb, {
+        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, double, double, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb, lz);
+    });
+    check_launch();
+}
+
+void residual_samples(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, bool do_exp, double* out) {
+    check_offsets32(A, nb);
+    if (A.bv) throw Error(PMC_ERR_INTERNAL, "residual_samples: shared values only");
+    if (A.nrows == 0) return;
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        if (do_exp)
+            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+    });
+    check_launch();
+}
+
+void residual(hipStream_t st, int nb, const SellView& A, const double* r, const double* x, double* out) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        if (A.bv && A.f32)
+            sell_spmm_kernel<NB, 2, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+        else if (A.bv)
+            sell_spmm_kernel<NB, true, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+        else
+            sell_spmm_kernel<NB, false, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
+    });
+    check_launch();
+}
+
+template <typename OT>
+static int cheb_step_t(hipStream_t st, int nb, const SellView& A, const double* dinv, bool dinv_bv, const double* r,
+                       const double* xin, double* d, OT* xout, double a, double b, double* dot_partial) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return 0;
+    if (A.bv != dinv_bv) throw Error(PMC_ERR_INTERNAL, "cheb_step: value/diagonal batching mismatch");
+    const dim3 g = grid_bounded(grid_slices(A.nslices), dot_partial != nullptr);
+    PMC_DISPATCH_NB(nb, {
+        if (A.bv && A.f32) {
+            if (dot_partial)
+                sell_cheb_kernel<NB, 2, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
+            else
+                sell_cheb_kernel<NB, 2, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
+        } else if (A.bv) {
+            if (dot_partial)
+                sell_cheb_kernel<NB, 1, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
+            else
+                sell_cheb_kernel<NB, 1, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
+        } else {
+            if (dot_partial)
+                sell_cheb_kernel<NB, 0, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
+            else
+                sell_cheb_kernel<NB, 0, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
+        }
+    });
+    check_launch();
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+
+int cheb_step(hipStream_t st, int nb, const SellView& A, const double* dinv, bool dinv_bv, const double* r,
+              const double* xin, double* d, double* xout, double a, double b, double* dot_partial) {
+    return cheb_step_t<double>(st, nb, A, dinv, dinv_bv, r, xin, d, xout, a, b, dot_partial);
+}
+
+// fp64 storage: the iterate of the last step goes straight to zout, d is left as it was (as the typed kernel does)
+int cheb_step_z(hipStream_t st, int nb, const SellView& A, const double* dinv, bool dinv_bv, const double* r,
+                const double* xin, double* d, zvec zout, double a, double b, double* dot_partial) {
+    if (zout.f32) return cheb_step_t<float>(st, nb, A, dinv, dinv_bv, r, xin, d, zout.as<float>(), a, b, dot_partial);
+    return cheb_step_t<double>(st, nb, A, dinv, dinv_bv, r, xin, d, zout.as<double>(), a, b, dot_partial);
+}
+
+template <typename OT>
+static int poly2_t(hipStream_t st, int nb, const SellView& As, const double* dinv, bool dinv_bv, const double* r, OT* xout,
+                   double c0, double c1, double* dot_partial, const double* xadd, const double* dot_with, const int* padd_idx,
+                   const double* padd_x) {
+    check_offsets32(As, nb);
+    if (As.nrows == 0) return 0;
+    if (As.bv != dinv_bv) throw Error(PMC_ERR_INTERNAL, "poly2: value/diagonal batching mismatch");
+    const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
+    PMC_DISPATCH_NB(nb, {
+        if (As.bv && As.f32) {
+            if (dot_partial)
+                sell_poly2_kernel<NB, 2, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
+            else
+                sell_poly2_kernel<NB, 2, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
+        } else if (As.bv) {
+            if (dot_partial)
+                sell_poly2_kernel<NB, 1, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
+            else
+                sell_poly2_kernel<NB, 1, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
+        } else if (nt_poly(As, NB)) {
+            if (dot_partial)
+                sell_poly2_kernel<NB, 0, true, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
+            else
+                sell_poly2_kernel<NB, 0, false, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
+        } else {
+            if (dot_partial)
+                sell_poly2_kernel<NB, 0, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
+            else
+                sell_poly2_kernel<NB, 0, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
+        }
+    });
+    check_launch();
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+
+int poly2(hipStream_t st, int nb, const SellView& As, const double* dinv, bool dinv_bv, const double* r, double* xout,
+          double c0, double c1, double* dot_partial, const double* xadd, const double* dot_with, const int* padd_idx,
+          const double* padd_x) {
+    return poly2_t<double>(st, nb, As, dinv, dinv_bv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
+}
+
+int poly2_z(hipStream_t st, int nb, const SellView& As, const double* dinv, bool dinv_bv, const double* r, zvec xout,
+            double c0, double c1, double* dot_partial, const double* xadd, const double* dot_with, const int* padd_idx,
+            const double* padd_x) {
+    if (xout.f32)
+        return poly2_t<float>(st, nb, As, dinv, dinv_bv, r, xout.as<float>(), c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
+    return poly2_t<double>(st, nb, As, dinv, dinv_bv, r, xout.as<double>(), c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
+}
+
+// a level runs the deep gather loop (sell_row_range_deep) when its launch has at most this many wavefronts - about two per
+// SIMD of the chip (PMC_DEEP_WAVES in laboratory builds; 0 = never)
+static inline bool deep_level(const SellView& A, int nb) {
+    static const long limit = [] {
+        const char* e = lab_env("PMC_DEEP_WAVES");
+        return e ? atol(e) : 0L;   // off in the product: measured neutral on config 2 (LAB_NOTES 10), kept for laboratory runs
+    }();
+    return nb >= kGroup && !A.bv && (long)A.nslices * (nb / kGroup) <= limit;
+}
+
+// the launchers below take the right-hand side and the inter-level vectors (coarse right-hand side, coarse correction) of a
+// shared-value level in either storage: T names the element type inside the braces
+#define PMC_DISPATCH_F32(is_f32, T, ...)                \
+    if (is_f32) { using T = float; __VA_ARGS__; }       \
+    else { using T = double; __VA_ARGS__; }
+
+// r in fp32: the copy of the Lanczos vector the MINRES loop keeps for the top level of a cycle (k::lincomb3) - gathered, and
+// read at the own row, as 128-byte rows instead of 256-byte ones - or the coarse right-hand side the level above wrote
+template <typename RT>
+static void vc_presmooth32_t(hipStream_t st, int nb, const SellView& As, const double* dinv, const RT* r, float* xout, double c0,
+                             double c1) {
+    check_offsets32(As, nb);
+    if (As.nrows == 0) return;
+    if (As.bv) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32: shared values expected");
+    const dim3 g = grid_slices(As.nslices);
+    if (As.split_log2) {
+        PMC_DISPATCH_NARROW(nb, {
+            vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, true><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb, As.split_log2);
+        });
+        check_launch();
+        return;
+    }
+    if (deep_level(As, nb)) {
+        vc_poly2_kernel<kGroup, RT, float, float, false, false, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+        check_launch();
+        return;
+    }
+    PMC_DISPATCH_NB(nb, {
+        if (nt_poly(As, NB))
+            vc_poly2_kernel<NB, RT, float, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+        else
+            vc_poly2_kernel<NB, RT, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+    });
+    check_launch();
+}
+void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, zvec r, float* xout, double c0, double c1) {
+    PMC_DISPATCH_F32(r.f32, RT, vc_presmooth32_t<RT>(st, nb, As, dinv, r.as<RT>(), xout, c0, c1));
+}
+
+void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (A.bv || A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict8_32: shared values and groups of 8 rows expected");
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, RT, float, true, 0, true, 1, false, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb);
+    })));
+    check_launch();
+}
+
+template <typename RT>
+static void vc_residual32_t(hipStream_t st, int nb, const SellView& A, const RT* r, const float* x, float* out) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual32: shared values expected");
+    const dim3 g = grid_slices(A.nslices);
+    if (A.split_log2) {
+        PMC_DISPATCH_NARROW(nb, {
+            vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, false, true><<<g, kBlock, 0, st>>>(A.nrows >> A.split_log2, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb, nullptr, nullptr, nullptr, A.split_log2);
+        });
+        check_launch();
+        return;
+    }
+    if (deep_level(A, nb)) {
+        vc_residual_kernel<kGroup, float, RT, float, false, 0, true, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
+        check_launch();
+        return;
+    }
+    PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, RT, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
+    });
+    check_launch();
+}
+void vc_residual32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out) {
+    PMC_DISPATCH_F32(r.f32, RT, vc_residual32_t<RT>(st, nb, A, r.as<RT>(), x, out));
+}
+
+void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse,
+                                const int* seg_ptr, const int* seg_cid, const int* seg_pos) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict_agg32: shared values expected");
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, true, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb, seg_ptr, seg_cid, seg_pos);
+    })));
+    check_launch();
+}
+
+// coarse = Pt res (the restriction of a level without a fused one): fp64 through the product every caller uses, fp32 through
+// the same kernel with a typed result
+void vc_restrict32(hipStream_t st, int nb, const SellView& Pt, const float* res, zvec coarse) {
+    if (!coarse.f32) {
+        spmm_z(st, nb, Pt, zvec(const_cast<float*>(res), true), coarse.as<double>(), nullptr, zvec());
+        return;
+    }
+    check_offsets32(Pt, nb);
+    if (Pt.nrows == 0) return;
+    if (Pt.bv) throw Error(PMC_ERR_INTERNAL, "vc_restrict32: shared values expected");
+    const dim3 g = grid_slices(Pt.nslices);
+    PMC_DISPATCH_NB(nb, {
+        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, float, float><<<groups_xcd(g, nb), kBlock, 0, st>>>(Pt.nrows, Pt.nslices, Pt.slice_off, Pt.sched, Pt.cols, Pt.vals, res, coarse.as<float>(), nullptr, nullptr, nullptr, nb);
+    });
+    check_launch();
+}
+
+template <typename XT>
+static void vc_residual_coarse32_t(hipStream_t st, int nb, const SellView& SP, float* res, const XT* xc) {
+    check_offsets32(SP, nb);
+    if (SP.nrows == 0) return;
+    if (SP.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_coarse32: shared values expected");
+    const dim3 g = grid_slices(SP.nslices);
+    if (SP.split_log2) {
+        PMC_DISPATCH_NARROW(nb, {
+            vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, true, double, 1><<<g, kBlock, 0, st>>>(SP.nrows >> SP.split_log2, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb, nullptr, nullptr, nullptr, SP.split_log2);
+        });
+        check_launch();
+        return;
+    }
+    if (deep_level(SP, nb)) {
+        vc_residual_kernel<kGroup, XT, float, float, false, 0, true, 2, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
+        check_launch();
+        return;
+    }
+    PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
+    });
+    check_launch();
+}
+void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, zvec xc) {
+    PMC_DISPATCH_F32(xc.f32, XT, vc_residual_coarse32_t<XT>(st, nb, SP, res, xc.as<XT>()));
+}
+
+template <typename OT, typename PT>
+static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                             OT* xout, double c0, double c1, const double* r, const int* parent, const PT* xc,
+                             double* dot_partial) {
+    check_offsets32(As, nb);
+    if (As.nrows == 0) return 0;
+    if (As.bv) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: shared values expected");
+    const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
+    if (As.split_log2) {
+        if (dot_partial) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: the row-split form serves inner levels (no fused dot)");
+        PMC_DISPATCH_NARROW(nb, {
+            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, true, false, PT><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb, As.split_log2);
+        });
+        check_launch();
+        return 0;
+    }
+    if (deep_level(As, nb)) {
+        if (dot_partial)
+            vc_poly2_kernel<kGroup, float, OT, float, true, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+        else
+            vc_poly2_kernel<kGroup, float, OT, float, false, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        check_launch();
+        return dot_partial ? dot_blocks(g, nb) : 0;
+    }
+    // 64 per launch on a large level: both column groups of a slice in one workgroup (vc_poly2_kernel, GIB).  Off in the
+    // product: one lane 2 870 -> 2 815 samples/s, four lanes 3 745 -> 3 757 (LAB_NOTES 10.19); laboratory switch PMC_GIB=1
+    static const bool gib = [] { const char* e = lab_env("PMC_GIB"); return e && atoi(e) != 0; }();
+    if (gib && nb == 2 * kGroup && nt_poly(As, kGroup) && !xcd_layout(g, nb)) {
+        if (dot_partial)
+            vc_poly2_kernel<kGroup, float, OT, float, true, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+        else
+            vc_poly2_kernel<kGroup, float, OT, float, false, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        check_launch();
+        return dot_partial ? (int)g.x : 0;
+    }
+    PMC_DISPATCH_NB(nb, {
+        if (nt_poly(As, NB)) {
+            if (dot_partial)
+                vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+            else
+                vc_poly2_kernel<NB, float, OT, float, false, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        } else if (dot_partial)
+            vc_poly2_kernel<NB, float, OT, float, true, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+        else
+            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+    });
+    check_launch();
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+
+int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                      zvec xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial) {
+    int nblk = 0;
+    PMC_DISPATCH_F32(xout.f32, OT, PMC_DISPATCH_F32(xc.f32, PT, {
+        nblk = vc_postsmooth32_t<OT, PT>(st, nb, As, dinv, res, x, xout.as<OT>(), c0, c1, r, parent, xc.as<PT>(), dot_partial);
+    }));
+    return nblk;
+}
+
+// ---- the same level with per-realization fp32 values (Darcy; SellView::f32) and per-realization diagonals
+void vc_presmooth32_bv(hipStream_t st, int nb, const SellView& As, const double* dinv, const double* r, float* xout, double c0,
+                       double c1) {
+    check_offsets32(As, nb);
+    if (As.nrows == 0) return;
+    if (!(As.bv && As.f32)) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32_bv: per-realization fp32 values expected");
+    const dim3 g = grid_slices(As.nslices);
+    PMC_DISPATCH_NB(nb, {
+        vc_poly2_kernel<NB, double, float, float, false, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+    });
+    check_launch();
+}
+
+void vc_restrict8_32_bv(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, double* coarse) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (!(A.bv && A.f32) || A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "vc_restrict8_32_bv: operand mismatch");
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, double, float, true, 2, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, nullptr, coarse, nb);
+    });
+    check_launch();
+}
+
+void vc_prolong8_32(hipStream_t st, int nb, int n, float* x, const double* xc) {
+    if (n == 0) return;
+    PMC_DISPATCH_NB(nb, { vc_prolong8_kernel<NB><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), x, xc, nb); });
+    check_launch();
+}
+
+void vc_residual32_bv(hipStream_t st, int nb, const SellView& A, const double* r, const float* x, float* out) {
+    check_offsets32(A, nb);
+    if (A.nrows == 0) return;
+    if (!(A.bv && A.f32)) throw Error(PMC_ERR_INTERNAL, "vc_residual32_bv: per-realization fp32 values expected");
+    const dim3 g = grid_slices(A.nslices);
+    PMC_DISPATCH_NB(nb, {
+        vc_residual_kernel<NB, float, double, float, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
+    });
+    check_launch();
+}
+
+template <typename OT>
+static int vc_postsmooth32_bv_t(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                                OT* xout, double c0, double c1, const double* r, double* dot_partial) {
+    check_offsets32(As, nb);
+    if (As.nrows == 0) return 0;
+    if (!(As.bv && As.f32)) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32_bv: per-realization fp32 values expected");
+    const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
+    PMC_DISPATCH_NB(nb, {
+        if (dot_partial)
+            vc_poly2_kernel<NB, float, OT, float, true, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, nullptr, nullptr, nb);
+        else
+            vc_poly2_kernel<NB, float, OT, float, false, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, nullptr, nullptr, nb);
+    });
+    check_launch();
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+
+int vc_postsmooth32_bv(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                       double* xout, double c0, double c1, const double* r, double* dot_partial) {
+    return vc_postsmooth32_bv_t<double>(st, nb, As, dinv, res, x, xout, c0, c1, r, dot_partial);
+}
+int vc_postsmooth32_bv_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
+                         zvec xout, double c0, double c1, const double* r, double* dot_partial) {
+    if (xout.f32) return vc_postsmooth32_bv_t<float>(st, nb, As, dinv, res, x, xout.as<float>(), c0, c1, r, dot_partial);
+    return vc_postsmooth32_bv_t<double>(st, nb, As, dinv, res, x, xout.as<double>(), c0, c1, r, dot_partial);
+}
+
+template <typename XT>
+static int pair_spmm_t(hipStream_t st, int nb, const SellView& A1, const XT* x1, const SellView& A2, const XT* x2, double* y,
+                       double* dot_partial, const XT* dot_with) {
+    check_offsets32(A1, nb);
+    if (A1.nrows == 0) return 0;
+    if (!A1.bv || A2.bv || A1.nrows != A2.nrows || A1.nslices != A2.nslices)
+        throw Error(PMC_ERR_INTERNAL, "pair_spmm: operand mismatch");
+    const dim3 g = grid_bounded(grid_slices(A1.nslices), dot_partial != nullptr);
+    PMC_DISPATCH_NB(nb, {
+        if (dot_partial)
+            sell_pair_spmm_kernel<NB, true, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A1.nrows, A1.nslices, A1.slice_off, A1.cols, A1.vals, A2.slice_off, A2.cols, A2.vals, x1, x2, y, dot_with, dot_partial, nb);
+        else
+            sell_pair_spmm_kernel<NB, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A1.nrows, A1.nslices, A1.slice_off, A1.cols, A1.vals, A2.slice_off, A2.cols, A2.vals, x1, x2, y, nullptr, nullptr, nb);
+    });
+    check_launch();
+    return dot_partial ? dot_blocks(g, nb) : 0;
+}
+
+int pair_spmm_z(hipStream_t st, int nb, const SellView& A1, zvec x1, const SellView& A2, zvec x2, double* y,
+                double* dot_partial, zvec dot_with) {
+    if (x1.f32) return pair_spmm_t<float>(st, nb, A1, x1.as<float>(), A2, x2.as<float>(), y, dot_partial, dot_with.as<float>());
+    return pair_spmm_t<double>(st, nb, A1, x1.as<double>(), A2, x2.as<double>(), y, dot_partial, dot_with.as<double>());
+}
+
+}  // namespace k
+}  // namespace pmc

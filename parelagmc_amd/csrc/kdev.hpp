@@ -1,4 +1,4 @@
-// Device-side helpers of the kernels (kernels.hip): tuning constants, batch layout, typed loads / stores, block reductions,
+// Device-side helpers of the kernels (the units k_*.hip): tuning constants, batch layout, typed loads / stores, block reductions,
 // the XCD-aware slice walk.  Included by the kernel sources only; kernels.hpp stays the interface the rest of the library sees.
 #pragma once
 #include "kernels.hpp"
@@ -401,7 +401,7 @@ __device__ __forceinline__ SliceWalk slice_walk(int nslices) {
 }
 
 // Launch-side dispatch on the batch width: the body sees the compile-time interleave NB of a launch of nb realizations
-// (kernels.hip and every other translation unit that starts a batched kernel).
+// (the units k_*.hip and every other translation unit that starts a batched kernel).
 #define PMC_DISPATCH_NB(nb, ...)                                          \
     switch (nb) {                                                         \
         case 1: { constexpr int NB = 1; __VA_ARGS__; } break;             \

@@ -1,5 +1,18 @@
-// Launchers of the CDNA4 kernels (kernels.hip, over kdev.hpp: device-side helpers, and sell_rows.hpp: the SELL-64 gather
-// loops; this header is the one interface the rest of the library sees).  All vectors are "interleaved" batches:
+// Launchers of the CDNA4 (gfx950) kernels of the ParELAGMC hot path (the units k_*.hip, over kdev.hpp: device-side helpers,
+// sell_rows.hpp: the SELL-64 gather loops, and klaunch.hpp: host-side launch helpers; this header is the one interface the
+// rest of the library sees).  A banner names the unit that defines the declarations below it.  A kernel template and every
+// launcher that instantiates it live in the same unit: each unit carries its own device code object, and an instantiation
+// reachable from two units would be compiled and shipped twice.
+//
+// Kernel <-> reference operation:
+//   sell_spmm / sell_residual / sell_cheb_step : K5 block saddle-point SpMV, K7 smoother on M,
+//        K8 V-cycle smoothing/residual/transfer, K3/K4 restriction/prolongation, K11 projection
+//   minres_* / lincomb3 / dot                  : K6 MINRES vector operations
+//   normal_fill                                : K1 NormalDistributionSampler
+//   interleave / deinterleave                  : K2 white-noise RHS scaling, K9 exp, K10 gather (fused with the layout change)
+//   darcy_*                                    : K12-K15 per-sample M(k), BC elimination, Schur refresh, QoI
+//
+// All vectors are "interleaved" batches:
 // row i, column (realization) k of a batch of nb lives at v[i*nb + k], nb in {1,2,4,8,16,32} or - as 2, 4, 8 column groups
 // of 32 handled by one launch (gridDim.y) - 64, 128, 256.
 #pragma once
@@ -83,9 +96,11 @@ struct EgView {
     const int* e12 = nullptr;      // [nrows][2] coefficient rows (n_elem = constant-one row for eliminated dofs)
 };
 
+// ---- k_sell.hip
 // capacity (in blocks of nb doubles) of a partial-sum buffer for (fused) dots over nrows rows of a batch of nb columns:
 // allocate dot_capacity(nrows, nb) * nb doubles
 int dot_capacity(int nrows, int nb);
+// ---- k_krylov.hip
 // kernels this process has launched through the library so far (all handles, all threads): launch-rate diagnostics
 uint64_t kernel_launch_count();
 void count_kernel_launches(int n);
@@ -103,7 +118,7 @@ namespace k {
 // A pass walks its window in trips: the preconditioned vectors of a trip's iterations are requested together, w0 / w1 / x
 // stay in registers across the trips.  A thread owns several entries in the same columns (one load of an iteration's
 // coefficients serves all of them), so a trip is as many iterations as about 64 registers of u hold - four at four values
-// per thread and four entries - and at most kWxDefer (WxShape in kernels.hip).
+// per thread and four entries - and at most kWxDefer (WxShape in k_krylov.hip).
 #ifndef PMC_WX_DEFER_N
 #define PMC_WX_DEFER_N 8
 #endif
@@ -134,6 +149,8 @@ struct MinresState {
 };
 static constexpr size_t kMinresHeadBytes = offsetof(MinresState, cW);
 
+// ---- k_sell.hip (the vc_* launchers too: their kernels share sell_row_range specialisations with sell_spmm_kernel, and
+// vc_restrict32 starts sell_spmm_kernel itself - see the head of k_sell.hip)
 // y = A x (accumulate=false) or y += A x.  If dot_partial != nullptr (accumulate must be false) also
 // writes per-block partial sums of <dot_with, A x>; returns the number of partial blocks written.
 int spmm(hipStream_t st, int nb, const SellView& A, const double* x, double* y, bool accumulate,
@@ -214,12 +231,14 @@ int vc_postsmooth32_bv_z(hipStream_t st, int nb, const SellView& As, const doubl
 // y = A1 x1 + A2 x2 (A1 per-realization values, A2 shared values, same rows); optional fused dot
 int pair_spmm_z(hipStream_t st, int nb, const SellView& A1, zvec x1, const SellView& A2, zvec x2, double* y,
                 double* dot_partial, zvec dot_with);
+// ---- k_darcy.hip
 // out[slot][k] = vals[slot][k] * colscale[cols[slot]][k]
 void scale_cols_bv(hipStream_t st, int nb, int64_t nslots, const int* cols, const double* vals, const double* colscale,
                    double* out);
 // the fp32 copies the preconditioner kernels read: out_scaled = (float)(vals * colscale[cols]), out_vals = (float)vals
 void scale_cols_bv32(hipStream_t st, int nb, int64_t nslots, const int* cols, const double* vals, const double* colscale,
                      float* out_scaled, float* out_vals);
+// ---- k_krylov.hip
 // MINRES w/x update on an index list of rows (w0, w1, x compact [nsel][nb]; u full)
 void minres_wx_idx(hipStream_t st, int nb, int nsel, const int* rows, const double* c0, zvec u, const double* c1,
                    double* w0, const double* c2, const double* w1, const double* c3, double* x);
@@ -264,6 +283,7 @@ void minres_scal2(hipStream_t st, int nb, MinresState* s, const DotParts& d);
 void minres_scal21(hipStream_t st, int nb, MinresState* s, const DotParts& d2, const DotParts& d1, double* stage = nullptr);
 size_t scal_stage_doubles();
 
+// ---- k_fields.hip
 // realization b of the batch = generator realization first_id + b * id_stride
 void normal_fill(hipStream_t st, int n, int nbatch, uint64_t seed, uint64_t first_id, uint32_t stream, double mean,
                  double sigma, double* out, uint64_t id_stride = 1);
@@ -275,6 +295,7 @@ void deinterleave(hipStream_t st, int nb, int m, const double* in, const int* id
                   double* out);
 void broadcast(hipStream_t st, int nb, int n, const double* a, double* out);
 
+// ---- k_darcy.hip
 void darcy_coef(hipStream_t st, int nb, int n, const double* kfield, bool k_divides, double* coef);
 void darcy_assemble(hipStream_t st, int nb, const SellView& Mp, const int* slot_src, const int* c_ptr, const int* c_elem,
                     const double* c_val, const double* coef, const unsigned char* ess, const double* ess_data,
@@ -362,6 +383,7 @@ struct MiniSamplerParams {
     int x_row0, x_nrows;            // maintained rows of the solution
     size_t scratch_per_col;         // doubles of scratch per realization: 5 n + 3 x_nrows
 };
+// ---- k_tail.hip
 namespace k {
 // Whole preconditioned MINRES solves of nb realizations, one workgroup each (see mini_sampler_kernel).  b, x: interleaved
 // [row][nb] vectors as in minres_solve; stats: nb device entries.

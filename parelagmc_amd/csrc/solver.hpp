@@ -1,4 +1,4 @@
-// Krylov solver and preconditioner building blocks (host orchestration of kernels.hip).
+// Krylov solver and preconditioner building blocks (host orchestration of the kernel units k_*.hip).
 #pragma once
 #include <functional>
 #include <map>
