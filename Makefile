@@ -118,3 +118,11 @@ $(ABIBIN)/gradient_smoke: tests/c/gradient_smoke.cpp tests/c/prob_io.h parelagmc
 	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/gradient_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-gradient: $(ABIBIN)/gradient_smoke
 .PHONY: test-gradient
+
+# the V-cycle's path decision (csrc/vcycle_plan.hpp) against the predicates it replaced: plain C++, no library, no device
+# (tests/test_vcycle_plan.py builds and runs it)
+$(ABIBIN)/vcycle_plan_check: tests/c/vcycle_plan_check.cpp $(CSRC)/vcycle_plan.hpp
+	@mkdir -p $(ABIBIN)
+	g++ -std=c++17 -O2 -Wall -Wextra -Werror -I$(CSRC) -o $@ tests/c/vcycle_plan_check.cpp
+test-vcycle-plan: $(ABIBIN)/vcycle_plan_check
+.PHONY: test-vcycle-plan

@@ -591,26 +591,26 @@ int pmc_sampler_smoother_bytes(const pmc_sampler* s, int level, int nbatch, doub
     });
 }
 
+// The two-call CSR export of the prolongator entry points: sizes always (*nnz holds the arrays' capacity on entry), the arrays
+// when all three are given
+static void export_csr(const HostCsr& P, int* nrows, int* ncols, int64_t* nnz, int32_t* rowptr, int32_t* colind, double* vals,
+                       const char* too_small) {
+    const int64_t cap = *nnz;
+    *nrows = P.nrows;
+    *ncols = P.ncols;
+    *nnz = (int64_t)P.colind.size();
+    if (rowptr == nullptr && colind == nullptr && vals == nullptr) return;   // size query
+    PMC_REQUIRE(rowptr != nullptr && colind != nullptr && vals != nullptr && cap >= *nnz, too_small);
+    std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
+    std::copy(P.colind.begin(), P.colind.end(), colind);
+    std::copy(P.vals.begin(), P.vals.end(), vals);
+}
+
 int pmc_sampler_vcycle_info(const pmc_sampler* s, int level, int vlevel, int* nvlevels, int64_t info[7]) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr && nvlevels != nullptr && info != nullptr, "pmc_sampler_vcycle_info: NULL argument");
         refuse_kl(s, "pmc_sampler_vcycle_info");
-        PMC_REQUIRE(level >= 0 && level < s->impl.n_mc, "pmc_sampler_vcycle_info: level out of range");
-        const bool own = level < (int)s->impl.amg.size() && s->impl.amg[level];
-        const Multigrid& mg = own ? *s->impl.amg[level] : s->impl.mg;
-        const int first = own ? 0 : level;
-        *nvlevels = (int)mg.L.size() - first;
-        PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_sampler_vcycle_info: vlevel out of range");
-        const MgLevel& m = mg.L[(size_t)(first + vlevel)];
-        bool in_tail = false;
-        for (int l = first; l <= first + vlevel; ++l) in_tail = in_tail || (l < (int)mg.tail.size() && mg.tail[l].p != nullptr);
-        info[0] = m.n;
-        info[1] = m.S.nnz;
-        info[2] = m.S.nslots;
-        info[3] = m.has_sp ? m.SP.nnz : 0;
-        info[4] = m.has_sp ? m.SP.nslots : 0;
-        info[5] = (in_tail ? 1 : 0) | (m.dense_inv.p ? 2 : 0) | ((int64_t)m.split_log2 << 4);
-        info[6] = (m.p_agg || m.p_oct) ? 1 : 0;
+        s->impl.vcycle_info(level, vlevel, nvlevels, info);
     });
 }
 
@@ -629,16 +629,7 @@ int pmc_sampler_vcycle_prolongator(const pmc_sampler* s, int level, int vlevel, 
         refuse_kl(s, "pmc_sampler_vcycle_prolongator");
         HostCsr scratch;
         const HostCsr& P = s->impl.vcycle_prolongator(level, vlevel, scratch);
-        const int64_t cap = *nnz;
-        *nrows = P.nrows;
-        *ncols = P.ncols;
-        *nnz = (int64_t)P.colind.size();
-        if (rowptr == nullptr && colind == nullptr && vals == nullptr) return;   // size query
-        PMC_REQUIRE(rowptr != nullptr && colind != nullptr && vals != nullptr && cap >= *nnz,
-                    "pmc_sampler_vcycle_prolongator: arrays missing or smaller than nnz");
-        std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
-        std::copy(P.colind.begin(), P.colind.end(), colind);
-        std::copy(P.vals.begin(), P.vals.end(), vals);
+        export_csr(P, nrows, ncols, nnz, rowptr, colind, vals, "pmc_sampler_vcycle_prolongator: arrays missing or smaller than nnz");
     });
 }
 
@@ -854,16 +845,7 @@ int pmc_darcy_vcycle_prolongator(const pmc_darcy* d, int level, int vlevel, int*
         PMC_REQUIRE(d != nullptr && nrows != nullptr && ncols != nullptr && nnz != nullptr,
                     "pmc_darcy_vcycle_prolongator: NULL argument");
         const HostCsr& P = d->impl.vcycle_prolongator(level, vlevel);
-        const int64_t cap = *nnz;
-        *nrows = P.nrows;
-        *ncols = P.ncols;
-        *nnz = (int64_t)P.colind.size();
-        if (rowptr == nullptr && colind == nullptr && vals == nullptr) return;   // size query
-        PMC_REQUIRE(rowptr != nullptr && colind != nullptr && vals != nullptr && cap >= *nnz,
-                    "pmc_darcy_vcycle_prolongator: arrays missing or smaller than nnz");
-        std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
-        std::copy(P.colind.begin(), P.colind.end(), colind);
-        std::copy(P.vals.begin(), P.vals.end(), vals);
+        export_csr(P, nrows, ncols, nnz, rowptr, colind, vals, "pmc_darcy_vcycle_prolongator: arrays missing or smaller than nnz");
     });
 }
 int pmc_darcy_set_observations(pmc_darcy* d, int level, const pmc_csr* Gobs) {

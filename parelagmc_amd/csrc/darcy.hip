@@ -1230,11 +1230,19 @@ void Darcy::apply_operator(int level, int nbatch, const double* k, const double*
     apply_one(level, nbatch, k, x, y, memspace, false);
 }
 
+// the hierarchy the solves of `level` cycle on: the multiplier aggregation of a hybridized handle or the level's mg_coarsening
+// chain, each from its level 0, or the caller's from `level`
+CycleHierarchy Darcy::cycle_hierarchy(int level) const {
+    const bool own = hybrid || (level < (int)chains.size() && chains[level]);
+    return CycleHierarchy{hybrid ? hyb[level]->chain->mg : own ? chains[level]->mg : mg, own ? 0 : level, own};
+}
+
 void Darcy::vcycle_level(int level, int vlevel, int* nvlevels, double* info) const {
     PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_vcycle_level: level out of range");
-    const bool own = hybrid || (level < (int)chains.size() && chains[level]);
-    const Multigrid& g = hybrid ? hyb[level]->chain->mg : own ? chains[level]->mg : mg;
-    const int first = own ? 0 : level;
+    const CycleHierarchy h = cycle_hierarchy(level);
+    const Multigrid& g = h.g;
+    const int first = h.first;
+    const bool own = h.own;
     *nvlevels = (int)g.L.size() - first;
     PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_darcy_vcycle_level: vlevel out of range");
     const MgLevel& m = g.L[(size_t)(first + vlevel)];
@@ -1257,9 +1265,10 @@ void Darcy::vcycle_level(int level, int vlevel, int* nvlevels, double* info) con
 // handle in the order of fe/darcy_hybrid.py).
 const HostCsr& Darcy::vcycle_prolongator(int level, int vlevel) const {
     PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_vcycle_prolongator: level out of range");
-    const bool own = hybrid || (level < (int)chains.size() && chains[level]);
-    const Multigrid& g = hybrid ? hyb[level]->chain->mg : own ? chains[level]->mg : mg;
-    const int first = own ? 0 : level;
+    const CycleHierarchy h = cycle_hierarchy(level);
+    const Multigrid& g = h.g;
+    const int first = h.first;
+    const bool own = h.own;
     PMC_REQUIRE(vlevel >= 0 && first + vlevel + 1 < (int)g.L.size(), "pmc_darcy_vcycle_prolongator: vlevel out of range");
     const HostCsr& P = own ? g.L[(size_t)vlevel].P_host : P_host[(size_t)(first + vlevel)];
     PMC_REQUIRE(P.nrows == g.L[(size_t)(first + vlevel)].n, "pmc_darcy_vcycle_prolongator: no prolongator kept");

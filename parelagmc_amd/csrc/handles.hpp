@@ -94,6 +94,8 @@ struct Sampler {
     // setup values / prolongator of level `vlevel` of the V-cycle `level`'s solves run (pmc_sampler_vcycle_level / _prolongator)
     void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
     const HostCsr& vcycle_prolongator(int level, int vlevel, HostCsr& scratch) const;
+    // sizes and kernel-selection flags of that level (pmc_sampler_vcycle_info)
+    void vcycle_info(int level, int vlevel, int* nvlevels, int64_t* info) const;
     size_t system_rows(int level) const { return hybrid ? (size_t)lv[level].n_u : (size_t)lv[level].n_u + lv[level].n_s; }
     void set_projection(int level, int kind, const pmc_csr* Gt, const int32_t* idx, const double* inv_w, int orig_size);
     void sample(int level, uint64_t first_id, int nbatch, double* xi, int memspace);
@@ -114,6 +116,7 @@ struct Sampler {
     int launch_width(int level) const;
 
   private:
+    CycleHierarchy cycle_hierarchy(int level) const;
     void ensure(int level, int nb);
     // rhs (hybridized solver): the kernel that would write the multiplier right-hand side, handed to the solve (RhsFn)
     void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs = nullptr);
@@ -364,6 +367,7 @@ struct Darcy {
     std::vector<HostCsr> P_host;
 
   private:
+    CycleHierarchy cycle_hierarchy(int level) const;
     void ensure(int level, int nb);
     void setup_chunk(int level, int nb, const double* k_d);
     void chunk_ops(int level, int nb, bool timing_ok, LinOp& A, PrecFn& prec);

@@ -667,7 +667,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
     // (cube_tet_embed: lambda_max / lambda_min = 22 against 8 on uniform tetrahedra) pay for degree 4 (69.6 -> 55.9
     // iterations, 20.0 -> 19.5 ms per batch at 314 k DoF), well shaped ones do not
     const int degM = opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (d.ratio_M > 16.0 ? 4 : 2);
-    const bool mini = !hybrid && n <= mini_max_rows && degM == 2 && opts.use_graph == 0 && mgp->use_tail &&
+    const bool mini = !hybrid && n <= mini_max_rows && degM == 2 && opts.use_graph == 0 &&
                       mg_l0 < (int)mgp->tail.size() && mgp->tail[mg_l0].p != nullptr;
     if (mini) {
         MiniSamplerParams mp{};
@@ -964,12 +964,41 @@ void Sampler::eval(int level, int xi_level, int nbatch, const double* xi, double
     if (init_copy.p) PMC_HIP(hipStreamSynchronize(st));   // the private copy is released on return
 }
 
+// the hierarchy the solves of `level` cycle on: the level's internal one from its level 0, or the caller's from `level`
+CycleHierarchy Sampler::cycle_hierarchy(int level) const {
+    const bool own = level < (int)amg.size() && amg[level];
+    return CycleHierarchy{own ? *amg[level] : mg, own ? 0 : level, own};
+}
+
+// sizes and kernel-selection flags of one level of that cycle (pmc_sampler_vcycle_info; layout in include/pmc.h)
+void Sampler::vcycle_info(int level, int vlevel, int* nvlevels, int64_t* info) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_sampler_vcycle_info: level out of range");
+    const CycleHierarchy h = cycle_hierarchy(level);
+    const Multigrid& g = h.g;
+    const int first = h.first;
+    *nvlevels = (int)g.L.size() - first;
+    PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_sampler_vcycle_info: vlevel out of range");
+    const MgLevel& m = g.L[(size_t)(first + vlevel)];
+    // bit 0 is a statement about the tail DESCRIPTORS, not about a launch: one exists on this level or on one above it.  (The
+    // in_tail of cycle_role is per launch width, and false below an is_last level outside the tail, which ends the cycle.)
+    bool in_tail = false;
+    for (int l = first; l <= first + vlevel; ++l) in_tail = in_tail || (l < (int)g.tail.size() && g.tail[l].p != nullptr);
+    info[0] = m.n;
+    info[1] = m.S.nnz;
+    info[2] = m.S.nslots;
+    info[3] = m.has_sp ? m.SP.nnz : 0;
+    info[4] = m.has_sp ? m.SP.nslots : 0;
+    info[5] = (in_tail ? 1 : 0) | (m.dense_inv.p ? 2 : 0) | ((int64_t)m.split_log2 << 4);
+    info[6] = (m.p_agg || m.p_oct) ? 1 : 0;
+}
+
 // setup values of the V-cycle of `level` (pmc_sampler_vcycle_level; layout in include/pmc.h).  Reads setup only.
 void Sampler::vcycle_level(int level, int vlevel, int* nvlevels, double* info) const {
     PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_sampler_vcycle_level: level out of range");
-    const bool own = level < (int)amg.size() && amg[level];
-    const Multigrid& g = own ? *amg[level] : mg;
-    const int first = own ? 0 : level;
+    const CycleHierarchy h = cycle_hierarchy(level);
+    const Multigrid& g = h.g;
+    const int first = h.first;
+    const bool own = h.own;
     *nvlevels = (int)g.L.size() - first;
     PMC_REQUIRE(vlevel >= 0 && vlevel < *nvlevels, "pmc_sampler_vcycle_level: vlevel out of range");
     const MgLevel& m = g.L[(size_t)(first + vlevel)];
@@ -998,9 +1027,10 @@ void Sampler::vcycle_level(int level, int vlevel, int* nvlevels, double* info) c
 // the caller's multiplier numbering (the agg_pack_rows renumbering undone into `scratch`)
 const HostCsr& Sampler::vcycle_prolongator(int level, int vlevel, HostCsr& scratch) const {
     PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_sampler_vcycle_prolongator: level out of range");
-    const bool own = level < (int)amg.size() && amg[level];
-    const Multigrid& g = own ? *amg[level] : mg;
-    const int first = own ? 0 : level;
+    const CycleHierarchy h = cycle_hierarchy(level);
+    const Multigrid& g = h.g;
+    const int first = h.first;
+    const bool own = h.own;
     PMC_REQUIRE(vlevel >= 0 && first + vlevel + 1 < (int)g.L.size(), "pmc_sampler_vcycle_prolongator: vlevel out of range");
     const HostCsr& P = own ? g.L[(size_t)vlevel].P_host : lv[(size_t)(first + vlevel)].P_host;
     PMC_REQUIRE(P.nrows == g.L[(size_t)(first + vlevel)].n, "pmc_sampler_vcycle_prolongator: no prolongator kept");

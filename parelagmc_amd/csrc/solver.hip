@@ -197,164 +197,183 @@ static bool coarse_f32_on() {
     return v;
 }
 
-Multigrid::LevelPath Multigrid::level_path(int l, int l0, int nb) const {
-    const MgLevel& lv = L[(size_t)l];
-    LevelPath p;
-    p.last = (l == (int)L.size() - 1) || lv.is_last;
-    p.dense = l > l0 && nb <= dense_nb && lv.dense_inv.p;
-    if (p.dense) return p;
-    const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && !p.last && l + 1 < (int)tail.size() && tail[(size_t)l + 1].p;
-    p.tail_here = use_tail && l < (int)tail.size() && tail[(size_t)l].p && !tail_later;
-    if (p.tail_here) return p;
-    p.f32_shared = !p.last && !lv.bv && lv.has_sp && (lv.p_oct || f32_any_injection) && smooth_degree == 2 &&
-                   lv.vals_scaled.p && f32_intermediates;
-    p.f32_bv = !p.last && lv.bv && lv.f32 && lv.p_oct && smooth_degree == 2 && lv.scaled32.p && f32_intermediates;
-    return p;
+CycleFacts Multigrid::cycle_facts() const {
+    CycleFacts c;
+    c.smooth_degree = smooth_degree;
+    c.f32_intermediates = f32_intermediates;
+    c.f32_any_injection = f32_any_injection;
+    c.tail_later_nb = tail_later_nb;
+    c.dense_nb = dense_nb;
+    c.nlevels = (int)L.size();
+    c.coarse_f32 = coarse_f32_on();
+    return c;
 }
 
-bool Multigrid::inner_f32(int l, int l0, int nb) const {
-    if (!f32_intermediates || !coarse_f32_on() || l <= l0 || l >= (int)L.size() || L[(size_t)l].bv) return false;
-    const LevelPath p = level_path(l, l0, nb);
-    return p.dense || p.tail_here || p.f32_shared;
-}
-
-zvec Multigrid::cycle(hipStream_t st, int nb, int l, int l0, zvec rz, double* target, zvec ztarget, double* dot_partial,
-                      int* dot_blocks, const std::function<void()>* side) {
-    MgLevel& lv = L[l];
-    lv.ensure(nb);
+// One level of the cycle: the checks and the bookkeeping every path shares, then the body of the level's path.
+// A launch of few realizations (the drop-in path: one per call) runs the LDS tail on as many compute units as it has
+// realizations, and a tail that starts at a level of several thousand rows with 17-27 entries each is bound by ONE
+// unit's L2 port (LAB_NOTES 9.16: 142 us per cycle - half of a one-realization Eval of the hybridized sampler).  Such
+// a level runs as kernels then and the tail starts one level further down.
+// ... and it ends on the first level that carries a dense inverse: x = A^-1 r by n wavefronts (k::dense_apply) instead of
+// one workgroup cycling through the remaining levels (573 rows at 400 k multipliers: 25 -> 4 us per cycle)
+zvec Multigrid::cycle(const CycleArgs& cx, int l, zvec rz, const LevelStep& step) {
+    L[l].ensure(cx.nb);
     struct ClearR32 {   // whatever path the top level takes, a copy offered for THIS cycle is not seen by the next one
         Multigrid* m; bool top;
         ~ClearR32() { if (top) m->r32_top = nullptr; }
-    } clear_r32{this, l == l0};
-    const LevelPath path = level_path(l, l0, nb);
-    const bool last = path.last;
-    // r in fp32: an inner level whose parent found inner_f32() true - the result goes back in fp32 too (the buffer xa holds it)
-    const bool io32 = rz.f32;
-    if (io32 && !(l > l0 && inner_f32(l, l0, nb) && !target && !ztarget && !dot_partial))
+    } clear_r32{this, l == cx.l0};
+    // r in fp32: an inner level below the fp32 shared path (LevelStep::io32) - the result goes back in fp32 too (the buffer
+    // xa holds it)
+    if (rz.f32 && !(l > cx.l0 && step.f32_capable && !cx.target && !cx.ztarget && !cx.dot_partial))
         throw Error(PMC_ERR_INTERNAL, "V-cycle: fp32 right-hand side on a level that does not take one");
-    const double* r = io32 ? nullptr : rz.as<double>();   // every path but the two fp32 ones below reads this
-    // A launch of few realizations (the drop-in path: one per call) runs the LDS tail on as many compute units as it has
-    // realizations, and a tail that starts at a level of several thousand rows with 17-27 entries each is bound by ONE
-    // unit's L2 port (LAB_NOTES 9.16: 142 us per cycle - half of a one-realization Eval of the hybridized sampler).  Such
-    // a level runs as kernels then and the tail starts one level further down.
-    // ... and it ends on the first level that carries a dense inverse: x = A^-1 r by n wavefronts (k::dense_apply) instead of
-    // one workgroup cycling through the remaining levels (573 rows at 400 k multipliers: 25 -> 4 us per cycle)
-    if (path.dense && !target && !ztarget && !dot_partial) {
-        if (side && *side) (*side)();
-        const zvec x(lv.xa.p, io32);
-        k::dense_apply(st, nb, lv.n, lv.dense_inv.p, rz, x);
-        return x;
+    if (cx.ztarget && cx.target) throw Error(PMC_ERR_INTERNAL, "V-cycle: two result buffers");
+    // beside the bottom of the V: the least parallel kernels of the cycle
+    if (cx.side && *cx.side && step.ends) (*cx.side)();
+    switch (step.path) {
+        case LevelPath::Dense: return cycle_dense(cx, l, rz);
+        case LevelPath::Tail: return cycle_tail(cx, l, rz);
+        case LevelPath::F32Shared:
+        case LevelPath::F32SharedSplit: return cycle_f32_shared(cx, l, rz, step);
+        case LevelPath::F32Bv: return cycle_f32_bv(cx, l, rz, step);
+        case LevelPath::GenericBottom: return cycle_bottom(cx, l, rz);
+        case LevelPath::Generic: return cycle_generic(cx, l, rz, step);
     }
-    const bool tail_here = path.tail_here, f32_shared = path.f32_shared, f32_bv = path.f32_bv;
-    if (ztarget && target) throw Error(PMC_ERR_INTERNAL, "V-cycle: two result buffers");
-    const bool ends_here = tail_here || last;
-    if (side && *side && ends_here) (*side)();   // beside the bottom of the V: the least parallel kernels of the cycle
-    if (tail_here) {
-        if (ztarget) {
-            const int nblk = k::mg_tail_z(st, nb, tail[l].p, tail_lds[l], r, ztarget, dot_partial);
-            if (dot_blocks) *dot_blocks = nblk;
-            return zvec();
-        }
-        double* out = target ? target : lv.xa.p;
-        const int nblk = k::mg_tail(st, nb, tail[l].p, tail_lds[l], rz.as<double>(), out, dot_partial, io32, io32);
-        if (dot_blocks) *dot_blocks = nblk;
-        return zvec(out, io32);
+    throw Error(PMC_ERR_INTERNAL, "V-cycle: unknown level path");
+}
+
+// inner level only (level_step): its result stays in the level's own buffer
+zvec Multigrid::cycle_dense(const CycleArgs& cx, int l, zvec rz) {
+    MgLevel& lv = L[l];
+    const zvec x(lv.xa.p, rz.f32);
+    k::dense_apply(cx.st, cx.nb, lv.n, lv.dense_inv.p, rz, x);
+    return x;
+}
+
+zvec Multigrid::cycle_tail(const CycleArgs& cx, int l, zvec rz) {
+    MgLevel& lv = L[l];
+    const bool io32 = rz.f32;
+    if (cx.ztarget) {
+        const int nblk = k::mg_tail_z(cx.st, cx.nb, tail[l].p, tail_lds[l], io32 ? nullptr : rz.as<double>(), cx.ztarget,
+                                      cx.dot_partial);
+        if (cx.dot_blocks) *cx.dot_blocks = nblk;
+        return zvec();
     }
+    double* out = cx.target ? cx.target : lv.xa.p;
+    const int nblk = k::mg_tail(cx.st, cx.nb, tail[l].p, tail_lds[l], rz.as<double>(), out, cx.dot_partial, io32, io32);
+    if (cx.dot_blocks) *cx.dot_blocks = nblk;
+    return zvec(out, io32);
+}
+
+// Shared-value level with an injection prolongator (over groups of 8: uniform refinement; or over aggregates) and the
+// one-pass degree-2 smoothers: the iterate and the residuals of the level - vectors that live only inside this application
+// of the preconditioner - are kept in fp32 (k::vc_* kernels; the buffers xb / res hold them).  So are the vectors BETWEEN
+// such levels (LevelStep::io32): the coarse right-hand side (buffer r of the next level) and the coarse correction it returns
+// (its buffer xa) - the correction is the only thing `res - (S P) xc` gathers.  The cycle's own input and output and all
+// arithmetic stay fp64.
+zvec Multigrid::cycle_f32_shared(const CycleArgs& cx, int l, zvec rz, const LevelStep& step) {
+    MgLevel& lv = L[l];
+    hipStream_t st = cx.st;
+    const int nb = cx.nb;
+    const bool io32 = rz.f32;
+    const double* r = io32 ? nullptr : rz.as<double>();   // the operand of the fused dot only: top level, fp64
+    double c0, c1;
+    cheb2_coefficients(lv.lmax, smooth_ratio, &c0, &c1);
+    // inner level of a launch of at most dense_nb realizations: the row-split forms of the operators (MgLevel::S_split), a
+    // plain restriction (such a level is neither p_oct nor p_agg, and an inner level has no r32 copy and no fused dot)
+    const bool split = step.path == LevelPath::F32SharedSplit;
+    const SellView A = split ? view_split(lv.S_split, lv.split_log2) : lv.sview();
+    SellView As = A;
+    As.vals = split ? lv.scaled_split.p : lv.vals_scaled.p;
+    const SellView SPv = (split && lv.sp_split_log2 > 0) ? view_split(lv.SP_split, lv.sp_split_log2) : view(lv.SP);
+    float* xf = reinterpret_cast<float*>(lv.xb.p);
+    float* resf = reinterpret_cast<float*>(lv.res.p);
+    const zvec out = cx.ztarget ? cx.ztarget : zvec(cx.target ? cx.target : lv.xa.p, io32);
+    // top level of a cycle inside the MINRES loop of an aggregation hierarchy: the fp32 copy of r, if the caller has one
+    const float* r32 = (l == cx.l0 && !lv.p_oct) ? r32_top : nullptr;
+    if (l == cx.l0) r32_top = nullptr;
+    const zvec rin = r32 ? zconst(r32) : rz;
+    MgLevel& lc = L[l + 1];
+    lc.ensure(nb);
+    const LevelStep child = level_step(l + 1, cx.l0, nb, &step);
+    const zvec rc(lc.r.p, child.io32);
+    k::vc_presmooth32(st, nb, As, lv.dinv.p, rin, xf, c0, c1);
+    if (lv.p_oct) {
+        k::vc_residual_restrict8_32(st, nb, A, rz, xf, resf, rc);
+    } else if (lv.p_agg) {
+        k::vc_residual_restrict_agg32(st, nb, A, rin, xf, resf, rc, lv.seg_ptr.p, lv.seg_cid.p, lv.seg_pos.p);
+    } else {
+        k::vc_residual32(st, nb, A, rin, xf, resf);
+        k::vc_restrict32(st, nb, view(lv.Pt), resf, rc);
+    }
+    const zvec xc = cycle(cx.inner(), l + 1, rc, child);
+    k::vc_residual_coarse32(st, nb, SPv, resf, xc);
+    const bool timed = smooth_timer && smooth_timer->on && l == cx.l0;
+    if (timed) smooth_timer->begin(st);
+    const int nblk = k::vc_postsmooth32_z(st, nb, As, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xc, cx.dot_partial);
+    if (timed) smooth_timer->end(st);
+    if (cx.dot_blocks) *cx.dot_blocks = cx.dot_partial ? nblk : 0;
+    return cx.ztarget ? zvec() : out;
+}
+
+// The same for a per-realization level with fp32 values (Darcy): pre-smoothing into an fp32 iterate, restriction of its
+// residual without storing the fine residual (nothing reads it: there is no S P for per-realization values), the coarse
+// correction added to the fp32 iterate, residual (fp32) and post-smoothing from it.
+zvec Multigrid::cycle_f32_bv(const CycleArgs& cx, int l, zvec rz, const LevelStep& step) {
+    MgLevel& lv = L[l];
+    hipStream_t st = cx.st;
+    const int nb = cx.nb;
+    const double* r = rz.as<double>();
     const SellView A = lv.sview();
-    // Shared-value level with an injection prolongator (over groups of 8: uniform refinement; or over aggregates) and the
-    // one-pass degree-2 smoothers: the iterate and the residuals of the level - vectors that live only inside this application
-    // of the preconditioner - are kept in fp32 (k::vc_* kernels; the buffers xb / res hold them).  So are the vectors BETWEEN
-    // such levels (inner_f32): the coarse right-hand side (buffer r of the next level) and the coarse correction it returns
-    // (its buffer xa) - the correction is the only thing `res - (S P) xc` gathers.  The cycle's own input and output and all
-    // arithmetic stay fp64.
-    if (f32_shared) {
-        double c0, c1;
-        cheb2_coefficients(lv.lmax, smooth_ratio, &c0, &c1);
-        SellView As = A;
-        As.vals = lv.vals_scaled.p;
-        float* xf = reinterpret_cast<float*>(lv.xb.p);
-        float* resf = reinterpret_cast<float*>(lv.res.p);
-        const zvec out = ztarget ? ztarget : zvec(target ? target : lv.xa.p, io32);
-        // top level of a cycle inside the MINRES loop of an aggregation hierarchy: the fp32 copy of r, if the caller has one
-        const float* r32 = (l == l0 && !lv.p_oct) ? r32_top : nullptr;
-        if (l == l0) r32_top = nullptr;
-        const zvec rin = r32 ? zconst(r32) : rz;
-        MgLevel& lc = L[l + 1];
-        lc.ensure(nb);
-        const zvec rc(lc.r.p, inner_f32(l + 1, l0, nb));
-        // inner level of a launch of at most 8 realizations: the row-split forms of the four kernels (MgLevel::S_split)
-        if (l > l0 && nb <= dense_nb && lv.split_log2 > 0 && !lv.p_oct && !lv.p_agg && !dot_partial) {
-            const SellView Asp = view_split(lv.S_split, lv.split_log2);
-            SellView Assp = Asp;
-            Assp.vals = lv.scaled_split.p;
-            const SellView SPv = lv.sp_split_log2 > 0 ? view_split(lv.SP_split, lv.sp_split_log2) : view(lv.SP);
-            k::vc_presmooth32(st, nb, Assp, lv.dinv.p, rz, xf, c0, c1);
-            k::vc_residual32(st, nb, Asp, rz, xf, resf);
-            k::vc_restrict32(st, nb, view(lv.Pt), resf, rc);
-            const zvec xcs = cycle(st, nb, l + 1, l0, rc, nullptr, zvec(), nullptr, nullptr, side);
-            k::vc_residual_coarse32(st, nb, SPv, resf, xcs);
-            k::vc_postsmooth32_z(st, nb, Assp, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xcs, nullptr);
-            if (dot_blocks) *dot_blocks = 0;
-            return ztarget ? zvec() : out;
-        }
-        k::vc_presmooth32(st, nb, As, lv.dinv.p, rin, xf, c0, c1);
-        if (lv.p_oct) {
-            k::vc_residual_restrict8_32(st, nb, A, rz, xf, resf, rc);
-        } else if (lv.p_agg) {
-            k::vc_residual_restrict_agg32(st, nb, A, rin, xf, resf, rc, lv.seg_ptr.p, lv.seg_cid.p, lv.seg_pos.p);
-        } else {
-            k::vc_residual32(st, nb, A, rin, xf, resf);
-            k::vc_restrict32(st, nb, view(lv.Pt), resf, rc);
-        }
-        const zvec xc = cycle(st, nb, l + 1, l0, rc, nullptr, zvec(), nullptr, nullptr, side);
-        k::vc_residual_coarse32(st, nb, view(lv.SP), resf, xc);
-        const bool timed = smooth_timer && smooth_timer->on && l == l0;
-        if (timed) smooth_timer->begin(st);
-        // (r is the operand of the fused dot only: top level, fp64)
-        const int nblk = k::vc_postsmooth32_z(st, nb, As, lv.dinv.p, resf, xf, out, c0, c1, r, lv.parent.p, xc, dot_partial);
-        if (timed) smooth_timer->end(st);
-        if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? zvec() : out;
+    double c0, c1;
+    cheb2_coefficients(lv.lmax, smooth_ratio, &c0, &c1);
+    SellView As = A;
+    As.vals = lv.scaled_ptr();
+    float* xf = reinterpret_cast<float*>(lv.xb.p);
+    float* df = reinterpret_cast<float*>(lv.d.p);
+    double* out = cx.target ? cx.target : lv.xa.p;
+    k::vc_presmooth32_bv(st, nb, As, lv.dinv.p, r, xf, c0, c1);
+    MgLevel& lc = L[l + 1];
+    lc.ensure(nb);
+    k::vc_restrict8_32_bv(st, nb, A, r, xf, lc.r.p);
+    double* xc = cycle(cx.inner(), l + 1, zvec(lc.r.p, false), level_step(l + 1, cx.l0, nb, &step)).as<double>();
+    k::vc_prolong8_32(st, nb, lv.n, xf, xc);
+    k::vc_residual32_bv(st, nb, A, r, xf, df);
+    const int nblk = cx.ztarget ? k::vc_postsmooth32_bv_z(st, nb, As, lv.dinv.p, df, xf, cx.ztarget, c0, c1, r, cx.dot_partial)
+                                : k::vc_postsmooth32_bv(st, nb, As, lv.dinv.p, df, xf, out, c0, c1, r, cx.dot_partial);
+    if (cx.dot_blocks) *cx.dot_blocks = cx.dot_partial ? nblk : 0;
+    return cx.ztarget ? zvec() : zvec(out, false);
+}
+
+// the two buffers a fp64 polynomial ping-pongs between, chosen so that after `flips` flips the result is in `target` (if any)
+static void pick_buffers(MgLevel& lv, double* target, int flips, double** start, double** other) {
+    *start = lv.xa.p;
+    *other = lv.xb.p;
+    if (target) {
+        if (flips % 2 == 0) *start = target; else *other = target;
     }
-    // The same for a per-realization level with fp32 values (Darcy): pre-smoothing into an fp32 iterate, restriction of its
-    // residual without storing the fine residual (nothing reads it: there is no S P for per-realization values), the coarse
-    // correction added to the fp32 iterate, residual (fp32) and post-smoothing from it.
-    if (f32_bv) {
-        double c0, c1;
-        cheb2_coefficients(lv.lmax, smooth_ratio, &c0, &c1);
-        SellView As = A;
-        As.vals = lv.scaled_ptr();
-        float* xf = reinterpret_cast<float*>(lv.xb.p);
-        float* df = reinterpret_cast<float*>(lv.d.p);
-        double* out = target ? target : lv.xa.p;
-        k::vc_presmooth32_bv(st, nb, As, lv.dinv.p, r, xf, c0, c1);
-        MgLevel& lc = L[l + 1];
-        lc.ensure(nb);
-        k::vc_restrict8_32_bv(st, nb, A, r, xf, lc.r.p);
-        double* xc = cycle(st, nb, l + 1, l0, zvec(lc.r.p, false), nullptr, zvec(), nullptr, nullptr, side).as<double>();
-        k::vc_prolong8_32(st, nb, lv.n, xf, xc);
-        k::vc_residual32_bv(st, nb, A, r, xf, df);
-        const int nblk = ztarget ? k::vc_postsmooth32_bv_z(st, nb, As, lv.dinv.p, df, xf, ztarget, c0, c1, r, dot_partial)
-                                 : k::vc_postsmooth32_bv(st, nb, As, lv.dinv.p, df, xf, out, c0, c1, r, dot_partial);
-        if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? zvec() : zvec(out, false);
-    }
+}
+
+zvec Multigrid::cycle_bottom(const CycleArgs& cx, int l, zvec rz) {
+    MgLevel& lv = L[l];
     const int last_deg = lv.is_last ? lv.last_degree : coarse_degree;
     const double last_rat = lv.is_last ? lv.last_ratio : coarse_ratio;
-    const double* sv = lv.scaled_ptr();   // shared (sampler) or per-realization (Darcy: fp32 storage) column-scaled values
-    const ChebParams cp_last{last_deg, lv.lmax, last_rat, sv};
-    const ChebParams cp_smooth{smooth_degree, lv.lmax, smooth_ratio, sv};
-    const int flips = last ? cheb_flips(cp_last, true) : cheb_flips(cp_smooth, true) + cheb_flips(cp_smooth, false);
-    double* start = lv.xa.p;
-    double* other = lv.xb.p;
-    if (target) {
-        if (flips % 2 == 0) start = target; else other = target;
-    }
-    if (last) {
-        const ChebParams& cp = cp_last;
-        return zvec(cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, start, other, lv.d.p, true, dot_partial, dot_blocks, ztarget), false);
-    }
-    const ChebParams& cp = cp_smooth;
+    // shared (sampler) or per-realization (Darcy: fp32 storage) column-scaled values
+    const ChebParams cp{last_deg, lv.lmax, last_rat, lv.scaled_ptr()};
+    double *start, *other;
+    pick_buffers(lv, cx.target, cheb_flips(cp, true), &start, &other);
+    return zvec(cheb_apply(cx.st, cx.nb, lv.sview(), lv.dinv.p, lv.bv, cp, rz.as<double>(), start, other, lv.d.p, true,
+                           cx.dot_partial, cx.dot_blocks, cx.ztarget), false);
+}
+
+zvec Multigrid::cycle_generic(const CycleArgs& cx, int l, zvec rz, const LevelStep& step) {
+    MgLevel& lv = L[l];
+    hipStream_t st = cx.st;
+    const int nb = cx.nb;
+    const double* r = rz.as<double>();
+    const SellView A = lv.sview();
+    const ChebParams cp{smooth_degree, lv.lmax, smooth_ratio, lv.scaled_ptr()};
+    double *start, *other;
+    pick_buffers(lv, cx.target, cheb_flips(cp, true) + cheb_flips(cp, false), &start, &other);
     double* x = cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, start, other, lv.d.p, true);
     double* oth = (x == start) ? other : start;
     MgLevel& lc = L[l + 1];
@@ -365,48 +384,33 @@ zvec Multigrid::cycle(hipStream_t st, int nb, int l, int l0, zvec rz, double* ta
         k::residual(st, nb, A, r, x, lv.res.p);
         k::spmm(st, nb, view(lv.Pt), lv.res.p, lc.r.p, false, nullptr, nullptr);
     }
-    double* xc = cycle(st, nb, l + 1, l0, zvec(lc.r.p, false), nullptr, zvec(), nullptr, nullptr, side).as<double>();
+    double* xc = cycle(cx.inner(), l + 1, zvec(lc.r.p, false), level_step(l + 1, cx.l0, nb, &step)).as<double>();
     if (lv.has_sp && !lv.bv && cheb_fused(cp, false)) {
         // r - S (x + P xc) = res - (S P) xc, in place; then x <- x + P xc + p2(that residual) in one pass
         k::residual(st, nb, view(lv.SP), lv.res.p, xc, lv.res.p);
         const int nblk = cheb_post_from_residual(st, nb, A, lv.dinv.p, lv.bv, cp, r, lv.res.p, x, lv.parent.p, xc,
-                                                 dot_partial, ztarget);
-        if (dot_blocks) *dot_blocks = dot_partial ? nblk : 0;
-        return ztarget ? zvec() : zvec(x, false);
+                                                 cx.dot_partial, cx.ztarget);
+        if (cx.dot_blocks) *cx.dot_blocks = cx.dot_partial ? nblk : 0;
+        return cx.ztarget ? zvec() : zvec(x, false);
     }
     k::spmm(st, nb, view(lv.P), xc, x, true, nullptr, nullptr);
-    return zvec(cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, x, oth, lv.d.p, false, dot_partial, dot_blocks, ztarget), false);
+    return zvec(cheb_apply(st, nb, A, lv.dinv.p, lv.bv, cp, r, x, oth, lv.d.p, false, cx.dot_partial, cx.dot_blocks, cx.ztarget),
+                false);
 }
 
 int Multigrid::cycle_role(int l0, int nb, int l, bool* in_tail) const {
-    bool tail_on = false;
-    for (int q = l0; q < (int)L.size(); ++q) {
-        const MgLevel& lv = L[(size_t)q];
-        const bool last = q == (int)L.size() - 1 || lv.is_last;
-        int role = -1;
-        if (!tail_on) {
-            if (q > l0 && nb <= dense_nb && lv.dense_inv.p) {
-                role = 2;
-            } else {
-                const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && !last && q + 1 < (int)tail.size() && tail[q + 1].p;
-                tail_on = use_tail && q < (int)tail.size() && tail[q].p && !tail_later;
-            }
-        }
-        if (role < 0) role = !last ? 0 : (tail_on && lv.ainv.p) ? 2 : 1;
-        if (q == l) {
-            if (in_tail) *in_tail = tail_on;
-            return role;
-        }
-        if (role != 0) break;
-    }
-    if (in_tail) *in_tail = false;
-    return 3;
+    std::vector<LevelFacts> lev(L.size());
+    for (int q = 0; q < (int)L.size(); ++q) lev[(size_t)q] = level_facts(q);
+    const LevelRole role = pmc::cycle_role(lev.data(), cycle_facts(), l0, nb, l);
+    if (in_tail) *in_tail = role.in_tail;
+    return role.role;
 }
 
 int Multigrid::vcycle(hipStream_t st, int nb, int l0, const double* r, double* xout, double* dot_partial,
                       const std::function<void()>& side) {
     int nblk = 0;
-    const zvec res = cycle(st, nb, l0, l0, zconst(r), xout, zvec(), dot_partial, &nblk, side ? &side : nullptr);
+    const CycleArgs cx{st, nb, l0, xout, zvec(), dot_partial, &nblk, side ? &side : nullptr};
+    const zvec res = cycle(cx, l0, zconst(r), level_step(l0, l0, nb));
     if (res.p != xout || res.f32) throw Error(PMC_ERR_INTERNAL, "V-cycle result landed in the wrong buffer");
     return nblk;
 }
@@ -414,7 +418,8 @@ int Multigrid::vcycle(hipStream_t st, int nb, int l0, const double* r, double* x
 int Multigrid::vcycle_z(hipStream_t st, int nb, int l0, const double* r, zvec zout, double* dot_partial,
                         const std::function<void()>& side) {
     int nblk = 0;
-    cycle(st, nb, l0, l0, zconst(r), nullptr, zout, dot_partial, &nblk, side ? &side : nullptr);
+    const CycleArgs cx{st, nb, l0, nullptr, zout, dot_partial, &nblk, side ? &side : nullptr};
+    cycle(cx, l0, zconst(r), level_step(l0, l0, nb));
     return nblk;
 }
 

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "vcycle_plan.hpp"
 
 namespace pmc {
 
@@ -110,6 +111,15 @@ struct MgLevel {
     SellView sview() const { return bv ? (f32 ? view_bv32(S, vals32.p) : view_bv(S, vals_bv.p)) : view(S); }
     // column-scaled values in the storage sview() uses
     const double* scaled_ptr() const { return (bv && f32) ? reinterpret_cast<const double*>(scaled32.p) : vals_scaled.p; }
+    // what the V-cycle's decision (vcycle_plan.hpp) reads from this level; the tail descriptors belong to the Multigrid
+    LevelFacts facts(bool tail_here, bool tail_next) const {
+        LevelFacts f;
+        f.n = n; f.is_last = is_last; f.bv = bv; f.f32 = f32; f.has_sp = has_sp; f.p_oct = p_oct; f.p_agg = p_agg;
+        f.has_scaled = vals_scaled.p != nullptr; f.has_scaled32 = scaled32.p != nullptr;
+        f.has_dense_inv = dense_inv.p != nullptr; f.has_ainv = ainv.p != nullptr;
+        f.split_log2 = split_log2; f.tail_here = tail_here; f.tail_next = tail_next;
+        return f;
+    }
 };
 
 struct OpTimer;
@@ -123,7 +133,6 @@ struct Multigrid {
     // then finishes in a single kernel from level l on.  Call build_tails() once all levels are set up.
     std::vector<DevBuf<TailParams>> tail;
     std::vector<size_t> tail_lds;
-    bool use_tail = true;
     // pmc_solver_opts.precond_storage: the intermediates of a level (iterate, residuals) of the structured hierarchies live
     // in fp32 (k::vc_* kernels) or - false - in fp64 like everything else
     bool f32_intermediates = true;
@@ -141,14 +150,10 @@ struct Multigrid {
     // MINRES loop provides it for free-standing cost of one more fp32 stream in the Lanczos update (MinresWork::r32).
     const float* r32_top = nullptr;
     // would a cycle from level l0 at width nb read such a copy?  (the fp32-intermediate path of a shared-value level whose
-    // restriction is not the 8-children tree, not inside the LDS tail)
+    // restriction is not the 8-children tree: the condition under which cycle() consumes r32_top)
     bool top_reads_r32(int l0, int nb) const {
-        if (l0 < 0 || l0 + 1 >= (int)L.size()) return false;
-        const MgLevel& lv = L[(size_t)l0];
-        const bool tail_later = nb <= tail_later_nb && lv.n > 4096 && l0 + 1 < (int)tail.size() && tail[(size_t)l0 + 1].p;
-        const bool tail_here = use_tail && l0 < (int)tail.size() && tail[(size_t)l0].p && !tail_later;
-        return !tail_here && !lv.is_last && !lv.bv && lv.has_sp && !lv.p_oct && f32_any_injection && smooth_degree == 2 &&
-               lv.vals_scaled.p && f32_intermediates;
+        if (l0 < 0 || l0 >= (int)L.size()) return false;
+        return level_path(l0, l0, nb) == LevelPath::F32Shared && !L[(size_t)l0].p_oct;
     }
     // in-situ timing (HIP events) of the top level's post-smoothing kernel - the largest single kernel of a cycle on an
     // aggregation hierarchy; set per solve by the owner, null = off
@@ -181,23 +186,58 @@ struct Multigrid {
     int vcycle_z(hipStream_t st, int nb, int l0, const double* r, zvec zout, double* dot_partial = nullptr,
                  const std::function<void()>& side = nullptr);
 
-    // what cycle() does on level l of a cycle from level l0 at width nb: ends with the dense inverse (narrow launches), runs the
-    // LDS tail from here on, or one of the fp32-intermediate branches (none of them: the generic fp64 path)
-    struct LevelPath {
-        bool last = false, dense = false, tail_here = false, f32_shared = false, f32_bv = false;
-    };
-    LevelPath level_path(int l, int l0, int nb) const;
+    // the settings and the level facts the decision of vcycle_plan.hpp reads
+    CycleFacts cycle_facts() const;
+    LevelFacts level_facts(int l) const {
+        auto has_tail = [&](int q) { return q < (int)tail.size() && tail[(size_t)q].p != nullptr; };
+        return L[(size_t)l].facts(has_tail(l), has_tail(l + 1));
+    }
+    // what cycle() does on level l of a cycle from level l0 at width nb (level_step of vcycle_plan.hpp on this hierarchy;
+    // parent: the step of level l - 1, null for l == l0 or when only the level's own path is asked for)
+    LevelStep level_step(int l, int l0, int nb, const LevelStep* parent = nullptr) const {
+        return pmc::level_step(level_facts(l), cycle_facts(), l, l0, nb, parent);
+    }
+    LevelPath level_path(int l, int l0, int nb) const { return level_step(l, l0, nb).path; }
     // does level l > l0 take its right-hand side and return its correction in fp32?  The vectors between two levels of the
     // fp32-intermediate path of a shared-value hierarchy live only inside one application of the preconditioner, like the
-    // levels' iterates and residuals: such a level (f32_shared branch, LDS tail, dense inverse) reads MgLevel::r and writes
-    // MgLevel::xa as fp32.  False with PMC_STORAGE_FP64, for per-realization (Darcy) levels and for levels on the generic path.
-    bool inner_f32(int l, int l0, int nb) const;
+    // levels' iterates and residuals: such a level (fp32 shared path, LDS tail, dense inverse) reads MgLevel::r and writes
+    // MgLevel::xa as fp32 when the level above it is on the fp32 shared path.  False with PMC_STORAGE_FP64, for per-realization
+    // (Darcy) levels and for levels on the generic path.
+    bool inner_f32(int l, int l0, int nb) const {
+        return l > l0 && l < (int)L.size() && level_step(l, l0, nb).f32_capable;
+    }
 
   private:
-    // rz: the level's right-hand side; fp32 only where inner_f32() says so, and then the result is fp32 too.
+    // what every body of cycle() forwards unchanged: the stream, the launch, where the TOP level's result goes (target: fp64,
+    // ztarget: zvec storage, neither: the level's own buffer; the levels below always use their own) and the side callback
+    struct CycleArgs {
+        hipStream_t st;
+        int nb, l0;
+        double* target;
+        zvec ztarget;
+        double* dot_partial;
+        int* dot_blocks;
+        const std::function<void()>* side;
+        CycleArgs inner() const { return CycleArgs{st, nb, l0, nullptr, zvec(), nullptr, nullptr, side}; }
+    };
+    // rz: the level's right-hand side; fp32 only where step.io32 says so, and then the result is fp32 too.
     // ztarget non-null (top level of vcycle_z only): the result goes there and the return value is null
-    zvec cycle(hipStream_t st, int nb, int l, int l0, zvec rz, double* target, zvec ztarget, double* dot_partial,
-               int* dot_blocks, const std::function<void()>* side);
+    zvec cycle(const CycleArgs& cx, int l, zvec rz, const LevelStep& step);
+    // the bodies of cycle(), one per LevelPath (F32Shared and F32SharedSplit share one)
+    zvec cycle_dense(const CycleArgs& cx, int l, zvec rz);
+    zvec cycle_tail(const CycleArgs& cx, int l, zvec rz);
+    zvec cycle_f32_shared(const CycleArgs& cx, int l, zvec rz, const LevelStep& step);
+    zvec cycle_f32_bv(const CycleArgs& cx, int l, zvec rz, const LevelStep& step);
+    zvec cycle_bottom(const CycleArgs& cx, int l, zvec rz);
+    zvec cycle_generic(const CycleArgs& cx, int l, zvec rz, const LevelStep& step);
+};
+
+// The hierarchy the solves of one Monte Carlo level of a handle cycle on, and the level of it they start from: an internal
+// hierarchy of that level alone (own: from its level 0) or the caller's, which all Monte Carlo levels share (from `level`)
+struct CycleHierarchy {
+    const Multigrid& g;
+    int first;
+    bool own;
 };
 
 // Abstract pieces MINRES needs.
