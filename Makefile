@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
+SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -126,3 +126,10 @@ $(ABIBIN)/vcycle_plan_check: tests/c/vcycle_plan_check.cpp $(CSRC)/vcycle_plan.h
 	g++ -std=c++17 -O2 -Wall -Wextra -Werror -I$(CSRC) -o $@ tests/c/vcycle_plan_check.cpp
 test-vcycle-plan: $(ABIBIN)/vcycle_plan_check
 .PHONY: test-vcycle-plan
+
+# the adjoint of Eval from C (tests/test_gpu_sampler_adjoint.py builds and runs it)
+$(ABIBIN)/sampler_adjoint_smoke: tests/c/sampler_adjoint_smoke.c tests/c/prob_io.h include/pmc.h | $(LIB)
+	@mkdir -p $(ABIBIN)
+	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/sampler_adjoint_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-sampler-adjoint: $(ABIBIN)/sampler_adjoint_smoke
+.PHONY: test-sampler-adjoint

@@ -352,6 +352,33 @@ int pmc_sampler_sample(pmc_sampler* s, int level, uint64_t first_sample_id, int 
 int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const double* xi, double* s_out,
                      const double* init_s, int init_level, int use_init, double* embed_s_out, int memspace,
                      pmc_stats* stats);
+/* The adjoint (transpose of the derivative) of Eval in the white noise (an extension of this project):
+ * for J a function of Eval's output s_out and v = dJ/ds_out,
+ *     grad_xi = (d s_out / d xi)^T v = dJ/dxi,
+ * per realization, sample-major like Eval and cut into the same launch widths.  SPDE handles (saddle-point and hybridized,
+ * every output map of pmc_sampler_set_projection): the level's own solve from a zero guess with O^T (v o f') in the s-rows
+ * of the right-hand side, prolongated from `level` to xi_level and scaled by -g w_sqrt[xi_level]; stats (may be NULL)
+ * reports that solve.  KL handles: grad_xi[:nmodes] = (Phi_level Lambda^1/2)^T (v o f'), the other xi_size(xi_level) - nmodes
+ * entries 0; calls of more than 4 realizations run the fp64 MFMA kernel, narrower ones a VALU kernel (a column's bits may
+ * differ between the two); within either, a column's bits do not depend on nbatch or on how a call was split.
+ *   v       : in, nbatch x sample_size(level)
+ *   s_out   : in, NULL or Eval's output for the same xi: v is multiplied by it (f' of the exp() of a lognormal handle).
+ *             NULL for callers that hold dJ/dlog s_out already (wrt_log of the Darcy gradients) and on Gaussian handles
+ *   grad_xi : out, nbatch x xi_size(xi_level)
+ * PMC_ERR_INVALID: level outside [0, number of Monte Carlo levels), xi_level outside [0, level], nbatch < 1, NULL v or
+ * grad_xi, s_out != NULL on a handle that is not lognormal, a handle with a conditioner attached.  Conditioned fields are
+ * out of scope here: their adjoint adds (I - K A^-1 H)^T in front of f', and K is n x nobs column-major like Phi, so the KL
+ * adjoint kernel can serve it in a later change. */
+int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
+                             double* grad_xi, int memspace, pmc_stats* stats);
+/* 1 if Eval applies exp() (the lognormal flag of the create call), 0 if not */
+int pmc_sampler_is_lognormal(const pmc_sampler* s);
+/* The prior's part of a log-posterior gradient in the white noise xi ~ N(0, I), on the handle's stream:
+ *     grad -= xi (in place; xi, grad: nbatch x n in `memspace`),     logprior[b] = -|xi_b|^2 / 2 (host array, may be NULL).
+ * The sum has a fixed order: a realization's value does not depend on how its call was split.  PMC_ERR_INVALID: n < 1,
+ * nbatch < 1, NULL xi or grad. */
+int pmc_sampler_logprior_gradient(pmc_sampler* s, int n, int nbatch, const double* xi, double* grad, double* logprior,
+                                  int memspace);
 
 /* ---- Field statistics and errors of the sampler drivers (examples/PDESamplerTest.cpp:205-274) ---------------------- */
 /* Accumulators of ONE level's Eval output s (pmc_sampler_sample_size(level) entries per realization) on the device:

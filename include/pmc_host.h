@@ -135,6 +135,15 @@ int pmc_bayes_likelihood(pmc_darcy* solver, int level, int nbatch, const double*
  * pmc_darcy_loglik_gradient.  loglik: host array of nbatch or NULL; grad: nbatch x n_p(level) in `memspace`, as k. */
 int pmc_bayes_loglik_gradient(pmc_darcy* solver, int level, int nbatch, const double* k, int memspace, const double* G_obs,
                               int nobs, double noise, int wrt_log, double* loglik, double* grad);
+/* BayesianInverseProblem::ComputeGradLogPosterior (an extension): for nbatch realizations of the
+ * white noise xi (nbatch x xi_size(xi_level), xi_level <= level),
+ *     logpost = loglik(k) - |xi|^2 / 2,  k = Eval(level, xi),      grad = dlogpost/dxi = -xi + (dk/dxi)^T dloglik/dk,
+ * through pmc_sampler_eval, pmc_darcy_loglik_gradient (with respect to log k on a lognormal sampler) and
+ * pmc_sampler_eval_adjoint.  logpost: host array of nbatch or NULL; grad: nbatch x xi_size(xi_level) in `memspace`, as xi.
+ * With device memory only the scalars cross to the host.  ctx: the context both handles were created on. */
+int pmc_bayes_logpost_gradient(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                               const double* xi, int memspace, const double* G_obs, int nobs, double noise, double* logpost,
+                               double* grad);
 
 /* ---- ML_BayesRatio_Manager / SL_BayesRatio_Manager (src/ML_BayesRatio_Manager.hpp:315-728, src/SL_BayesRatio_Manager.hpp)
  * Multilevel ratio estimator E[Q * likelihood] / E[likelihood]: per realization two INDEPENDENT prior draws, one for

@@ -159,6 +159,9 @@ SYMBOLS = {
     "pmc_sampler_eval": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.c_int, _DP, C.c_int,
                                    C.POINTER(pmc_stats)]),
     "pmc_sampler_mult": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_sampler_eval_adjoint": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_sampler_is_lognormal": (C.c_int, [_VP]),
+    "pmc_sampler_logprior_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.POINTER(C.c_double), C.c_int]),
     "pmc_sampler_apply_preconditioner": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int]),
     "pmc_sampler_apply_operator": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.c_int, C.POINTER(C.c_double),
                                              C.POINTER(C.c_double)]),
@@ -643,6 +646,40 @@ class PDESampler:
         if return_stats:
             out.append([(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in stats])
         return out[0] if len(out) == 1 else tuple(out)
+
+    def EvalAdjoint(self, level, v, s_out=None, xi_level=None, grad_out=None, nbatch=None, return_stats=False):
+        """dJ/dxi = (d Eval / d xi)^T v (pmc_sampler_eval_adjoint).  v: (nbatch, SampleSize(level)) numpy (host) or a device
+        array (then with nbatch=... and grad_out=...); s_out: None, or Eval's output on a lognormal handle (v is multiplied
+        by it).  Returns grad_xi (nbatch, xi_size(xi_level)); xi_level defaults to level."""
+        if not (0 <= level < self.nlevels):
+            raise PmcError(-1, f"EvalAdjoint: level {level} out of range")
+        if xi_level is None:
+            xi_level = level
+        single = False
+        if isinstance(v, np.ndarray):
+            single = v.ndim == 1
+            v = _f64(np.atleast_2d(v))
+            nbatch = v.shape[0]
+            if v.shape[1] != self.SampleSize(level):
+                raise PmcError(-1, "EvalAdjoint: v does not match SampleSize(level)")
+            if s_out is not None:
+                s_out = _f64(np.atleast_2d(s_out))
+                if s_out.shape != v.shape:
+                    raise PmcError(-1, "EvalAdjoint: s_out does not match v")
+            if grad_out is None and 0 <= xi_level < self.nlevels:
+                grad_out = np.empty((nbatch, self.xi_size(xi_level)))
+        elif nbatch is None:
+            nbatch = v.n // self.SampleSize(level)
+        stats = (pmc_stats * max(1, nbatch))()
+        pv, ms = _addr(v)
+        ps, _ = _addr(s_out)
+        pg, _ = _addr(grad_out)
+        _check(self.ctx.lib.pmc_sampler_eval_adjoint(self.h, level, xi_level, nbatch, pv, ps, pg, ms, stats))
+        self.last_phase_ms = (sum(s.setup_ms for s in stats), sum(s.solve_ms for s in stats))
+        g = grad_out[0] if single else grad_out
+        if return_stats:
+            return g, [(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in stats]
+        return g
 
     def set_operator_timing(self, on: bool):
         """Bracket every K5 launch of the MINRES loop with HIP events (in-situ kernel time for the roofline)."""

@@ -437,6 +437,23 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
     });
 }
 
+int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
+                             double* grad_xi, int memspace, pmc_stats* stats) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.eval_adjoint(level, xi_level, nbatch, v, s_out, grad_xi, memspace, stats);
+    });
+}
+
+int pmc_sampler_is_lognormal(const pmc_sampler* s) { return s ? (s->impl.lognormal ? 1 : 0) : PMC_ERR_INVALID; }
+int pmc_sampler_logprior_gradient(pmc_sampler* s, int n, int nbatch, const double* xi, double* grad, double* logprior,
+                                  int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.prior_gradient(n, nbatch, xi, grad, logprior, memspace);
+    });
+}
+
 int pmc_conditioner_create(pmc_sampler* s, int nobs, const pmc_csr* H0, const double* y, const double* sigma2,
                            pmc_conditioner** out) {
     return guarded([&] {

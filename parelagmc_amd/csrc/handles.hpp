@@ -38,6 +38,13 @@ struct SamplerLevel {
     // row i is the caller's row lam_new2old[i]; empty = the caller's numbering
     DevBuf<int> lam_new2old, lam_old2new;
     std::vector<int> lam_n2o_host;   // lam_new2old on the host (setup export of the V-cycle's finest prolongator)
+    // Adjoint of Eval (sampler_adjoint.hip), built at the first pmc_sampler_eval_adjoint of the level
+    // from gather / Gt / inv_w / zw_sqrt / w_sqrt read back from the device: adj_Ot = (output map)^T as a SELL matrix (n_s x
+    // out_size: the gather's 0/1 matrix or Gt^T diag(inv_w); on a hybridized handle its rows times z) and, on a hybridized
+    // handle, z alone (the solve's right-hand side is Gz (z q); setup keeps z only folded into zw_sqrt and Ptz)
+    bool has_adj = false;
+    Sell adj_Ot;
+    DevBuf<double> adj_z;
 };
 
 // evaluations (launches of one batch) of this process whose back-substitution wrote the field sample-major itself
@@ -83,6 +90,8 @@ struct Sampler {
     MinresWork work;
     DevBuf<double> rhs, sol, tA, tB, cx, cd, cx2, stage_in, stage_out, stage_emb, mini_scratch;
     DevBuf<pmc_stats> mini_stats;
+    DevBuf<double> adj_part;                       // KL handles: partials of the adjoint's split reduction (kl_adjoint.hip)
+    DevBuf<double> adj_lp;                         // prior_gradient: -|xi_b|^2 / 2 per realization
 
     Sampler(Ctx& c, int nlevels, int n_mc, const pmc_sampler_level* in, double alpha, double g, bool lognormal,
             const pmc_solver_opts& o);
@@ -101,6 +110,13 @@ struct Sampler {
     void sample(int level, uint64_t first_id, int nbatch, double* xi, int memspace);
     void eval(int level, int xi_level, int nbatch, const double* xi, double* s_out, const double* init_s, int init_level,
               bool use_init, double* emb_out, int memspace, pmc_stats* stats);
+    // dJ/dxi = (d Eval / d xi)^T v (pmc_sampler_eval_adjoint): v, s_out nbatch x sample_size(level), grad_xi nbatch x
+    // xi_size(xi_level), sample-major; s_out (lognormal handles, may be NULL) multiplies v
+    void eval_adjoint(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* grad_xi, int memspace,
+                      pmc_stats* stats);
+    // the white-noise prior's part of a log-posterior gradient (pmc_sampler_logprior_gradient): grad -= xi in place (nbatch x
+    // n, `memspace`), logprior[b] = -|xi_b|^2 / 2 (host, may be NULL)
+    void prior_gradient(int n, int nbatch, const double* xi, double* grad, double* logprior, int memspace);
     void apply_operator(int level, int nb, const double* x, double* y, int memspace, int repeat, double* avg_ms,
                         double* bytes);
     // invA[level]->Mult(rhs, sol) on full vectors of n_u + n_s entries per realization (sample-major)
@@ -119,13 +135,21 @@ struct Sampler {
     CycleHierarchy cycle_hierarchy(int level) const;
     void ensure(int level, int nb);
     // rhs (hybridized solver): the kernel that would write the multiplier right-hand side, handed to the solve (RhsFn)
-    void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs = nullptr);
+    // key_salt != 0: a solver configuration (graph key) apart from Eval's with the same level / width / rows
+    void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs = nullptr,
+                      uint64_t key_salt = 0);
     PrecFn preconditioner(int level, int nb, int degM, Multigrid* mgp, int mg_l0);
     void eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                     int init_level, bool use_init, double* emb_d, pmc_stats* stats);
     // Eval of a KL handle: every realization in one launch
     void eval_kl(int level, int xi_level, int nbatch, const double* xi, double* s_out, double* emb_out, int memspace,
                  pmc_stats* stats);
+    // sampler_adjoint.hip / kl_adjoint.hip
+    void ensure_adjoint(int level);
+    void eval_adjoint_chunk(int level, int xi_level, int nb, const double* v_d, const double* s_d, double* grad_d,
+                            pmc_stats* stats);
+    void eval_adjoint_kl(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* grad_xi,
+                         int memspace, pmc_stats* stats);
 };
 
 // Conditioning on linear observations of the Gaussian field (condition.hip, pmc_conditioner_*): per
@@ -217,6 +241,13 @@ void kl_matern_eigs(pmc_ctx* c, int dim, int n, const double* centroids, const d
 // b < nb, i < n, k < m, in fp64 (MFMA for nb > 4, a bandwidth GEMV below); phi column-major n x m.
 void kl_eval(hipStream_t st, int n, int m, int nb, const double* phi, const double* xi, int n_xi, double* s, double* emb,
              bool lognormal);
+// kl_adjoint.hip: grad[b n_xi + k] = sum_i phi[k n + i] v[b n + i] (sv ? sv[b n + i] : 1) for k < m, 0 for m <= k < n_xi, in
+// fp64 (MFMA for nb > 4, a bandwidth kernel below); part: kl_adjoint_partials(n, m, nb) doubles of scratch.  The reduction
+// over i is split into chunks that depend on n alone and summed in a fixed order: column b has the same bits for every
+// nb > 4 and every split of a call into pieces wider than 4 (narrower calls take the VALU kernel, whose bits may differ).
+size_t kl_adjoint_partials(int n, int m, int nb);
+void kl_eval_adjoint(hipStream_t st, int n, int m, int nb, const double* phi, const double* v, const double* sv, int n_xi,
+                     double* grad, double* part);
 
 struct DarcyLevel {
     int n_u = 0, n_p = 0, n_coef = 0;

@@ -111,6 +111,26 @@ __global__ __launch_bounds__(kBlock) void interleave_kernel(int n, const double*
     store_row<NB>(out + (size_t)i * LD + c0, v);
 }
 
+// out[i*NB + k] = scale * v[k*n + i] * (s ? s[k*n + i] : 1) * (rowscale ? rowscale[i] : 1): the seed of Eval's adjoint
+// (Sampler::eval_adjoint_chunk), dJ/ds_out through the exp() of a lognormal handle, sample-major in and interleaved out
+template <int NB>
+__global__ __launch_bounds__(kBlock) void seed_interleave_kernel(int n, const double* __restrict__ v,
+                                                                 const double* __restrict__ s,
+                                                                 const double* __restrict__ rowscale, double scale,
+                                                                 double* __restrict__ out, int ld) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int LD = row_ld<NB>(ld), c0 = col0<NB>();
+    const double f = rowscale ? scale * rowscale[i] : scale;
+    double t[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const size_t o = (size_t)(c0 + k) * n + i;
+        t[k] = f * (s ? v[o] * s[o] : v[o]);
+    }
+    store_row<NB>(out + (size_t)i * LD + c0, t);
+}
+
 // out[k*m + i] = post( rowscale[i] * in[idx ? idx[i] : i][k] ),  post = exp if do_exp   (K9, K10)
 template <int NB>
 __global__ __launch_bounds__(kBlock) void deinterleave_kernel(int m, const double* __restrict__ in,
@@ -160,6 +180,13 @@ void normal_fill(hipStream_t st, int n, int nbatch, uint64_t seed, uint64_t firs
 
 void interleave(hipStream_t st, int nb, int n, const double* in, const double* w, double scale, double* out, const int* src) {
     PMC_DISPATCH_NB(nb, { interleave_kernel<NB><<<groups(grid_rows(n), nb), kBlock, 0, st>>>(n, in, w, scale, out, nb, src); });
+    check_launch();
+}
+
+void seed_interleave(hipStream_t st, int nb, int n, const double* v, const double* s, const double* rowscale, double scale,
+                     double* out) {
+    if (n == 0) return;
+    PMC_DISPATCH_NB(nb, { seed_interleave_kernel<NB><<<groups(grid_rows(n), nb), kBlock, 0, st>>>(n, v, s, rowscale, scale, out, nb); });
     check_launch();
 }
 

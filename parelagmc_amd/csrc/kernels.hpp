@@ -290,6 +290,9 @@ void normal_fill(hipStream_t st, int n, int nbatch, uint64_t seed, uint64_t firs
 // out[i*nb+k] = scale * in[k*n+i] * (w ? w[i] : 1)
 void interleave(hipStream_t st, int nb, int n, const double* in, const double* w, double scale, double* out,
                 const int* src = nullptr);
+// out[i*nb+k] = scale * v[k*n+i] * (s ? s[k*n+i] : 1) * (rowscale ? rowscale[i] : 1)   (seed of Eval's adjoint)
+void seed_interleave(hipStream_t st, int nb, int n, const double* v, const double* s, const double* rowscale, double scale,
+                     double* out);
 // out[k*m+i] = post(rowscale[i] * in[(idx?idx[i]:i)*nb + k])
 void deinterleave(hipStream_t st, int nb, int m, const double* in, const int* idx, const double* rowscale, bool do_exp,
                   double* out);

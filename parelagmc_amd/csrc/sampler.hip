@@ -485,6 +485,7 @@ void Sampler::set_projection(int level, int kind, const pmc_csr* Gt, const int32
     SamplerLevel& d = lv[level];
     ctx.activate();
     hipStream_t st = ctx.stream;
+    d.has_adj = false;   // the adjoint's transposed output map is rebuilt at the next pmc_sampler_eval_adjoint
     if (kind == PMC_PROJ_NONE) {
         d.proj = PMC_PROJ_NONE;
         d.out_size = d.n_s;
@@ -649,7 +650,8 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
 
 // invA[level]->Mult(rhs, sol) (PDESampler.cpp:397,521): preconditioned MINRES on the interleaved member vectors rhs -> sol
 // for nb realizations; rows [x_row0, x_row0 + x_nrows) of the solution are maintained.  The caller has marked phase 1.
-void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs_fn) {
+void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs_fn,
+                           uint64_t key_salt) {
     hipStream_t st = ctx.stream;
     SamplerLevel& d = lv[level];
     const int n_u = d.n_u, n_s = d.n_s, n = (int)system_rows(level);
@@ -722,6 +724,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
     vc_timer.on = mgp->smooth_timer != nullptr;
     GraphHint hint;
     hint.key = hash_mix(hash_mix(hash_mix(0x5a, (uint64_t)level + 1), (uint64_t)nb), (uint64_t)x_row0);
+    if (key_salt) hint.key = hash_mix(hint.key, key_salt);
     hint.sig = hash_ptr(hash_ptr(hash_ptr(mgp->signature(mg_l0), cx.p), cd.p), cx2.p);
     MinresResult res = minres_solve(ctx, nb, A, prec, rhs.p, sol.p, zero_guess, opts, work, x_row0, x_nrows, nullptr, hint, rhs_fn);
     if (vc_timer.on) vc_timer.harvest();   // minres_solve has synchronised the stream

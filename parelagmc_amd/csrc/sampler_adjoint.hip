@@ -1,0 +1,222 @@
+// Adjoint of the SPDE samplers' Eval (pmc_sampler_eval_adjoint).
+//
+// Eval(level, xi_level) is s_out = f(O S R D xi): D = -g diag(w_sqrt[xi_level]), R = Ps[level-1]^T ... Ps[xi_level]^T, S the
+// s-block of A_level^-1 (symmetric; the saddle-point and the hybridized solver compute the same S), O the output map
+// (identity, gather, diag(inv_w) Gt), f = exp on a lognormal handle.  So
+//     dJ/dxi = D R^T S O^T (v o f'),   f' = s_out,
+// i.e. the level's own solve with O^T (v o s_out) in the s-rows of the right-hand side, prolongated to xi_level and scaled.
+// The solve IS Eval's (Sampler::solve_system, zero guess) under a graph key of its own.  The factor -g is applied in the
+// seed: everything after it is linear.
+#include "handles.hpp"
+
+namespace pmc {
+
+namespace {
+constexpr uint64_t kAdjointKey = 0xad;   // graph-key salt: a captured graph of a forward Eval is never replayed here
+
+// grad[b][:] -= xi[b][:] and logprior[b] = -|xi_b|^2 / 2: one workgroup per realization, a fixed summation order (strided
+// partial sums per thread, then a tree over the workgroup), so the value does not depend on how a call was split
+constexpr int kPriorThreads = 256;
+__global__ __launch_bounds__(kPriorThreads) void prior_gradient_kernel(int n, const double* __restrict__ xi,
+                                                                       double* __restrict__ grad, double* __restrict__ logprior) {
+    __shared__ double red[kPriorThreads];
+    const size_t o = (size_t)blockIdx.x * n;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += kPriorThreads) {
+        const double x = xi[o + i];
+        grad[o + i] -= x;
+        acc = fma(x, x, acc);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = kPriorThreads / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) logprior[blockIdx.x] = -0.5 * red[0];
+}
+}
+
+void Sampler::prior_gradient(int n, int nbatch, const double* xi, double* grad, double* logprior, int memspace) {
+    PMC_REQUIRE(n >= 1 && nbatch >= 1 && xi != nullptr && grad != nullptr, "logprior_gradient: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "logprior_gradient: bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const size_t cnt = (size_t)n * nbatch;
+    // the handle's own buffers (grown, never shrunk): a call per MCMC step allocates nothing
+    adj_lp.ensure((size_t)nbatch);
+    const double* xi_d = xi;
+    double* g_d = grad;
+    if (memspace == PMC_MEM_HOST) {
+        stage_in.ensure(cnt);
+        stage_out.ensure(cnt);
+        PMC_HIP(hipMemcpyAsync(stage_in.p, xi, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        PMC_HIP(hipMemcpyAsync(stage_out.p, grad, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        xi_d = stage_in.p;
+        g_d = stage_out.p;
+    }
+    prior_gradient_kernel<<<(unsigned)nbatch, kPriorThreads, 0, st>>>(n, xi_d, g_d, adj_lp.p);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    if (memspace == PMC_MEM_HOST) PMC_HIP(hipMemcpyAsync(grad, stage_out.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+    // the scalars cross to the host only when asked for; a device-memory call without them does not synchronise
+    if (logprior) PMC_HIP(hipMemcpyAsync(logprior, adj_lp.p, sizeof(double) * nbatch, hipMemcpyDeviceToHost, st));
+    if (logprior || memspace == PMC_MEM_HOST) PMC_HIP(hipStreamSynchronize(st));
+}
+
+namespace {
+template <class T>
+std::vector<T> read_back(const DevBuf<T>& b, size_t cnt, hipStream_t st) {
+    std::vector<T> h(cnt);
+    if (cnt) PMC_HIP(hipMemcpyAsync(h.data(), b.p, sizeof(T) * cnt, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+    return h;
+}
+// A^T diag(rowscale) of a shared-value SELL matrix as host CSR, read back from the device (padding slots carry the value 0)
+HostCsr sell_transpose_host(const Sell& A, const std::vector<double>& rowscale, hipStream_t st) {
+    const std::vector<int> off = read_back(A.slice_off, (size_t)A.nslices + 1, st);
+    const std::vector<int> cols = read_back(A.cols, (size_t)A.nslots, st);
+    const std::vector<double> vals = read_back(A.vals, (size_t)A.nslots, st);
+    HostCsr O;   // A diag-scaled, row by row, then transposed
+    O.nrows = A.nrows;
+    O.ncols = A.ncols;
+    O.rowptr.assign((size_t)A.nrows + 1, 0);
+    for (int r = 0; r < A.nrows; ++r) {
+        const int s = r / 64, lane = r % 64;
+        const int w = (off[(size_t)s + 1] - off[(size_t)s]) / 64;
+        for (int j = 0; j < w; ++j) {
+            const size_t slot = (size_t)off[(size_t)s] + (size_t)j * 64 + lane;
+            if (vals[slot] == 0.0) continue;
+            O.colind.push_back(cols[slot]);
+            O.vals.push_back(vals[slot] * rowscale[(size_t)r]);
+        }
+        O.rowptr[(size_t)r + 1] = (int)O.colind.size();
+    }
+    return csr_transpose(O);
+}
+}
+
+// device side of the adjoint of `level`, built at the first adjoint call from what setup left on the device (a handle that
+// never asks allocates nothing, on the host or on the device)
+void Sampler::ensure_adjoint(int level) {
+    SamplerLevel& d = lv[level];
+    if (d.has_adj) return;
+    hipStream_t st = ctx.stream;
+    std::vector<double> z;
+    if (hybrid) {   // z = zw_sqrt / w_sqrt, the two exactly as setup uploaded them
+        std::vector<double> zw((size_t)d.n_s), wsq((size_t)d.n_s);
+        PMC_HIP(hipMemcpyAsync(zw.data(), d.zw_sqrt.p, sizeof(double) * d.n_s, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipMemcpyAsync(wsq.data(), d.w_sqrt.p, sizeof(double) * d.n_s, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipStreamSynchronize(st));
+        z.resize((size_t)d.n_s);
+        for (int i = 0; i < d.n_s; ++i) z[(size_t)i] = zw[(size_t)i] / wsq[(size_t)i];
+        d.adj_z.upload(z, st);
+    }
+    if (d.proj != PMC_PROJ_NONE) {
+        HostCsr Ot;
+        if (d.proj == PMC_PROJ_GATHER) {   // O (out_size x n_s): row j is e_idx[j]
+            HostCsr O;
+            O.nrows = d.out_size;
+            O.ncols = d.n_s;
+            O.rowptr.resize((size_t)d.out_size + 1);
+            for (int j = 0; j <= d.out_size; ++j) O.rowptr[(size_t)j] = j;
+            O.colind = read_back(d.gather, (size_t)d.out_size, st);
+            O.vals.assign((size_t)d.out_size, 1.0);
+            Ot = csr_transpose(O);
+        } else {                           // O = diag(inv_w) Gt, both as set_projection uploaded them
+            Ot = sell_transpose_host(d.Gt, read_back(d.inv_w, (size_t)d.out_size, st), st);
+        }
+        if (hybrid)
+            for (int i = 0; i < Ot.nrows; ++i)
+                for (int p = Ot.rowptr[(size_t)i]; p < Ot.rowptr[(size_t)i + 1]; ++p) Ot.vals[(size_t)p] *= z[(size_t)i];
+        sell_build(d.adj_Ot, Ot, true, false, st);
+    }
+    PMC_HIP(hipStreamSynchronize(st));
+    d.has_adj = true;
+}
+
+void Sampler::eval_adjoint_chunk(int level, int xi_level, int nb, const double* v_d, const double* s_d, double* grad_d,
+                                 pmc_stats* stats) {
+    hipStream_t st = ctx.stream;
+    SamplerLevel& d = lv[level];
+    const int n_u = d.n_u, n_s = d.n_s;
+    ensure(level, nb);
+    if (stats) ctx.phase_mark(0);
+    // s-rows of the right-hand side: q = -g O^T (v o s_out); the hybridized solve wants z q there (fz of eval_chunk)
+    double* rhs_s = rhs.p + (size_t)n_u * nb;
+    if (d.proj == PMC_PROJ_NONE) {
+        k::seed_interleave(st, nb, n_s, v_d, s_d, hybrid ? d.adj_z.p : nullptr, -g, rhs_s);
+    } else {
+        k::seed_interleave(st, nb, d.out_size, v_d, s_d, nullptr, -g, tA.p);
+        k::spmm(st, nb, view(d.adj_Ot), tA.p, rhs_s, false, nullptr, nullptr);
+    }
+    if (hybrid) {
+        // rhs = Gz (z q) = G q; lambda = H^-1 rhs; S q = z q - G^T lambda: eval_chunk's solve and back-substitution
+        const SellView Gzv = view(d.Gz);
+        double* fz = rhs_s;
+        RhsFn make_rhs;
+        make_rhs.store = rhs.p;
+        make_rhs.write = [Gzv, fz](const Lanes& L, int nb_, double* y, float* y32) {
+            if (y32) k::spmm_store32(L.main, nb_, Gzv, fz, y, y32);
+            else k::spmm(L.main, nb_, Gzv, fz, y, false, nullptr, nullptr);
+        };
+        if (stats) ctx.phase_mark(1);
+        solve_system(level, nb, true, 0, n_u, stats, &make_rhs, kAdjointKey);
+        k::residual(st, nb, view(d.Gl), fz, sol.p, sol.p + (size_t)n_u * nb);
+    } else {
+        k::fill(st, (size_t)n_u * nb, rhs.p, 0.0);
+        if (stats) ctx.phase_mark(1);
+        solve_system(level, nb, true, n_u, n_s, stats, nullptr, kAdjointKey);
+    }
+    // R^T: down the levels with the prolongators, then the row scale of D
+    const double* cur = sol.p + (size_t)n_u * nb;
+    double* nxt = tA.p;
+    double* other = tB.p;
+    for (int l = level - 1; l >= xi_level; --l) {
+        k::spmm(st, nb, view(mg.L[l].P), cur, nxt, false, nullptr, nullptr);
+        cur = nxt;
+        std::swap(nxt, other);
+    }
+    k::deinterleave(st, nb, lv[xi_level].n_s, cur, nullptr, lv[xi_level].w_sqrt.p, false, grad_d);
+}
+
+void Sampler::eval_adjoint(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* grad_xi,
+                           int memspace, pmc_stats* stats) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "EvalAdjoint: level out of range");
+    PMC_REQUIRE(xi_level >= 0 && xi_level <= level, "EvalAdjoint: xi_level must satisfy 0 <= xi_level <= level");
+    PMC_REQUIRE(nbatch >= 1 && v != nullptr && grad_xi != nullptr, "EvalAdjoint: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "EvalAdjoint: bad memspace");
+    PMC_REQUIRE(s_out == nullptr || lognormal, "EvalAdjoint: s_out given on a handle that is not lognormal");
+    PMC_REQUIRE(cond == nullptr, "EvalAdjoint: a conditioner is attached (pmc_sampler_set_conditioner); the adjoint of the "
+                                 "conditional field is not implemented");
+    if (kl) {
+        eval_adjoint_kl(level, xi_level, nbatch, v, s_out, grad_xi, memspace, stats);
+        return;
+    }
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    ensure_adjoint(level);
+    const int n_xi = lv[xi_level].n_s, n_out = lv[level].out_size;
+    int done = 0;
+    while (done < nbatch) {   // the launch widths of Sampler::eval
+        int nb = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
+        while (nb > nbatch - done) nb >>= 1;
+        const double* v_d = v + (size_t)done * n_out;
+        const double* s_d = s_out ? s_out + (size_t)done * n_out : nullptr;
+        double* g_d = grad_xi + (size_t)done * n_xi;
+        if (memspace == PMC_MEM_HOST) {
+            ensure(level, nb);
+            PMC_HIP(hipMemcpyAsync(stage_in.p, v_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
+            if (s_d) PMC_HIP(hipMemcpyAsync(stage_emb.p, s_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
+            eval_adjoint_chunk(level, xi_level, nb, stage_in.p, s_d ? stage_emb.p : nullptr, stage_out.p,
+                               stats ? stats + done : nullptr);
+            PMC_HIP(hipMemcpyAsync(g_d, stage_out.p, sizeof(double) * n_xi * nb, hipMemcpyDeviceToHost, st));
+            PMC_HIP(hipStreamSynchronize(st));
+        } else {
+            eval_adjoint_chunk(level, xi_level, nb, v_d, s_d, g_d, stats ? stats + done : nullptr);
+        }
+        done += nb;
+    }
+}
+
+}  // namespace pmc

@@ -91,8 +91,8 @@ void PDESampler::Sample(const int level, Vector& xi, uint64_t first_id, int nbat
     xi.SetSize(n, nbatch);
     check(pmc_sampler_sample(h_, level, first_id, nbatch, xi.GetData(), xi.MemSpace()), "PDESampler::Sample");
 }
-void PDESampler::Eval(const int level, const Vector& xi, Vector& s) {
-    const int xi_level = level_of_xi(xi.Size());
+void PDESampler::Eval(const int level, const Vector& xi, Vector& s) { EvalAt(level, level_of_xi(xi.Size()), xi, s); }
+void PDESampler::EvalAt(const int level, const int xi_level, const Vector& xi, Vector& s) {
     if (xi_level > level) throw std::runtime_error("PDESampler::Eval: xi_level <= level violated");
     s.SetSize(SampleSize(level), xi.Batch());
     std::vector<pmc_stats> st(xi.Batch());
@@ -128,6 +128,24 @@ void PDESampler::Eval(const int level, const Vector& xi, Vector& s, Vector& u, b
               "PDESampler::Eval");
     }
     record(level, st);
+}
+void PDESampler::EvalAdjoint(const int level, const Vector& v, const Vector* s_or_null, Vector& grad_xi, int xi_level) {
+    if (xi_level < 0) xi_level = level;
+    const int n_xi = pmc_sampler_xi_size(h_, xi_level), n_out = SampleSize(level);
+    if (n_xi < 0 || n_out < 0) throw std::out_of_range("PDESampler::EvalAdjoint: level");
+    if (v.Size() != n_out) throw std::invalid_argument("PDESampler::EvalAdjoint: v does not match SampleSize(level)");
+    if (grad_xi.MemSpace() != v.MemSpace() || (s_or_null && s_or_null->MemSpace() != v.MemSpace()))
+        throw std::invalid_argument("PDESampler::EvalAdjoint: v, s and grad_xi must share a memory space");
+    if (s_or_null && (s_or_null->Size() != n_out || s_or_null->Batch() != v.Batch()))
+        throw std::invalid_argument("PDESampler::EvalAdjoint: s does not match v");
+    grad_xi.SetSize(n_xi, v.Batch());
+    std::vector<pmc_stats> st(v.Batch());
+    check_arg(pmc_sampler_eval_adjoint(h_, level, xi_level, v.Batch(), v.GetData(), s_or_null ? s_or_null->GetData() : nullptr,
+                                       grad_xi.GetData(), v.MemSpace(), st.data()),
+              "PDESampler::EvalAdjoint");
+    if ((int)adj_times_.size() <= level) adj_times_.resize(level + 1);
+    adj_times_[level].add(st.data(), (int)st.size());
+    last_adj_iters_ = st.empty() ? -1 : st[0].iterations;
 }
 void PDESampler::BuildHierarchy() {
     if (!h_ || pmc_sampler_num_levels(h_) < 1) throw std::runtime_error("PDESampler::BuildHierarchy: no device handle");
@@ -283,6 +301,31 @@ void BayesianInverseProblem::ComputeGradLogLikelihood(int ilevel, Vector& k, dou
     check(pmc_darcy_loglik_gradient(solver_, ilevel, k.Batch(), k.GetData(), G_obs_.data(), noise_, wrt_log ? 1 : 0, loglik,
                                     nullptr, grad.GetData(), k.MemSpace(), nullptr),
           "BayesianInverseProblem::ComputeGradLogLikelihood");
+}
+void BayesianInverseProblem::ComputeGradLogPosterior(int ilevel, PDESampler& sampler, const Vector& xi, double* logpost,
+                                                     Vector& grad, int xi_level) {
+    if (grad.MemSpace() != xi.MemSpace())
+        throw std::invalid_argument("ComputeGradLogPosterior: xi and grad must share a memory space");
+    const int nb = xi.Batch();
+    for (int l = 0; l <= ilevel && xi_level < 0; ++l)
+        if (pmc_sampler_xi_size(sampler.Handle(), l) == xi.Size()) xi_level = l;
+    if (xi_level < 0 || xi_level > ilevel || pmc_sampler_xi_size(sampler.Handle(), xi_level) != xi.Size())
+        throw std::invalid_argument("ComputeGradLogPosterior: xi matches no level up to ilevel (or not the xi_level named)");
+    const bool logn = sampler.IsLognormal();
+    if (!work_k_ || work_k_->MemSpace() != xi.MemSpace()) {
+        work_k_.reset(new Vector(sampler.Context(), xi.MemSpace()));
+        work_gk_.reset(new Vector(sampler.Context(), xi.MemSpace()));
+    }
+    Vector &k = *work_k_, &gk = *work_gk_;
+    sampler.EvalAt(ilevel, xi_level, xi, k);
+    std::vector<double> ll((size_t)nb), lp((size_t)nb);
+    ComputeGradLogLikelihood(ilevel, k, ll.data(), gk, /*wrt_log=*/logn);
+    sampler.EvalAdjoint(ilevel, gk, nullptr, grad, xi_level);   // wrt_log carries the factor k of a lognormal handle
+    check_arg(pmc_sampler_logprior_gradient(sampler.Handle(), xi.Size(), nb, xi.GetData(), grad.GetData(), lp.data(),
+                                            xi.MemSpace()),
+              "BayesianInverseProblem::ComputeGradLogPosterior");
+    if (logpost)
+        for (int b = 0; b < nb; ++b) logpost[b] = ll[(size_t)b] + lp[(size_t)b];
 }
 void BayesianInverseProblem::ComputeR(int ilevel, Vector& k, double* R, double* C) {
     std::vector<double> q(k.Batch());
@@ -1743,6 +1786,26 @@ int pmc_bayes_loglik_gradient(pmc_darcy* solver, int level, int nbatch, const do
         BayesianInverseProblem prob(solver, noise, std::vector<double>(G_obs, G_obs + nobs));
         View kv(const_cast<double*>(k), n_k, nbatch, memspace), gv(grad, n_k, nbatch, memspace);
         prob.ComputeGradLogLikelihood(level, kv, loglik, gv, wrt_log != 0);
+    });
+}
+
+int pmc_bayes_logpost_gradient(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                               const double* xi, int memspace, const double* G_obs, int nobs, double noise, double* logpost,
+                               double* grad) {
+    return hguard([&] {
+        if (!ctx || !sampler || !solver || !xi || !G_obs || !grad || nbatch < 1 || nobs < 1 || !(noise > 0.0))
+            throw std::invalid_argument("pmc_bayes_logpost_gradient: bad argument");
+        struct View : Vector {     // non-owning batch views of xi and grad
+            View(double* p, int n, int nb, int ms) : Vector(nullptr, ms) { Adopt(p, n, nb); }
+            ~View() { Release(); }
+        };
+        if (level < 0 || level >= pmc_sampler_num_levels(sampler) || xi_level < 0 || xi_level > level)
+            throw std::invalid_argument("pmc_bayes_logpost_gradient: level / xi_level out of range");
+        const int n_xi = pmc_sampler_xi_size(sampler, xi_level);
+        PDESampler smp(ctx, sampler);
+        BayesianInverseProblem prob(solver, noise, std::vector<double>(G_obs, G_obs + nobs));
+        View xv(const_cast<double*>(xi), n_xi, nbatch, memspace), gv(grad, n_xi, nbatch, memspace);
+        prob.ComputeGradLogPosterior(level, smp, xv, logpost, gv, xi_level);
     });
 }
 

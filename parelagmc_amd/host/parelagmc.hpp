@@ -150,13 +150,15 @@ class PDESampler : public MLSampler {
     void Sample(const int level, Vector& xi, uint64_t first_id = 0, int nbatch = 1) override;
     void Eval(const int level, const Vector& xi, Vector& s) override;
     void Eval(const int level, const Vector& xi, Vector& s, Vector& u, bool use_init) override;
+    /// Eval with the level xi was drawn on named instead of inferred from xi.Size()
+    void EvalAt(const int level, const int xi_level, const Vector& xi, Vector& s);
     int SampleSize(int level) const override;
     size_t GetNNZ(int level) const override;
     void BuildHierarchy() override;
     pmc_csr GetTrueP(int level) const override;
     int PreferredBatch(int level) const override { return pmc_sampler_batch_width(h_, level); }
     PhaseTimes GetPhaseTimes(int level) const override { return level < (int)times_.size() ? times_[level] : PhaseTimes(); }
-    void ResetPhaseTimes() override { times_.clear(); }
+    void ResetPhaseTimes() override { times_.clear(); adj_times_.clear(); }
     int GetNumIters() const { return last_iters_; }   // the reference returns -1 (PDESampler.hpp:142-145)
     /// MLSampler::ComputeL2Error / ComputeMaxError of ONE field (coeff.Batch() == 1; pmc_sampler_l2_error / _max_error).
     /// L2: the squared error, as the reference returns.
@@ -165,10 +167,19 @@ class PDESampler : public MLSampler {
     /// the batched forms: err[c] of each of coeff.Batch() fields (err: coeff.Batch() host doubles)
     void ComputeL2Error(int level, const Vector& coeff, double exact, double* err) const;
     void ComputeMaxError(int level, const Vector& coeff, double exact, double* err) const;
+    /// The adjoint of Eval in the white noise (pmc_sampler_eval_adjoint): grad_xi = (d Eval / d xi)^T v for every
+    /// realization of v (v.Batch() x SampleSize(level)); s_or_null: nullptr, or Eval's output on a lognormal handle (v is
+    /// multiplied by it).  grad_xi is sized to v.Batch() x xi_size(xi_level) in v's memory space; xi_level < 0: level.
+    /// The adjoint solves are timed apart from Eval's: GetPhaseTimes / GetNumIters keep meaning the forward solves.
+    void EvalAdjoint(const int level, const Vector& v, const Vector* s_or_null, Vector& grad_xi, int xi_level = -1);
+    PhaseTimes GetAdjointPhaseTimes(int level) const { return level < (int)adj_times_.size() ? adj_times_[level] : PhaseTimes(); }
+    int GetNumAdjointIters() const { return last_adj_iters_; }
+    bool IsLognormal() const { return pmc_sampler_is_lognormal(h_) == 1; }
     /// Eval returns fields conditioned on the data of `c` (pmc_conditioner_create on this handle, exact data); nullptr
     /// detaches (pmc_sampler_set_conditioner).  The caller keeps ownership of `c`.
     void SetConditioner(pmc_conditioner* c);
     pmc_sampler* Handle() const { return h_; }
+    pmc_ctx* Context() const { return ctx_; }
 
   private:
     int level_of_xi(int size) const;
@@ -180,8 +191,8 @@ class PDESampler : public MLSampler {
     }
     pmc_ctx* ctx_;
     pmc_sampler* h_;
-    int last_iters_ = -1;
-    std::vector<PhaseTimes> times_;
+    int last_iters_ = -1, last_adj_iters_ = -1;
+    std::vector<PhaseTimes> times_, adj_times_;
 };
 
 /// Device truncated Karhunen-Loeve sampler: a handle from pmc_sampler_create_kl behind the same calls (GetNumIters() = 0).
@@ -318,12 +329,22 @@ class BayesianInverseProblem {
     /// log of ComputeLikelihood and its adjoint gradient with respect to k (wrt_log: log k) for every realization: loglik
     /// host array of k.Batch() (may be NULL), grad sized to n_p x k.Batch() in k's memory space (pmc_darcy_loglik_gradient)
     void ComputeGradLogLikelihood(int ilevel, Vector& k_over_k_ref, double* loglik, Vector& grad, bool wrt_log = false);
+    /// log pi(xi) = loglik(Eval(ilevel, xi)) - |xi|^2 / 2 and its gradient in the white noise xi for every realization of xi
+    /// (drawn on ilevel or finer): Eval, pmc_darcy_loglik_gradient (with respect to log k on a lognormal sampler, which
+    /// carries the factor k of the exp chain), pmc_sampler_eval_adjoint, the prior.  logpost: host array of xi.Batch() (may
+    /// be NULL); grad sized like xi, in xi's memory space.  With device vectors only the scalars cross to the host.
+    /// xi_level: the level xi was drawn on; < 0 infers it from xi.Size() (the first level up to ilevel of that size - name it
+    /// for samplers whose levels share a size, such as KL handles).  The two work vectors (k and dloglik/dk) are kept between
+    /// calls.
+    void ComputeGradLogPosterior(int ilevel, PDESampler& sampler, const Vector& xi, double* logpost, Vector& grad,
+                                 int xi_level = -1);
     int SizeOfObservationalData() const { return (int)G_obs_.size(); }
 
   private:
     pmc_darcy* solver_;
     double noise_;
     std::vector<double> G_obs_;
+    std::unique_ptr<Vector> work_k_, work_gk_;   // ComputeGradLogPosterior
 };
 
 double expWRegression(const std::vector<double>& y, const std::vector<double>& x, int skip_n_last);

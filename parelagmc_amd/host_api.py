@@ -71,6 +71,8 @@ HOST_SYMBOLS = {
                                        _DPTR]),
     "pmc_bayes_loglik_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double, C.c_int, _DPTR,
                                             _VP]),
+    "pmc_bayes_logpost_gradient": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double,
+                                             _DPTR, _VP]),
     "pmc_ratio_create": (C.c_int, [_VP, _VP, _VP, C.c_int, _DPTR, C.c_int, C.c_double, C.POINTER(pmc_mlmc_params),
                                    C.POINTER(_VP)]),
     "pmc_ratio_create_callbacks": (C.c_int, [C.c_int, C.POINTER(pmc_plugin_callbacks), _VP, C.POINTER(pmc_mlmc_params),
@@ -180,6 +182,26 @@ def bayes_loglik_gradient(solver, level, k, G_obs, noise, wrt_log=False):
                                           len(G_obs), float(noise), 1 if wrt_log else 0, ll.ctypes.data_as(_DPTR),
                                           grad.ctypes.data))
     return ll, grad
+
+
+def bayes_logpost_gradient(sampler, solver, level, xi, G_obs, noise, xi_level=None, nbatch=None, grad_out=None):
+    """BayesianInverseProblem::ComputeGradLogPosterior (pmc_bayes_logpost_gradient): (logpost (nbatch,), grad (nbatch,
+    xi_size(xi_level))) of log pi(xi) = loglik(Eval(level, xi)) - |xi|^2 / 2.  xi: numpy (host), or a capi.DeviceArray with
+    nbatch=... and grad_out=... (device: grad is written there and returned)."""
+    lib = load_host_library()
+    xi_level = level if xi_level is None else xi_level
+    G_obs = np.ascontiguousarray(G_obs, np.float64)
+    if isinstance(xi, np.ndarray):
+        xi = np.ascontiguousarray(np.atleast_2d(xi), np.float64)
+        nbatch = xi.shape[0]
+        grad_out = np.empty_like(xi)
+        pxi, pg, ms = xi.ctypes.data, grad_out.ctypes.data, capi.PMC_MEM_HOST
+    else:
+        pxi, pg, ms = xi.ptr, grad_out.ptr, capi.PMC_MEM_DEVICE
+    lp = np.empty(nbatch)
+    _hcheck(lib.pmc_bayes_logpost_gradient(sampler.ctx.h, sampler.h, solver.h, level, xi_level, nbatch, pxi, ms, G_obs.ctypes.data_as(_DPTR),
+                                           len(G_obs), float(noise), lp.ctypes.data_as(_DPTR), pg))
+    return lp, grad_out
 
 
 CB_LIKE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
