@@ -194,6 +194,27 @@ uint64_t pmc_fused_lanczos_solves(void);
  * wrote the field sample-major itself (identity output map, no embedded copy, no conditioner): path diagnostics */
 uint64_t pmc_adopted_rhs_solves(void);
 uint64_t pmc_fused_field_evals(void);
+/* MINRES solves of this process by the loop that ran them (all handles, all host threads): path diagnostics.  A solve counts
+ * once, for the first of these that applies: the persistent one-workgroup kernel of small sampler levels (mini_max_rows); pairs
+ * of iterations replayed as a captured graph (use_graph with check_every 2); the two-stream schedule with the w / x update one
+ * iteration late; the eager loop that updates the rows of a compact index list once per iteration (the Darcy solves); the
+ * eager loop that applies the w / x updates of a whole window of iterations in one pass; the eager loop with one plain update
+ * per iteration (laboratory builds with the window switched off only).  The path is counted when the solve SELECTS its loop: a
+ * solve on PMC_PATH_GRAPH that ends within its first, eager pair of iterations (or whose max_iter is 1: only the eager tail
+ * runs) never replays a graph.  Two further values count events, not solves: PMC_COUNT_GRAPH_REPLAYS the graph launches, and
+ * PMC_COUNT_POLLS the convergence polls (device-to-host reads of the active-column count) of all solves - a solve that starts
+ * polling late, at the iteration count its predecessor on the handle needed, shows fewer.  Another value returns 0. */
+enum pmc_solve_path {
+    PMC_PATH_MINI = 0,
+    PMC_PATH_GRAPH = 1,
+    PMC_PATH_LATE = 2,
+    PMC_PATH_INDEXED = 3,
+    PMC_PATH_WINDOW = 4,
+    PMC_PATH_PLAIN = 5,
+    PMC_COUNT_GRAPH_REPLAYS = 6,
+    PMC_COUNT_POLLS = 7
+};
+uint64_t pmc_solve_path_count(int path);
 const char* pmc_last_error(void);
 void pmc_solver_opts_default(pmc_solver_opts* opts);
 

@@ -41,6 +41,9 @@ class pmc_solver_opts(C.Structure):
 
 PMC_ABI_VERSION = 3          # include/pmc.h: layout of pmc_solver_opts / pmc_stats these classes restate
 PMC_STORAGE_FP32, PMC_STORAGE_FP64 = 0, 1
+# enum pmc_solve_path: the loops pmc_solve_path_count counts
+PMC_PATH_MINI, PMC_PATH_GRAPH, PMC_PATH_LATE, PMC_PATH_INDEXED, PMC_PATH_WINDOW, PMC_PATH_PLAIN = range(6)
+PMC_COUNT_GRAPH_REPLAYS, PMC_COUNT_POLLS = 6, 7     # ... events, not solves: graph launches, convergence polls
 
 
 class pmc_stats(C.Structure):
@@ -100,6 +103,7 @@ SYMBOLS = {
     "pmc_fused_lanczos_solves": (C.c_uint64, []),
     "pmc_adopted_rhs_solves": (C.c_uint64, []),
     "pmc_fused_field_evals": (C.c_uint64, []),
+    "pmc_solve_path_count": (C.c_uint64, [C.c_int]),
     "pmc_ctx_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_create_abi": (C.c_int, [C.c_int, C.c_int, C.POINTER(_VP)]),
     "pmc_ctx_destroy": (None, [_VP]),
@@ -235,7 +239,7 @@ SYMBOLS = {
 
 # path diagnostics added after the boundary settled: a library built from an older commit (the parent in a same-box A/B,
 # scripts/ab_libs.sh) lacks them and still loads; calling one on such a library raises AttributeError
-_LATE_DIAGNOSTICS = ("pmc_adopted_rhs_solves", "pmc_fused_field_evals")
+_LATE_DIAGNOSTICS = ("pmc_adopted_rhs_solves", "pmc_fused_field_evals", "pmc_solve_path_count")
 
 _lib = None
 

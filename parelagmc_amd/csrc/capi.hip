@@ -108,6 +108,7 @@ uint64_t pmc_kernel_launches(void) { return kernel_launch_count(); }
 uint64_t pmc_fused_lanczos_solves(void) { return fused_lanczos_solve_count(); }
 uint64_t pmc_adopted_rhs_solves(void) { return adopted_rhs_solve_count(); }
 uint64_t pmc_fused_field_evals(void) { return fused_field_eval_count(); }
+uint64_t pmc_solve_path_count(int path) { return solve_path_count(path); }
 const char* pmc_last_error(void) { return g_last_error.c_str(); }
 
 static void check_abi(const pmc_solver_opts& o) {

@@ -688,6 +688,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
         mini_scratch.ensure(mp.scratch_per_col * nb);
         mini_stats.ensure(kMaxBatch);
         k::mini_sampler_solve(st, nb, mp, mgp->tail_lds[mg_l0], rhs.p, sol.p, zero_guess, mini_scratch.p, mini_stats.p);
+        count_solve_path(PMC_PATH_MINI);
         if (stats) {
             ctx.phase_mark(2);
             PMC_HIP(hipMemcpyAsync(ctx.h_scal, mini_stats.p, sizeof(pmc_stats) * nb, hipMemcpyDeviceToHost, st));

@@ -597,6 +597,12 @@ static bool fused_lanczos_on() {
 static std::atomic<uint64_t> g_adopted_rhs_solves{0};
 uint64_t adopted_rhs_solve_count() { return g_adopted_rhs_solves.load(std::memory_order_relaxed); }
 
+static std::atomic<uint64_t> g_path_solves[PMC_COUNT_POLLS + 1];
+uint64_t solve_path_count(int path) {
+    return path >= 0 && path <= PMC_COUNT_POLLS ? g_path_solves[path].load(std::memory_order_relaxed) : 0;
+}
+void count_solve_path(int path) { g_path_solves[path].fetch_add(1, std::memory_order_relaxed); }
+
 // PMC_LATE_WX=0 keeps the w / x update inside its own iteration also on two streams (A/B switch)
 static bool late_wx() {
     static const bool v = [] {
@@ -655,6 +661,7 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     // schedule (its update already runs beside other work) and not inside a captured graph.  Its first pass starts w0, w1
     // and (zero guess) the maintained rows of x from literal zeros, so none of the three is filled here.
     const bool defer = !graphs && !late && !x_rows && wx_defer_on();
+    count_solve_path(graphs ? PMC_PATH_GRAPH : late ? PMC_PATH_LATE : x_rows ? PMC_PATH_INDEXED : defer ? PMC_PATH_WINDOW : PMC_PATH_PLAIN);
     if (zero_guess) {
         if (defer) {   // only the rows the update never writes
             k::fill(st, xoff, x, 0.0);
@@ -693,6 +700,7 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
     const int* d_nactive = reinterpret_cast<const int*>(reinterpret_cast<const char*>(S) + offsetof(k::MinresState, n_active));
 
     auto poll = [&]() {
+        count_solve_path(PMC_COUNT_POLLS);
         PMC_HIP(hipMemcpyAsync(ctx.h_flag, d_nactive, sizeof(int), hipMemcpyDeviceToHost, st));
         PMC_HIP(hipStreamSynchronize(st));
         return *ctx.h_flag;
@@ -829,6 +837,7 @@ MinresResult minres_solve(Ctx& ctx, int nb, const LinOp& A, const PrecFn& prec, 
             }
             while (n_active > 0 && it + 2 <= o.max_iter) {
                 PMC_HIP(hipGraphLaunch(ge.exec, st));
+                count_solve_path(PMC_COUNT_GRAPH_REPLAYS);
                 it += 2;
                 if (it >= first_poll || it == mid_poll) n_active = poll();
             }

@@ -1,0 +1,111 @@
+"""The handle registries the preconditioner tests (test_gpu_sampler_precond.py, test_gpu_precond.py) and the MINRES
+trajectory tests (test_gpu_minres_trajectory.py) share: the sampler handles with what the fp64 oracles need from them, the
+permeability fields of the Darcy batches, and the bound of a preconditioner column against its fp64 reference."""
+import numpy as np
+
+from conftest import golden_path
+
+# relative L2 bound of a column of B^-1 r against the fp64 reference, per preconditioner storage
+REF_TOL = {"fp64": 1e-12, "fp32": 1e-5}
+
+# sampler handles of the preconditioner tests (MC level 0 of each; n_mc_levels = 1), see test_gpu_sampler_precond.py
+HANDLES = {
+    "hex32-saddle": dict(mesh=("hex", 3), kind="saddle", corlen=0.3, coarsening=0),
+    "tet-saddle": dict(mesh=("tet", 2), kind="saddle", corlen=0.5, coarsening=0),
+    "hex32-sa": dict(mesh=("hex", 3), kind="saddle", corlen=0.3, coarsening=1),
+    "hex12-hybrid": dict(mesh=("hex3", 2), kind="hybrid", corlen=0.3, coarsening=0),
+    "hex24-hybrid": dict(mesh=("hex3", 3), kind="hybrid", corlen=0.3, coarsening=0),
+}
+# ... and the two small saddle-point handles only the trajectory tests solve on: hex 4^3 refined twice (17 152 rows; corlen
+# 0.5 needs about 40 iterations) and once (2 240 rows: inside mini_max_rows)
+SOLVE_HANDLES = dict(HANDLES)
+SOLVE_HANDLES.update({
+    "hex16-saddle": dict(mesh=("hex", 2), kind="saddle", corlen=0.5, coarsening=0),
+    "hex8-saddle": dict(mesh=("hex", 1), kind="saddle", corlen=0.1, coarsening=0),
+})
+
+
+def rel(a, b):
+    nb = np.linalg.norm(b)
+    return np.linalg.norm(a - b) / nb if nb > 0 else np.linalg.norm(a)
+
+
+_HIER = {}
+
+
+def hierarchy(mesh):
+    if mesh not in _HIER:
+        from parelagmc_amd.fe import box_mesh, build_hierarchy, mesh_from_json
+        kind, nref = mesh
+        if kind == "tet":
+            m = mesh_from_json(golden_path("meshes", "cube_tet.json"))
+            _HIER[mesh] = build_hierarchy(m, nref)
+        else:
+            n = 4 if kind == "hex" else 3
+            _HIER[mesh] = build_hierarchy(box_mesh([n, n, n], [2, 2, 2], "hex"), nref)
+    return _HIER[mesh]
+
+
+_PROBLEMS = {}
+
+
+def sampler_problem(name):
+    """the problem of a registered handle, built once: the handles of one name (both storages, every option set) share it.
+    PDESampler only reads it - the arrays are copied to the device at create time - so sharing changes nothing a handle sees"""
+    if name not in _PROBLEMS:
+        from parelagmc_amd.fe import build_hybrid_sampler_problem, build_sampler_problem
+        cfg = SOLVE_HANDLES[name]
+        build = build_hybrid_sampler_problem if cfg["kind"] == "hybrid" else build_sampler_problem
+        _PROBLEMS[name] = build(hierarchy(cfg["mesh"]), corlen=cfg["corlen"], lognormal=True, n_mc_levels=1)
+    return _PROBLEMS[name]
+
+
+class Handle:
+    """one sampler handle with what the tests read from it; **opts: solver options beyond the storage and mg_coarsening"""
+
+    def __init__(self, ctx, name, storage, **opts):
+        from parelagmc_amd import capi
+        cfg = SOLVE_HANDLES[name]
+        self.hybrid = cfg["kind"] == "hybrid"
+        self.prob = sampler_problem(name)
+        st = capi.PMC_STORAGE_FP64 if storage == "fp64" else capi.PMC_STORAGE_FP32
+        self.opts = capi.solver_opts(precond_storage=st, mg_coarsening=cfg["coarsening"], **opts)
+        self.smp = capi.PDESampler(ctx, self.prob, self.opts)
+        self.setup = self.smp.vcycle_setup(0)
+        self.info = self.smp.vcycle_levels(0)
+        self.P = [self.smp.vcycle_prolongator(0, v) for v in range(len(self.setup) - 1)]
+        L = self.prob.levels[0]
+        self.n = L.n_lambda if self.hybrid else L.n_u + L.n_s
+        self.top = self.smp.BatchWidth(0)
+        self.dense_nb = int(self.setup[0]["dense_nb"])
+        self._oracle = None
+
+    @property
+    def oracle(self):
+        if self._oracle is None:
+            from oracle.precond_oracle import SamplerPrecondOracle
+            self._oracle = SamplerPrecondOracle(self.prob, 0, self.setup, self.P, self.opts.schur_scale)
+        return self._oracle
+
+    def narrow(self, nb):
+        return nb <= self.dense_nb
+
+
+def darcy_fields(rng, nb, n_p):
+    """one permeability per column: log-normal with variances 0.25 .. 9, k == 1, and a 1e3-contrast two-valued field"""
+    k = np.empty((nb, n_p))
+    for j in range(nb):
+        kind = j % 6
+        if kind == 1:
+            k[j] = 1.0
+        elif kind == 4:
+            k[j] = np.where(rng.random(n_p) < 0.3, 1e3, 1.0)
+        else:
+            k[j] = np.exp([0.5, 1.0, 3.0, 2.0, 0.0, 1.5][kind] * rng.standard_normal(n_p))
+    return k
+
+
+def darcy_hex_problem(hex_hierarchy):
+    """the `hex` problem of test_gpu_precond.py: the octree hierarchy, flow from x = min to x = max"""
+    from parelagmc_amd.fe import build_darcy_problem
+    return build_darcy_problem(hex_hierarchy, [0, 1, 1, 1, 1, 0], [1, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 1])

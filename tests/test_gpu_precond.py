@@ -25,9 +25,9 @@ The Darcy internal hierarchies (mg_coarsening and the hybridized Darcy handle) a
 test_gpu_darcy_internal_precond.py; here hex-sa (mg_coarsening = 1) and spe10-hybrid join the width-consistency and
 column-independence tests.
 
-Not covered by this file: the preconditioner inside mini_sampler_kernel (covered indirectly by
-test_persistent_small_level_solver_equals_the_batched_kernels) and the r32_top input of the hybridized sampler's cycle, which
-only the MINRES loop provides.
+Not covered by this file: the preconditioner inside mini_sampler_kernel and the r32_top input of the hybridized sampler's
+cycle, which only the MINRES loop provides - test_gpu_minres_trajectory.py compares the iterates of whole solves on those
+paths (and of the Darcy solves of this file's `hex` problem) with single-vector MINRES over the reference preconditioners.
 
 Measured on the MI355X (the printed lines), widths 1 .. 256 on every level:
 - against the fp64 reference: at most 2.8e-15 with PMC_STORAGE_FP64, 2.6e-9 with PMC_STORAGE_FP32 (these levels keep the
@@ -48,6 +48,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_path
+from precond_cases import REF_TOL, darcy_fields as _fields   # shared with test_gpu_minres_trajectory.py
 
 pytestmark = pytest.mark.gpu
 
@@ -119,20 +120,6 @@ def _rows(problems, name, hybrid, lvl):
         return L.n_u + L.n_p
     from parelagmc_amd.fe.darcy_hybrid import darcy_hybrid_level
     return darcy_hybrid_level(h.spaces[lvl], L).n_lambda
-
-
-def _fields(rng, nb, n_p):
-    """one permeability per column: log-normal with variances 0.25 .. 9, k == 1, and a 1e3-contrast two-valued field"""
-    k = np.empty((nb, n_p))
-    for j in range(nb):
-        kind = j % 6
-        if kind == 1:
-            k[j] = 1.0
-        elif kind == 4:
-            k[j] = np.where(rng.random(n_p) < 0.3, 1e3, 1.0)
-        else:
-            k[j] = np.exp([0.5, 1.0, 3.0, 2.0, 0.0, 1.5][kind] * rng.standard_normal(n_p))
-    return k
 
 
 def _rel(a, b):
@@ -310,10 +297,6 @@ def test_sampler_preconditioner_columns_are_independent(gpu_ctx, hex_hierarchy, 
             perm = seeded_rng.permutation(nb)
             assert np.array_equal(smp.ApplyPreconditioner(lvl, r[perm]), z[perm])
     smp.close()
-
-
-# relative L2 bound of a column against the fp64 reference, per preconditioner storage
-REF_TOL = {"fp64": 1e-12, "fp32": 1e-5}
 
 
 @pytest.mark.parametrize("storage", ["fp64", "fp32"])

@@ -31,8 +31,10 @@ The handles (MC level 0 of each; n_mc_levels = 1):
 - hex24-hybrid: hybridized, hex 3^3 refined 3 times (43 200 multipliers): level 0 outside the tail at every width (fused
   aggregate restriction after agg_pack_rows), level 1 row-split (S_split, SP_split) for narrow launches.
 
-Not covered here: mini_sampler_kernel (test_persistent_small_level_solver_equals_the_batched_kernels), the r32_top input of the
-hybridized cycle (only the MINRES loop provides it).  The Darcy internal hierarchies: test_gpu_darcy_internal_precond.py.
+Not covered here, because only a solve reaches them: the preconditioner inside mini_sampler_kernel and the r32_top input of the
+hybridized cycle (the fp32 copy the Lanczos update of the MINRES loop writes).  test_gpu_minres_trajectory.py covers both: it
+compares the iterates of whole solves on tet-saddle, hex12-hybrid and hex24-hybrid with single-vector MINRES over THIS file's
+reference preconditioner.  The Darcy internal hierarchies: test_gpu_darcy_internal_precond.py.
 
 Tolerances: REF_TOL / WIDTH_TOL of test_gpu_precond.py.  Outside the tail the fp32 storage keeps the level's iterate and
 residuals in fp32 (the matrix values of these shared-value levels stay fp64): 1e-5 holds with more than two orders of margin.
@@ -50,21 +52,12 @@ import pytest
 import scipy.sparse as sp
 from scipy.sparse.linalg import eigsh
 
-from conftest import golden_path
+from precond_cases import HANDLES, REF_TOL, Handle as _Handle, rel as _rel   # shared with test_gpu_minres_trajectory.py
 
 pytestmark = pytest.mark.gpu
 
-# relative L2 bound of a column against the fp64 reference / against the same column in another launch, per storage
-REF_TOL = {"fp64": 1e-12, "fp32": 1e-5}
+# relative L2 bound of a column against the same column in another launch, per storage (REF_TOL: against the fp64 reference)
 WIDTH_TOL = {"fp64": 1e-12, "fp32": 1e-5}
-
-HANDLES = {
-    "hex32-saddle": dict(mesh=("hex", 3), kind="saddle", corlen=0.3, coarsening=0),
-    "tet-saddle": dict(mesh=("tet", 2), kind="saddle", corlen=0.5, coarsening=0),
-    "hex32-sa": dict(mesh=("hex", 3), kind="saddle", corlen=0.3, coarsening=1),
-    "hex12-hybrid": dict(mesh=("hex3", 2), kind="hybrid", corlen=0.3, coarsening=0),
-    "hex24-hybrid": dict(mesh=("hex3", 3), kind="hybrid", corlen=0.3, coarsening=0),
-}
 STORAGES = ("fp64", "fp32")
 
 
@@ -74,61 +67,6 @@ def _widths(top):
         out.append(w)
         w *= 2
     return out
-
-
-def _rel(a, b):
-    nb = np.linalg.norm(b)
-    return np.linalg.norm(a - b) / nb if nb > 0 else np.linalg.norm(a)
-
-
-_HIER = {}
-
-
-def _hierarchy(mesh):
-    if mesh not in _HIER:
-        from parelagmc_amd.fe import box_mesh, build_hierarchy, mesh_from_json
-        kind, nref = mesh
-        if kind == "tet":
-            m = mesh_from_json(golden_path("meshes", "cube_tet.json"))
-            _HIER[mesh] = build_hierarchy(m, nref)
-        else:
-            n = 4 if kind == "hex" else 3
-            _HIER[mesh] = build_hierarchy(box_mesh([n, n, n], [2, 2, 2], "hex"), nref)
-    return _HIER[mesh]
-
-
-class _Handle:
-    """one sampler handle with what the tests read from it"""
-
-    def __init__(self, ctx, name, storage):
-        from parelagmc_amd import capi
-        from parelagmc_amd.fe import build_hybrid_sampler_problem, build_sampler_problem
-        cfg = HANDLES[name]
-        h = _hierarchy(cfg["mesh"])
-        self.hybrid = cfg["kind"] == "hybrid"
-        build = build_hybrid_sampler_problem if self.hybrid else build_sampler_problem
-        self.prob = build(h, corlen=cfg["corlen"], lognormal=True, n_mc_levels=1)
-        st = capi.PMC_STORAGE_FP64 if storage == "fp64" else capi.PMC_STORAGE_FP32
-        self.opts = capi.solver_opts(precond_storage=st, mg_coarsening=cfg["coarsening"])
-        self.smp = capi.PDESampler(ctx, self.prob, self.opts)
-        self.setup = self.smp.vcycle_setup(0)
-        self.info = self.smp.vcycle_levels(0)
-        self.P = [self.smp.vcycle_prolongator(0, v) for v in range(len(self.setup) - 1)]
-        L = self.prob.levels[0]
-        self.n = L.n_lambda if self.hybrid else L.n_u + L.n_s
-        self.top = self.smp.BatchWidth(0)
-        self.dense_nb = int(self.setup[0]["dense_nb"])
-        self._oracle = None
-
-    @property
-    def oracle(self):
-        if self._oracle is None:
-            from oracle.precond_oracle import SamplerPrecondOracle
-            self._oracle = SamplerPrecondOracle(self.prob, 0, self.setup, self.P, self.opts.schur_scale)
-        return self._oracle
-
-    def narrow(self, nb):
-        return nb <= self.dense_nb
 
 
 _HANDLES = {}
