@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
+SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/darcy_hessian.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -133,3 +133,11 @@ $(ABIBIN)/sampler_adjoint_smoke: tests/c/sampler_adjoint_smoke.c tests/c/prob_io
 	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/sampler_adjoint_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-sampler-adjoint: $(ABIBIN)/sampler_adjoint_smoke
 .PHONY: test-sampler-adjoint
+
+# the Gauss-Newton Hessian action through the mirror classes of parelagmc.hpp (tests/test_gpu_darcy_gn_hessian.py builds and
+# runs it)
+$(ABIBIN)/gn_hessian_smoke: tests/c/gn_hessian_smoke.cpp tests/c/prob_io.h parelagmc_amd/host/parelagmc.hpp include/pmc.h include/pmc_host.h | $(HOSTLIB)
+	@mkdir -p $(ABIBIN)
+	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/gn_hessian_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-gn-hessian: $(ABIBIN)/gn_hessian_smoke
+.PHONY: test-gn-hessian

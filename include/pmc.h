@@ -392,6 +392,18 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
  * adjoint kernel can serve it in a later change. */
 int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
                              double* grad_xi, int memspace, pmc_stats* stats);
+/* Tangent of Eval (an extension): ds_out = (d Eval(level, xi_level) / d xi) v = f' o (L v), with L the
+ * linear part of Eval - Eval of v without the exp() of a lognormal handle, through the same output map, the same solve from a
+ * zero guess and the same launch widths, on every handle kind Eval serves (saddle-point, hybridized, KL; identity, gather and
+ * L2 output maps).  <ds_out, u> = <v, pmc_sampler_eval_adjoint(u)> with the same s_out.
+ *   v       : in, nbatch x xi_size(xi_level)
+ *   s_out   : in, NULL or Eval's output for the xi of the linearization: L v is multiplied by it (f' of the exp()).  NULL
+ *             for callers that want the direction in log s_out (wrt_log of the Darcy entries) and on Gaussian handles,
+ *             where the result is Eval of v bit for bit
+ *   ds_out  : out, nbatch x sample_size(level)
+ * PMC_ERR_INVALID: as pmc_sampler_eval_adjoint (NULL v or ds_out, s_out on a handle that is not lognormal, a conditioner). */
+int pmc_sampler_eval_tangent(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
+                             double* ds_out, int memspace, pmc_stats* stats);
 /* 1 if Eval applies exp() (the lognormal flag of the create call), 0 if not */
 int pmc_sampler_is_lognormal(const pmc_sampler* s);
 /* The prior's part of a log-posterior gradient in the white noise xi ~ N(0, I), on the handle's stream:
@@ -400,6 +412,9 @@ int pmc_sampler_is_lognormal(const pmc_sampler* s);
  * nbatch < 1, NULL xi or grad. */
 int pmc_sampler_logprior_gradient(pmc_sampler* s, int n, int nbatch, const double* xi, double* grad, double* logprior,
                                   int memspace);
+/* The prior's part of a Hessian action of -log pi in the white noise xi ~ N(0, I), on the handle's stream: hv += v (in
+ * place; v, hv: nbatch x n in `memspace`).  PMC_ERR_INVALID: n < 1, nbatch < 1, NULL v or hv. */
+int pmc_sampler_logprior_hessvec(pmc_sampler* s, int n, int nbatch, const double* v, double* hv, int memspace);
 
 /* ---- Field statistics and errors of the sampler drivers (examples/PDESamplerTest.cpp:205-274) ---------------------- */
 /* Accumulators of ONE level's Eval output s (pmc_sampler_sample_size(level) entries per realization) on the device:
@@ -705,6 +720,36 @@ int pmc_darcy_solve_gradient(pmc_darcy* d, int level, int nbatch, const double* 
  * Also refused: no observation functionals on the level, noise <= 0, NULL data. */
 int pmc_darcy_loglik_gradient(pmc_darcy* d, int level, int nbatch, const double* k, const double* data, double noise,
                               int wrt_log, double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj);
+
+/* ---- Gauss-Newton Hessian-vector products of the negative log-likelihood in k (an extension)
+ * With J = dG/dk of the handle's observation functionals: hv = J^T (1/noise) J dk, symmetric positive semi-definite.  For a
+ * direction dk per element (wrt_log != 0: a direction in log k, and hv with respect to log k) the coefficient changes by
+ * dc_e = c'(k_e) dk_e (times k_e), the tangent right-hand side is t_u[f] = -sum_{e has f} dc_e sum_a' M_e[a(f), a'] x_u[f_e(a')]
+ * on the free rows (0 on the essential rows, t_p = 0), A(k) dx = t gives dG_i = <g_i, dp> / sum(g_i) = (J dk)_i, and
+ * A(k) lam = [0; (1/noise) sum_i dG_i g_i / sum(g_i)] gives hv = pmc_darcy_mass_sensitivity(k, x, lam).  Array shapes, memory
+ * spaces, the saddle-point path on hybridized handles and the bitwise independence of a column from the launch width and the
+ * split of a call: as for the gradients above. */
+/* In-situ timing of the tangent right-hand side kernel (the one new kernel), on the pmc_darcy_set_operator_timing switch and
+ * with the meaning of pmc_darcy_operator_time; ALGORITHMIC bytes of one launch for nbatch realizations: per face and side an
+ * element id (4 B), n_fe face indices (4 B) and n_fe matrix entries (8 B) - n_u nside (4 + 12 n_fe) -, k and dk read once
+ * (nbatch x 16 n_p), every row of x_u read and of t_u written once (nbatch x 16 n_u).  The bytes call builds the level's
+ * face-major data when no tangent has been asked for yet. */
+int pmc_darcy_mass_tangent_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms);
+int pmc_darcy_mass_tangent_bytes(pmc_darcy* d, int level, int nbatch, double* bytes);
+/* t_out[b*(n_u+n_p) + f] = the tangent right-hand side for caller-supplied x and dk; the p-rows are zero.  No solve.
+ * Refused with PMC_ERR_INVALID: a level outside [0, n_mc_levels), nbatch < 1, a NULL array. */
+int pmc_darcy_mass_tangent(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, const double* dk,
+                           int wrt_log, double* t_out, int memspace);
+/* hv = J^T (1/noise) J dk.  x_in NULL: the forward solve A(k) x = rhs_bc runs inside, as in pmc_darcy_solve_gradient, and
+ * x_out (may be NULL) returns x; x_in given (sol_out of pmc_darcy_solve_gradient, or x_out of an earlier call): no forward
+ * solve runs, and the result is the same bit for bit.  dG: HOST array nbatch x nobs, may be NULL: J dk.  One per-realization
+ * setup serves all solves; the tangent and the adjoint solve use the operator, preconditioner and options of the forward
+ * solve from a zero guess.  stats_tan / stats_adj (may be NULL): nbatch entries for the two solves.  Refused with
+ * PMC_ERR_INVALID: a level out of range, nbatch < 1, NULL k / dk / hv, no observation functionals on the level, noise <= 0,
+ * x_out together with x_in. */
+int pmc_darcy_gn_hessvec(pmc_darcy* d, int level, int nbatch, const double* k, const double* x_in, const double* dk,
+                         double noise, int wrt_log, double* hv, double* dG, double* x_out, int memspace, pmc_stats* stats_tan,
+                         pmc_stats* stats_adj);
 
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */

@@ -144,6 +144,18 @@ int pmc_bayes_loglik_gradient(pmc_darcy* solver, int level, int nbatch, const do
 int pmc_bayes_logpost_gradient(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
                                const double* xi, int memspace, const double* G_obs, int nobs, double noise, double* logpost,
                                double* grad);
+/* BayesianInverseProblem::ApplyGNHessian (an extension): the Gauss-Newton Hessian of -logpost at xi
+ * applied to nbatch directions v (both nbatch x xi_size(xi_level)),
+ *     hv = v + (dk/dxi)^T J^T (1/noise) J (dk/dxi) v,     J = dG/dk at k = Eval(level, xi),
+ * symmetric positive definite and equal to the full Hessian where G(k) = data, through pmc_sampler_eval_tangent,
+ * pmc_darcy_gn_hessvec (in log k on a lognormal sampler) and pmc_sampler_eval_adjoint; the prior's v is added on the device.
+ * k_state (nbatch x n_p(level)) and x_state (nbatch x (n_u + n_p)) are caller-owned buffers in `memspace`, the linearization
+ * state: have_state == 0: filled from xi (Eval, then the forward solve) and written; have_state != 0: read (xi is not, and
+ * may be NULL), and the call costs two sampler solves and two Darcy solves - a CG loop at a fixed xi pays for the
+ * linearization once.  The observed data do not enter.  xi, v, hv and the state share `memspace`. */
+int pmc_bayes_logpost_gn_hessvec(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                                 const double* xi, const double* v, int memspace, double noise, double* k_state,
+                                 double* x_state, int have_state, double* hv);
 
 /* ---- ML_BayesRatio_Manager / SL_BayesRatio_Manager (src/ML_BayesRatio_Manager.hpp:315-728, src/SL_BayesRatio_Manager.hpp)
  * Multilevel ratio estimator E[Q * likelihood] / E[likelihood]: per realization two INDEPENDENT prior draws, one for

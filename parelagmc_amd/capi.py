@@ -164,8 +164,10 @@ SYMBOLS = {
                                    C.POINTER(pmc_stats)]),
     "pmc_sampler_mult": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.c_int, C.POINTER(pmc_stats)]),
     "pmc_sampler_eval_adjoint": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_sampler_eval_tangent": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats)]),
     "pmc_sampler_is_lognormal": (C.c_int, [_VP]),
     "pmc_sampler_logprior_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.POINTER(C.c_double), C.c_int]),
+    "pmc_sampler_logprior_hessvec": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int]),
     "pmc_sampler_apply_preconditioner": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int]),
     "pmc_sampler_apply_operator": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.c_int, C.POINTER(C.c_double),
                                              C.POINTER(C.c_double)]),
@@ -225,6 +227,11 @@ SYMBOLS = {
     "pmc_darcy_mass_sensitivity_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "pmc_darcy_mass_sensitivity_bytes": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "pmc_darcy_mass_sensitivity": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, _DP, C.c_int]),
+    "pmc_darcy_mass_tangent_time": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "pmc_darcy_mass_tangent_bytes": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "pmc_darcy_mass_tangent": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, _DP, C.c_int]),
+    "pmc_darcy_gn_hessvec": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_double, C.c_int, _DP, C.POINTER(C.c_double),
+                                       _DP, C.c_int, C.POINTER(pmc_stats), C.POINTER(pmc_stats)]),
     "pmc_darcy_solve_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, C.c_int, C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats),
                                            C.POINTER(pmc_stats)]),
@@ -684,6 +691,39 @@ class PDESampler:
         if return_stats:
             return g, [(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in stats]
         return g
+
+    def EvalTangent(self, level, v, s_out=None, xi_level=None, ds_out=None, nbatch=None, return_stats=False):
+        """ds_out = (d Eval / d xi) v (pmc_sampler_eval_tangent): Eval of v without exp(), times s_out when given.  v: (nbatch,
+        xi_size(xi_level)) numpy (host) or a device array (then with nbatch=... and ds_out=...); s_out: None, or Eval's
+        output on a lognormal handle.  Returns ds_out (nbatch, SampleSize(level)); xi_level defaults to level."""
+        if not (0 <= level < self.nlevels):
+            raise PmcError(-1, f"EvalTangent: level {level} out of range")
+        if xi_level is None:
+            xi_level = level
+        single = False
+        if isinstance(v, np.ndarray):
+            single = v.ndim == 1
+            v = _f64(np.atleast_2d(v))
+            nbatch = v.shape[0]
+            if 0 <= xi_level < self.nlevels and v.shape[1] != self.xi_size(xi_level):
+                raise PmcError(-1, "EvalTangent: v does not match xi_size(xi_level)")
+            if s_out is not None:
+                s_out = _f64(np.atleast_2d(s_out))
+                if s_out.shape != (nbatch, self.SampleSize(level)):
+                    raise PmcError(-1, "EvalTangent: s_out does not match SampleSize(level)")
+            if ds_out is None:
+                ds_out = np.empty((nbatch, self.SampleSize(level)))
+        assert nbatch is not None
+        stats = (pmc_stats * max(1, nbatch))()
+        pv, ms = _addr(v)
+        ps, _ = _addr(s_out)
+        pd, _ = _addr(ds_out)
+        _check(self.ctx.lib.pmc_sampler_eval_tangent(self.h, level, xi_level, nbatch, pv, ps, pd, ms, stats))
+        self.last_phase_ms = (sum(s.setup_ms for s in stats), sum(s.solve_ms for s in stats))
+        d = ds_out[0] if single else ds_out
+        if return_stats:
+            return d, [(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in stats]
+        return d
 
     def set_operator_timing(self, on: bool):
         """Bracket every K5 launch of the MINRES loop with HIP events (in-situ kernel time for the roofline)."""
@@ -1364,6 +1404,55 @@ class DarcySolver:
                                                       1 if wrt_log else 0, _ptr(ll, C.c_double), _ptr(G, C.c_double),
                                                       _addr(grad)[0], ms, None))
         return ll, G, grad
+
+    # ---- Gauss-Newton Hessian-vector products in k ----------------------------------------------
+    def mass_tangent_time(self):
+        """the tangent right-hand side kernel under set_operator_timing: (bracket ms, launches, empty-bracket ms)"""
+        ms, n, gap = C.c_double(0.0), C.c_int64(0), C.c_double(0.0)
+        _check(self.ctx.lib.pmc_darcy_mass_tangent_time(self.h, C.byref(ms), C.byref(n), C.byref(gap)))
+        return ms.value, n.value, gap.value
+
+    def mass_tangent_bytes(self, level, nbatch):
+        b = C.c_double(0.0)
+        _check(self.ctx.lib.pmc_darcy_mass_tangent_bytes(self.h, level, nbatch, C.byref(b)))
+        return b.value
+
+    def mass_tangent(self, level, k, x, dk, wrt_log=False, nbatch=None, t_out=None):
+        """t[b, :] = the tangent right-hand side -dA/dk[dk] x on the free u-rows, 0 elsewhere, for caller-supplied full
+        vectors x (nbatch, n_u + n_p) and directions dk (nbatch, n_p); no solve (pmc_darcy_mass_tangent).  numpy arrays, or
+        DeviceArrays / device tensors with nbatch and t_out."""
+        if isinstance(k, np.ndarray):
+            k = _f64(np.atleast_2d(k))
+            nbatch = k.shape[0]
+            if t_out is None:
+                t_out = np.empty((nbatch, self.GetGlobalNumberOfDofs(level)))
+        assert nbatch is not None and t_out is not None
+        pk, ms = _addr(k)
+        (x, px), (dk, pd), (t_out, pt) = self._same_space(ms, x, dk, t_out)
+        _check(self.ctx.lib.pmc_darcy_mass_tangent(self.h, level, nbatch, pk, px, pd, 1 if wrt_log else 0, pt, ms))
+        return t_out
+
+    def gn_hessvec(self, level, k, dk, noise, wrt_log=False, x_in=None, nbatch=None, hv_out=None, want_solution=False,
+                   x_out=None, return_stats=False):
+        """hv = J^T (1/noise) J dk of the observation functionals set with SetObservations (pmc_darcy_gn_hessvec): returns
+        (hv, dG (nbatch, nobs)) - plus x with want_solution or a given x_out (only without x_in: the forward solve then runs
+        inside), plus the (tangent, adjoint) stats lists with return_stats."""
+        k, nbatch, hv = self._grad_out(level, k, nbatch, hv_out)
+        pk, ms = _addr(k)
+        if want_solution and ms == PMC_MEM_HOST and x_out is None:
+            x_out = np.empty((nbatch, self.GetGlobalNumberOfDofs(level)))
+        (dk, pd), (x_in, pi), (x_out, po) = self._same_space(ms, dk, x_in, x_out)
+        nobs = max(self.ctx.lib.pmc_darcy_num_observations(self.h, level), 0)
+        dG = np.empty((nbatch, nobs))
+        st, sa = (pmc_stats * nbatch)(), (pmc_stats * nbatch)()
+        _check(self.ctx.lib.pmc_darcy_gn_hessvec(self.h, level, nbatch, pk, pi, pd, float(noise), 1 if wrt_log else 0,
+                                                 _addr(hv)[0], _ptr(dG, C.c_double), po, ms, st, sa))
+        out = [hv, dG]
+        if x_out is not None:
+            out.append(x_out)
+        if return_stats:
+            out += [[(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in t] for t in (st, sa)]
+        return tuple(out)
 
     def close(self):
         if getattr(self, "h", None):

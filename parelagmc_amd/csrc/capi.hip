@@ -446,6 +446,20 @@ int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch
     });
 }
 
+int pmc_sampler_logprior_hessvec(pmc_sampler* s, int n, int nbatch, const double* v, double* hv, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.prior_hessvec(n, nbatch, v, hv, memspace);
+    });
+}
+int pmc_sampler_eval_tangent(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
+                             double* ds_out, int memspace, pmc_stats* stats) {
+    return guarded([&] {
+        PMC_REQUIRE(s != nullptr, "sampler is NULL");
+        s->impl.eval_tangent(level, xi_level, nbatch, v, s_out, ds_out, memspace, stats);
+    });
+}
+
 int pmc_sampler_is_lognormal(const pmc_sampler* s) { return s ? (s->impl.lognormal ? 1 : 0) : PMC_ERR_INVALID; }
 int pmc_sampler_logprior_gradient(pmc_sampler* s, int n, int nbatch, const double* xi, double* grad, double* logprior,
                                   int memspace) {
@@ -706,6 +720,7 @@ int pmc_darcy_set_operator_timing(pmc_darcy* d, int on) {
         d->impl.op_timer.on = on != 0;
         d->impl.poly_timer.on = on != 0;
         d->impl.grad_timer.on = on != 0;
+        d->impl.tan_timer.on = on != 0;
     });
 }
 int pmc_darcy_operator_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms) {
@@ -754,6 +769,22 @@ int pmc_darcy_mass_sensitivity_bytes(pmc_darcy* d, int level, int nbatch, double
         PMC_REQUIRE(d != nullptr && bytes != nullptr && level >= 0 && level < d->impl.n_mc && valid_batch(nbatch),
                     "pmc_darcy_mass_sensitivity_bytes: bad arguments");
         *bytes = d->impl.mass_sensitivity_bytes(level, nbatch);
+    });
+}
+int pmc_darcy_mass_tangent_time(pmc_darcy* d, double* total_ms, int64_t* launches, double* event_overhead_ms) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy handle is NULL");
+        if (total_ms) *total_ms = d->impl.tan_timer.ms;
+        if (launches) *launches = d->impl.tan_timer.launches;
+        if (event_overhead_ms) *event_overhead_ms = d->impl.tan_timer.gap_ms;
+        d->impl.tan_timer.clear();
+    });
+}
+int pmc_darcy_mass_tangent_bytes(pmc_darcy* d, int level, int nbatch, double* bytes) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr && bytes != nullptr && level >= 0 && level < d->impl.n_mc && valid_batch(nbatch),
+                    "pmc_darcy_mass_tangent_bytes: bad arguments");
+        *bytes = d->impl.mass_tangent_bytes(level, nbatch);
     });
 }
 int pmc_darcy_batch_width(const pmc_darcy* d, int level) {
@@ -907,6 +938,23 @@ int pmc_darcy_loglik_gradient(pmc_darcy* d, int level, int nbatch, const double*
         PMC_REQUIRE(d != nullptr, "darcy is NULL");
         PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
         d->impl.loglik_gradient(level, nbatch, k, data, noise, wrt_log != 0, loglik, G, grad, memspace, stats_adj);
+    });
+}
+int pmc_darcy_mass_tangent(pmc_darcy* d, int level, int nbatch, const double* k, const double* x, const double* dk,
+                           int wrt_log, double* t_out, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.mass_tangent(level, nbatch, k, x, dk, wrt_log != 0, t_out, memspace);
+    });
+}
+int pmc_darcy_gn_hessvec(pmc_darcy* d, int level, int nbatch, const double* k, const double* x_in, const double* dk,
+                         double noise, int wrt_log, double* hv, double* dG, double* x_out, int memspace, pmc_stats* stats_tan,
+                         pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "darcy is NULL");
+        PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "bad memspace");
+        d->impl.gn_hessvec(level, nbatch, k, x_in, dk, noise, wrt_log != 0, hv, dG, x_out, memspace, stats_tan, stats_adj);
     });
 }
 

@@ -177,9 +177,11 @@ void darcy_mass_sensitivity(hipStream_t st, int nb, const ElemMassView& E, const
 // Faces and dense unit-coefficient matrix of every element from the contribution lists the handle already holds on the device
 // (pattern of M in SELL order, c_ptr / c_elem / c_val): the faces of element e are the rows whose DIAGONAL entry e contributes
 // to - the columns of row e of the uneliminated B - in ascending order.  Built once per level, at its first gradient call.
-void Darcy::ensure_gradient(int level) {
+// tangent: also the face-major copy of the same data the tangent right-hand side reads (darcy_hessian.hip), at the level's
+// first tangent / Hessian call; a handle that never asks for one allocates nothing for it.
+void Darcy::ensure_gradient(int level, bool tangent) {
     DarcyLevel& d = lv[level];
-    if (d.has_grad) return;
+    if (d.has_grad && (!tangent || d.has_tan)) return;
     hipStream_t st = ctx.stream;
     const Sell& M = d.M;
     const size_t nslots = (size_t)M.nslots;
@@ -241,12 +243,53 @@ void Darcy::ensure_gradient(int level) {
             me[(sl * nfe * nfe + (size_t)local(e, row) * nfe + local(e, col)) * kWave + le] += c_val[t];
         }
     });
-    d.grad_faces.upload(faces, st);
-    d.grad_me.upload(me, st);
+    if (!d.has_grad) {
+        d.grad_faces.upload(faces, st);
+        d.grad_me.upload(me, st);
+        PMC_HIP(hipStreamSynchronize(st));
+        d.grad_nfe = nfe;
+        d.grad_nslices = nslices;
+        d.has_grad = true;
+    }
+    if (!tangent || d.has_tan) return;
+    // face-major: the sides of face f are the elements that have f among their faces, in ascending element id (the loop
+    // below visits them in that order); side s of f holds the element's faces and row a(f) of its M_e
+    std::vector<int> cnt((size_t)n_u, 0);
+    for (int e = 0; e < n_p; ++e)
+        for (int f : ef[e]) cnt[f]++;
+    int nside = 1;
+    for (int f = 0; f < n_u; ++f) nside = std::max(nside, cnt[f]);
+    const int fslices = (n_u + kWave - 1) / kWave;
+    std::vector<int> selem((size_t)fslices * nside * kWave, -1), scols((size_t)fslices * nside * nfe * kWave, 0);
+    std::vector<double> sw((size_t)fslices * nside * nfe * kWave, 0.0);
+    // padding (a missing side, a slot past the last face): the face itself or the slice's first face, with weight zero
+    for (size_t sl = 0; sl < (size_t)fslices; ++sl)
+        for (size_t j = 0; j < (size_t)nside * nfe; ++j)
+            for (size_t lf = 0; lf < (size_t)kWave; ++lf) {
+                const size_t f = sl * kWave + lf;
+                scols[(sl * nside * nfe + j) * kWave + lf] = (int)(f < (size_t)n_u ? f : sl * kWave);
+            }
+    std::fill(cnt.begin(), cnt.end(), 0);
+    for (int e = 0; e < n_p; ++e) {
+        const size_t esl = (size_t)e / kWave, ele = (size_t)e % kWave;
+        for (int a = 0; a < (int)ef[e].size(); ++a) {
+            const int f = ef[e][a], s = cnt[f]++;
+            const size_t sl = (size_t)f / kWave, lf = (size_t)f % kWave;
+            selem[(sl * nside + s) * kWave + lf] = e;
+            for (int a2 = 0; a2 < nfe; ++a2) {
+                const size_t at = ((sl * nside + s) * nfe + a2) * kWave + lf;
+                scols[at] = faces[(esl * nfe + a2) * kWave + ele];
+                sw[at] = me[(esl * nfe * nfe + (size_t)a * nfe + a2) * kWave + ele];
+            }
+        }
+    }
+    d.tan_elem.upload(selem, st);
+    d.tan_cols.upload(scols, st);
+    d.tan_w.upload(sw, st);
     PMC_HIP(hipStreamSynchronize(st));
-    d.grad_nfe = nfe;
-    d.grad_nslices = nslices;
-    d.has_grad = true;
+    d.tan_nside = nside;
+    d.tan_nslices = fslices;
+    d.has_tan = true;
 }
 
 double Darcy::mass_sensitivity_bytes(int level, int nb) {

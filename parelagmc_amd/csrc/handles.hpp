@@ -114,9 +114,15 @@ struct Sampler {
     // xi_size(xi_level), sample-major; s_out (lognormal handles, may be NULL) multiplies v
     void eval_adjoint(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* grad_xi, int memspace,
                       pmc_stats* stats);
+    // ds_out = (d Eval / d xi) v (pmc_sampler_eval_tangent): Eval of v without exp(), times s_out (lognormal handles, may be
+    // NULL); v nbatch x xi_size(xi_level), s_out / ds_out nbatch x sample_size(level)
+    void eval_tangent(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* ds_out, int memspace,
+                      pmc_stats* stats);
     // the white-noise prior's part of a log-posterior gradient (pmc_sampler_logprior_gradient): grad -= xi in place (nbatch x
     // n, `memspace`), logprior[b] = -|xi_b|^2 / 2 (host, may be NULL)
     void prior_gradient(int n, int nbatch, const double* xi, double* grad, double* logprior, int memspace);
+    // ... and of a Hessian action of -log pi (pmc_sampler_logprior_hessvec): hv += v in place (nbatch x n, `memspace`)
+    void prior_hessvec(int n, int nbatch, const double* v, double* hv, int memspace);
     void apply_operator(int level, int nb, const double* x, double* y, int memspace, int repeat, double* avg_ms,
                         double* bytes);
     // invA[level]->Mult(rhs, sol) on full vectors of n_u + n_s entries per realization (sample-major)
@@ -292,6 +298,13 @@ struct DarcyLevel {
     int grad_nfe = 0, grad_nslices = 0;
     DevBuf<int> grad_faces;
     DevBuf<double> grad_me;
+    // ... and, from the first tangent / Hessian call on (darcy_hessian.hip), the same data face-major
+    // in slices of 64 faces: per face its tan_nside elements in ascending order (-1: none), and per side the element's
+    // faces and the row of M_e that belongs to the face - tan_elem [slice][s][64], tan_cols / tan_w [slice][s n_fe + a'][64]
+    bool has_tan = false;
+    int tan_nside = 0, tan_nslices = 0;
+    DevBuf<int> tan_elem, tan_cols;
+    DevBuf<double> tan_w;
     // the observation functionals as handed over and, for the log-likelihood gradient, diag(1 / sum g_i) Gobs transposed
     // (CSR over the elements, uploaded at the first pmc_darcy_loglik_gradient after a set_observations)
     HostCsr Gobs_host;
@@ -362,9 +375,14 @@ struct Darcy {
     // ... and of the gradient's mass-sensitivity kernel (darcy_gradient.hip), on the same switch
     OpTimer grad_timer;
     double mass_sensitivity_bytes(int level, int nb);   // builds the level's gradient data when it is not there yet
+    // ... and of the tangent right-hand side kernel (darcy_hessian.hip), on the same switch
+    OpTimer tan_timer;
+    double mass_tangent_bytes(int level, int nb);       // builds the level's face-major data when it is not there yet
     DevBuf<double> sol, sol_compact, cx, cd, cx2, stage_k, stage_sol, qpartial, qout, gtmp, gout;
     // adjoint solve (darcy_gradient.hip): right-hand side and second full solution, host staging; allocated at first use
     DevBuf<double> adj_rhs, adj_sol, stage_adj, stage_grad, obs_data;
+    // tangent solve (darcy_hessian.hip): third full solution, host staging of the direction; allocated at first use
+    DevBuf<double> tan_sol, stage_dk;
     bool use_eg(const DarcyLevel& d) const;
     void set_observations(int level, const pmc_csr* Gobs);
     void compute_G(int level, int nbatch, const double* k, double* G, double* C, double* Q, int memspace, pmc_stats* stats);
@@ -387,6 +405,12 @@ struct Darcy {
                         pmc_stats* stats_adj);
     void loglik_gradient(int level, int nbatch, const double* k, const double* data, double noise, bool wrt_log,
                          double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj);
+    // Tangent right-hand side and Gauss-Newton Hessian action (pmc_darcy_mass_tangent / _gn_hessvec, darcy_hessian.hip);
+    // the saddle-point path on every handle, as the gradients
+    void mass_tangent(int level, int nbatch, const double* k, const double* x, const double* dk, bool wrt_log, double* t_out,
+                      int memspace);
+    void gn_hessvec(int level, int nbatch, const double* k, const double* x_in, const double* dk, double noise, bool wrt_log,
+                    double* hv, double* dG, double* x_out, int memspace, pmc_stats* stats_tan, pmc_stats* stats_adj);
     // setup values of one level of the V-cycle `level`'s solves run (pmc_darcy_vcycle_level)
     void vcycle_level(int level, int vlevel, int* nvlevels, double* info) const;
     // P from V-cycle level vlevel + 1 to vlevel of that cycle (pmc_darcy_vcycle_prolongator), rows of vlevel 0 in the caller's
@@ -420,8 +444,12 @@ struct Darcy {
         const double* data = nullptr;     // loglik: observed values (host, n_gobs)
         double noise = 1.0;
     };
-    void ensure_gradient(int level);
+    void ensure_gradient(int level, bool tangent = false);   // tangent: the face-major copy as well
     void ensure_loglik(int level);
+    // darcy_hessian.hip
+    void gn_hessvec_chunk(int level, int nb, const double* k_d, const double* x_in_d, const double* dk_d, double noise,
+                          bool wrt_log, double* hv_d, double* dG_host, double* x_out_d, pmc_stats* stats_tan,
+                          pmc_stats* stats_adj);
     void gradient_chunk(int level, int nb, const double* k_d, const AdjointSpec& adj, bool wrt_log, double* Q_host,
                         double* G_host, double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd,
                         pmc_stats* stats_adj);

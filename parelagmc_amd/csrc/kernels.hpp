@@ -341,6 +341,20 @@ struct ElemMassView {
 void darcy_mass_sensitivity(hipStream_t st, int nb, const ElemMassView& E, const double* kfield, const double* x,
                             const double* lam, bool k_divides, bool wrt_log, double* out);
 
+// Tangent right-hand side (darcy_hessian.hip), the transpose of the above in (dk, lam):
+// out[f][b] = sum_s ndc[elem_s(f)][b] (sum_a' w_s(f)[a'] x[cols_s(f)(a')][b]) on the rows f < n_rows, exactly 0 where ess[f];
+// ndc = f(k) dk with the f above (= -dc).  Face-major in slices of 64 faces, column-major inside a slice: elem [slice][s][64]
+// (-1: no such side; its cols are valid rows, its w zero), cols / w [slice][s nfe + a'][64].  x and out interleaved [row][nb],
+// kfield and dk sample-major.  Sides in ascending element id, a' ascending, no atomics: column b does not depend on nb.
+struct FaceMassView {
+    int n_rows = 0, n_elem = 0, nslices = 0, nfe = 0, nside = 0;
+    const int* elem = nullptr;
+    const int* cols = nullptr;
+    const double* w = nullptr;
+};
+void darcy_mass_tangent(hipStream_t st, int nb, const FaceMassView& F, const double* kfield, const double* dk, const double* x,
+                        const unsigned char* ess, bool k_divides, bool wrt_log, double* out);
+
 }  // namespace k
 }  // namespace pmc
 

@@ -7,6 +7,10 @@
 // i.e. the level's own solve with O^T (v o s_out) in the s-rows of the right-hand side, prolongated to xi_level and scaled.
 // The solve IS Eval's (Sampler::solve_system, zero guess) under a graph key of its own.  The factor -g is applied in the
 // seed: everything after it is linear.
+//
+// Tangent of Eval (pmc_sampler_eval_tangent): ds_out = f' o (O S R D v), the linear part of Eval applied
+// to the direction - Eval itself with the exp() of its stores switched off, so the same solve from a zero guess at the same
+// launch widths on every handle kind - times s_out, the f' of a lognormal handle, when the caller hands it over.
 #include "handles.hpp"
 
 namespace pmc {
@@ -37,6 +41,46 @@ __global__ __launch_bounds__(kPriorThreads) void prior_gradient_kernel(int n, co
 }
 }
 
+namespace {
+// out[i] *= s[i]: the f' = s_out of a lognormal handle on the tangent
+__global__ void mul_inplace_kernel(size_t total, const double* __restrict__ s, double* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < total) out[t] *= s[t];
+}
+}
+
+void Sampler::eval_tangent(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* ds_out,
+                           int memspace, pmc_stats* stats) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "EvalTangent: level out of range");
+    PMC_REQUIRE(xi_level >= 0 && xi_level <= level, "EvalTangent: xi_level must satisfy 0 <= xi_level <= level");
+    PMC_REQUIRE(nbatch >= 1 && v != nullptr && ds_out != nullptr, "EvalTangent: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "EvalTangent: bad memspace");
+    PMC_REQUIRE(s_out == nullptr || lognormal, "EvalTangent: s_out given on a handle that is not lognormal");
+    PMC_REQUIRE(cond == nullptr, "EvalTangent: a conditioner is attached (pmc_sampler_set_conditioner); the tangent of the "
+                                 "conditional field is not implemented");
+    // Eval of v with the exp() of the stores off: the flag is a plain argument of every store Eval ends in
+    struct FlagOff {
+        bool& f;
+        const bool keep;
+        explicit FlagOff(bool& flag) : f(flag), keep(flag) { f = false; }
+        ~FlagOff() { f = keep; }
+    };
+    {
+        FlagOff off(lognormal);
+        eval(level, xi_level, nbatch, v, ds_out, nullptr, 0, false, nullptr, memspace, stats);
+    }
+    if (!s_out) return;
+    const size_t total = (size_t)lv[level].out_size * nbatch;
+    if (memspace == PMC_MEM_HOST) {           // Eval has synchronised; host arrays are staged, so the product is the host's
+        for (size_t i = 0; i < total; ++i) ds_out[i] *= s_out[i];
+        return;
+    }
+    hipStream_t st = ctx.stream;
+    mul_inplace_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(total, s_out, ds_out);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+}
+
 void Sampler::prior_gradient(int n, int nbatch, const double* xi, double* grad, double* logprior, int memspace) {
     PMC_REQUIRE(n >= 1 && nbatch >= 1 && xi != nullptr && grad != nullptr, "logprior_gradient: bad arguments");
     PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "logprior_gradient: bad memspace");
@@ -62,6 +106,39 @@ void Sampler::prior_gradient(int n, int nbatch, const double* xi, double* grad, 
     // the scalars cross to the host only when asked for; a device-memory call without them does not synchronise
     if (logprior) PMC_HIP(hipMemcpyAsync(logprior, adj_lp.p, sizeof(double) * nbatch, hipMemcpyDeviceToHost, st));
     if (logprior || memspace == PMC_MEM_HOST) PMC_HIP(hipStreamSynchronize(st));
+}
+
+namespace {
+// hv[i] += v[i]: the N(0, I) prior's part of a Hessian action in the white noise
+__global__ void add_inplace_kernel(size_t total, const double* __restrict__ v, double* __restrict__ hv) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < total) hv[t] += v[t];
+}
+}
+
+void Sampler::prior_hessvec(int n, int nbatch, const double* v, double* hv, int memspace) {
+    PMC_REQUIRE(n >= 1 && nbatch >= 1 && v != nullptr && hv != nullptr, "logprior_hessvec: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "logprior_hessvec: bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const size_t cnt = (size_t)n * nbatch;
+    const double* v_d = v;
+    double* h_d = hv;
+    if (memspace == PMC_MEM_HOST) {
+        stage_in.ensure(cnt);
+        stage_out.ensure(cnt);
+        PMC_HIP(hipMemcpyAsync(stage_in.p, v, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        PMC_HIP(hipMemcpyAsync(stage_out.p, hv, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        v_d = stage_in.p;
+        h_d = stage_out.p;
+    }
+    add_inplace_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, st>>>(cnt, v_d, h_d);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    if (memspace == PMC_MEM_HOST) {
+        PMC_HIP(hipMemcpyAsync(hv, stage_out.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipStreamSynchronize(st));
+    }
 }
 
 namespace {

@@ -1,6 +1,7 @@
 """Adjoint gradients of the mixed Darcy solve with respect to the permeability field, in numpy / scipy with sparse direct
 solves: the twin of pmc_darcy_mass_sensitivity / _solve_gradient / _loglik_gradient (csrc/darcy_gradient.hip, DESIGN.md
-section 16).  The reference has no gradients; everything here follows from the level data of a DarcyProblem alone.
+section 16) and of pmc_darcy_mass_tangent / _gn_hessvec (csrc/darcy_hessian.hip, section 18).  The reference has no
+derivatives; everything here follows from the level data of a DarcyProblem alone.
 
 With the essential rows and columns of A(k) = [M(k) B^T; B 0] eliminated (unit diagonal, the essential values in the
 right-hand side) the system stays symmetric, so for a functional J(x)
@@ -11,6 +12,13 @@ right-hand side) the system stays symmetric, so for a functional J(x)
 x_u holds the essential values and lam_u vanishes on the essential rows, so the derivative of the eliminated right-hand side
 -M(k)[:, ess] ess_data is part of the same bilinear form.  M_e is the unit-coefficient element matrix of the level's
 contribution lists.
+
+Second order (Gauss-Newton): for a direction dk the coefficient changes by dc_e = c'(k_e) dk_e and the solution by dx with
+
+    A(k) dx = t,    t_u[f] = -sum_{e has f} dc_e sum_a' M_e[a(f), a'] x_u[f_e(a')]  (0 on the essential rows),   t_p = 0,
+
+so J dk = dG with dG_i = <g_i, dp> / sum(g_i), and J^T (1/noise) J dk = mass_sensitivity(k, x, lam) with
+A(k) lam = [0; (1/noise) sum_i dG_i g_i / sum(g_i)]: the Hessian of the NEGATIVE log-likelihood where the misfit vanishes.
 """
 from __future__ import annotations
 
@@ -131,3 +139,69 @@ def loglik_gradient(problem, level, k, Gobs, data, noise, wrt_log=False):
     b[L.n_u:] = -(1.0 / noise) * (Gobs.T @ (norm * r))
     lam = lu.solve(b)
     return loglik, G, mass_sensitivity(L, k, x, lam, problem.k_divides, wrt_log)[0]
+
+
+def mass_tangent(level, k, x, dk, k_divides, wrt_log=False, return_abs=False, dtype=np.float64):
+    """t = -dA/dk[dk] x on the free u-rows (0 on the essential rows and on the p-rows) for full vectors x of n_u + n_p
+    entries and directions dk of n_p entries (one realization, or rows of 2-D arrays): the transpose of mass_sensitivity in
+    the pair (dk, lam), <lam, mass_tangent(dk)> = <dk, mass_sensitivity(lam)> for lam zero on the essential rows.
+    return_abs: also sum |dc| |M_aa' x_a'| per row (the scale of a summation error bound).  dtype: the precision the sums
+    are formed in."""
+    faces, Me = element_matrices(level)
+    L = level
+    k, x, dk = (np.atleast_2d(np.asarray(a, dtype=dtype)) for a in (k, x, dk))
+    ndc = _minus_dc(k, k_divides, wrt_log) * dk                       # -dc, (nb, n_p)
+    # an element with fewer than n_fe faces repeats its first face with zero rows: the scatter below adds zeros there
+    Me = Me.astype(dtype)
+    xu = x[:, faces]                                                  # (nb, n_p, n_fe)
+    free = ~L.ess_mask.astype(bool)
+    nb, n = x.shape[0], L.n_u + L.n_p
+
+    def scatter(contrib):                                             # (nb, n_p, n_fe) -> (nb, n)
+        t = np.zeros((nb, n), dtype=dtype)
+        for b in range(nb):
+            np.add.at(t[b], faces.ravel(), contrib[b].ravel())
+        t[:, :L.n_u] *= free
+        return t
+
+    t = scatter(ndc[:, :, None] * np.einsum("eac,bec->bea", Me, xu))
+    if return_abs:
+        return t, scatter(np.abs(ndc)[:, :, None] * np.einsum("eac,bec->bea", np.abs(Me), np.abs(xu)))
+    return t
+
+
+def _observations(Gobs):
+    Gobs = sp.csr_matrix(Gobs)
+    return Gobs, 1.0 / np.asarray(Gobs.sum(axis=1)).ravel()
+
+
+def tangent(problem, level, k, dk, Gobs=None, wrt_log=False, return_all=False):
+    """dx = (dx/dk) dk of the forward solution of one realization by two direct solves; with Gobs: dG = J dk instead.
+    return_all: (dG or dx, x, dx, lu)."""
+    L = problem.levels[level]
+    A, rhs, ess = assemble(problem, level, k)
+    lu = spla.splu(A)
+    x = lu.solve(rhs)
+    dx = lu.solve(mass_tangent(L, k, x, dk, problem.k_divides, wrt_log)[0])
+    out = dx
+    if Gobs is not None:
+        Gobs, norm = _observations(Gobs)
+        out = norm * (Gobs @ dx[L.n_u:])
+    if return_all:
+        return out, x, dx, lu
+    return out
+
+
+def gn_hessvec(problem, level, k, dk, Gobs, noise, wrt_log=False, return_all=False):
+    """hv = J^T (1/noise) J dk of the negative log-likelihood of loglik_gradient, J = dG/dk (dG/dlog k with wrt_log, dk then
+    a direction in log k): symmetric positive semi-definite, the full Hessian where G(k) = data.  return_all: (hv, dG, x)."""
+    L = problem.levels[level]
+    dG, x, _, lu = tangent(problem, level, k, dk, Gobs, wrt_log, return_all=True)
+    Gobs, norm = _observations(Gobs)
+    b = np.zeros(L.n_u + L.n_p)
+    b[L.n_u:] = (1.0 / noise) * (Gobs.T @ (norm * dG))
+    lam = lu.solve(b)
+    hv = mass_sensitivity(L, k, x, lam, problem.k_divides, wrt_log)[0]
+    if return_all:
+        return hv, dG, x
+    return hv

@@ -14,6 +14,10 @@ The block operator is symmetric, so S is, and for v = dJ/ds_out
 
 Eval of a KL sampler is s = f(Phi_level Lambda^1/2 xi[:m]); its adjoint is (Phi_level Lambda^1/2)^T (v o f') in the first m
 entries and zero in the others.
+
+Second order: the tangent of Eval is ds_out = f' o (L v) with L = O S R D the linear part (Eval of v
+without exp), and the Gauss-Newton Hessian of -log pi is H_GN v = v + L^T J^T (1/noise) J L v (in log k on a lognormal
+problem): pmc_sampler_eval_tangent and BayesianInverseProblem::ApplyGNHessian.
 """
 from __future__ import annotations
 
@@ -109,3 +113,38 @@ def logpost_gradient(sampler_problem, darcy_problem, level, xi, Gobs, data, nois
     loglik, _, gk = darcy_adjoint.loglik_gradient(darcy_problem, level, k, Gobs, data, noise, wrt_log=logn)
     grad = -xi + eval_adjoint(sampler_problem, level, xi_level, gk, None, projection, cache)
     return loglik - 0.5 * float(xi @ xi), grad
+
+
+def eval_tangent(problem, level, xi_level, v, s_out=None, projection=None, cache=None):
+    """ds_out = (d Eval / d xi) v of one realization: L v, the Gaussian part of Eval applied to v (no exp), times s_out when
+    given (Eval's output on a lognormal problem: the f' of the exp).  <eval_tangent(v), u> = <v, eval_adjoint(u)>."""
+    if s_out is not None and not problem.lognormal:
+        raise ValueError("s_out given for a problem that is not lognormal")
+    if not 0 <= xi_level <= level < problem.n_mc_levels:
+        raise ValueError("need 0 <= xi_level <= level < n_mc_levels")
+    v = np.asarray(v, dtype=np.float64)
+    if _is_kl(problem):
+        g = kl_modes(problem, level) @ v[:problem.nmodes]
+    else:
+        r = -problem.matern_g * np.sqrt(problem.levels[xi_level].w_diag) * v
+        for lvl in range(xi_level, level):
+            r = problem.levels[lvl].P.T @ r
+        L = problem.levels[level]
+        g = _block_solver(problem, level, cache).solve(np.concatenate([np.zeros(L.n_u), r]))[L.n_u:]
+        if projection is not None:
+            g = g[np.asarray(projection[1])] if projection[0] == "gather" else (projection[1] @ g) * projection[2]
+    return g if s_out is None else g * np.asarray(s_out, dtype=np.float64)
+
+
+def logpost_gn_hessvec(sampler_problem, darcy_problem, level, xi, v, Gobs, noise, xi_level=None, projection=None, cache=None):
+    """H_GN v = v + (dk/dxi)^T J^T (1/noise) J (dk/dxi) v of -log pi at xi (logpost_gradient's log pi): symmetric positive
+    definite, the full Hessian where G(k) = data.  On a lognormal problem the chain runs in log k (wrt_log, no s_out), as
+    logpost_gradient chains the first derivatives; on a Gaussian one k is the field itself."""
+    xi = np.asarray(xi, dtype=np.float64)
+    v = np.asarray(v, dtype=np.float64)
+    xi_level = level if xi_level is None else xi_level
+    k = eval_forward(sampler_problem, level, xi_level, xi, projection, cache)
+    logn = bool(sampler_problem.lognormal)
+    dk = eval_tangent(sampler_problem, level, xi_level, v, None, projection, cache)
+    hk = darcy_adjoint.gn_hessvec(darcy_problem, level, k, dk, Gobs, noise, wrt_log=logn)
+    return v + eval_adjoint(sampler_problem, level, xi_level, hk, None, projection, cache)

@@ -129,6 +129,23 @@ void PDESampler::Eval(const int level, const Vector& xi, Vector& s, Vector& u, b
     }
     record(level, st);
 }
+void PDESampler::EvalTangent(const int level, const Vector& v, const Vector* s_or_null, Vector& ds, int xi_level) {
+    if (xi_level < 0) xi_level = level;
+    const int n_xi = pmc_sampler_xi_size(h_, xi_level), n_out = SampleSize(level);
+    if (n_xi < 0 || n_out < 0) throw std::out_of_range("PDESampler::EvalTangent: level");
+    if (v.Size() != n_xi) throw std::invalid_argument("PDESampler::EvalTangent: v does not match xi_size(xi_level)");
+    if (ds.MemSpace() != v.MemSpace() || (s_or_null && s_or_null->MemSpace() != v.MemSpace()))
+        throw std::invalid_argument("PDESampler::EvalTangent: v, s and ds must share a memory space");
+    if (s_or_null && (s_or_null->Size() != n_out || s_or_null->Batch() != v.Batch()))
+        throw std::invalid_argument("PDESampler::EvalTangent: s does not match SampleSize(level) x v.Batch()");
+    ds.SetSize(n_out, v.Batch());
+    std::vector<pmc_stats> st(v.Batch());
+    check_arg(pmc_sampler_eval_tangent(h_, level, xi_level, v.Batch(), v.GetData(), s_or_null ? s_or_null->GetData() : nullptr,
+                                       ds.GetData(), v.MemSpace(), st.data()),
+              "PDESampler::EvalTangent");
+    if ((int)adj_times_.size() <= level) adj_times_.resize(level + 1);
+    adj_times_[level].add(st.data(), (int)st.size());
+}
 void PDESampler::EvalAdjoint(const int level, const Vector& v, const Vector* s_or_null, Vector& grad_xi, int xi_level) {
     if (xi_level < 0) xi_level = level;
     const int n_xi = pmc_sampler_xi_size(h_, xi_level), n_out = SampleSize(level);
@@ -257,6 +274,25 @@ void DarcySolver::SolveFwd_Gradient(int ilevel, Vector& k, double* Q, double* C,
     record(ilevel, st);
     record(ilevel, sta);
 }
+void DarcySolver::SolveFwd_GNHessVec(int ilevel, Vector& k, const Vector& dk, double noise, Vector& x, bool x_given, Vector& hv,
+                                     double* dG, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel), n = pmc_darcy_num_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::SolveFwd_GNHessVec: level");
+    if (dk.MemSpace() != k.MemSpace() || x.MemSpace() != k.MemSpace() || hv.MemSpace() != k.MemSpace())
+        throw std::invalid_argument("SolveFwd_GNHessVec: k, dk, x and hv must share a memory space");
+    if (dk.Size() != k.Size() || dk.Batch() != k.Batch()) throw std::invalid_argument("SolveFwd_GNHessVec: dk does not match k");
+    if (x_given && (x.Size() != n || x.Batch() != k.Batch()))
+        throw std::invalid_argument("SolveFwd_GNHessVec: x does not hold the forward solutions of k");
+    if (!x_given) x.SetSize(n, k.Batch());
+    hv.SetSize(np, k.Batch());
+    std::vector<pmc_stats> st(k.Batch()), sta(k.Batch());
+    check_arg(pmc_darcy_gn_hessvec(h_, ilevel, k.Batch(), k.GetData(), x_given ? x.GetData() : nullptr, dk.GetData(), noise,
+                                   wrt_log ? 1 : 0, hv.GetData(), dG, x_given ? nullptr : x.GetData(), k.MemSpace(), st.data(),
+                                   sta.data()),
+              "DarcySolver::SolveFwd_GNHessVec");
+    record(ilevel, st);
+    record(ilevel, sta);
+}
 int DarcySolver::GetSizeOfStochasticData(int l) const { return pmc_darcy_num_pressure_dofs(h_, l); }
 int DarcySolver::GetNumberOfDofs(int l) const { return pmc_darcy_num_dofs(h_, l); }
 int DarcySolver::GetGlobalNumberOfDofs(int l) const { return pmc_darcy_num_dofs(h_, l); }
@@ -326,6 +362,49 @@ void BayesianInverseProblem::ComputeGradLogPosterior(int ilevel, PDESampler& sam
               "BayesianInverseProblem::ComputeGradLogPosterior");
     if (logpost)
         for (int b = 0; b < nb; ++b) logpost[b] = ll[(size_t)b] + lp[(size_t)b];
+}
+void BayesianInverseProblem::ApplyGNHessian(int ilevel, PDESampler& sampler, const Vector& xi, const Vector& v, Vector& hv,
+                                            int xi_level, bool reuse_state) {
+    if (!state_k_ || state_k_->MemSpace() != xi.MemSpace()) {
+        if (reuse_state) throw std::invalid_argument("ApplyGNHessian: reuse_state without a state in this memory space");
+        state_k_.reset(new Vector(sampler.Context(), xi.MemSpace()));
+        state_x_.reset(new Vector(sampler.Context(), xi.MemSpace()));
+    }
+    ApplyGNHessian(ilevel, sampler, xi, v, hv, xi_level, *state_k_, *state_x_, reuse_state);
+}
+void BayesianInverseProblem::ApplyGNHessian(int ilevel, PDESampler& sampler, const Vector& xi, const Vector& v, Vector& hv,
+                                            int xi_level, Vector& k, Vector& x, bool have_state) {
+    const int ms = xi.MemSpace(), nb = xi.Batch();
+    if (v.MemSpace() != ms || hv.MemSpace() != ms || k.MemSpace() != ms || x.MemSpace() != ms)
+        throw std::invalid_argument("ApplyGNHessian: xi, v, hv and the state must share a memory space");
+    if (v.Size() != xi.Size() || v.Batch() != nb) throw std::invalid_argument("ApplyGNHessian: v does not match xi");
+    for (int l = 0; l <= ilevel && xi_level < 0; ++l)
+        if (pmc_sampler_xi_size(sampler.Handle(), l) == xi.Size()) xi_level = l;
+    if (xi_level < 0 || xi_level > ilevel || pmc_sampler_xi_size(sampler.Handle(), xi_level) != xi.Size())
+        throw std::invalid_argument("ApplyGNHessian: xi matches no level up to ilevel (or not the xi_level named)");
+    const int np = pmc_darcy_num_pressure_dofs(solver_, ilevel), n = pmc_darcy_num_dofs(solver_, ilevel);
+    if (np < 0) throw std::out_of_range("BayesianInverseProblem::ApplyGNHessian: level");
+    if (have_state && (k.Size() != np || k.Batch() != nb || x.Size() != n || x.Batch() != nb))
+        throw std::invalid_argument("ApplyGNHessian: the state does not belong to this level and batch");
+    const bool logn = sampler.IsLognormal();
+    if (!work_dk_ || work_dk_->MemSpace() != ms) {
+        work_dk_.reset(new Vector(sampler.Context(), ms));
+        work_hk_.reset(new Vector(sampler.Context(), ms));
+    }
+    Vector &dk = *work_dk_, &hk = *work_hk_;
+    if (!have_state) {
+        if (sampler.SampleSize(ilevel) != np) throw std::invalid_argument("ApplyGNHessian: the sampler's output is not the solver's k");
+        sampler.EvalAt(ilevel, xi_level, xi, k);
+        x.SetSize(n, nb);
+    }
+    sampler.EvalTangent(ilevel, v, nullptr, dk, xi_level);      // d(log k) on a lognormal handle: wrt_log carries the factor k
+    hk.SetSize(np, nb);
+    check_arg(pmc_darcy_gn_hessvec(solver_, ilevel, nb, k.GetData(), have_state ? x.GetData() : nullptr, dk.GetData(), noise_,
+                                   logn ? 1 : 0, hk.GetData(), nullptr, have_state ? nullptr : x.GetData(), ms, nullptr, nullptr),
+              "BayesianInverseProblem::ApplyGNHessian");
+    sampler.EvalAdjoint(ilevel, hk, nullptr, hv, xi_level);
+    check_arg(pmc_sampler_logprior_hessvec(sampler.Handle(), xi.Size(), nb, v.GetData(), hv.GetData(), ms),
+              "BayesianInverseProblem::ApplyGNHessian");
 }
 void BayesianInverseProblem::ComputeR(int ilevel, Vector& k, double* R, double* C) {
     std::vector<double> q(k.Batch());
@@ -1806,6 +1885,31 @@ int pmc_bayes_logpost_gradient(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* so
         BayesianInverseProblem prob(solver, noise, std::vector<double>(G_obs, G_obs + nobs));
         View xv(const_cast<double*>(xi), n_xi, nbatch, memspace), gv(grad, n_xi, nbatch, memspace);
         prob.ComputeGradLogPosterior(level, smp, xv, logpost, gv, xi_level);
+    });
+}
+
+int pmc_bayes_logpost_gn_hessvec(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                                 const double* xi, const double* v, int memspace, double noise, double* k_state,
+                                 double* x_state, int have_state, double* hv) {
+    return hguard([&] {
+        if (!ctx || !sampler || !solver || !v || !hv || !k_state || !x_state || nbatch < 1 || !(noise > 0.0) ||
+            (!xi && !have_state))
+            throw std::invalid_argument("pmc_bayes_logpost_gn_hessvec: bad argument");
+        struct View : Vector {     // non-owning batch views of the caller's arrays
+            View(double* p, int n, int nb, int ms) : Vector(nullptr, ms) { Adopt(p, n, nb); }
+            ~View() { Release(); }
+        };
+        if (level < 0 || level >= pmc_sampler_num_levels(sampler) || xi_level < 0 || xi_level > level)
+            throw std::invalid_argument("pmc_bayes_logpost_gn_hessvec: level / xi_level out of range");
+        const int n_xi = pmc_sampler_xi_size(sampler, xi_level);
+        const int np = pmc_darcy_num_pressure_dofs(solver, level), n = pmc_darcy_num_dofs(solver, level);
+        if (np <= 0 || n <= 0) throw std::invalid_argument("pmc_bayes_logpost_gn_hessvec: level out of the solver's range");
+        PDESampler smp(ctx, sampler);
+        BayesianInverseProblem prob(solver, noise, std::vector<double>());
+        // (with have_state xi may be NULL: the view is sized, never read)
+        View xv(const_cast<double*>(xi), n_xi, nbatch, memspace), vv(const_cast<double*>(v), n_xi, nbatch, memspace);
+        View gv(hv, n_xi, nbatch, memspace), kv(k_state, np, nbatch, memspace), sv(x_state, n, nbatch, memspace);
+        prob.ApplyGNHessian(level, smp, xv, vv, gv, xi_level, kv, sv, have_state != 0);
     });
 }
 

@@ -172,6 +172,11 @@ class PDESampler : public MLSampler {
     /// multiplied by it).  grad_xi is sized to v.Batch() x xi_size(xi_level) in v's memory space; xi_level < 0: level.
     /// The adjoint solves are timed apart from Eval's: GetPhaseTimes / GetNumIters keep meaning the forward solves.
     void EvalAdjoint(const int level, const Vector& v, const Vector* s_or_null, Vector& grad_xi, int xi_level = -1);
+    /// The tangent of Eval in the white noise (pmc_sampler_eval_tangent): ds = (d Eval / d xi) v for every realization of v
+    /// (v.Batch() x xi_size(xi_level)): Eval of v without exp(), times s_or_null when given (Eval's output on a lognormal
+    /// handle).  ds is sized to v.Batch() x SampleSize(level) in v's memory space; xi_level < 0: level.  Timed with the adjoint
+    /// solves, apart from Eval's.
+    void EvalTangent(const int level, const Vector& v, const Vector* s_or_null, Vector& ds, int xi_level = -1);
     PhaseTimes GetAdjointPhaseTimes(int level) const { return level < (int)adj_times_.size() ? adj_times_[level] : PhaseTimes(); }
     int GetNumAdjointIters() const { return last_adj_iters_; }
     bool IsLognormal() const { return pmc_sampler_is_lognormal(h_) == 1; }
@@ -268,6 +273,13 @@ class DarcySolver : public PhysicalMLSolver {
     /// GetSizeOfStochasticData(ilevel) x k.Batch() in k's memory space (pmc_darcy_solve_gradient; an extension, the
     /// reference has no gradients).  Q, C: host arrays of k.Batch(), may be NULL.
     void SolveFwd_Gradient(int ilevel, Vector& k_over_k_ref, double* Q, double* C, Vector& grad, bool wrt_log = false);
+    /// Gauss-Newton Hessian action hv = J^T (1/noise) J dk of the negative log-likelihood of the handle's observation
+    /// functionals, J = dG/dk (wrt_log: in log k), for every realization (pmc_darcy_gn_hessvec; an extension).  x: the forward
+    /// solutions, GetNumberOfDofs(ilevel) x k.Batch() - x_given false: solved inside and written to x; true: read, and no
+    /// forward solve runs.  hv is sized like k; k, dk, x, hv share a memory space.  dG: host array k.Batch() x nobs = J dk,
+    /// may be NULL.
+    void SolveFwd_GNHessVec(int ilevel, Vector& k_over_k_ref, const Vector& dk, double noise, Vector& x, bool x_given, Vector& hv,
+                            double* dG = nullptr, bool wrt_log = false);
     int GetSizeOfStochasticData(int ilevel) const;   // entries of k (src/DarcySolver.hpp:127-130)
     int GetNumberOfDofs(int ilevel) const override;
     int GetGlobalNumberOfDofs(int ilevel) const override;
@@ -338,6 +350,18 @@ class BayesianInverseProblem {
     /// calls.
     void ComputeGradLogPosterior(int ilevel, PDESampler& sampler, const Vector& xi, double* logpost, Vector& grad,
                                  int xi_level = -1);
+    /// Gauss-Newton Hessian of -log pi at xi applied to v for every realization: hv = v + (dk/dxi)^T J^T (1/noise) J (dk/dxi) v,
+    /// symmetric positive definite, the full Hessian where G(k) = data (pmc_sampler_eval_tangent, pmc_darcy_gn_hessvec - in log k
+    /// on a lognormal sampler, as ComputeGradLogPosterior chains the first derivatives -, pmc_sampler_eval_adjoint; the prior's
+    /// v is added on the device).  v and hv are sized like xi, in xi's memory space; xi_level as in ComputeGradLogPosterior.
+    /// reuse_state false: the linearization state - k = Eval(xi) and the forward solution - is computed from xi and kept;
+    /// true: the state of the previous call is used (same ilevel, batch and memory space; xi is not read), and the call
+    /// costs two sampler solves and two Darcy solves: a CG loop at a fixed xi pays for the linearization once.
+    void ApplyGNHessian(int ilevel, PDESampler& sampler, const Vector& xi, const Vector& v, Vector& hv, int xi_level = -1,
+                        bool reuse_state = false);
+    /// the same on caller-owned state vectors k (n_p x batch) and x (n_u + n_p x batch)
+    void ApplyGNHessian(int ilevel, PDESampler& sampler, const Vector& xi, const Vector& v, Vector& hv, int xi_level,
+                        Vector& k_state, Vector& x_state, bool have_state);
     int SizeOfObservationalData() const { return (int)G_obs_.size(); }
 
   private:
@@ -345,6 +369,7 @@ class BayesianInverseProblem {
     double noise_;
     std::vector<double> G_obs_;
     std::unique_ptr<Vector> work_k_, work_gk_;   // ComputeGradLogPosterior
+    std::unique_ptr<Vector> state_k_, state_x_, work_dk_, work_hk_;   // ApplyGNHessian: linearization state, dk, J^T J dk
 };
 
 double expWRegression(const std::vector<double>& y, const std::vector<double>& x, int skip_n_last);

@@ -73,6 +73,8 @@ HOST_SYMBOLS = {
                                             _VP]),
     "pmc_bayes_logpost_gradient": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double,
                                              _DPTR, _VP]),
+    "pmc_bayes_logpost_gn_hessvec": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_double, _VP, _VP,
+                                               C.c_int, _VP]),
     "pmc_ratio_create": (C.c_int, [_VP, _VP, _VP, C.c_int, _DPTR, C.c_int, C.c_double, C.POINTER(pmc_mlmc_params),
                                    C.POINTER(_VP)]),
     "pmc_ratio_create_callbacks": (C.c_int, [C.c_int, C.POINTER(pmc_plugin_callbacks), _VP, C.POINTER(pmc_mlmc_params),
@@ -202,6 +204,33 @@ def bayes_logpost_gradient(sampler, solver, level, xi, G_obs, noise, xi_level=No
     _hcheck(lib.pmc_bayes_logpost_gradient(sampler.ctx.h, sampler.h, solver.h, level, xi_level, nbatch, pxi, ms, G_obs.ctypes.data_as(_DPTR),
                                            len(G_obs), float(noise), lp.ctypes.data_as(_DPTR), pg))
     return lp, grad_out
+
+
+def bayes_logpost_gn_hessvec(sampler, solver, level, xi, v, noise, xi_level=None, state=None, nbatch=None, hv_out=None):
+    """BayesianInverseProblem::ApplyGNHessian (pmc_bayes_logpost_gn_hessvec): hv = v + (dk/dxi)^T J^T (1/noise) J (dk/dxi) v
+    at k = Eval(level, xi).  Returns (hv, state); state = (k_state, x_state) is the linearization: None computes it from xi
+    and returns new buffers, a state returned by an earlier call at the same xi is reused (two sampler and two Darcy
+    solves; xi is not read).  numpy arrays (host), or capi.DeviceArrays with nbatch=..., hv_out=... and, for a first call,
+    state=(k_buf, x_buf, False) naming the device buffers to fill."""
+    lib = load_host_library()
+    xi_level = level if xi_level is None else xi_level
+    have = state is not None and (len(state) < 3 or bool(state[2]))
+    if isinstance(v, np.ndarray):
+        v = np.ascontiguousarray(np.atleast_2d(v), np.float64)
+        nbatch = v.shape[0]
+        xi = None if xi is None else np.ascontiguousarray(np.atleast_2d(xi), np.float64)
+        hv_out = np.empty_like(v)
+        if state is None:
+            n_p = solver.problem.levels[level].n_p
+            state = (np.empty((nbatch, n_p)), np.empty((nbatch, solver.GetGlobalNumberOfDofs(level))))
+        ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+        ms = capi.PMC_MEM_HOST
+    else:
+        ptr = lambda a: None if a is None else a.ptr              # noqa: E731
+        ms = capi.PMC_MEM_DEVICE
+    _hcheck(lib.pmc_bayes_logpost_gn_hessvec(sampler.ctx.h, sampler.h, solver.h, level, xi_level, nbatch, ptr(xi), ptr(v), ms,
+                                             float(noise), ptr(state[0]), ptr(state[1]), 1 if have else 0, ptr(hv_out)))
+    return hv_out, (state[0], state[1])
 
 
 CB_LIKE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
