@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/darcy_hessian.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
+SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/darcy_hessian.hip $(CSRC)/newton_cg.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=
@@ -141,3 +141,10 @@ $(ABIBIN)/gn_hessian_smoke: tests/c/gn_hessian_smoke.cpp tests/c/prob_io.h parel
 	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/gn_hessian_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
 test-gn-hessian: $(ABIBIN)/gn_hessian_smoke
 .PHONY: test-gn-hessian
+
+# MAP estimation through the mirror classes of parelagmc.hpp (tests/test_gpu_map_estimate.py builds and runs it)
+$(ABIBIN)/map_smoke: tests/c/map_smoke.cpp tests/c/prob_io.h parelagmc_amd/host/parelagmc.hpp include/pmc.h include/pmc_host.h | $(HOSTLIB)
+	@mkdir -p $(ABIBIN)
+	g++ -std=c++17 -O1 -Wall -Wextra -Iinclude -Itests/c -o $@ tests/c/map_smoke.cpp -Lparelagmc_amd/lib -lpmc_host -lpmc -pthread -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-map: $(ABIBIN)/map_smoke
+.PHONY: test-map

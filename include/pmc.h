@@ -751,6 +751,39 @@ int pmc_darcy_gn_hessvec(pmc_darcy* d, int level, int nbatch, const double* k, c
                          double noise, int wrt_log, double* hv, double* dG, double* x_out, int memspace, pmc_stats* stats_tan,
                          pmc_stats* stats_adj);
 
+/* ---- Batched conjugate-gradient vector algebra for Newton-CG (an extension)
+ * A workspace for nb <= nbatch_max independent CG iterations H_b d_b = g_b on columns of length n, vectors sample-major
+ * nb x n.  The caller owns the operator: it applies H to pmc_ncg_search_direction (p) for the whole batch and hands Hp to
+ * pmc_ncg_step; everything between two applications (<p, Hp>, alpha, d += alpha p, r -= alpha Hp, <r, r>, the tolerance test,
+ * beta, p = r + beta p) runs on the device in three launches, and the per-column scalars never leave it: pmc_ncg_status is
+ * the one small copy a CG step needs.
+ *   begin: on the columns with active_mask[b] != 0 (NULL: all) d = 0, r = p = g and the column ends once <r, r> <=
+ *          (eta_b |g_b|)^2; on the others p = 0 and nothing else is written.  eta, active_mask: HOST arrays of nb.
+ *   step:  one CG step of every unfinished column with Hp = H p.  A column whose <p, Hp> is not positive ends with its
+ *          non-positive-curvature flag set and keeps its d (d = g when this was its first step).  A column that ends gets
+ *          p = 0, once; after that none of its vectors is written.  The cap on the steps is the caller's loop.
+ *   status (host arrays of nb, each may be NULL): <r, r>, steps taken, finished, ended on non-positive curvature.
+ *   axpy_cols: out_b = x_b + t_b d_b on the columns with t_b != 0 (d NULL: out_b = x_b, a masked copy); a column with
+ *          t_b == 0 is masked and not written.  t: HOST array of nb.  out may be x.
+ *   dot_cols: out_host[b] = <a_b, b_b> for all nb columns.
+ * Every sum has a fixed order that depends on n alone (chunks of 4096 entries, a fixed tree inside a chunk, the chunk sums
+ * added in ascending order, no atomics): a column's vectors and scalars have the same bits at every nb, beside any other
+ * columns, in either memory space and in repeated calls.  With PMC_MEM_HOST the arrays are staged through the workspace; the
+ * workspace's own vectors (the three pointers below, device memory) may be passed as arguments in either memory space.
+ * Refused with PMC_ERR_INVALID: n or nbatch_max < 1, nb outside [1, nbatch_max], a NULL array, a negative eta, a step whose
+ * nb differs from its begin. */
+typedef struct pmc_ncg pmc_ncg;
+int pmc_ncg_create(pmc_ctx* ctx, int n, int nbatch_max, pmc_ncg** out);
+void pmc_ncg_destroy(pmc_ncg* w);
+int pmc_ncg_begin(pmc_ncg* w, int nb, const double* g, const double* eta, const int32_t* active_mask, int memspace);
+int pmc_ncg_step(pmc_ncg* w, int nb, const double* Hp, int memspace);
+double* pmc_ncg_direction(pmc_ncg* w);          /* d: nbatch_max x n on the device */
+double* pmc_ncg_search_direction(pmc_ncg* w);   /* p */
+double* pmc_ncg_residual(pmc_ncg* w);           /* r */
+int pmc_ncg_status(pmc_ncg* w, int nb, double* rr, int32_t* cg_count, int32_t* done, int32_t* nonpos_curvature);
+int pmc_ncg_axpy_cols(pmc_ncg* w, int nb, const double* t, const double* x, const double* d, double* out, int memspace);
+int pmc_ncg_dot_cols(pmc_ncg* w, int nb, const double* a, const double* b, double* out_host, int memspace);
+
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */
 int pmc_comm_unique_id(void* id128);                                        /* 128 bytes    */

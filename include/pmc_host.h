@@ -157,6 +157,60 @@ int pmc_bayes_logpost_gn_hessvec(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* 
                                  const double* xi, const double* v, int memspace, double noise, double* k_state,
                                  double* x_state, int have_state, double* hv);
 
+/* BayesianInverseProblem::ComputeMAP (an extension): the maximiser of pmc_bayes_logpost_gradient's
+ * logpost in the white noise, by inexact Gauss-Newton-CG, for nbatch independent columns that share the data G_obs.
+ * Per outer iteration, all columns together: a column is converged once |g| <= max(grad_rtol |g0|, grad_atol) and is frozen
+ * from then on (its xi keeps its bits, it enters later Hessian actions with a zero direction); CG on H_GN d = g from d = 0
+ * through pmc_bayes_logpost_gn_hessvec and the pmc_ncg kernels of pmc.h, the linearization state computed by the first action
+ * of the iteration, with the per-column forcing term eta = min(eta_max, sqrt(|g| / |g0|)), ended per column at
+ * |r| <= eta |g|, after max_cg actions or on p.Hp <= 0 (possible through inexact solves only: the column keeps its d, or
+ * takes d = g at its first step, and the event is counted); Armijo backtracking from t = 1 by halving, at most max_backtracks
+ * halvings, accepting logpost(xi + t d) >= logpost(xi) + c1 t <g, d>, each trial one pmc_bayes_logpost_gradient of the whole
+ * batch (accepted columns recompute their point, so the accepted gradient is the next iteration's).  A column whose
+ * backtracks are exhausted stops at its last accepted xi.
+ * grad_rtol's default belongs to the default solver options: under the 1e-6 MINRES rule gradients are accurate to about 1e-4
+ * (DESIGN.md section 16), so a tighter gradient tolerance needs tighter solver options on both handles. */
+typedef struct pmc_map_opts {
+    int32_t max_newton;      /* outer iterations (default 50) */
+    int32_t max_cg;          /* Hessian actions per outer iteration (default 100) */
+    int32_t max_backtracks;  /* halvings of the step (default 10) */
+    double eta_max;          /* cap of the forcing term, in (0, 1) (default 0.5) */
+    double c1;               /* Armijo constant, in (0, 1) (default 1e-4) */
+    double grad_atol;        /* >= 0 (default 0) */
+    double grad_rtol;        /* > 0 (default 1e-4) */
+} pmc_map_opts;
+void pmc_map_opts_default(pmc_map_opts* o);
+enum pmc_map_status {
+    PMC_MAP_CONVERGED = 0,
+    PMC_MAP_MAX_NEWTON = 1,
+    PMC_MAP_LINE_SEARCH_FAILED = 2,
+    PMC_MAP_NON_FINITE = 3   /* logpost or its gradient is not finite at the column's iterate */
+};
+/* Caller-owned HOST arrays; the per-column ones hold nbatch entries, the history ones (max_newton + 1) x nbatch, row i =
+ * outer iterate i.  Every pointer may be NULL.  History rows a column never reached hold NaN / -1. */
+typedef struct pmc_map_result {
+    int32_t* status;                /* enum pmc_map_status */
+    int32_t* newton_iterations;     /* accepted steps */
+    int32_t* hessian_actions;       /* CG steps of the column over all iterations */
+    int32_t* gradient_evaluations;  /* pmc_bayes_logpost_gradient calls while the column was running */
+    int32_t* nonpos_curvature;      /* CG runs ended on p.Hp <= 0 */
+    double* logpost0;
+    double* logpost;
+    double* grad_norm0;
+    double* grad_norm;
+    double* hist_logpost;           /* logpost at iterate i */
+    double* hist_grad_norm;         /* |g| at iterate i */
+    int32_t* hist_cg;               /* CG steps taken from iterate i (0: none, the column stopped there) */
+    double* hist_t;                 /* step accepted from iterate i (0: none) */
+} pmc_map_result;
+/* xi_inout: nbatch x xi_size(xi_level) in `memspace`, the starting points on entry and the results on exit; with device
+ * memory only scalars cross to the host.  opts NULL: the defaults.  Refused with PMC_ERR_INVALID: whatever
+ * pmc_bayes_logpost_gradient refuses (a conditioned sampler handle among it), NULL xi_inout or res, max_newton / max_cg /
+ * max_backtracks / grad_rtol <= 0, eta_max or c1 outside (0, 1), grad_atol < 0. */
+int pmc_bayes_map(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                  double* xi_inout, int memspace, const double* G_obs, int nobs, double noise, const pmc_map_opts* opts,
+                  pmc_map_result* res);
+
 /* ---- ML_BayesRatio_Manager / SL_BayesRatio_Manager (src/ML_BayesRatio_Manager.hpp:315-728, src/SL_BayesRatio_Manager.hpp)
  * Multilevel ratio estimator E[Q * likelihood] / E[likelihood]: per realization two INDEPENDENT prior draws, one for
  * Z = likelihood and one for R = Q * likelihood, each evaluated on level l and (same xi) on level l+1; the same

@@ -238,6 +238,17 @@ SYMBOLS = {
     "pmc_darcy_loglik_gradient": (C.c_int, [_VP, C.c_int, C.c_int, _DP, C.POINTER(C.c_double), C.c_double, C.c_int,
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), _DP, C.c_int,
                                             C.POINTER(pmc_stats)]),
+    "pmc_ncg_create": (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "pmc_ncg_destroy": (None, [_VP]),
+    "pmc_ncg_begin": (C.c_int, [_VP, C.c_int, _DP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]),
+    "pmc_ncg_step": (C.c_int, [_VP, C.c_int, _DP, C.c_int]),
+    "pmc_ncg_direction": (_VP, [_VP]),
+    "pmc_ncg_search_direction": (_VP, [_VP]),
+    "pmc_ncg_residual": (_VP, [_VP]),
+    "pmc_ncg_status": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32)]),
+    "pmc_ncg_axpy_cols": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), _DP, _DP, _DP, C.c_int]),
+    "pmc_ncg_dot_cols": (C.c_int, [_VP, C.c_int, _DP, _DP, C.POINTER(C.c_double), C.c_int]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -1457,6 +1468,95 @@ class DarcySolver:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.pmc_darcy_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NewtonCG:
+    """Batched CG vector algebra for Newton-CG (pmc_ncg_*, csrc/newton_cg.hip): nb <= nbatch_max independent CG iterations
+    on columns of length n.  The caller applies the operator to search_direction() and hands the product to step().  Array
+    arguments: numpy (host), DeviceArray or torch tensors (device), sample-major nb x n."""
+
+    def __init__(self, ctx: Context, n: int, nbatch_max: int):
+        self.ctx, self.n, self.nbatch_max = ctx, int(n), int(nbatch_max)
+        h = _VP()
+        _check(ctx.lib.pmc_ncg_create(ctx.h, self.n, self.nbatch_max, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    @staticmethod
+    def _space(*arrays):
+        spaces = {_addr(a)[1] for a in arrays if a is not None and not isinstance(a, int)}
+        assert len(spaces) <= 1, "arguments in different memory spaces"
+        return spaces.pop() if spaces else PMC_MEM_DEVICE
+
+    @staticmethod
+    def _p(a):
+        return a if a is None or isinstance(a, int) else _addr(a)[0]
+
+    def begin(self, nb, g, eta, active=None):
+        eta = _f64(eta)
+        assert eta.size == nb
+        act = None if active is None else _i32(active)
+        _check(self.ctx.lib.pmc_ncg_begin(self.h, nb, self._p(g), _ptr(eta, C.c_double),
+                                          None if act is None else _ptr(act, C.c_int32), self._space(g)))
+
+    def step(self, nb, Hp):
+        _check(self.ctx.lib.pmc_ncg_step(self.h, nb, self._p(Hp), self._space(Hp)))
+
+    def status(self, nb):
+        """(rr, cg_count, done, nonpos_curvature): numpy arrays of nb"""
+        rr = np.empty(nb)
+        cnt, done, npc = (np.empty(nb, np.int32) for _ in range(3))
+        _check(self.ctx.lib.pmc_ncg_status(self.h, nb, _ptr(rr, C.c_double), _ptr(cnt, C.c_int32), _ptr(done, C.c_int32),
+                                           _ptr(npc, C.c_int32)))
+        return rr, cnt, done, npc
+
+    # the workspace's own vectors: device addresses (ints), accepted by axpy_cols / dot_cols in either memory space
+    def direction_ptr(self) -> int:
+        return self.ctx.lib.pmc_ncg_direction(self.h) or 0
+
+    def search_direction_ptr(self) -> int:
+        return self.ctx.lib.pmc_ncg_search_direction(self.h) or 0
+
+    def residual_ptr(self) -> int:
+        return self.ctx.lib.pmc_ncg_residual(self.h) or 0
+
+    def _download(self, ptr, nb):
+        out = np.empty((nb, self.n))
+        _check(self.ctx.lib.pmc_memcpy_d2h(self.ctx.h, out.ctypes.data, ptr, out.nbytes))
+        return out
+
+    def direction(self, nb) -> np.ndarray:
+        return self._download(self.direction_ptr(), nb)
+
+    def search_direction(self, nb) -> np.ndarray:
+        return self._download(self.search_direction_ptr(), nb)
+
+    def residual(self, nb) -> np.ndarray:
+        return self._download(self.residual_ptr(), nb)
+
+    def axpy_cols(self, nb, t, x, d, out):
+        """out_b = x_b + t_b d_b on the columns with t_b != 0 (d None: a masked copy); the others are not written"""
+        t = _f64(t)
+        assert t.size == nb
+        _check(self.ctx.lib.pmc_ncg_axpy_cols(self.h, nb, _ptr(t, C.c_double), self._p(x), self._p(d), self._p(out),
+                                              self._space(x, d, out)))
+        return out
+
+    def dot_cols(self, nb, a, b) -> np.ndarray:
+        out = np.empty(nb)
+        _check(self.ctx.lib.pmc_ncg_dot_cols(self.h, nb, self._p(a), self._p(b), _ptr(out, C.c_double), self._space(a, b)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pmc_ncg_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -706,6 +706,49 @@ void pmc_darcy_destroy(pmc_darcy* d) {
     (void)hipStreamSynchronize(d->impl.ctx.stream);
     delete d;
 }
+// ---- batched CG vector algebra (newton_cg.hip) ----
+int pmc_ncg_create(pmc_ctx* ctx, int n, int nbatch_max, pmc_ncg** out) {
+    return guarded([&] {
+        PMC_REQUIRE(ctx != nullptr && out != nullptr, "pmc_ncg_create: NULL argument");
+        *out = nullptr;
+        *out = new pmc_ncg(*ctx, n, nbatch_max);
+    });
+}
+void pmc_ncg_destroy(pmc_ncg* w) { delete w; }
+int pmc_ncg_begin(pmc_ncg* w, int nb, const double* g, const double* eta, const int32_t* active_mask, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(w != nullptr, "pmc_ncg_begin: workspace is NULL");
+        w->impl.begin(nb, g, eta, active_mask, memspace);
+    });
+}
+int pmc_ncg_step(pmc_ncg* w, int nb, const double* Hp, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(w != nullptr, "pmc_ncg_step: workspace is NULL");
+        w->impl.step(nb, Hp, memspace);
+    });
+}
+double* pmc_ncg_direction(pmc_ncg* w) { return w ? w->impl.d.p : nullptr; }
+double* pmc_ncg_search_direction(pmc_ncg* w) { return w ? w->impl.p.p : nullptr; }
+double* pmc_ncg_residual(pmc_ncg* w) { return w ? w->impl.r.p : nullptr; }
+int pmc_ncg_status(pmc_ncg* w, int nb, double* rr, int32_t* cg_count, int32_t* done, int32_t* nonpos_curvature) {
+    return guarded([&] {
+        PMC_REQUIRE(w != nullptr, "pmc_ncg_status: workspace is NULL");
+        w->impl.status(nb, rr, cg_count, done, nonpos_curvature);
+    });
+}
+int pmc_ncg_axpy_cols(pmc_ncg* w, int nb, const double* t, const double* x, const double* d, double* out, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(w != nullptr, "pmc_ncg_axpy_cols: workspace is NULL");
+        w->impl.axpy(nb, t, x, d, out, memspace);
+    });
+}
+int pmc_ncg_dot_cols(pmc_ncg* w, int nb, const double* a, const double* b, double* out_host, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(w != nullptr, "pmc_ncg_dot_cols: workspace is NULL");
+        w->impl.dot(nb, a, b, out_host, memspace);
+    });
+}
+
 int pmc_darcy_num_dofs(const pmc_darcy* d, int level) {
     if (!d || level < 0 || level >= d->impl.nlevels) return PMC_ERR_INVALID;
     return d->impl.lv[level].n_u + d->impl.lv[level].n_p;

@@ -455,6 +455,48 @@ struct Darcy {
                         pmc_stats* stats_adj);
 };
 
+// Batched CG vector algebra for Newton-CG (pmc_ncg_*; newton_cg.hip)
+constexpr int kNcgThreads = 256;                   // workgroup of every pmc_ncg kernel
+constexpr int kNcgPer = 16;                        // entries per thread: eight 16-byte accesses per vector
+constexpr int kNcgChunk = kNcgThreads * kNcgPer;   // entries per workgroup = the unit of the fixed summation order
+struct NcgCol {                                    // one column's scalars, kept on the device
+    double rr, gg, tol2, pHp;                      // <r, r>, <g, g>, (eta |g|)^2, the last <p, Hp>
+    int32_t count, done, npc, active;              // steps taken, finished, ended on <p, Hp> <= 0, active at pmc_ncg_begin
+};
+struct Ncg {
+    Ctx& ctx;
+    int n, nbmax, nch;                             // column length, widest batch, chunks per column
+    DevBuf<double> d, r, p, part_a, part_b, scal, dots;
+    DevBuf<int32_t> mask;
+    DevBuf<NcgCol> cols;                           // 2 x nbmax, double-buffered by step parity
+    DevBuf<double> stage[3];                       // host-memory callers: staged operands (allocated at first use)
+    NcgCol* h_cols = nullptr;                      // pinned
+    double* h_dots = nullptr;                      // pinned
+    int cur = 0, nb_cur = 0;
+    static constexpr int kNcgSlots = 8;
+    struct Slot {                                  // pinned staging of one call's per-column host arrays (16 B per column)
+        char* h = nullptr;
+        hipEvent_t ev = nullptr;
+        bool used = false;
+    };
+    Slot slots[kNcgSlots];
+    int slot_at = 0;
+    Ncg(Ctx& c, int n, int nbmax);
+    ~Ncg();
+    Ncg(const Ncg&) = delete;
+    Ncg& operator=(const Ncg&) = delete;
+    void begin(int nb, const double* g, const double* eta, const int32_t* active, int memspace);
+    void step(int nb, const double* hp, int memspace);
+    void status(int nb, double* rr, int32_t* count, int32_t* done, int32_t* npc);
+    void axpy(int nb, const double* t, const double* x, const double* dd, double* out, int memspace);
+    void dot(int nb, const double* a, const double* b, double* out_host, int memspace);
+
+private:
+    const double* in(const double* a, int nb, int memspace, int slot);
+    Slot& next_slot();
+    void check(int nb, int memspace, const char* what) const;
+};
+
 }  // namespace pmc
 
 struct pmc_sampler { pmc::Sampler impl; template <class... A> explicit pmc_sampler(A&&... a) : impl(std::forward<A>(a)...) {} };
@@ -462,3 +504,4 @@ struct pmc_conditioner { pmc::Conditioner impl; template <class... A> explicit p
 struct pmc_field_stats { pmc::FieldStats impl; template <class... A> explicit pmc_field_stats(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_level_fields { pmc::LevelFields impl; template <class... A> explicit pmc_level_fields(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_darcy { pmc::Darcy impl; template <class... A> explicit pmc_darcy(A&&... a) : impl(std::forward<A>(a)...) {} };
+struct pmc_ncg { pmc::Ncg impl; template <class... A> explicit pmc_ncg(A&&... a) : impl(std::forward<A>(a)...) {} };

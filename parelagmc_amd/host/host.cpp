@@ -406,6 +406,170 @@ void BayesianInverseProblem::ApplyGNHessian(int ilevel, PDESampler& sampler, con
     check_arg(pmc_sampler_logprior_hessvec(sampler.Handle(), xi.Size(), nb, v.GetData(), hv.GetData(), ms),
               "BayesianInverseProblem::ApplyGNHessian");
 }
+namespace {
+struct MapView : Vector {     // a non-owning batch view
+    MapView(double* p, int n, int nb, int ms) : Vector(nullptr, ms) { Adopt(p, n, nb); }
+    ~MapView() { Release(); }
+};
+void check_map_opts(const pmc_map_opts& o) {
+    if (o.max_newton <= 0 || o.max_cg <= 0 || o.max_backtracks <= 0 || !(o.grad_rtol > 0.0) || !(o.grad_atol >= 0.0) ||
+        !(o.eta_max > 0.0 && o.eta_max < 1.0) || !(o.c1 > 0.0 && o.c1 < 1.0))
+        throw std::invalid_argument("ComputeMAP: max_newton, max_cg, max_backtracks and grad_rtol must be positive, eta_max "
+                                    "and c1 inside (0, 1), grad_atol not negative");
+}
+}  // namespace
+
+void BayesianInverseProblem::ComputeMAP(int ilevel, PDESampler& sampler, Vector& xi_io, const pmc_map_opts& o,
+                                        pmc_map_result& res, int xi_level) {
+    check_map_opts(o);
+    const int nb = xi_io.Batch(), n = xi_io.Size();
+    if (nb < 1 || n < 1 || !xi_io.GetData()) throw std::invalid_argument("ComputeMAP: xi is empty");
+    pmc_ctx* ctx = sampler.Context();
+    const int dev = PMC_MEM_DEVICE;
+    if (!map_trial_) {
+        for (auto* v : {&map_xi_, &map_trial_, &map_g_, &map_gt_, &map_hp_, &map_k_, &map_x_}) v->reset(new Vector(ctx, dev));
+    }
+    if (!map_ncg_ || map_ncg_n_ != n || map_ncg_nb_ < nb) {
+        pmc_ncg* w = nullptr;
+        map_ncg_.reset();
+        check_arg(pmc_ncg_create(ctx, n, nb, &w), "BayesianInverseProblem::ComputeMAP");
+        map_ncg_.reset(w);
+        map_ncg_n_ = n;
+        map_ncg_nb_ = nb;
+    }
+    pmc_ncg* w = map_ncg_.get();
+    // the loop runs on device vectors; a host caller's xi is staged once each way
+    const bool host_io = xi_io.MemSpace() != dev;
+    const size_t bytes = sizeof(double) * (size_t)n * nb;
+    if (host_io) {
+        map_xi_->SetSize(n, nb);
+        check(pmc_memcpy_h2d(ctx, map_xi_->GetData(), xi_io.GetData(), bytes), "BayesianInverseProblem::ComputeMAP");
+    }
+    MapView xi(host_io ? map_xi_->GetData() : xi_io.GetData(), n, nb, dev);
+    Vector &trial = *map_trial_, &g = *map_g_, &gt = *map_gt_, &hp = *map_hp_;
+    trial.SetSize(n, nb);
+    g.SetSize(n, nb);
+    gt.SetSize(n, nb);
+    hp.SetSize(n, nb);
+    MapView p(pmc_ncg_search_direction(w), n, nb, dev);
+    double* const d = pmc_ncg_direction(w);
+    const char* what = "BayesianInverseProblem::ComputeMAP";
+
+    enum { RUNNING = -1 };
+    std::vector<int32_t> status((size_t)nb, RUNNING), iters((size_t)nb, 0), nhess((size_t)nb, 0), ngrad((size_t)nb, 0),
+        nnpc((size_t)nb, 0), mask((size_t)nb), cgc((size_t)nb), done((size_t)nb), npc((size_t)nb);
+    std::vector<double> lp((size_t)nb), lpt((size_t)nb), lp0((size_t)nb), gn((size_t)nb), gn0((size_t)nb), gg((size_t)nb),
+        gd((size_t)nb), eta((size_t)nb), t((size_t)nb), sel((size_t)nb), ones((size_t)nb, 1.0);
+    const size_t hist = (size_t)(o.max_newton + 1) * nb;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (res.hist_logpost) std::fill(res.hist_logpost, res.hist_logpost + hist, nan);
+    if (res.hist_grad_norm) std::fill(res.hist_grad_norm, res.hist_grad_norm + hist, nan);
+    if (res.hist_cg) std::fill(res.hist_cg, res.hist_cg + hist, -1);
+    if (res.hist_t) std::fill(res.hist_t, res.hist_t + hist, nan);
+
+    ComputeGradLogPosterior(ilevel, sampler, xi, lp.data(), g, xi_level);
+    check_arg(pmc_ncg_dot_cols(w, nb, g.GetData(), g.GetData(), gg.data(), dev), what);
+    check_arg(pmc_ncg_axpy_cols(w, nb, ones.data(), xi.GetData(), nullptr, trial.GetData(), dev), what);   // trial = xi
+    for (int b = 0; b < nb; ++b) {
+        ngrad[b] = 1;
+        lp0[b] = lp[b];
+        gn0[b] = gn[b] = std::sqrt(gg[b]);
+        if (!std::isfinite(lp[b]) || !std::isfinite(gn[b])) status[b] = PMC_MAP_NON_FINITE;
+    }
+    for (int it = 0;; ++it) {
+        int running = 0;
+        for (int b = 0; b < nb; ++b) {
+            if (status[b] != RUNNING) continue;
+            if (gn[b] <= std::max(o.grad_rtol * gn0[b], o.grad_atol)) status[b] = PMC_MAP_CONVERGED;
+            else if (it == o.max_newton) status[b] = PMC_MAP_MAX_NEWTON;
+            else ++running;
+            const size_t h = (size_t)it * nb + b;
+            if (res.hist_logpost) res.hist_logpost[h] = lp[b];
+            if (res.hist_grad_norm) res.hist_grad_norm[h] = gn[b];
+            if (res.hist_cg) res.hist_cg[h] = 0;
+            if (res.hist_t) res.hist_t[h] = 0.0;
+        }
+        if (!running) break;
+        // ---- CG on H_GN d = g
+        for (int b = 0; b < nb; ++b) {
+            mask[b] = status[b] == RUNNING ? 1 : 0;
+            eta[b] = mask[b] ? std::min(o.eta_max, std::sqrt(gn[b] / gn0[b])) : 0.0;
+        }
+        check_arg(pmc_ncg_begin(w, nb, g.GetData(), eta.data(), mask.data(), dev), what);
+        for (int j = 0; j < o.max_cg; ++j) {
+            ApplyGNHessian(ilevel, sampler, xi, p, hp, xi_level, *map_k_, *map_x_, /*have_state=*/j > 0);
+            check_arg(pmc_ncg_step(w, nb, hp.GetData(), dev), what);
+            check_arg(pmc_ncg_status(w, nb, nullptr, cgc.data(), done.data(), npc.data()), what);
+            if (std::all_of(done.begin(), done.end(), [](int32_t f) { return f != 0; })) break;
+        }
+        check_arg(pmc_ncg_dot_cols(w, nb, g.GetData(), d, gd.data(), dev), what);
+        // ---- Armijo backtracking: every trial is one gradient evaluation of the whole batch
+        std::vector<char> searching((size_t)nb), accepted((size_t)nb, 0);
+        for (int b = 0; b < nb; ++b) {
+            searching[b] = mask[b] != 0;
+            t[b] = mask[b] ? 1.0 : 0.0;
+            if (mask[b]) {
+                nhess[b] += cgc[b];
+                nnpc[b] += npc[b];
+            }
+        }
+        for (int ls = 0; ls <= o.max_backtracks; ++ls) {
+            check_arg(pmc_ncg_axpy_cols(w, nb, t.data(), xi.GetData(), d, trial.GetData(), dev), what);
+            ComputeGradLogPosterior(ilevel, sampler, trial, lpt.data(), gt, xi_level);
+            bool any = false;
+            for (int b = 0; b < nb; ++b) {
+                if (mask[b]) ++ngrad[b];
+                if (!searching[b]) continue;
+                if (std::isfinite(lpt[b]) && lpt[b] >= lp[b] + o.c1 * t[b] * gd[b]) {
+                    searching[b] = 0;
+                    accepted[b] = 1;
+                } else if (ls == o.max_backtracks) {
+                    searching[b] = 0;
+                } else {
+                    t[b] *= 0.5;
+                    any = true;
+                }
+            }
+            if (!any) break;
+        }
+        // accepted columns move to the trial point and take its gradient; failed ones stay, and their trial column is put back
+        bool failed = false;
+        for (int b = 0; b < nb; ++b) sel[b] = accepted[b] ? 1.0 : 0.0;
+        check_arg(pmc_ncg_axpy_cols(w, nb, sel.data(), trial.GetData(), nullptr, xi.GetData(), dev), what);
+        check_arg(pmc_ncg_axpy_cols(w, nb, sel.data(), gt.GetData(), nullptr, g.GetData(), dev), what);
+        check_arg(pmc_ncg_dot_cols(w, nb, g.GetData(), g.GetData(), gg.data(), dev), what);
+        for (int b = 0; b < nb; ++b) {
+            sel[b] = 0.0;
+            if (!mask[b]) continue;
+            const size_t h = (size_t)it * nb + b;
+            if (res.hist_cg) res.hist_cg[h] = cgc[b];
+            if (accepted[b]) {
+                lp[b] = lpt[b];
+                gn[b] = std::sqrt(gg[b]);
+                ++iters[b];
+                if (res.hist_t) res.hist_t[h] = t[b];
+                if (!std::isfinite(gn[b])) status[b] = PMC_MAP_NON_FINITE;
+            } else {
+                status[b] = PMC_MAP_LINE_SEARCH_FAILED;
+                sel[b] = 1.0;
+                failed = true;
+            }
+        }
+        if (failed) check_arg(pmc_ncg_axpy_cols(w, nb, sel.data(), xi.GetData(), nullptr, trial.GetData(), dev), what);
+    }
+    if (host_io) check(pmc_memcpy_d2h(ctx, xi_io.GetData(), xi.GetData(), bytes), what);
+    for (int b = 0; b < nb; ++b) {
+        if (res.status) res.status[b] = status[b];
+        if (res.newton_iterations) res.newton_iterations[b] = iters[b];
+        if (res.hessian_actions) res.hessian_actions[b] = nhess[b];
+        if (res.gradient_evaluations) res.gradient_evaluations[b] = ngrad[b];
+        if (res.nonpos_curvature) res.nonpos_curvature[b] = nnpc[b];
+        if (res.logpost0) res.logpost0[b] = lp0[b];
+        if (res.logpost) res.logpost[b] = lp[b];
+        if (res.grad_norm0) res.grad_norm0[b] = gn0[b];
+        if (res.grad_norm) res.grad_norm[b] = gn[b];
+    }
+}
 void BayesianInverseProblem::ComputeR(int ilevel, Vector& k, double* R, double* C) {
     std::vector<double> q(k.Batch());
     ComputeLikelihoodAndQ(ilevel, k, R, C, q.data());
@@ -1910,6 +2074,40 @@ int pmc_bayes_logpost_gn_hessvec(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* 
         View xv(const_cast<double*>(xi), n_xi, nbatch, memspace), vv(const_cast<double*>(v), n_xi, nbatch, memspace);
         View gv(hv, n_xi, nbatch, memspace), kv(k_state, np, nbatch, memspace), sv(x_state, n, nbatch, memspace);
         prob.ApplyGNHessian(level, smp, xv, vv, gv, xi_level, kv, sv, have_state != 0);
+    });
+}
+
+void pmc_map_opts_default(pmc_map_opts* o) {
+    if (!o) return;
+    o->max_newton = 50;
+    o->max_cg = 100;
+    o->max_backtracks = 10;
+    o->eta_max = 0.5;
+    o->c1 = 1e-4;
+    o->grad_atol = 0.0;
+    o->grad_rtol = 1e-4;    // what gradients under the default 1e-6 solver rule can resolve
+}
+
+int pmc_bayes_map(pmc_ctx* ctx, pmc_sampler* sampler, pmc_darcy* solver, int level, int xi_level, int nbatch,
+                  double* xi_inout, int memspace, const double* G_obs, int nobs, double noise, const pmc_map_opts* opts,
+                  pmc_map_result* res) {
+    return hguard([&] {
+        if (!ctx || !sampler || !solver || !xi_inout || !res || !G_obs || nbatch < 1 || nobs < 1 || !(noise > 0.0))
+            throw std::invalid_argument("pmc_bayes_map: bad argument");
+        if (memspace != PMC_MEM_HOST && memspace != PMC_MEM_DEVICE) throw std::invalid_argument("pmc_bayes_map: bad memspace");
+        if (level < 0 || level >= pmc_sampler_num_levels(sampler) || xi_level < 0 || xi_level > level)
+            throw std::invalid_argument("pmc_bayes_map: level / xi_level out of range");
+        pmc_map_opts o;
+        pmc_map_opts_default(&o);
+        if (opts) o = *opts;
+        struct View : Vector {     // a non-owning batch view of xi
+            View(double* p, int n, int nb, int ms) : Vector(nullptr, ms) { Adopt(p, n, nb); }
+            ~View() { Release(); }
+        };
+        PDESampler smp(ctx, sampler);
+        BayesianInverseProblem prob(solver, noise, std::vector<double>(G_obs, G_obs + nobs));
+        View xv(xi_inout, pmc_sampler_xi_size(sampler, xi_level), nbatch, memspace);
+        prob.ComputeMAP(level, smp, xv, o, *res, xi_level);
     });
 }
 

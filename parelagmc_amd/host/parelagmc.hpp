@@ -362,12 +362,23 @@ class BayesianInverseProblem {
     /// the same on caller-owned state vectors k (n_p x batch) and x (n_u + n_p x batch)
     void ApplyGNHessian(int ilevel, PDESampler& sampler, const Vector& xi, const Vector& v, Vector& hv, int xi_level,
                         Vector& k_state, Vector& x_state, bool have_state);
+    /// The maximiser of log pi in the white noise by inexact Gauss-Newton-CG, for every column of xi (the starting points on
+    /// entry, the results on exit; host or device memory): the algorithm, options and result arrays of pmc_bayes_map
+    /// (include/pmc_host.h).  ComputeGradLogPosterior and ApplyGNHessian do the solves; the CG algebra between two Hessian
+    /// actions runs in the pmc_ncg kernels.  xi_level as in ComputeGradLogPosterior.  The work vectors and the CG workspace
+    /// are kept between calls.
+    void ComputeMAP(int ilevel, PDESampler& sampler, Vector& xi, const pmc_map_opts& opts, pmc_map_result& result,
+                    int xi_level = -1);
     int SizeOfObservationalData() const { return (int)G_obs_.size(); }
 
   private:
     pmc_darcy* solver_;
     double noise_;
     std::vector<double> G_obs_;
+    // ComputeMAP: iterate (host callers), trial point, gradients at both, H p, linearization state; the CG workspace
+    std::unique_ptr<Vector> map_xi_, map_trial_, map_g_, map_gt_, map_hp_, map_k_, map_x_;
+    std::unique_ptr<pmc_ncg, void (*)(pmc_ncg*)> map_ncg_{nullptr, pmc_ncg_destroy};
+    int map_ncg_n_ = 0, map_ncg_nb_ = 0;
     std::unique_ptr<Vector> work_k_, work_gk_;   // ComputeGradLogPosterior
     std::unique_ptr<Vector> state_k_, state_x_, work_dk_, work_hk_;   // ApplyGNHessian: linearization state, dk, J^T J dk
 };

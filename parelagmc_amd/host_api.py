@@ -46,8 +46,28 @@ class pmc_mlmc_result(C.Structure):
                [("sums", _DPTR), ("nsamples", _LPTR), ("nsamples_missing", _LPTR), ("level_seconds", _DPTR)]
 
 
+_IPTR = C.POINTER(C.c_int32)
+
+
+class pmc_map_opts(C.Structure):
+    _fields_ = [("max_newton", C.c_int32), ("max_cg", C.c_int32), ("max_backtracks", C.c_int32), ("eta_max", C.c_double),
+                ("c1", C.c_double), ("grad_atol", C.c_double), ("grad_rtol", C.c_double)]
+
+
+class pmc_map_result(C.Structure):
+    _fields_ = [(n, _IPTR) for n in ("status", "newton_iterations", "hessian_actions", "gradient_evaluations",
+                                     "nonpos_curvature")] + \
+               [(n, _DPTR) for n in ("logpost0", "logpost", "grad_norm0", "grad_norm", "hist_logpost", "hist_grad_norm")] + \
+               [("hist_cg", _IPTR), ("hist_t", _DPTR)]
+
+
+MAP_CONVERGED, MAP_MAX_NEWTON, MAP_LINE_SEARCH_FAILED, MAP_NON_FINITE = range(4)
+
 _VP = C.c_void_p
 HOST_SYMBOLS = {
+    "pmc_map_opts_default": (None, [C.POINTER(pmc_map_opts)]),
+    "pmc_bayes_map": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _DPTR, C.c_int, C.c_double,
+                                C.POINTER(pmc_map_opts), C.POINTER(pmc_map_result)]),
     "pmc_mlmc_params_default": (None, [C.POINTER(pmc_mlmc_params)]),
     "pmc_mlmc_create": (C.c_int, [_VP, _VP, _VP, C.c_int, C.POINTER(pmc_mlmc_params), C.POINTER(_VP)]),
     "pmc_mlmc_create_callbacks": (C.c_int, [C.c_int, C.POINTER(pmc_plugin_callbacks), C.POINTER(pmc_mlmc_params),
@@ -231,6 +251,49 @@ def bayes_logpost_gn_hessvec(sampler, solver, level, xi, v, noise, xi_level=None
     _hcheck(lib.pmc_bayes_logpost_gn_hessvec(sampler.ctx.h, sampler.h, solver.h, level, xi_level, nbatch, ptr(xi), ptr(v), ms,
                                              float(noise), ptr(state[0]), ptr(state[1]), 1 if have else 0, ptr(hv_out)))
     return hv_out, (state[0], state[1])
+
+
+def map_opts(**kw) -> pmc_map_opts:
+    """pmc_map_opts_default with the named fields overridden"""
+    o = pmc_map_opts()
+    load_host_library().pmc_map_opts_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown MAP option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def bayes_map(sampler, solver, level, xi, G_obs, noise, xi_level=None, opts=None, nbatch=None, history=True):
+    """BayesianInverseProblem::ComputeMAP (pmc_bayes_map): the maximiser of bayes_logpost_gradient's logpost by inexact
+    Gauss-Newton-CG from the starting points xi - numpy (nbatch, n_xi) (host; not modified, the result is returned), or a
+    capi.DeviceArray / torch tensor with nbatch=... (device; overwritten in place).  Returns (xi_map, result): result is a dict
+    of per-column numpy arrays (status, newton_iterations, hessian_actions, gradient_evaluations, nonpos_curvature, logpost0,
+    logpost, grad_norm0, grad_norm) and, with history, hist_logpost / hist_grad_norm / hist_cg / hist_t of shape
+    (max_newton + 1, nbatch).  opts: a pmc_map_opts (map_opts(...)) or None for the defaults."""
+    lib = load_host_library()
+    xi_level = level if xi_level is None else xi_level
+    G_obs = np.ascontiguousarray(G_obs, np.float64)
+    if isinstance(xi, np.ndarray):
+        xi = np.array(np.atleast_2d(xi), np.float64, order="C")     # a copy: the caller's start is kept
+        nbatch = xi.shape[0]
+    pxi, ms = (None, capi.PMC_MEM_HOST) if xi is None else capi._addr(xi)
+    o = opts if opts is not None else map_opts()
+    nb = int(nbatch) if nbatch is not None else 0
+    rows = max(int(o.max_newton), 0) + 1
+    out = {n: np.zeros(nb, np.int32) for n in ("status", "newton_iterations", "hessian_actions", "gradient_evaluations",
+                                               "nonpos_curvature")}
+    out.update({n: np.zeros(nb) for n in ("logpost0", "logpost", "grad_norm0", "grad_norm")})
+    if history:
+        out.update({"hist_logpost": np.zeros((rows, nb)), "hist_grad_norm": np.zeros((rows, nb)),
+                    "hist_cg": np.zeros((rows, nb), np.int32), "hist_t": np.zeros((rows, nb))})
+    res = pmc_map_result()
+    for name, ctype in pmc_map_result._fields_:
+        if name in out:
+            setattr(res, name, out[name].ctypes.data_as(ctype))
+    _hcheck(lib.pmc_bayes_map(sampler.ctx.h, sampler.h, solver.h, level, xi_level, nb, pxi, ms, G_obs.ctypes.data_as(_DPTR),
+                              len(G_obs), float(noise), C.byref(o), C.byref(res)))
+    return xi, out
 
 
 CB_LIKE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
