@@ -681,7 +681,8 @@ int pmc_darcy_vcycle_prolongator(const pmc_darcy* d, int level, int vlevel, int*
 /* Bayesian observation operator (src/BayesianInverseProblem.cpp:178-186, ComputeG): Gobs is nobs x n_p(level), row i
  * = the observation functional g_obs_i (e.g. the indicator of the cells around an observation point, restricted to the
  * level).  pmc_darcy_compute_G solves like SolveFwd and returns G[b*nobs + i] = <g_i, p_b> / sum(g_i) (host array) plus
- * Q and C (host, may be NULL); only the rows of the solution that Q and G read are maintained by the Krylov solver. */
+ * Q and C (host, may be NULL); only the rows of the solution that Q and G read are maintained by the Krylov solver.  Q is
+ * <obs, x> also on a level with a tracer attached (pmc_darcy_set_tracer). */
 int pmc_darcy_set_observations(pmc_darcy* d, int level, const pmc_csr* Gobs);
 int pmc_darcy_num_observations(const pmc_darcy* d, int level);
 int pmc_darcy_compute_G(pmc_darcy* d, int level, int nbatch, const double* k, double* G, double* C, double* Q,
@@ -693,7 +694,8 @@ int pmc_darcy_compute_G(pmc_darcy* d, int level, int nbatch, const double* k, do
  * contribution lists, and dJ/dk_e = c'(k_e) dJ/dc_e, c = 1/k (k_divides) or k.  wrt_log != 0: the gradient with respect to
  * log k (times k).  k, grad: nbatch x n_p(level); full vectors: nbatch x (n_u + n_p), sample-major; arrays in `memspace`
  * unless stated.  Column b of every result is the same, bit for bit, however nbatch is split into calls and launches.  All
- * three functions take the saddle-point path, also on a handle from pmc_darcy_create_hybrid (as pmc_darcy_compute_G does).
+ * three functions take the saddle-point path, also on a handle from pmc_darcy_create_hybrid (as pmc_darcy_compute_G does),
+ * and their Q and J = Q are <obs, x> also on a level with a tracer attached (pmc_darcy_set_tracer).
  * Refused with PMC_ERR_INVALID: a level outside [0, n_mc_levels), nbatch < 1, NULL k / grad; non-positive k is the caller's
  * problem, as in pmc_darcy_solve_fwd. */
 /* In-situ timing of the mass-sensitivity kernel (the one new kernel of a gradient), on the pmc_darcy_set_operator_timing switch
@@ -728,7 +730,8 @@ int pmc_darcy_loglik_gradient(pmc_darcy* d, int level, int nbatch, const double*
  * on the free rows (0 on the essential rows, t_p = 0), A(k) dx = t gives dG_i = <g_i, dp> / sum(g_i) = (J dk)_i, and
  * A(k) lam = [0; (1/noise) sum_i dG_i g_i / sum(g_i)] gives hv = pmc_darcy_mass_sensitivity(k, x, lam).  Array shapes, memory
  * spaces, the saddle-point path on hybridized handles and the bitwise independence of a column from the launch width and the
- * split of a call: as for the gradients above. */
+ * split of a call: as for the gradients above.  A tracer attached to the level (pmc_darcy_set_tracer) changes nothing here:
+ * these entries read the observation functionals and <obs, x> only. */
 /* In-situ timing of the tangent right-hand side kernel (the one new kernel), on the pmc_darcy_set_operator_timing switch and
  * with the meaning of pmc_darcy_operator_time; ALGORITHMIC bytes of one launch for nbatch realizations: per face and side an
  * element id (4 B), n_fe face indices (4 B) and n_fe matrix entries (8 B) - n_u nside (4 + 12 n_fe) -, k and dk read once
@@ -783,6 +786,63 @@ double* pmc_ncg_residual(pmc_ncg* w);           /* r */
 int pmc_ncg_status(pmc_ncg* w, int nb, double* rr, int32_t* cg_count, int32_t* done, int32_t* nonpos_curvature);
 int pmc_ncg_axpy_cols(pmc_ncg* w, int nb, const double* t, const double* x, const double* d, double* out, int memspace);
 int pmc_ncg_dot_cols(pmc_ncg* w, int nb, const double* a, const double* b, double* out_host, int memspace);
+
+/* ---- Particle travel times on the Darcy flux as a QoI (an extension: the reference has none)
+ * How long a particle released at a point takes to leave the domain in the RT0 velocity field of a solve, u / porosity.  A
+ * u-dof is the total flux through a face along the face's global normal, so inside an element every coordinate - a box axis,
+ * a barycentric coordinate of a tetrahedron - obeys a scalar linear ODE, and the time to the next face is closed-form
+ * (Pollock's method): no time stepper, no step-size parameter.  One thread walks one particle of one realization.
+ *   create: the mesh arrays are copied and packed; the particles are sorted by start element (the outputs are in the caller's
+ *           order).  A start point may lie outside its elem0 by at most 1e-12 of the element's extent and is clamped into it.
+ *   run:    u: nbatch rows of n_face fluxes, row b at u + b * ld (sol_out of pmc_darcy_solve_fwd passes as it is with
+ *           ld = n_u + n_p).  Outputs, nbatch x nparticles each, in `memspace` like u: T the travel time (the time
+ *           accumulated so far when the path did not exit), exit_face the global id of the boundary face (-1: none), status,
+ *           nsteps the elements crossed, x_exit (may be NULL) nbatch x nparticles x 3 the last position.
+ *   status: PMC_TRACER_EXITED through a boundary face; PMC_TRACER_STAGNANT: no face of the current element can be reached
+ *           (all candidate velocities zero or inward); PMC_TRACER_MAX_STEPS: the step counter reached max_steps.
+ *   reduce: Q[b] (host) = mean of T over all particles of realization b, censored times included (PMC_TRACER_MEAN), or their
+ *           minimum (PMC_TRACER_MIN); not_exited[b] (host, may be NULL) = particles whose status is not EXITED.  T, status in
+ *           `memspace`.  The sum has a fixed order (ascending particles per thread, a fixed tree across the workgroup).
+ * A particle's outputs have the same bits at every nbatch, beside any other realizations, in either memory space, in repeated
+ * calls, and when the walk runs inside a solve (pmc_darcy_set_tracer).
+ * Scope: 3-D meshes of axis-aligned hexahedra or of tetrahedra with element geometry.  2-D meshes and agglomerated levels
+ * (no element geometry) are not supported.
+ * Refused with PMC_ERR_INVALID (nothing is written, the handle stays usable): a kind other than the two, a NULL array
+ * (porosity and x_exit excepted), nparticles < 1, max_steps < 0 or > 2^22, porosity <= 0, elem_face / elem_sign and face_elem
+ * that disagree, boxes that are not axis-aligned and conforming (lo >= hi; a neighbour across local face l that does not meet
+ * the box with its opposite face in the same plane and cross-section), a simplex of non-positive volume, an elem0 out of
+ * range or a start point outside its elem0, nbatch < 1, ld < n_face, a bad memspace. */
+enum pmc_tracer_kind { PMC_TRACER_BOX = 0, PMC_TRACER_SIMPLEX = 1 };
+enum pmc_tracer_status { PMC_TRACER_EXITED = 0, PMC_TRACER_STAGNANT = 1, PMC_TRACER_MAX_STEPS = 2 };
+enum pmc_tracer_qoi { PMC_TRACER_MEAN = 0, PMC_TRACER_MIN = 1 };
+typedef struct pmc_tracer_mesh {      /* host arrays, copied at create */
+    int32_t kind;                     /* PMC_TRACER_BOX (axis-aligned hexahedra) | PMC_TRACER_SIMPLEX (tetrahedra) */
+    int32_t n_elem, n_face;
+    const int32_t* elem_face;         /* n_elem x n_fe (6 | 4); hexahedra: z-, y-, x+, y+, x-, z+; face i of a tetrahedron is opposite vertex i */
+    const int8_t*  elem_sign;         /* n_elem x n_fe, +1: outward = the face's global normal */
+    const int32_t* face_elem;         /* n_face x 2, second -1 on the boundary */
+    const double*  geom;              /* BOX: n_elem x 6 (lo, hi); SIMPLEX: n_elem x 4 x 3 vertex coordinates, positively oriented */
+    const double*  porosity;          /* n_elem, > 0; NULL = 1 */
+} pmc_tracer_mesh;
+typedef struct pmc_tracer pmc_tracer;
+int pmc_tracer_create(pmc_ctx* ctx, const pmc_tracer_mesh* mesh, int nparticles, const double* x0 /* nparticles x 3 */,
+                      const int32_t* elem0, int max_steps /* 0: 64 + 32 ceil(cbrt(n_elem)) */, pmc_tracer** out);
+void pmc_tracer_destroy(pmc_tracer* t);   /* detach it first (pmc_darcy_set_tracer with NULL); before the ctx */
+int pmc_tracer_num_particles(const pmc_tracer* t);
+int pmc_tracer_run(pmc_tracer* t, int nbatch, const double* u, int64_t ld, double* T, int32_t* exit_face,
+                   int32_t* status, int32_t* nsteps, double* x_exit /* may be NULL */, int memspace);
+int pmc_tracer_reduce(pmc_tracer* t, int nbatch, const double* T, const int32_t* status, int kind,
+                      double* Q /* host */, int32_t* not_exited /* host, may be NULL */, int memspace);
+/* Makes the travel-time QoI (kind: PMC_TRACER_MEAN | PMC_TRACER_MIN) the Q of pmc_darcy_solve_fwd and of
+ * pmc_darcy_solve_fwd_pressure (compute_Q) on `level`: it is computed on the solver's internal solution before any copy-out,
+ * equals pmc_tracer_reduce of pmc_tracer_run on sol_out bit for bit, and is what the managers, lanes and farms then see.  The
+ * solve maintains the full solution also when sol_out is NULL.  Every other entry keeps Q = <obs, x>: pmc_darcy_compute_G,
+ * the gradients (pmc_darcy_solve_gradient, pmc_darcy_loglik_gradient) and the Hessian actions (pmc_darcy_gn_hessvec) - the
+ * Q of pmc_darcy_solve_gradient is then no longer that of pmc_darcy_solve_fwd.  t == NULL detaches and restores <obs, x>.
+ * The tracer is not owned, serves one Darcy handle at a time (each lane its own), and must outlive the attachment.
+ * Refused with PMC_ERR_INVALID: a level outside [0, n_mc_levels), n_face != n_u(level) or n_elem != n_p(level), a tracer
+ * created on another context's device, a kind other than the two. */
+int pmc_darcy_set_tracer(pmc_darcy* d, int level, pmc_tracer* t, int kind);
 
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */

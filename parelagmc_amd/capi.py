@@ -88,6 +88,12 @@ class pmc_darcy_level(C.Structure):
                 ("ess_data", C.POINTER(C.c_double)), ("obs", C.POINTER(C.c_double)), ("P", pmc_csr)]
 
 
+class pmc_tracer_mesh(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_elem", C.c_int32), ("n_face", C.c_int32), ("elem_face", C.POINTER(C.c_int32)),
+                ("elem_sign", C.POINTER(C.c_int8)), ("face_elem", C.POINTER(C.c_int32)), ("geom", C.POINTER(C.c_double)),
+                ("porosity", C.POINTER(C.c_double))]
+
+
 # every symbol include/pmc.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _DP = C.c_void_p   # double* that may be a host or a device address
@@ -249,6 +255,13 @@ SYMBOLS = {
                                  C.POINTER(C.c_int32)]),
     "pmc_ncg_axpy_cols": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), _DP, _DP, _DP, C.c_int]),
     "pmc_ncg_dot_cols": (C.c_int, [_VP, C.c_int, _DP, _DP, C.POINTER(C.c_double), C.c_int]),
+    "pmc_tracer_create": (C.c_int, [_VP, C.POINTER(pmc_tracer_mesh), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                    C.c_int, C.POINTER(_VP)]),
+    "pmc_tracer_destroy": (None, [_VP]),
+    "pmc_tracer_num_particles": (C.c_int, [_VP]),
+    "pmc_tracer_run": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _VP, _VP, _VP, _DP, C.c_int]),
+    "pmc_tracer_reduce": (C.c_int, [_VP, C.c_int, _DP, _VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]),
+    "pmc_darcy_set_tracer": (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -405,6 +418,22 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+class DeviceInt32Array(DeviceArray):
+    """int32 array in HBM (the integer outputs of Tracer.Run on device memory): n entries in a DeviceArray of (n + 1) // 2"""
+
+    def __init__(self, ctx: "Context", n: int):
+        super().__init__(ctx, (int(n) + 1) // 2)
+        self.n_int = int(n)
+
+    def upload(self, a):
+        raise TypeError("DeviceInt32Array is an output buffer")
+
+    def download(self) -> np.ndarray:
+        out = np.empty(self.n_int, np.int32)
+        _check(self.ctx.lib.pmc_memcpy_d2h(self.ctx.h, out.ctypes.data, self.ptr, out.nbytes))
+        return out
 
 
 def _batch_of(x, n):
@@ -1304,6 +1333,13 @@ class DarcySolver:
         g = keep.csr(Gobs)
         _check(self.ctx.lib.pmc_darcy_set_observations(self.h, level, C.byref(g)))
 
+    def SetTracer(self, level, tracer, kind=0):
+        """Make the travel-time QoI of `tracer` (kind: Tracer.MEAN | Tracer.MIN) the Q of SolveFwd / SolveFwd_RtnPressure on
+        `level` (pmc_darcy_set_tracer); None detaches.  ComputeG, the gradients and the Hessian actions keep <obs, x>."""
+        _check(self.ctx.lib.pmc_darcy_set_tracer(self.h, level, None if tracer is None else tracer.h, int(kind)))
+        self._tracers = getattr(self, "_tracers", {})
+        self._tracers[level] = tracer          # keeps an attached tracer alive
+
     def ComputeG(self, level, k, nbatch=None):
         """BayesianInverseProblem::ComputeG: returns (G (nbatch, nobs), C, Q)."""
         if isinstance(k, np.ndarray):
@@ -1557,6 +1593,93 @@ class NewtonCG:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.pmc_ncg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Tracer:
+    """Particle travel times on the RT0 Darcy flux (pmc_tracer_*, csrc/tracer.hip).
+
+    mesh: a parelagmc_amd.fe.tracer.TracerMesh (fe.tracer.tracer_mesh of a level); x0: (nparticles, 3) start points;
+    elem0: their elements (None: found geometrically, fe.tracer.locate); max_steps 0: 64 + 32 ceil(cbrt(n_elem))."""
+
+    EXITED, STAGNANT, MAX_STEPS = 0, 1, 2
+    MEAN, MIN = 0, 1
+
+    def __init__(self, ctx: Context, mesh, x0, elem0=None, max_steps: int = 0):
+        self.ctx = ctx
+        x0 = _f64(np.atleast_2d(x0))
+        if elem0 is None:
+            from .fe.tracer import locate
+            elem0 = locate(mesh, x0)
+        elem0 = _i32(elem0)
+        if x0.shape != (elem0.size, 3):
+            raise ValueError("x0 must be nparticles x 3 and elem0 nparticles")
+        keep = _Keep()
+        sign = np.ascontiguousarray(mesh.elem_sign, dtype=np.int8)
+        m = pmc_tracer_mesh(int(mesh.kind), int(mesh.n_elem), int(mesh.n_face), keep.i32(mesh.elem_face),
+                            sign.ctypes.data_as(C.POINTER(C.c_int8)), keep.i32(mesh.face_elem), keep.f64(mesh.geom),
+                            None if mesh.porosity is None else keep.f64(mesh.porosity))
+        h = _VP()
+        _check(ctx.lib.pmc_tracer_create(ctx.h, C.byref(m), int(elem0.size), _ptr(x0, C.c_double), _ptr(elem0, C.c_int32),
+                                         int(max_steps), C.byref(h)))
+        self.h = h
+        self.n_face, self.nparticles = int(mesh.n_face), int(elem0.size)
+        ctx._adopt(self)
+
+    def Run(self, u, nbatch=None, ld=None, want_x=True):
+        """Walk every particle through nbatch flux fields.  u: numpy (nbatch, ld >= n_face) - e.g. sol_out of SolveFwd - or a
+        DeviceArray / torch tensor on the device with nbatch (and ld, default n_face) given.  Returns a dict of T, exit_face,
+        status, nsteps (nbatch x nparticles) and x_exit (nbatch x nparticles x 3, unless want_x is False): numpy arrays for
+        a numpy u, flat DeviceArray / DeviceInt32Array buffers on the device otherwise."""
+        npart = self.nparticles
+        if isinstance(u, np.ndarray):
+            u = _f64(np.atleast_2d(u))
+            nbatch, ld = u.shape
+            T = np.empty((nbatch, npart))
+            ints = [np.empty((nbatch, npart), np.int32) for _ in range(3)]
+            x = np.empty((nbatch, npart, 3)) if want_x else None
+            pu, ms = u.ctypes.data, PMC_MEM_HOST
+            addr = lambda a: None if a is None else a.ctypes.data
+        else:
+            assert nbatch is not None
+            ld = self.n_face if ld is None else int(ld)
+            pu, ms = _addr(u)
+            assert ms == PMC_MEM_DEVICE
+            T = DeviceArray(self.ctx, nbatch * npart)
+            ints = [DeviceInt32Array(self.ctx, nbatch * npart) for _ in range(3)]
+            x = DeviceArray(self.ctx, nbatch * npart * 3) if want_x else None
+            addr = lambda a: None if a is None else a.ptr
+        _check(self.ctx.lib.pmc_tracer_run(self.h, int(nbatch), pu, int(ld), addr(T), addr(ints[0]), addr(ints[1]),
+                                           addr(ints[2]), addr(x), ms))
+        out = dict(T=T, exit_face=ints[0], status=ints[1], nsteps=ints[2])
+        if want_x:
+            out["x_exit"] = x
+        return out
+
+    def Reduce(self, T, status, kind=0):
+        """(Q, not_exited) per realization: the mean (MEAN) or minimum (MIN) travel time and the particles that did not exit"""
+        if isinstance(T, np.ndarray):
+            T = _f64(np.atleast_2d(T))
+            status = _i32(np.atleast_2d(status))
+            nbatch = T.shape[0]
+            pT, ps, ms = T.ctypes.data, status.ctypes.data, PMC_MEM_HOST
+        else:
+            nbatch = T.n // self.nparticles
+            pT, ps, ms = T.ptr, status.ptr, PMC_MEM_DEVICE
+        Q = np.empty(nbatch)
+        nex = np.empty(nbatch, np.int32)
+        _check(self.ctx.lib.pmc_tracer_reduce(self.h, nbatch, pT, ps, int(kind), _ptr(Q, C.c_double), _ptr(nex, C.c_int32), ms))
+        return Q, nex
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pmc_tracer_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -749,6 +749,43 @@ int pmc_ncg_dot_cols(pmc_ncg* w, int nb, const double* a, const double* b, doubl
     });
 }
 
+// ---- particle travel times (tracer.hip) ----
+int pmc_tracer_create(pmc_ctx* ctx, const pmc_tracer_mesh* mesh, int nparticles, const double* x0, const int32_t* elem0,
+                      int max_steps, pmc_tracer** out) {
+    return guarded([&] {
+        PMC_REQUIRE(ctx != nullptr && mesh != nullptr && out != nullptr, "pmc_tracer_create: NULL argument");
+        *out = nullptr;
+        *out = new pmc_tracer(*ctx, *mesh, nparticles, x0, elem0, max_steps);
+    });
+}
+void pmc_tracer_destroy(pmc_tracer* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->impl.ctx.device);
+    (void)hipStreamSynchronize(t->impl.ctx.stream);
+    delete t;
+}
+int pmc_tracer_num_particles(const pmc_tracer* t) { return t ? t->impl.npart : PMC_ERR_INVALID; }
+int pmc_tracer_run(pmc_tracer* t, int nbatch, const double* u, int64_t ld, double* T, int32_t* exit_face, int32_t* status,
+                   int32_t* nsteps, double* x_exit, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_tracer_run: tracer is NULL");
+        t->impl.run(nbatch, u, ld, T, exit_face, status, nsteps, x_exit, memspace);
+    });
+}
+int pmc_tracer_reduce(pmc_tracer* t, int nbatch, const double* T, const int32_t* status, int kind, double* Q,
+                      int32_t* not_exited, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_tracer_reduce: tracer is NULL");
+        t->impl.reduce(nbatch, T, status, kind, Q, not_exited, memspace);
+    });
+}
+int pmc_darcy_set_tracer(pmc_darcy* d, int level, pmc_tracer* t, int kind) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_set_tracer: darcy is NULL");
+        d->impl.set_tracer(level, t ? &t->impl : nullptr, kind);
+    });
+}
+
 int pmc_darcy_num_dofs(const pmc_darcy* d, int level) {
     if (!d || level < 0 || level >= d->impl.nlevels) return PMC_ERR_INVALID;
     return d->impl.lv[level].n_u + d->impl.lv[level].n_p;

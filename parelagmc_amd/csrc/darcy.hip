@@ -776,8 +776,11 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     const int mg_l0 = chain ? 0 : level;
     // SolveFwd only needs Q = <obs, sol>: unless the solution itself is requested, MINRES maintains just the rows in
     // the support of obs (compact w / x vectors)
+    // With a tracer on the level (pmc_darcy_set_tracer) Q is the travel-time QoI, which reads the whole flux block: the full
+    // solution is maintained also when the caller does not ask for it.  ComputeG (gmode) keeps Q = <obs, x>.
     const bool gmode = G_host != nullptr;
-    const bool obs_rows_only = !gmode && d.n_obs > 0 && d.n_obs < n;
+    Tracer* tracer = gmode ? nullptr : tracer_of(level);
+    const bool obs_rows_only = !gmode && !tracer && d.n_obs > 0 && d.n_obs < n;
     const bool compact = gmode || (sol_d == nullptr && obs_rows_only);
     const int ncomp = gmode ? d.n_grows : d.n_obs;
     const int* comp_rows = gmode ? d.g_rows.p : d.obs_rows.p;
@@ -804,10 +807,15 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     // leave its QoI sums unchanged)
     const bool gather_q = !compact && obs_rows_only && row0 == d.n_u;
     if (gather_q) gather_rows(st, nb, ncomp, comp_rows, sol.p, sol_compact.p);
-    // K15: Q = <obs, sol>
-    const int qblocks = compact || gather_q ? k::wdot(st, nb, ncomp, comp_w, sol_compact.p, qpartial.p)
-                                            : k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
-    k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
+    if (tracer) {
+        // Q = the travel-time QoI on the interleaved solution, before any copy-out
+        tracer->qoi_interleaved(st, nb, sol.p, tracer_kind[level], qout.p);
+    } else {
+        // K15: Q = <obs, sol>
+        const int qblocks = compact || gather_q ? k::wdot(st, nb, ncomp, comp_w, sol_compact.p, qpartial.p)
+                                                : k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
+        k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
+    }
     PMC_HIP(hipMemcpyAsync(ctx.h_scal, qout.p, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
     if (sol_d) k::deinterleave(st, nb, nrows, sol.p + (size_t)row0 * nb, nullptr, nullptr, false, sol_d);
     if (gmode) {
@@ -1134,13 +1142,34 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
     k::darcy_backsub_u(st, nb, n_u, hy.owner.p, hy.coef.p, hy.U0.p, hy.ug.p, hy.tu.p, sol.p);
     k::spmm(st, nb, view(hy.PL), hy.lam.p, hy.tp.p, false, nullptr, nullptr);
     k::darcy_backsub_p(st, nb, n_p, hy.coef.p, hy.P0.p, hy.zg.p, hy.tp.p, sol.p + (size_t)n_u * nb);
-    // Q = <obs, sol>
-    const int qblocks = k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
-    k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
+    // Q = <obs, sol>, or the travel-time QoI of the level's tracer (pmc_darcy_set_tracer); the back-substitution always
+    // leaves the full flux block in sol
+    if (Tracer* tracer = tracer_of(level)) {
+        tracer->qoi_interleaved(st, nb, sol.p, tracer_kind[level], qout.p);
+    } else {
+        const int qblocks = k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
+        k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
+    }
     PMC_HIP(hipMemcpyAsync(ctx.h_scal, qout.p, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
     if (sol_d) k::deinterleave(st, nb, nrows, sol.p + (size_t)row0 * nb, nullptr, nullptr, false, sol_d);
     PMC_HIP(hipStreamSynchronize(st));
     for (int kcol = 0; kcol < nb; ++kcol) Q_host[kcol] = ctx.h_scal[kcol];
+}
+
+void Darcy::set_tracer(int level, Tracer* t, int kind) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_set_tracer: level out of range");
+    if (t) {
+        PMC_REQUIRE(kind == PMC_TRACER_MEAN || kind == PMC_TRACER_MIN, "pmc_darcy_set_tracer: kind must be PMC_TRACER_MEAN or _MIN");
+        PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
+                    "pmc_darcy_set_tracer: the tracer's mesh does not match the level (n_face != n_u or n_elem != n_p)");
+        PMC_REQUIRE(t->ctx.device == ctx.device, "pmc_darcy_set_tracer: the tracer was created on another device");
+    }
+    if ((int)tracers.size() < n_mc) {
+        tracers.resize(n_mc, nullptr);
+        tracer_kind.resize(n_mc, PMC_TRACER_MEAN);
+    }
+    tracers[level] = t;
+    tracer_kind[level] = t ? kind : PMC_TRACER_MEAN;
 }
 
 void Darcy::solve_fwd(int level, int nbatch, const double* kf, double* Q, double* C, double* sol_out, int memspace,

@@ -365,7 +365,8 @@ void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSp
     }
     if (op_timer.on) op_timer.harvest();
     if (poly_timer.on) poly_timer.harvest();
-    // Q = <obs, sol> over all rows, as solve_fwd forms it when the solution is requested
+    // Q = <obs, sol> over all rows, as solve_fwd forms it when the solution is requested - also on a level with a tracer
+    // attached (pmc_darcy_set_tracer): the gradient is that of <obs, x>, so its Q stays <obs, x>
     const int qblocks = k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
     k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
     PMC_HIP(hipMemcpyAsync(ctx.h_scal, qout.p, sizeof(double) * nb, hipMemcpyDeviceToHost, st));

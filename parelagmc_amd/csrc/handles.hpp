@@ -255,6 +255,33 @@ size_t kl_adjoint_partials(int n, int m, int nb);
 void kl_eval_adjoint(hipStream_t st, int n, int m, int nb, const double* phi, const double* v, const double* sv, int n_xi,
                      double* grad, double* part);
 
+// Particle travel times on the RT0 flux (tracer.hip, pmc_tracer_*): per element one packed record
+// (faces with the sign folded in, neighbours, porosity, geometry), the particles sorted by start element, and the output
+// buffers of the hooked SolveFwd / the staging of host-memory callers.  Work on ctx's stream, except qoi_interleaved, which
+// runs on the stream of the Darcy handle it is attached to: attach a tracer to one handle at a time.
+struct Tracer {
+    Ctx& ctx;
+    int kind, n_elem, n_face, npart, max_steps = 0;
+    DevBuf<char> recs;
+    DevBuf<double> x0;
+    DevBuf<int32_t> e0, orig;      // start elements in sorted order; orig[p]: the caller's index of sorted particle p
+    DevBuf<double> out_T, out_x, stage_u, red_T, q;
+    DevBuf<int32_t> out_i, red_s, nex;
+    Tracer(Ctx& c, const pmc_tracer_mesh& m, int nparticles, const double* x0, const int32_t* elem0, int max_steps);
+    static int default_max_steps(int n_elem);      // 64 + 32 ceil(cbrt(n_elem))
+    void run(int nbatch, const double* u, int64_t ld, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps,
+             double* x_exit, int memspace);
+    void reduce(int nbatch, const double* T, const int32_t* status, int kind, double* Q, int32_t* not_exited, int memspace);
+    // Q of a launch of the Darcy solver: walk on its interleaved solution sol[row * nb + col], reduce into q_d (device, nb)
+    void qoi_interleaved(hipStream_t st, int nb, const double* sol, int kind, double* q_d);
+
+  private:
+    void launch_walk(hipStream_t st, int nb, bool by_batch, const double* u_d, int64_t stride_face, int64_t stride_batch,
+                     double* T_d, int32_t* face_d, int32_t* status_d, int32_t* steps_d, double* x_d);
+    void launch_reduce(hipStream_t st, int nb, const double* T_d, const int32_t* status_d, int kind, double* q_d,
+                       int32_t* nex_d);
+};
+
 struct DarcyLevel {
     int n_u = 0, n_p = 0, n_coef = 0;
     double ratio_M = 8.0;            // Chebyshev interval of the l1-scaled M-block (from M(k == 1) unless given)
@@ -383,6 +410,13 @@ struct Darcy {
     DevBuf<double> adj_rhs, adj_sol, stage_adj, stage_grad, obs_data;
     // tangent solve (darcy_hessian.hip): third full solution, host staging of the direction; allocated at first use
     DevBuf<double> tan_sol, stage_dk;
+    // travel-time QoI (pmc_darcy_set_tracer): with a tracer on a level, the Q of solve_fwd there is the tracer's reduction of
+    // the particles' travel times on the solve's flux block instead of <obs, x>.  compute_G, the gradients and the Hessian
+    // actions keep <obs, x>.  Not owned.
+    std::vector<Tracer*> tracers;
+    std::vector<int> tracer_kind;
+    void set_tracer(int level, Tracer* t, int kind);
+    Tracer* tracer_of(int level) const { return level < (int)tracers.size() ? tracers[level] : nullptr; }
     bool use_eg(const DarcyLevel& d) const;
     void set_observations(int level, const pmc_csr* Gobs);
     void compute_G(int level, int nbatch, const double* k, double* G, double* C, double* Q, int memspace, pmc_stats* stats);
@@ -503,5 +537,6 @@ struct pmc_sampler { pmc::Sampler impl; template <class... A> explicit pmc_sampl
 struct pmc_conditioner { pmc::Conditioner impl; template <class... A> explicit pmc_conditioner(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_field_stats { pmc::FieldStats impl; template <class... A> explicit pmc_field_stats(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_level_fields { pmc::LevelFields impl; template <class... A> explicit pmc_level_fields(A&&... a) : impl(std::forward<A>(a)...) {} };
+struct pmc_tracer { pmc::Tracer impl; template <class... A> explicit pmc_tracer(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_darcy { pmc::Darcy impl; template <class... A> explicit pmc_darcy(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_ncg { pmc::Ncg impl; template <class... A> explicit pmc_ncg(A&&... a) : impl(std::forward<A>(a)...) {} };

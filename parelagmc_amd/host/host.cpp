@@ -244,7 +244,24 @@ int64_t FieldStatistics::Read(double* expectation, double* second_moment, double
     return n;
 }
 
+// ---- ParticleTracer ---------------------------------------------------------------------------
+ParticleTracer::ParticleTracer(pmc_ctx* ctx, const pmc_tracer_mesh& mesh, int nparticles, const double* x0, const int32_t* elem0,
+                               int max_steps) {
+    check_arg(pmc_tracer_create(ctx, &mesh, nparticles, x0, elem0, max_steps, &h_), "ParticleTracer");
+}
+void ParticleTracer::Run(const Vector& u, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps, double* x_exit) {
+    check_arg(pmc_tracer_run(h_, u.Batch(), u.GetData(), u.Size(), T, exit_face, status, nsteps, x_exit, u.MemSpace()),
+              "ParticleTracer::Run");
+}
+void ParticleTracer::Reduce(int nbatch, const double* T, const int32_t* status, int kind, double* Q, int32_t* not_exited,
+                            int memspace) {
+    check_arg(pmc_tracer_reduce(h_, nbatch, T, status, kind, Q, not_exited, memspace), "ParticleTracer::Reduce");
+}
+
 // ---- DarcySolver ------------------------------------------------------------------------------
+void DarcySolver::SetTracer(int ilevel, ParticleTracer* tracer, int kind) {
+    check_arg(pmc_darcy_set_tracer(h_, ilevel, tracer ? tracer->Handle() : nullptr, kind), "DarcySolver::SetTracer");
+}
 void DarcySolver::SolveFwd(int ilevel, Vector& k, double* Q, double* C) {
     std::vector<pmc_stats> st(k.Batch());
     check(pmc_darcy_solve_fwd(h_, ilevel, k.Batch(), k.GetData(), Q, C, nullptr, k.MemSpace(), st.data()),

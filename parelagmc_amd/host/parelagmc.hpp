@@ -262,9 +262,35 @@ class FieldStatistics {
     int n_ = 0;
 };
 
+/// Particle travel times on the RT0 Darcy flux (an extension): an owning wrapper of pmc_tracer.
+/// Attach it to a level with DarcySolver::SetTracer to make the travel-time QoI the Q the managers see; detach it (or destroy
+/// the solver) before destroying it.  One tracer serves one DarcySolver at a time.
+class ParticleTracer {
+  public:
+    /// x0: nparticles x 3 start points, elem0: their elements; max_steps 0: 64 + 32 ceil(cbrt(n_elem))
+    ParticleTracer(pmc_ctx* ctx, const pmc_tracer_mesh& mesh, int nparticles, const double* x0, const int32_t* elem0,
+                   int max_steps = 0);
+    ~ParticleTracer() { pmc_tracer_destroy(h_); }
+    ParticleTracer(const ParticleTracer&) = delete;
+    ParticleTracer& operator=(const ParticleTracer&) = delete;
+    int NumParticles() const { return pmc_tracer_num_particles(h_); }
+    /// u: the flux rows of u.Batch() realizations (row stride u.Size() >= n_face, e.g. full solution vectors); the outputs are
+    /// u.Batch() x NumParticles() in u's memory space, x_exit (x 3) may be NULL
+    void Run(const Vector& u, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps, double* x_exit = nullptr);
+    /// Q (host, nbatch): mean (PMC_TRACER_MEAN) or minimum (PMC_TRACER_MIN) of T per realization; not_exited (host) may be NULL
+    void Reduce(int nbatch, const double* T, const int32_t* status, int kind, double* Q, int32_t* not_exited, int memspace);
+    pmc_tracer* Handle() const { return h_; }
+
+  private:
+    pmc_tracer* h_ = nullptr;
+};
+
 class DarcySolver : public PhysicalMLSolver {
   public:
     DarcySolver(pmc_ctx* ctx, pmc_darcy* handle) : ctx_(ctx), h_(handle) {}
+    /// Q of SolveFwd / SolveFwd_RtnPressure on ilevel becomes the tracer's travel-time QoI (kind: PMC_TRACER_MEAN | _MIN;
+    /// pmc_darcy_set_tracer); nullptr detaches.  The gradient and Hessian entries keep <obs, x>.
+    void SetTracer(int ilevel, ParticleTracer* tracer, int kind = PMC_TRACER_MEAN);
     using PhysicalMLSolver::SolveFwd;
     using PhysicalMLSolver::SolveFwd_RtnPressure;
     void SolveFwd(int ilevel, Vector& k_over_k_ref, double* Q, double* C) override;
