@@ -35,6 +35,19 @@ TOL_DG = min(10 * MEASURED_DG, 1e-7)
 TOL_TANGENT = min(10 * MEASURED_TANGENT, 1e-7)
 TOL_LOGPOST = min(10 * MEASURED_LOGPOST, 1e-7)
 TOL_LOOSE = 10 * MEASURED_LOOSE
+# The same figures on the element families of tests/derivative_family_cases.py (triangles, quadrilaterals, agglomerated levels;
+# the samplers: the agglomerated levels with unit and non-unit P_s weights, the 2-D hierarchy), measured on an MI355X with the
+# *_on_other_families tests and the family cases of test_pde_eval_tangent below; the lines they come from are quoted in those
+# docstrings.  One constant per family and quantity, the same rule.  The default-options figure keeps TOL_LOOSE: a comparison
+# of the device with itself sets no bound.
+MEASURED_HV_FAMILY = {"tri": 6.1e-11, "quad": 2.4e-11, "agg": 8.6e-11}
+MEASURED_DG_FAMILY = {"tri": 3.8e-11, "quad": 3.0e-11, "agg": 1.4e-10}
+MEASURED_TANGENT_FAMILY = {"tri": 4.0e-13, "agg": 3.2e-12}
+MEASURED_LOGPOST_TRI = 5.2e-12
+TOL_HV_FAMILY = {f: min(10 * m, 1e-7) for f, m in MEASURED_HV_FAMILY.items()}
+TOL_DG_FAMILY = {f: min(10 * m, 1e-7) for f, m in MEASURED_DG_FAMILY.items()}
+TOL_TANGENT_FAMILY = {f: min(10 * m, 1e-7) for f, m in MEASURED_TANGENT_FAMILY.items()}
+TOL_LOGPOST_TRI = min(10 * MEASURED_LOGPOST_TRI, 1e-7)
 PMC_ERR_INVALID = -1
 
 
@@ -51,23 +64,25 @@ def _widths(bw):
 
 
 # ---- the kernel alone ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k_divides", [True, False])
-@pytest.mark.parametrize("mesh", ["hex4", "hex543", "hex5", "hex8", "tet1"])
-def test_mass_tangent_kernel(gpu_ctx, mesh, k_divides):
-    """240 faces (hex4), 60 elements and a partial last face slice (hex543), 450 faces = seven full slices and a partial one
-    (hex5), hex8, tetrahedra; every launch width 1, 2, 4, ... BatchWidth and a ragged batch of 11 (8 + 2 + 1); host and
-    device memory.  Every entry within the first-order summation bound (nside n_fe + 3) 2^-52 sum |dc| |M_aa'| |x_a'| of a
-    reference summed in extended precision; essential rows and p-rows exactly zero; column b bitwise the same for every
-    width and split; <lam, t> against <dk, g> of the device's own mass sensitivity within the sum of the two bounds."""
+def _check_mass_tangent(gpu_ctx, dp, level, n_fe_expected, nside_expected, label, same_bits_as=None):
+    """every launch width 1, 2, 4, ... BatchWidth and a ragged batch of 11 (8 + 2 + 1); host and device memory.  Every entry
+    within the first-order summation bound (nside n_fe + 3) 2^-52 sum |dc| |M_aa'| |x_a'| of a reference summed in extended
+    precision (n_fe: the padded width, nside: the largest number of elements of a face); essential rows and p-rows exactly
+    +0; column b bitwise the same for every width and split; <lam, t> against <dk, g> of the device's own mass sensitivity
+    within the sum of the two bounds; the bytes of a launch as documented with n_fe and nside - the handle derived the
+    twin's padded width and side count, and with them the kernel form it launches (two sides and 3, 4 or 6 faces: the
+    register forms; anything else: the general form).  same_bits_as: a one-level problem whose handle must return the same
+    bits (derivative_family_cases.widened)."""
     from parelagmc_amd import capi
     from parelagmc_amd.fe import darcy_adjoint
-    h, dp = cases.problem(mesh, k_divides)
-    L = dp.levels[0]
+    k_divides = dp.k_divides
+    L = dp.levels[level]
     n = L.n_u + L.n_p
     ess = L.ess_mask.astype(bool)
     assert ess.any()
     ds = capi.DarcySolver(gpu_ctx, dp)
-    bw = ds.BatchWidth(0)
+    other = None if same_bits_as is None else capi.DarcySolver(gpu_ctx, same_bits_as)
+    bw = ds.BatchWidth(level)
     rng = np.random.default_rng(59)
     k = np.exp(rng.standard_normal((bw, L.n_p)))
     dk = rng.standard_normal((bw, L.n_p))
@@ -75,35 +90,37 @@ def test_mass_tangent_kernel(gpu_ctx, mesh, k_divides):
     lam = rng.standard_normal((bw, n))
     lam[:, :L.n_u][:, ess] = 0.0
     n_fe = darcy_adjoint.element_matrices(L)[0].shape[1]
-    assert n_fe == (4 if mesh == "tet1" else 6)
-    nside = 2
-    if mesh == "hex5":
-        assert L.n_u == 450
+    assert n_fe == n_fe_expected
+    nside = nside_expected
     ld = lambda a: a.astype(np.longdouble)      # noqa: E731
     for wrt_log in (False, True):
         ref, scale = darcy_adjoint.mass_tangent(L, k, x, dk, k_divides, wrt_log, return_abs=True, dtype=np.longdouble)
         bound = (nside * n_fe + 3) * 2.0 ** -52 * scale
-        full = ds.mass_tangent(0, k, x, dk, wrt_log)
+        full = ds.mass_tangent(level, k, x, dk, wrt_log)
         assert full.shape == (bw, n)
         err = np.abs(ld(full) - ref)
         free = np.zeros(n, bool)
         free[:L.n_u] = ~ess
         worst = float(np.max(err[:, free] / bound[:, free]))
-        print(f"{mesh} k_divides={k_divides} wrt_log={wrt_log}: width {bw}, max error / bound {worst:.3f}")
+        print(f"{label} k_divides={k_divides} wrt_log={wrt_log}: width {bw}, max error / bound {worst:.3f}")
         assert np.all(err <= bound)
         assert np.all(full[:, ~free] == 0.0) and not np.any(np.signbit(full[:, ~free]))
         for w in _widths(bw)[:-1] + [11]:
-            part = ds.mass_tangent(0, k[:w], x[:w], dk[:w], wrt_log)
+            part = ds.mass_tangent(level, k[:w], x[:w], dk[:w], wrt_log)
             assert np.array_equal(part, full[:w]), f"width {w}"
         for w in (bw, 11):
             kd, xd, dd = (gpu_ctx.array(a[:w]) for a in (k, x, dk))
             td = gpu_ctx.empty(w * n)
-            ds.mass_tangent(0, kd, xd, dd, wrt_log, nbatch=w, t_out=td)
+            ds.mass_tangent(level, kd, xd, dd, wrt_log, nbatch=w, t_out=td)
             assert np.array_equal(td.download().reshape(w, n), full[:w])
             for a in (kd, xd, dd, td):
                 a.free()
+        if other is not None:
+            assert other.BatchWidth(0) == bw
+            for w in (bw, 11, 1):
+                assert np.array_equal(other.mass_tangent(0, k[:w], x[:w], dk[:w], wrt_log), full[:w]), f"width {w}"
         # the transpose pair on the device: <lam, t(dk)> == <dk, g(lam)>
-        g = ds.mass_sensitivity(0, k, x, lam, wrt_log)
+        g = ds.mass_sensitivity(level, k, x, lam, wrt_log)
         g_scale = darcy_adjoint.mass_sensitivity(L, k, x, lam, k_divides, wrt_log, return_abs=True, dtype=np.longdouble)[1]
         g_bound = (n_fe * n_fe + 3) * 2.0 ** -52 * g_scale
         lhs = np.sum(ld(lam) * ld(full), axis=1)
@@ -112,8 +129,53 @@ def test_mass_tangent_kernel(gpu_ctx, mesh, k_divides):
         print(f"    transpose pair: max defect / bound {float(np.max(np.abs(lhs - rhs) / slack)):.3f}")
         assert np.all(np.abs(lhs - rhs) <= slack)
     # bytes of one launch, as documented
-    assert ds.mass_tangent_bytes(0, 16) == L.n_u * nside * (4 + 12 * n_fe) + 16 * (2 * 8 * L.n_p + 2 * 8 * L.n_u)
+    assert ds.mass_tangent_bytes(level, 16) == L.n_u * nside * (4 + 12 * n_fe) + 16 * (2 * 8 * L.n_p + 2 * 8 * L.n_u)
     ds.close()
+    if other is not None:       # derivative_family_cases.widened: one element of 5 faces, three sides on a face
+        assert other.mass_tangent_bytes(0, 16) == L.n_u * 3 * (4 + 12 * 5) + 16 * (2 * 8 * L.n_p + 2 * 8 * L.n_u)
+        other.close()
+
+
+@pytest.mark.parametrize("k_divides", [True, False])
+@pytest.mark.parametrize("mesh", ["hex4", "hex543", "hex5", "hex8", "tet1"])
+def test_mass_tangent_kernel(gpu_ctx, mesh, k_divides):
+    """240 faces (hex4), 60 elements and a partial last face slice (hex543), 450 faces = seven full slices and a partial one
+    (hex5), hex8, tetrahedra; every launch width 1, 2, 4, ... BatchWidth and a ragged batch of 11 (8 + 2 + 1); host and
+    device memory.  Every entry within the first-order summation bound (nside n_fe + 3) 2^-52 sum |dc| |M_aa'| |x_a'| of a
+    reference summed in extended precision; essential rows and p-rows exactly zero; column b bitwise the same for every
+    width and split; <lam, t> against <dk, g> of the device's own mass sensitivity within the sum of the two bounds."""
+    h, dp = cases.problem(mesh, k_divides)
+    if mesh == "hex5":
+        assert dp.levels[0].n_u == 450
+    _check_mass_tangent(gpu_ctx, dp, 0, 4 if mesh == "tet1" else 6, 2, mesh)
+
+
+FAMILY_KERNEL_CASES = [("tri", 0, 3, 2), ("tri", 1, 3, 2), ("quad", 0, 4, 2), ("agg2", 1, 12, 2), ("agg2s", 2, 22, 5),
+                       ("agg3", 1, 15, 2), ("agg3s", 2, 57, 11)]
+
+
+@pytest.mark.parametrize("case,level,n_fe,nside", FAMILY_KERNEL_CASES)
+def test_mass_tangent_kernel_on_other_families(gpu_ctx, case, level, n_fe, nside):
+    """The instantiations no older test launches (cases: tests/derivative_family_cases.py, both k_divides spread over them):
+    mass_tangent_kernel<NB, 3> on tri (2008 faces = 31 slices + 24; 512 = exactly 8 slices), <NB, 4> on quadrilaterals (136
+    faces), the general form <NB, 0> on the agglomerated levels: with two sides on agg2 level 1 (197 faces, 12 to 5 faces
+    per element) and agg3 level 1 (1630 faces = 25 slices + 30); with nside > 2 - the sides of Darcy::ensure_gradient that a
+    face does not have (selem == -1, their padding columns the face itself) - on agg2s level 2 (29 faces, up to 5 sides, 22
+    to 15 faces per element) and agg3s level 2 (234 faces, up to 11 sides, 57 to 10 faces per element).  The padded faces of
+    the narrower elements carry weight zero in every side's row.
+    The general form against the fixed form: as in test_mass_sensitivity_kernel_on_other_families of
+    tests/test_gpu_darcy_gradient.py, through derivative_family_cases.widened (its handle reports 5 faces and three sides
+    in its bytes) - bit for bit at every width.
+    Seeded faults (each built once into a copy of the library and run on an MI355X, none committed): the a2 loop of the
+    general form stopping at nfe - 1 fails all seven cases here (tri and quad in the widened comparison) and the five
+    agglomerated cases of test_gn_hessvec_on_other_families; its side loop stopping at min(nside, 2) fails agg2s and agg3s
+    here (nside 5 and 11), tri and quad in the widened comparison (three sides) and the agg2s / agg3s cases of
+    test_gn_hessvec_on_other_families.  Every older test passes with either fault."""
+    import derivative_family_cases as fcases
+    dp = fcases.problem(case)
+    assert fcases.structure(dp.levels[level])[::2] == (n_fe, nside)
+    wide = fcases.widened(case, level) if case in ("tri", "quad") else None
+    _check_mass_tangent(gpu_ctx, dp, level, n_fe, nside, f"{case} level {level}", same_bits_as=wide)
 
 
 # ---- the Hessian action -------------------------------------------------------------------------------------------------
@@ -123,10 +185,11 @@ def _twin_hv(dp, level, k, dk, Gobs, wrt_log, cols):
     return out                                                                   # b -> (hv, dG, x)
 
 
-def _check_hessvec_level(gpu_ctx, ds, ds_loose, dp, h, level, rng, worst):
+def _check_hessvec_level(gpu_ctx, ds, ds_loose, dp, h, level, rng, worst, Gobs=None, tol_hv=None):
+    tol_hv = TOL_HV if tol_hv is None else tol_hv
     L = dp.levels[level]
     n = L.n_u + L.n_p
-    Gobs = cases.two_cell_observations(h, level)
+    Gobs = cases.two_cell_observations(h, level) if Gobs is None else Gobs
     ds.SetObservations(level, Gobs)
     ds_loose.SetObservations(level, Gobs)
     bw = ds.BatchWidth(level)
@@ -154,7 +217,7 @@ def _check_hessvec_level(gpu_ctx, ds, ds_loose, dp, h, level, rng, worst):
             Hw = ds.gn_hessvec(level, k, w, NOISE, wrt_log, x_in=x)[0]
             for b in range(nb):
                 defect = abs(float(w[b] @ hv[b]) - float(dk[b] @ Hw[b]))
-                assert defect <= 2 * TOL_HV * np.linalg.norm(w[b]) * np.linalg.norm(hv[b])
+                assert defect <= 2 * tol_hv * np.linalg.norm(w[b]) * np.linalg.norm(hv[b])
             # device memory: the same bits, with the solution out and back in
             kd, dd = gpu_ctx.array(k), gpu_ctx.array(dk)
             hd, xd = gpu_ctx.empty(hv.size), gpu_ctx.empty(x.size)
@@ -200,6 +263,39 @@ def test_gn_hessvec_matches_the_direct_solve_twin(gpu_ctx, mesh, k_divides, stor
     assert worst["loose"] < TOL_LOOSE
 
 
+@pytest.mark.parametrize("case,storage,mg", [("tri", "fp64", 0), ("quad", "fp32", 0), ("agg2", "fp64", 0), ("agg2", "fp32", 1),
+                                             ("agg2s", "fp32", 0), ("agg2s", "fp64", 1), ("agg3s", "fp64", 1)])
+def test_gn_hessvec_on_other_families(gpu_ctx, case, storage, mg):
+    """pmc_darcy_gn_hessvec on EVERY level of the cases of tests/derivative_family_cases.py against the twin's direct
+    solves: the tangent right-hand side in its <NB, 3> form (tri), on quadrilaterals, in its general form with two sides
+    (levels 1 and 2 of agg2) and with up to 5 / 11 sides (level 2 of agg2s / agg3s), and the mass sensitivity behind the
+    adjoint solve.  Two observations with unit weights on the agglomerated levels; nb = 3 and BatchWidth + 3 on the finest
+    level; both wrt_log, both storages, both V-cycle modes on the agglomerated levels, both k_divides (the cases' own); host
+    and device memory.
+    Measured on an MI355X (printed by this test):
+        tri k_divides=True fp64 mg_coarsening=0: hv rel. error 6.02e-11, dG 3.80e-11, default options against tight 1.79e-05
+        quad k_divides=False fp32 mg_coarsening=0: hv rel. error 2.34e-11, dG 2.93e-11, default options against tight 1.03e-05
+        agg2 k_divides=False fp64 mg_coarsening=0: hv rel. error 3.98e-11, dG 4.47e-11, default options against tight 7.29e-05
+        agg2 k_divides=False fp32 mg_coarsening=1: hv rel. error 3.22e-11, dG 2.48e-11, default options against tight 1.80e-05
+        agg2s k_divides=True fp32 mg_coarsening=0: hv rel. error 8.58e-11, dG 1.33e-10, default options against tight 4.63e-05
+        agg2s k_divides=True fp64 mg_coarsening=1: hv rel. error 4.77e-11, dG 4.53e-11, default options against tight 2.02e-05
+        agg3s k_divides=False fp64 mg_coarsening=1: hv rel. error 1.22e-11, dG 1.00e-11, default options against tight 2.25e-05"""
+    import derivative_family_cases as fcases
+    from test_gpu_darcy_gradient import family_solvers
+    dp, ds, ds_loose, family = family_solvers(gpu_ctx, case, storage, mg)
+    rng = np.random.default_rng(61)
+    worst = dict(hv=0.0, dG=0.0, loose=0.0)
+    for level in range(dp.n_mc_levels):
+        _check_hessvec_level(gpu_ctx, ds, ds_loose, dp, None, level, rng, worst, Gobs=fcases.observations(case, level),
+                             tol_hv=TOL_HV_FAMILY[family])
+    print(f"{case} k_divides={dp.k_divides} {storage} mg_coarsening={mg}: hv rel. error {worst['hv']:.2e}, dG {worst['dG']:.2e}, "
+          f"default options against tight {worst['loose']:.2e}")
+    ds.close()
+    ds_loose.close()
+    assert worst["hv"] < TOL_HV_FAMILY[family] and worst["dG"] < TOL_DG_FAMILY[family]
+    assert worst["loose"] < TOL_LOOSE
+
+
 def test_hessvec_under_graph_replay(gpu_ctx):
     """gradient, Hessian action, gradient, Hessian action with different directions on one handle with captured MINRES
     iterations: a graph of one solve replayed for another right-hand side would show in either"""
@@ -232,6 +328,10 @@ def _pde_case(kind, mesh, lognormal):
     """(problem for the handle, problem for the twin, projection name, per-level projections for the twin, l2_ops): the cases
     of tests/test_gpu_sampler_adjoint.py"""
     from parelagmc_amd.fe import build_hybrid_sampler_problem, build_sampler_problem
+    if kind in ("agg-unit", "agg-nonunit", "tri"):
+        import derivative_family_cases as fcases
+        sp = fcases.sampler_problem(kind, lognormal)
+        return sp, sp, "none", None, None
     if kind in ("saddle", "hybrid"):
         h = scases.hierarchy(mesh)
         sp = build_sampler_problem(h, corlen=scases.CORLEN, lognormal=lognormal)
@@ -250,25 +350,37 @@ def _pde_case(kind, mesh, lognormal):
 
 
 PDE_CASES = [("saddle", "hex842"), ("saddle", "tet2"), ("hybrid", "hex842"), ("hybrid", "tet2"), ("gather", "ragged"),
-             ("l2", "ragged"), ("hybrid-gather", "ragged"), ("hybrid-l2", "ragged")]
+             ("l2", "ragged"), ("hybrid-gather", "ragged"), ("hybrid-l2", "ragged"), ("agg-unit", "tet2"), ("agg-nonunit", "tet2"),
+             ("tri", "square")]
 
 
 @pytest.mark.parametrize("kind,mesh", PDE_CASES)
 def test_pde_eval_tangent(gpu_ctx, kind, mesh):
     """every (level, xi_level) pair; nb = 3 (launches of 2 + 1) and BatchWidth + 3 on the finest level; the lognormal handle
     with s_out against the twin; bitwise Eval of the same vector on the Gaussian handle, and s_out times that on the lognormal
-    one; host and device memory"""
+    one; host and device memory.
+    agg-unit / agg-nonunit / tri (tests/derivative_family_cases.py; the pairs (0, 0), (1, 0), (2, 0), (2, 2), on tri (0, 0),
+    (1, 0), (1, 1)): the restriction chain of the tangent with 5 to 14 children per parent and weights of 0.5 to 1, and the
+    2-D SPDE (g = 50.13).
+    Measured on an MI355X (printed by this test):
+        agg-unit tet2: eval_tangent rel. error against the twin 2.80e-12
+        agg-nonunit tet2: eval_tangent rel. error against the twin 3.16e-12
+        tri square: eval_tangent rel. error against the twin 4.00e-13"""
     from parelagmc_amd import capi
     from parelagmc_amd.fe import sampler_adjoint
+    from test_gpu_sampler_adjoint import _family_of
+    family, pairs, tight = _family_of(kind)
     prob, twin_prob, projection, projs, ops = _pde_case(kind, mesh, True)
     gprob = _pde_case(kind, mesh, False)[0]
-    logn = capi.PDESampler(gpu_ctx, prob, capi.solver_opts(**TIGHT), projection=projection, l2_ops=ops)
-    gauss = capi.PDESampler(gpu_ctx, gprob, capi.solver_opts(**TIGHT), projection=projection, l2_ops=ops)
+    logn = capi.PDESampler(gpu_ctx, prob, capi.solver_opts(**tight), projection=projection, l2_ops=ops)
+    gauss = capi.PDESampler(gpu_ctx, gprob, capi.solver_opts(**tight), projection=projection, l2_ops=ops)
     rng = np.random.default_rng(71)
     cache = {}
     worst = 0.0
     for level in range(prob.n_mc_levels):
         for xi_level in range(level + 1):
+            if pairs is not None and (level, xi_level) not in pairs:
+                continue
             widths = (3, logn.BatchWidth(level) + 3) if (level, xi_level) == (0, 0) else (3,)
             for nb in widths:
                 xi = rng.standard_normal((nb, logn.xi_size(xi_level)))
@@ -294,7 +406,7 @@ def test_pde_eval_tangent(gpu_ctx, kind, mesh):
     print(f"{kind} {mesh}: eval_tangent rel. error against the twin {worst:.2e}")
     for smp in (logn, gauss):
         smp.close()
-    assert worst < TOL_TANGENT
+    assert worst < (TOL_TANGENT if family is None else TOL_TANGENT_FAMILY[family])
 
 
 @pytest.mark.parametrize("mesh,nm", [("hex16", (3, 3, 3)), ("ragged", (4, 4, 4))])
@@ -385,6 +497,40 @@ def test_logpost_gn_hessvec_matches_the_twin(gpu_ctx, bayes_setup):
             a.free()
     print(f"H_GN: largest rel. error {worst:.2e}")
     assert worst < TOL_LOGPOST
+
+
+def test_logpost_gn_hessvec_on_triangles(gpu_ctx):
+    """pmc_bayes_logpost_gn_hessvec on the 2-D hierarchy of tests/derivative_family_cases.py (1312 / 328 triangles, lognormal
+    sampler at corlen 0.1, two observations): mass_tangent_kernel<NB, 3>, mass_sensitivity_kernel<NB, 3> and the 2-D Eval
+    tangent and adjoint in one chain; both levels and a finer xi; a reused state reproduces the first call bit for bit.
+    Measured on an MI355X (printed by this test):
+        H_GN on triangles: largest rel. error 5.13e-12"""
+    import derivative_family_cases as fcases
+    from parelagmc_amd import capi, host_api
+    from parelagmc_amd.fe import sampler_adjoint
+    dp, sp = fcases.problem("tri"), fcases.sampler_problem("tri", True)
+    smp = capi.PDESampler(gpu_ctx, sp, capi.solver_opts(**TIGHT))
+    ds = capi.DarcySolver(gpu_ctx, dp, capi.solver_opts(**TIGHT))
+    rng = np.random.default_rng(79)
+    cache = {}
+    worst = 0.0
+    for level, xi_level in fcases.level_pairs("tri"):
+        Gobs = fcases.observations("tri", level)
+        ds.SetObservations(level, Gobs)
+        n_xi = sp.levels[xi_level].n_s
+        xi = 0.5 * rng.standard_normal((3, n_xi))
+        v = rng.standard_normal((3, n_xi))
+        hv, state = host_api.bayes_logpost_gn_hessvec(smp, ds, level, xi, v, NOISE, xi_level=xi_level)
+        assert np.array_equal(state[0], smp.Eval(level, xi, xi_level=xi_level))
+        for b in range(3):
+            ref = sampler_adjoint.logpost_gn_hessvec(sp, dp, level, xi[b], v[b], Gobs, NOISE, xi_level, cache=cache)
+            worst = max(worst, rel(hv[b], ref))
+        hv2, _ = host_api.bayes_logpost_gn_hessvec(smp, ds, level, None, v, NOISE, xi_level=xi_level, state=state)
+        assert np.array_equal(hv2, hv)
+    print(f"H_GN on triangles: largest rel. error {worst:.2e}")
+    ds.close()
+    smp.close()
+    assert worst < TOL_LOGPOST_TRI
 
 
 def test_newton_cg_step_through_the_entry(gpu_ctx, bayes_setup):

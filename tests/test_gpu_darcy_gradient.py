@@ -20,6 +20,14 @@ TIGHT = dict(rel_tol=1e-12, abs_tol=1e-12, max_iter=400)
 # this tolerance).
 TOL_GRAD = min(10 * 2.3e-11, 1e-7)
 TOL_LOGLIK = min(10 * 3.5e-11, 1e-7)
+# The same two figures on the element families of tests/derivative_family_cases.py (triangles, quadrilaterals, agglomerated
+# levels), measured on an MI355X with test_gradients_on_other_families below; the lines they come from are quoted in its
+# docstring.  One constant per family and quantity, the same rule.
+MEASURED_GRAD_FAMILY = {"tri": 2.7e-11, "quad": 7.0e-12, "agg": 2.6e-11}
+MEASURED_LOGLIK_FAMILY = {"tri": 1.9e-11, "quad": 6.9e-12, "agg": 2.1e-11}
+TOL_GRAD_FAMILY = {f: min(10 * m, 1e-7) for f, m in MEASURED_GRAD_FAMILY.items()}
+TOL_LOGLIK_FAMILY = {f: min(10 * m, 1e-7) for f, m in MEASURED_LOGLIK_FAMILY.items()}
+TIGHT_AGG = dict(TIGHT, max_iter=600)          # the iteration limit of tests/test_gpu_agglomerated.py
 PMC_ERR_INVALID = -1
 
 
@@ -36,6 +44,62 @@ def _widths(bw):
 
 
 # ---- 4. the kernel alone ------------------------------------------------------------------------------------------------
+def _check_mass_sensitivity(gpu_ctx, dp, level, n_fe_expected, label, same_bits_as=None):
+    """every launch width 1, 2, 4, ... BatchWidth and a ragged batch of 11 (8 + 2 + 1); host and device memory.  Every entry
+    within the first-order summation bound (n_fe^2 + 3) 2^-52 sum |c'| |lam_a M_aa' x_a'| of a reference summed in extended
+    precision (n_fe: the padded width); column b bitwise the same for every width and split; the bytes of a launch as
+    documented with n_fe - the handle derived the twin's padded width, and with it the kernel form it launches (3, 4, 6:
+    the register forms; anything else: the general form).  same_bits_as: a one-level problem whose handle must return the
+    same bits (derivative_family_cases.widened).  Returns the full-width results per wrt_log."""
+    from parelagmc_amd import capi
+    from parelagmc_amd.fe import darcy_adjoint
+    k_divides = dp.k_divides
+    L = dp.levels[level]
+    n = L.n_u + L.n_p
+    ds = capi.DarcySolver(gpu_ctx, dp)
+    other = None if same_bits_as is None else capi.DarcySolver(gpu_ctx, same_bits_as)
+    bw = ds.BatchWidth(level)
+    rng = np.random.default_rng(41)
+    k = np.exp(rng.standard_normal((bw, L.n_p)))
+    x = rng.standard_normal((bw, n))
+    lam = rng.standard_normal((bw, n))
+    n_fe = darcy_adjoint.element_matrices(L)[0].shape[1]
+    assert n_fe == n_fe_expected
+    assert ds.mass_sensitivity_bytes(level, 16) == L.n_p * (4 * n_fe + 8 * n_fe * n_fe + 2 * 8 * 16) + 2 * 8 * 16 * L.n_u
+    out = {}
+    for wrt_log in (False, True):
+        ref, scale = darcy_adjoint.mass_sensitivity(L, k, x, lam, k_divides, wrt_log, return_abs=True, dtype=np.longdouble)
+        bound = (n_fe * n_fe + 3) * 2.0 ** -52 * scale
+        full = ds.mass_sensitivity(level, k, x, lam, wrt_log)
+        assert full.shape == (bw, L.n_p)
+        err = np.abs(full.astype(np.longdouble) - ref)
+        worst = float(np.max(err / bound))
+        print(f"{label} k_divides={k_divides} wrt_log={wrt_log}: width {bw}, max error / bound {worst:.3f}")
+        assert np.all(err <= bound)
+        for w in _widths(bw)[:-1] + [11]:
+            part = ds.mass_sensitivity(level, k[:w], x[:w], lam[:w], wrt_log)
+            assert np.array_equal(part, full[:w]), f"width {w}"
+        # device memory: the full width and the ragged batch
+        for w in (bw, 11):
+            kd, xd, ld = (gpu_ctx.array(a[:w]) for a in (k, x, lam))
+            gd = gpu_ctx.empty(w * L.n_p)
+            ds.mass_sensitivity(level, kd, xd, ld, wrt_log, nbatch=w, grad_out=gd)
+            assert np.array_equal(gd.download().reshape(w, L.n_p), full[:w])
+            for a in (kd, xd, ld, gd):
+                a.free()
+        if other is not None:
+            assert other.BatchWidth(0) == bw
+            for w in (bw, 11, 1):
+                assert np.array_equal(other.mass_sensitivity(0, k[:w], x[:w], lam[:w], wrt_log), full[:w]), f"width {w}"
+        out[wrt_log] = full
+    ds.close()
+    if other is not None:
+        n_w = 5                  # derivative_family_cases.widened: none of the register forms
+        assert other.mass_sensitivity_bytes(0, 16) == L.n_p * (4 * n_w + 8 * n_w * n_w + 2 * 8 * 16) + 2 * 8 * 16 * L.n_u
+        other.close()
+    return out
+
+
 @pytest.mark.parametrize("k_divides", [True, False])
 @pytest.mark.parametrize("mesh", ["hex4", "hex543", "hex5", "hex8", "tet1"])
 def test_mass_sensitivity_kernel(gpu_ctx, mesh, k_divides):
@@ -43,40 +107,36 @@ def test_mass_sensitivity_kernel(gpu_ctx, mesh, k_divides):
     width 1, 2, 4, ... BatchWidth and a ragged batch of 11 (8 + 2 + 1); host and device memory.  Every entry within the
     first-order summation bound (n_fe^2 + 3) 2^-52 sum |c'| |lam_a M_aa' x_a'| of a reference summed in extended precision;
     column b bitwise the same for every width and split."""
-    from parelagmc_amd import capi
-    from parelagmc_amd.fe import darcy_adjoint
     h, dp = cases.problem(mesh, k_divides)
-    L = dp.levels[0]
-    n = L.n_u + L.n_p
-    ds = capi.DarcySolver(gpu_ctx, dp)
-    bw = ds.BatchWidth(0)
-    rng = np.random.default_rng(41)
-    k = np.exp(rng.standard_normal((bw, L.n_p)))
-    x = rng.standard_normal((bw, n))
-    lam = rng.standard_normal((bw, n))
-    n_fe = darcy_adjoint.element_matrices(L)[0].shape[1]
-    assert n_fe == (4 if mesh == "tet1" else 6)
-    for wrt_log in (False, True):
-        ref, scale = darcy_adjoint.mass_sensitivity(L, k, x, lam, k_divides, wrt_log, return_abs=True, dtype=np.longdouble)
-        bound = (n_fe * n_fe + 3) * 2.0 ** -52 * scale
-        full = ds.mass_sensitivity(0, k, x, lam, wrt_log)
-        assert full.shape == (bw, L.n_p)
-        err = np.abs(full.astype(np.longdouble) - ref)
-        worst = float(np.max(err / bound))
-        print(f"{mesh} k_divides={k_divides} wrt_log={wrt_log}: width {bw}, max error / bound {worst:.3f}")
-        assert np.all(err <= bound)
-        for w in _widths(bw)[:-1] + [11]:
-            part = ds.mass_sensitivity(0, k[:w], x[:w], lam[:w], wrt_log)
-            assert np.array_equal(part, full[:w]), f"width {w}"
-        # device memory: the full width and the ragged batch
-        for w in (bw, 11):
-            kd, xd, ld = (gpu_ctx.array(a[:w]) for a in (k, x, lam))
-            gd = gpu_ctx.empty(w * L.n_p)
-            ds.mass_sensitivity(0, kd, xd, ld, wrt_log, nbatch=w, grad_out=gd)
-            assert np.array_equal(gd.download().reshape(w, L.n_p), full[:w])
-            for a in (kd, xd, ld, gd):
-                a.free()
-    ds.close()
+    _check_mass_sensitivity(gpu_ctx, dp, 0, 4 if mesh == "tet1" else 6, mesh)
+
+
+FAMILY_KERNEL_CASES = [("tri", 0, 3, 2), ("tri", 1, 3, 2), ("quad", 0, 4, 2), ("agg2", 1, 12, 2), ("agg2s", 2, 22, 5),
+                       ("agg3", 1, 15, 2), ("agg3s", 2, 57, 11)]
+
+
+@pytest.mark.parametrize("case,level,n_fe,nside", FAMILY_KERNEL_CASES)
+def test_mass_sensitivity_kernel_on_other_families(gpu_ctx, case, level, n_fe, nside):
+    """The instantiations no older test launches (cases: tests/derivative_family_cases.py, both k_divides spread over them):
+    mass_sensitivity_kernel<NB, 3> on tri (1312 elements = 20 slices + 32; 328 = 5 slices + 8), <NB, 4> on quadrilaterals
+    (60 elements, one ragged slice), the general form <NB, 0> on the agglomerated levels: agg2 level 1 (41 elements of 12 to
+    5 faces), agg2s level 2 (5 elements of 22 to 15 faces: one nearly empty slice), agg3 level 1 (334 elements = 5 slices +
+    14, 15 to 4 faces), agg3s level 2 (37 elements of 57 to 10 faces).  On every agglomerated level the elements with fewer
+    faces than the widest run through the zero-weight padding of Darcy::ensure_gradient.
+    The general form against the fixed form: no entry point selects the form - the launch switches on the face count alone
+    - so the test changes the data instead: derivative_family_cases.widened gives one element of tri / quad further faces
+    of weight 0.0; that handle reports 5 faces in its bytes (the general form, every other element padded) and has to
+    return the bits of the fixed form at every width ("the same order, the same bits" of the kernel's comment).
+    Seeded faults (each built once into a copy of the library and run on an MI355X, none committed): the general form
+    skipping a == 0 fails all seven cases here (tri and quad in the widened comparison), the five agglomerated cases of
+    test_gradients_on_other_families and the four agglomerated cases of test_mass_tangent_kernel_on_other_families (its
+    transpose pair); Darcy::ensure_gradient padding with the element's last face at the neighbouring weight instead of
+    weight zero fails the same tests and all seven tangent kernel cases.  Every older test passes with either fault."""
+    import derivative_family_cases as fcases
+    dp = fcases.problem(case)
+    assert fcases.structure(dp.levels[level])[::2] == (n_fe, nside)
+    wide = fcases.widened(case, level) if case in ("tri", "quad") else None
+    _check_mass_sensitivity(gpu_ctx, dp, level, n_fe, f"{case} level {level}", same_bits_as=wide)
 
 
 # ---- 5. the full gradient -----------------------------------------------------------------------------------------------
@@ -87,9 +147,11 @@ def _twin(dp, level, k, adj_rhs, wrt_log):
     return tuple(np.stack([o[i] for o in out]) for i in range(4))   # grad, Q, x, lam
 
 
-def _check_level(ds, ds_loose, dp, level, rng, hybrid, nb=3):
+def _check_level(ds, ds_loose, dp, level, rng, hybrid, nb=3, tol=None):
     """both right-hand sides and both wrt_log on one level: gradient against the twin, Q bitwise against solve_fwd, the two
-    solutions through the operator, the default tolerance against the tight one.  Returns the largest gradient error."""
+    solutions through the operator, the default tolerance against the tight one.  tol: the bound on the gradient's error
+    (None: TOL_GRAD).  Returns the largest gradient error."""
+    tol = TOL_GRAD if tol is None else tol
     from parelagmc_amd.fe import darcy_adjoint
     L = dp.levels[level]
     n = L.n_u + L.n_p
@@ -105,7 +167,7 @@ def _check_level(ds, ds_loose, dp, level, rng, hybrid, nb=3):
             assert np.all(Cc == n)
             e = max(rel(g[b], g_ref[b]) for b in range(nb))
             worst = max(worst, e)
-            assert e < TOL_GRAD, e
+            assert e < tol, e
             assert rel(x, x_ref) < 1e-9 and rel(lam, lam_ref) < 1e-9
             if wrt_log or adj_rhs is not None:
                 continue
@@ -189,6 +251,71 @@ def test_loglik_gradient_matches_the_twin(gpu_ctx, k_divides):
             ll_h, g_h = host_api.bayes_loglik_gradient(ds, level, k, data, noise, wrt_log)
             assert np.array_equal(ll_h, ll) and np.array_equal(g_h, g)
     ds.close()
+
+
+FAMILY_SOLVE_CASES = [("tri", "fp32", 0), ("quad", "fp64", 0), ("agg2", "fp32", 0), ("agg2", "fp64", 1), ("agg2s", "fp64", 0),
+                      ("agg2s", "fp32", 1), ("agg3s", "fp32", 1)]
+
+
+def family_solvers(gpu_ctx, case, storage, mg):
+    """(problem, handle at the 1e-12 options, handle at the default options, family): saddle-point handles"""
+    import derivative_family_cases as fcases
+    from parelagmc_amd import capi
+    dp = fcases.problem(case)
+    st = capi.PMC_STORAGE_FP32 if storage == "fp32" else capi.PMC_STORAGE_FP64
+    agg = case.startswith("agg")
+    ds = capi.DarcySolver(gpu_ctx, dp, capi.solver_opts(precond_storage=st, mg_coarsening=mg, **(TIGHT_AGG if agg else TIGHT)))
+    ds_loose = capi.DarcySolver(gpu_ctx, dp, capi.solver_opts(precond_storage=st, mg_coarsening=mg))
+    return dp, ds, ds_loose, "agg" if agg else case
+
+
+@pytest.mark.parametrize("case,storage,mg", FAMILY_SOLVE_CASES)
+def test_gradients_on_other_families(gpu_ctx, case, storage, mg):
+    """solve_gradient (adj_rhs NULL and random, both wrt_log) and loglik_gradient on EVERY level of the cases of
+    tests/derivative_family_cases.py against the twins' direct solves: the mass sensitivity in its <NB, 3> form (tri), on
+    quadrilaterals, and in its general form with the padding of Darcy::ensure_gradient (levels 1 and 2 of the agglomerated
+    cases; level 2 of agg2s / agg3s with flux dofs of up to 5 / 11 agglomerates), behind the solves it serves.  nb = 3, and
+    one call of BatchWidth + 3 on the finest level; both storages of the preconditioned vectors, both V-cycle modes on the
+    agglomerated levels, both k_divides (the cases' own).
+    Measured on an MI355X (printed by this test):
+        tri k_divides=True fp32 mg_coarsening=0: gradient rel. error 2.67e-11, loglik gradient 1.87e-11
+        quad k_divides=False fp64 mg_coarsening=0: gradient rel. error 6.97e-12, loglik gradient 6.81e-12
+        agg2 k_divides=False fp32 mg_coarsening=0: gradient rel. error 5.44e-12, loglik gradient 1.86e-11
+        agg2 k_divides=False fp64 mg_coarsening=1: gradient rel. error 5.00e-12, loglik gradient 6.93e-12
+        agg2s k_divides=True fp64 mg_coarsening=0: gradient rel. error 2.26e-11, loglik gradient 2.10e-11
+        agg2s k_divides=True fp32 mg_coarsening=1: gradient rel. error 2.56e-11, loglik gradient 1.25e-11
+        agg3s k_divides=False fp32 mg_coarsening=1: gradient rel. error 8.79e-12, loglik gradient 5.53e-12"""
+    import derivative_family_cases as fcases
+    from parelagmc_amd.fe import darcy_adjoint
+    dp, ds, ds_loose, family = family_solvers(gpu_ctx, case, storage, mg)
+    rng = np.random.default_rng(43)
+    worst_g = worst_ll = 0.0
+    for level in range(dp.n_mc_levels):
+        worst_g = max(worst_g, _check_level(ds, ds_loose, dp, level, rng, False, tol=TOL_GRAD_FAMILY[family]))
+        L = dp.levels[level]
+        Gobs = fcases.observations(case, level)
+        ds.SetObservations(level, Gobs)
+        k = np.exp(rng.standard_normal((3, L.n_p)))
+        data = ds.ComputeG(level, np.exp(rng.standard_normal((1, L.n_p))))[0][0]
+        for wrt_log in (False, True):
+            ll, G, g = ds.loglik_gradient(level, k, data, 0.01, wrt_log)
+            for b in range(3):
+                ll_r, G_r, g_r = darcy_adjoint.loglik_gradient(dp, level, k[b], Gobs, data, 0.01, wrt_log)
+                worst_ll = max(worst_ll, rel(g[b], g_r))
+                assert abs(ll[b] - ll_r) <= 1e-9 * abs(ll_r) and np.allclose(G[b], G_r, rtol=1e-9, atol=0.0)
+    # one call wider than a launch on the finest level: the first and the last columns of every piece
+    L = dp.levels[0]
+    bw = ds.BatchWidth(0)
+    k = np.exp(rng.standard_normal((bw + 3, L.n_p)))
+    g = ds.solve_gradient(0, k)[2]
+    assert g.shape == (bw + 3, L.n_p)
+    for b in (0, bw - 1, bw, bw + 1, bw + 2):
+        worst_g = max(worst_g, rel(g[b], darcy_adjoint.gradient(dp, 0, k[b])))
+    print(f"{case} k_divides={dp.k_divides} {storage} mg_coarsening={mg}: gradient rel. error {worst_g:.2e}, loglik gradient "
+          f"{worst_ll:.2e}")
+    ds.close()
+    ds_loose.close()
+    assert worst_g < TOL_GRAD_FAMILY[family] and worst_ll < TOL_LOGLIK_FAMILY[family]
 
 
 def test_gradient_calls_refuse_bad_arguments(gpu_ctx):
