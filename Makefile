@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := parelagmc_amd/csrc
 OBJDIR := build/obj
-SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/darcy_hessian.hip $(CSRC)/newton_cg.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip $(CSRC)/tracer.hip
+SRCS := $(CSRC)/k_sell.hip $(CSRC)/k_darcy.hip $(CSRC)/k_krylov.hip $(CSRC)/k_tail.hip $(CSRC)/k_fields.hip $(CSRC)/sparse.hip $(CSRC)/solver.hip $(CSRC)/sampler.hip $(CSRC)/darcy.hip $(CSRC)/darcy_gradient.hip $(CSRC)/darcy_hessian.hip $(CSRC)/newton_cg.hip $(CSRC)/capi.hip $(CSRC)/hybrid_build.hip $(CSRC)/kl.hip $(CSRC)/kl_adjoint.hip $(CSRC)/sampler_adjoint.hip $(CSRC)/kl_eigs.hip $(CSRC)/field_stats.hip $(CSRC)/level_fields.hip $(CSRC)/condition.hip $(CSRC)/tracer.hip $(CSRC)/transport.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/pmc.h
 EXTRA ?=

@@ -844,6 +844,69 @@ int pmc_tracer_reduce(pmc_tracer* t, int nbatch, const double* T, const int32_t*
  * created on another context's device, a kind other than the two. */
 int pmc_darcy_set_tracer(pmc_darcy* d, int level, pmc_tracer* t, int kind);
 
+/* ---- Upwind solute transport on the Darcy flux as a QoI (an extension: the reference has none)
+ * First-order upwind finite-volume advection of a passive solute on the P0 elements of a level: the breakthrough curve at an
+ * outlet and the mass still in place at t_end.  It needs no geometry - only the rows of the level's divergence matrix B
+ * (n_elem x n_face CSR, not eliminated), the flux block of a solve and one pore volume per element - so it serves triangles,
+ * quadrilaterals, hexahedra, tetrahedra and unsmoothed agglomerated levels alike.
+ *   mesh:   every column of B has one entry (a boundary dof) or two entries in two elements, of opposite sign and with
+ *           |a + b| <= 1e-12 max(|a|, |b|) (an interior dof).  a_f = |B[e_first, f]| of the dof's lowest element, and the
+ *           outward rate of element e through its l-th row entry is g_l = sign(B[e, f]) * (a_f * u_f).
+ *   scheme: out_e = sum_l max(g_l, 0), in_e = sum_l max(-g_l, 0), r_e = max(out_e, in_e), rate = max_e r_e / V_e;
+ *           x = (t_end * rate) / cfl, nsteps = max(1, ceil(x)), dt = t_end / nsteps; per step
+ *           c_e' = (1 - (dt / V_e) r_e) c_e + (dt / V_e) sum_l max(-g_l, 0) cn_l with cn_l the neighbour's old concentration,
+ *           c_in[f] on a boundary dof.  A source dilutes with clean water, a sink extracts at c_e.
+ *   run:    u: nbatch rows of n_face fluxes, row b at u + b * ld (sol_out of pmc_darcy_solve_fwd passes as it is with
+ *           ld = n_u + n_p).  Outputs in `memspace` like u: c_out (nbatch x n_elem, may be NULL) the concentrations at
+ *           t_reached; curve (nbatch x nreport) the mass that left through the outlet dofs by r t_reached / nreport,
+ *           r = 1 .. nreport (linear within a step); stored = sum_e weight_e c_e; rate, t_reached, nsteps, status per column.
+ *   status: PMC_TRANSPORT_OK; PMC_TRANSPORT_STEP_LIMIT: nsteps would exceed max_steps - the column runs max_steps steps of
+ *           dt = cfl / rate and reaches t_reached = max_steps dt < t_end; PMC_TRANSPORT_BAD_FLUX: a flux of the column is not
+ *           finite (rate = +inf) - no step, nsteps = 0, t_reached = 0, c = c0, a zero curve.
+ *   reduce: Q[b] (host) = curve[b][nreport - 1] (PMC_TRANSPORT_MASS_OUT) or stored[b] (PMC_TRANSPORT_STORED).
+ * The sums over outlet dofs and over elements have a fixed order (that of pmc_tracer_reduce).  A column's outputs have the
+ * same bits at every nbatch, beside any other columns, in either memory space, in repeated calls, and when the transport runs
+ * inside a solve (pmc_darcy_set_transport).
+ * Refused with PMC_ERR_INVALID (nothing is written, the handle stays usable): a NULL required argument, n_elem < 1 or
+ * n_face < 1, a bad rowptr, a column index out of range, a zero or non-finite entry of val, a column of B that breaks the rule
+ * above, a pore volume that is not positive and finite, a non-finite entry of c0, c_in or weight, an outlet flag on an
+ * interior dof, t_end <= 0, cfl outside (0, 1], nreport outside [1, 4096], max_steps < 0 or > 2^24, nbatch < 1, ld < n_face,
+ * a bad memspace, a kind other than the two. */
+enum pmc_transport_status { PMC_TRANSPORT_OK = 0, PMC_TRANSPORT_STEP_LIMIT = 1, PMC_TRANSPORT_BAD_FLUX = 2 };
+enum pmc_transport_qoi { PMC_TRANSPORT_MASS_OUT = 0, PMC_TRANSPORT_STORED = 1 };
+typedef struct pmc_transport_mesh {   /* host arrays, copied at create */
+    int32_t n_elem, n_face;
+    const int32_t* rowptr;            /* B of the level, CSR: n_elem + 1 */
+    const int32_t* col;
+    const double*  val;
+    const double*  pore_volume;       /* n_elem, > 0 */
+    const double*  c0;                /* n_elem, NULL = 0 */
+    const double*  c_in;              /* n_face, NULL = 1; read on boundary dofs only */
+    const uint8_t* outlet;            /* n_face, NULL = every boundary dof; set only on boundary dofs */
+    const double*  weight;            /* n_elem, NULL = pore_volume */
+} pmc_transport_mesh;
+typedef struct pmc_transport_params {
+    double t_end, cfl;
+    int32_t nreport, max_steps;       /* max_steps 0: 65536 */
+} pmc_transport_params;
+typedef struct pmc_transport pmc_transport;
+int pmc_transport_create(pmc_ctx* ctx, const pmc_transport_mesh* mesh, const pmc_transport_params* params, pmc_transport** out);
+void pmc_transport_destroy(pmc_transport* t);   /* detach it first (pmc_darcy_set_transport with NULL); before the ctx */
+int pmc_transport_size(const pmc_transport* t, int* n_elem, int* n_face, int* n_outlet, int* nreport);
+int pmc_transport_run(pmc_transport* t, int nbatch, const double* u, int64_t ld, double* c_out /* may be NULL */, double* curve,
+                      double* stored, double* rate, double* t_reached, int32_t* nsteps, int32_t* status, int memspace);
+int pmc_transport_reduce(pmc_transport* t, int nbatch, const double* curve, const double* stored, int kind, double* Q /* host */,
+                         int memspace);
+/* Makes the transport QoI (kind: PMC_TRANSPORT_MASS_OUT | PMC_TRANSPORT_STORED) the Q of pmc_darcy_solve_fwd and of
+ * pmc_darcy_solve_fwd_pressure on `level`, as pmc_darcy_set_tracer does for the travel time: computed on the solver's internal
+ * solution before any copy-out, equal to pmc_transport_reduce of pmc_transport_run on sol_out bit for bit; the solve maintains
+ * the full solution.  pmc_darcy_compute_G, the gradients and the Hessian actions keep Q = <obs, x>.  t == NULL detaches.  A
+ * level holds a tracer or a transport, not both: attaching one while the other is attached is refused, here and in
+ * pmc_darcy_set_tracer.  The handle is not owned, serves one Darcy handle at a time and must outlive the attachment.
+ * Refused with PMC_ERR_INVALID: a level outside [0, n_mc_levels), n_face != n_u(level) or n_elem != n_p(level), a handle
+ * created on another context's device, a kind other than the two, a tracer attached to the level. */
+int pmc_darcy_set_transport(pmc_darcy* d, int level, pmc_transport* t, int kind);
+
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */
 int pmc_comm_unique_id(void* id128);                                        /* 128 bytes    */

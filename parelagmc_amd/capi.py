@@ -94,6 +94,16 @@ class pmc_tracer_mesh(C.Structure):
                 ("porosity", C.POINTER(C.c_double))]
 
 
+class pmc_transport_mesh(C.Structure):
+    _fields_ = [("n_elem", C.c_int32), ("n_face", C.c_int32), ("rowptr", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)),
+                ("val", C.POINTER(C.c_double)), ("pore_volume", C.POINTER(C.c_double)), ("c0", C.POINTER(C.c_double)),
+                ("c_in", C.POINTER(C.c_double)), ("outlet", C.POINTER(C.c_uint8)), ("weight", C.POINTER(C.c_double))]
+
+
+class pmc_transport_params(C.Structure):
+    _fields_ = [("t_end", C.c_double), ("cfl", C.c_double), ("nreport", C.c_int32), ("max_steps", C.c_int32)]
+
+
 # every symbol include/pmc.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _DP = C.c_void_p   # double* that may be a host or a device address
@@ -262,6 +272,12 @@ SYMBOLS = {
     "pmc_tracer_run": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _VP, _VP, _VP, _DP, C.c_int]),
     "pmc_tracer_reduce": (C.c_int, [_VP, C.c_int, _DP, _VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]),
     "pmc_darcy_set_tracer": (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
+    "pmc_transport_create": (C.c_int, [_VP, C.POINTER(pmc_transport_mesh), C.POINTER(pmc_transport_params), C.POINTER(_VP)]),
+    "pmc_transport_destroy": (None, [_VP]),
+    "pmc_transport_size": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pmc_transport_run": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _DP, _DP, _DP, _DP, _VP, _VP, C.c_int]),
+    "pmc_transport_reduce": (C.c_int, [_VP, C.c_int, _DP, _DP, C.c_int, C.POINTER(C.c_double), C.c_int]),
+    "pmc_darcy_set_transport": (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -1340,6 +1356,14 @@ class DarcySolver:
         self._tracers = getattr(self, "_tracers", {})
         self._tracers[level] = tracer          # keeps an attached tracer alive
 
+    def SetTransport(self, level, transport, kind=0):
+        """Make the solute-transport QoI of `transport` (kind: Transport.MASS_OUT | Transport.STORED) the Q of SolveFwd /
+        SolveFwd_RtnPressure on `level` (pmc_darcy_set_transport); None detaches.  ComputeG, the gradients and the Hessian
+        actions keep <obs, x>.  A level holds a tracer or a transport, not both."""
+        _check(self.ctx.lib.pmc_darcy_set_transport(self.h, level, None if transport is None else transport.h, int(kind)))
+        self._transports = getattr(self, "_transports", {})
+        self._transports[level] = transport    # keeps an attached handle alive
+
     def ComputeG(self, level, k, nbatch=None):
         """BayesianInverseProblem::ComputeG: returns (G (nbatch, nobs), C, Q)."""
         if isinstance(k, np.ndarray):
@@ -1680,6 +1704,90 @@ class Tracer:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.pmc_tracer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Transport:
+    """First-order upwind transport of a passive solute on the Darcy flux (pmc_transport_*, csrc/transport.hip; DESIGN.md
+    section 21).
+
+    mesh: a parelagmc_amd.fe.transport.TransportMesh (fe.transport.transport_mesh of a Darcy level and its element volumes);
+    t_end: the time to advance to; cfl in (0, 1]; nreport: points of the breakthrough curve; max_steps 0: 65536."""
+
+    OK, STEP_LIMIT, BAD_FLUX = 0, 1, 2
+    MASS_OUT, STORED = 0, 1
+
+    def __init__(self, ctx: Context, mesh, t_end: float, cfl: float = 0.9, nreport: int = 1, max_steps: int = 0):
+        self.ctx = ctx
+        keep = _Keep()
+        opt = lambda a: None if a is None else keep.f64(a)
+        outlet = None
+        if mesh.outlet is not None:
+            flags = np.ascontiguousarray(mesh.outlet, dtype=np.uint8)
+            keep.refs.append(flags)
+            outlet = flags.ctypes.data_as(C.POINTER(C.c_uint8))
+        m = pmc_transport_mesh(int(mesh.n_elem), int(mesh.n_face), keep.i32(mesh.rowptr), keep.i32(mesh.col), keep.f64(mesh.val),
+                               keep.f64(mesh.pore_volume), opt(mesh.c0), opt(mesh.c_in), outlet, opt(mesh.weight))
+        prm = pmc_transport_params(float(t_end), float(cfl), int(nreport), int(max_steps))
+        h = _VP()
+        _check(ctx.lib.pmc_transport_create(ctx.h, C.byref(m), C.byref(prm), C.byref(h)))
+        self.h = h
+        size = [C.c_int() for _ in range(4)]
+        _check(ctx.lib.pmc_transport_size(h, *[C.byref(x) for x in size]))
+        self.n_elem, self.n_face, self.n_outlet, self.nreport = (x.value for x in size)
+        ctx._adopt(self)
+
+    def Run(self, u, nbatch=None, ld=None, want_c=True):
+        """Advance nbatch flux fields to t_end.  u: numpy (nbatch, ld >= n_face) - e.g. sol_out of SolveFwd - or a DeviceArray /
+        torch tensor on the device with nbatch (and ld, default n_face) given.  Returns a dict of c (nbatch x n_elem, unless
+        want_c is False), curve (nbatch x nreport), stored, rate, t_reached, nsteps and status (nbatch): numpy arrays for a
+        numpy u, flat DeviceArray / DeviceInt32Array buffers on the device otherwise."""
+        ne, nr = self.n_elem, self.nreport
+        if isinstance(u, np.ndarray):
+            u = _f64(np.atleast_2d(u))
+            nbatch, ld = u.shape
+            out = dict(c=np.empty((nbatch, ne)) if want_c else None, curve=np.empty((nbatch, nr)), stored=np.empty(nbatch),
+                       rate=np.empty(nbatch), t_reached=np.empty(nbatch), nsteps=np.empty(nbatch, np.int32),
+                       status=np.empty(nbatch, np.int32))
+            pu, ms = u.ctypes.data, PMC_MEM_HOST
+            addr = lambda a: None if a is None else a.ctypes.data
+        else:
+            assert nbatch is not None
+            ld = self.n_face if ld is None else int(ld)
+            pu, ms = _addr(u)
+            assert ms == PMC_MEM_DEVICE
+            dev = lambda n: DeviceArray(self.ctx, n)
+            out = dict(c=dev(nbatch * ne) if want_c else None, curve=dev(nbatch * nr), stored=dev(nbatch), rate=dev(nbatch),
+                       t_reached=dev(nbatch), nsteps=DeviceInt32Array(self.ctx, nbatch), status=DeviceInt32Array(self.ctx, nbatch))
+            addr = lambda a: None if a is None else a.ptr
+        _check(self.ctx.lib.pmc_transport_run(self.h, int(nbatch), pu, int(ld), *[addr(out[k]) for k in
+                                              ("c", "curve", "stored", "rate", "t_reached", "nsteps", "status")], ms))
+        if not want_c:
+            del out["c"]
+        return out
+
+    def Reduce(self, curve, stored, kind=0):
+        """Q per realization: the mass that left through the outlet (MASS_OUT) or the weighted mass in place (STORED)"""
+        if isinstance(curve, np.ndarray):
+            curve, stored = _f64(np.atleast_2d(curve)), _f64(np.atleast_1d(stored))
+            nbatch = curve.shape[0]
+            pc, ps, ms = curve.ctypes.data, stored.ctypes.data, PMC_MEM_HOST
+        else:
+            nbatch = curve.n // self.nreport
+            pc, ps, ms = curve.ptr, stored.ptr, PMC_MEM_DEVICE
+        Q = np.empty(nbatch)
+        _check(self.ctx.lib.pmc_transport_reduce(self.h, nbatch, pc, ps, int(kind), _ptr(Q, C.c_double), ms))
+        return Q
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pmc_transport_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -786,6 +786,48 @@ int pmc_darcy_set_tracer(pmc_darcy* d, int level, pmc_tracer* t, int kind) {
     });
 }
 
+// ---- upwind solute transport (transport.hip) ----
+int pmc_transport_create(pmc_ctx* ctx, const pmc_transport_mesh* mesh, const pmc_transport_params* params, pmc_transport** out) {
+    return guarded([&] {
+        PMC_REQUIRE(ctx != nullptr && mesh != nullptr && params != nullptr && out != nullptr, "pmc_transport_create: NULL argument");
+        *out = nullptr;
+        *out = new pmc_transport(*ctx, *mesh, *params);
+    });
+}
+void pmc_transport_destroy(pmc_transport* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->impl.ctx.device);
+    (void)hipStreamSynchronize(t->impl.ctx.stream);
+    delete t;
+}
+int pmc_transport_size(const pmc_transport* t, int* n_elem, int* n_face, int* n_outlet, int* nreport) {
+    if (!t) return PMC_ERR_INVALID;
+    if (n_elem) *n_elem = t->impl.n_elem;
+    if (n_face) *n_face = t->impl.n_face;
+    if (n_outlet) *n_outlet = t->impl.n_outlet;
+    if (nreport) *nreport = t->impl.nreport;
+    return PMC_OK;
+}
+int pmc_transport_run(pmc_transport* t, int nbatch, const double* u, int64_t ld, double* c_out, double* curve, double* stored,
+                      double* rate, double* t_reached, int32_t* nsteps, int32_t* status, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_transport_run: transport is NULL");
+        t->impl.run(nbatch, u, ld, c_out, curve, stored, rate, t_reached, nsteps, status, memspace);
+    });
+}
+int pmc_transport_reduce(pmc_transport* t, int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_transport_reduce: transport is NULL");
+        t->impl.reduce(nbatch, curve, stored, kind, Q, memspace);
+    });
+}
+int pmc_darcy_set_transport(pmc_darcy* d, int level, pmc_transport* t, int kind) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_set_transport: darcy is NULL");
+        d->impl.set_transport(level, t ? &t->impl : nullptr, kind);
+    });
+}
+
 int pmc_darcy_num_dofs(const pmc_darcy* d, int level) {
     if (!d || level < 0 || level >= d->impl.nlevels) return PMC_ERR_INVALID;
     return d->impl.lv[level].n_u + d->impl.lv[level].n_p;

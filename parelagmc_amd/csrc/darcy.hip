@@ -779,8 +779,10 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     // With a tracer on the level (pmc_darcy_set_tracer) Q is the travel-time QoI, which reads the whole flux block: the full
     // solution is maintained also when the caller does not ask for it.  ComputeG (gmode) keeps Q = <obs, x>.
     const bool gmode = G_host != nullptr;
+    // A transport on the level (pmc_darcy_set_transport) does the same with its QoI.
     Tracer* tracer = gmode ? nullptr : tracer_of(level);
-    const bool obs_rows_only = !gmode && !tracer && d.n_obs > 0 && d.n_obs < n;
+    Transport* transport = gmode ? nullptr : transport_of(level);
+    const bool obs_rows_only = !gmode && !tracer && !transport && d.n_obs > 0 && d.n_obs < n;
     const bool compact = gmode || (sol_d == nullptr && obs_rows_only);
     const int ncomp = gmode ? d.n_grows : d.n_obs;
     const int* comp_rows = gmode ? d.g_rows.p : d.obs_rows.p;
@@ -810,6 +812,9 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     if (tracer) {
         // Q = the travel-time QoI on the interleaved solution, before any copy-out
         tracer->qoi_interleaved(st, nb, sol.p, tracer_kind[level], qout.p);
+    } else if (transport) {
+        // Q = the transport QoI on the interleaved solution, before any copy-out (minres_solve has synchronised the stream)
+        transport->qoi_interleaved(st, nb, sol.p, transport_kind[level], qout.p);
     } else {
         // K15: Q = <obs, sol>
         const int qblocks = compact || gather_q ? k::wdot(st, nb, ncomp, comp_w, sol_compact.p, qpartial.p)
@@ -1146,6 +1151,8 @@ void Darcy::solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_h
     // leaves the full flux block in sol
     if (Tracer* tracer = tracer_of(level)) {
         tracer->qoi_interleaved(st, nb, sol.p, tracer_kind[level], qout.p);
+    } else if (Transport* transport = transport_of(level)) {
+        transport->qoi_interleaved(st, nb, sol.p, transport_kind[level], qout.p);
     } else {
         const int qblocks = k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
         k::reduce_final(st, nb, qblocks, qpartial.p, qout.p);
@@ -1163,6 +1170,7 @@ void Darcy::set_tracer(int level, Tracer* t, int kind) {
         PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
                     "pmc_darcy_set_tracer: the tracer's mesh does not match the level (n_face != n_u or n_elem != n_p)");
         PMC_REQUIRE(t->ctx.device == ctx.device, "pmc_darcy_set_tracer: the tracer was created on another device");
+        PMC_REQUIRE(!transport_of(level), "pmc_darcy_set_tracer: a transport is attached to the level (detach it first)");
     }
     if ((int)tracers.size() < n_mc) {
         tracers.resize(n_mc, nullptr);
@@ -1170,6 +1178,24 @@ void Darcy::set_tracer(int level, Tracer* t, int kind) {
     }
     tracers[level] = t;
     tracer_kind[level] = t ? kind : PMC_TRACER_MEAN;
+}
+
+void Darcy::set_transport(int level, Transport* t, int kind) {
+    PMC_REQUIRE(level >= 0 && level < n_mc, "pmc_darcy_set_transport: level out of range");
+    if (t) {
+        PMC_REQUIRE(kind == PMC_TRANSPORT_MASS_OUT || kind == PMC_TRANSPORT_STORED,
+                    "pmc_darcy_set_transport: kind must be PMC_TRANSPORT_MASS_OUT or _STORED");
+        PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
+                    "pmc_darcy_set_transport: the transport's mesh does not match the level (n_face != n_u or n_elem != n_p)");
+        PMC_REQUIRE(t->ctx.device == ctx.device, "pmc_darcy_set_transport: the transport was created on another device");
+        PMC_REQUIRE(!tracer_of(level), "pmc_darcy_set_transport: a tracer is attached to the level (detach it first)");
+    }
+    if ((int)transports.size() < n_mc) {
+        transports.resize(n_mc, nullptr);
+        transport_kind.resize(n_mc, PMC_TRANSPORT_MASS_OUT);
+    }
+    transports[level] = t;
+    transport_kind[level] = t ? kind : PMC_TRANSPORT_MASS_OUT;
 }
 
 void Darcy::solve_fwd(int level, int nbatch, const double* kf, double* Q, double* C, double* sol_out, int memspace,

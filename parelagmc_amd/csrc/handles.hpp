@@ -282,6 +282,34 @@ struct Tracer {
                        int32_t* nex_d);
 };
 
+// Upwind transport of a passive solute on the Darcy flux (transport.hip, pmc_transport_*): the rows of
+// B packed as (dof with the sign folded in, neighbour element) pairs, one magnitude per dof, and the scratch of a call - two
+// concentration buffers, the outlet accumulators and their snapshots at the report times.  Work on ctx's stream, except
+// qoi_interleaved, which runs on the stream of the Darcy handle it is attached to: attach it to one handle at a time.
+struct Transport {
+    Ctx& ctx;
+    int n_elem, n_face, n_outlet = 0, nreport, max_steps = 0;
+    int width = 0;                 // 3 | 4 | 6: every row has that many entries (register form); 0: the general form
+    double t_end, cfl;
+    DevBuf<int32_t> rec, rowptr;
+    DevBuf<double> a, cin, vol, c0, wgt;
+    DevBuf<double> cbuf, acc, snap, col_rate, col_dt, stage_u, out_c, out_curve, out_stored;
+    DevBuf<int32_t> col_steps;
+    std::vector<double> h_rate, h_dt, h_treached;   // the plan of the last launch, per column
+    std::vector<int32_t> h_steps, h_status;
+    Transport(Ctx& c, const pmc_transport_mesh& m, const pmc_transport_params& p);
+    void run(int nbatch, const double* u, int64_t ld, double* c_out, double* curve, double* stored, double* rate,
+             double* t_reached, int32_t* nsteps, int32_t* status, int memspace);
+    void reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace);
+    // Q of a launch of the Darcy solver: the transport on its interleaved solution sol[row * nb + col] into q_d (device, nb)
+    void qoi_interleaved(hipStream_t st, int nb, const double* sol, int kind, double* q_d);
+
+  private:
+    int nnz_ = 0;
+    void compute(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
+                 double* stored_d, int kind, double* q_d);
+};
+
 struct DarcyLevel {
     int n_u = 0, n_p = 0, n_coef = 0;
     double ratio_M = 8.0;            // Chebyshev interval of the l1-scaled M-block (from M(k == 1) unless given)
@@ -417,6 +445,12 @@ struct Darcy {
     std::vector<int> tracer_kind;
     void set_tracer(int level, Tracer* t, int kind);
     Tracer* tracer_of(int level) const { return level < (int)tracers.size() ? tracers[level] : nullptr; }
+    // solute-transport QoI (pmc_darcy_set_transport): as the tracer's hook, with the mass that left through the outlet or the
+    // mass in place as Q.  A level holds a tracer or a transport, not both.  Not owned.
+    std::vector<Transport*> transports;
+    std::vector<int> transport_kind;
+    void set_transport(int level, Transport* t, int kind);
+    Transport* transport_of(int level) const { return level < (int)transports.size() ? transports[level] : nullptr; }
     bool use_eg(const DarcyLevel& d) const;
     void set_observations(int level, const pmc_csr* Gobs);
     void compute_G(int level, int nbatch, const double* k, double* G, double* C, double* Q, int memspace, pmc_stats* stats);
@@ -538,5 +572,6 @@ struct pmc_conditioner { pmc::Conditioner impl; template <class... A> explicit p
 struct pmc_field_stats { pmc::FieldStats impl; template <class... A> explicit pmc_field_stats(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_level_fields { pmc::LevelFields impl; template <class... A> explicit pmc_level_fields(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_tracer { pmc::Tracer impl; template <class... A> explicit pmc_tracer(A&&... a) : impl(std::forward<A>(a)...) {} };
+struct pmc_transport { pmc::Transport impl; template <class... A> explicit pmc_transport(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_darcy { pmc::Darcy impl; template <class... A> explicit pmc_darcy(A&&... a) : impl(std::forward<A>(a)...) {} };
 struct pmc_ncg { pmc::Ncg impl; template <class... A> explicit pmc_ncg(A&&... a) : impl(std::forward<A>(a)...) {} };

@@ -258,7 +258,25 @@ void ParticleTracer::Reduce(int nbatch, const double* T, const int32_t* status, 
     check_arg(pmc_tracer_reduce(h_, nbatch, T, status, kind, Q, not_exited, memspace), "ParticleTracer::Reduce");
 }
 
+// ---- SoluteTransport --------------------------------------------------------------------------
+SoluteTransport::SoluteTransport(pmc_ctx* ctx, const pmc_transport_mesh& mesh, const pmc_transport_params& params) {
+    check_arg(pmc_transport_create(ctx, &mesh, &params, &h_), "SoluteTransport");
+    check_arg(pmc_transport_size(h_, &n_elem_, &n_face_, &n_outlet_, &nreport_), "SoluteTransport");
+}
+void SoluteTransport::Run(const Vector& u, double* c_out, double* curve, double* stored, double* rate, double* t_reached,
+                          int32_t* nsteps, int32_t* status) {
+    check_arg(pmc_transport_run(h_, u.Batch(), u.GetData(), u.Size(), c_out, curve, stored, rate, t_reached, nsteps, status,
+                                u.MemSpace()),
+              "SoluteTransport::Run");
+}
+void SoluteTransport::Reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace) {
+    check_arg(pmc_transport_reduce(h_, nbatch, curve, stored, kind, Q, memspace), "SoluteTransport::Reduce");
+}
+
 // ---- DarcySolver ------------------------------------------------------------------------------
+void DarcySolver::SetTransport(int ilevel, SoluteTransport* transport, int kind) {
+    check_arg(pmc_darcy_set_transport(h_, ilevel, transport ? transport->Handle() : nullptr, kind), "DarcySolver::SetTransport");
+}
 void DarcySolver::SetTracer(int ilevel, ParticleTracer* tracer, int kind) {
     check_arg(pmc_darcy_set_tracer(h_, ilevel, tracer ? tracer->Handle() : nullptr, kind), "DarcySolver::SetTracer");
 }

@@ -285,9 +285,40 @@ class ParticleTracer {
     pmc_tracer* h_ = nullptr;
 };
 
+/// First-order upwind transport of a passive solute on the Darcy flux (an extension): an owning wrapper
+/// of pmc_transport.  Attach it to a level with DarcySolver::SetTransport to make the mass that left through the outlet, or
+/// the mass in place, the Q the managers see; detach it (or destroy the solver) before destroying it.  One handle serves one
+/// DarcySolver at a time.
+class SoluteTransport {
+  public:
+    SoluteTransport(pmc_ctx* ctx, const pmc_transport_mesh& mesh, const pmc_transport_params& params);
+    ~SoluteTransport() { pmc_transport_destroy(h_); }
+    SoluteTransport(const SoluteTransport&) = delete;
+    SoluteTransport& operator=(const SoluteTransport&) = delete;
+    int NumElements() const { return n_elem_; }
+    int NumFluxDofs() const { return n_face_; }
+    int NumOutletDofs() const { return n_outlet_; }
+    int NumReports() const { return nreport_; }
+    /// u: the flux rows of u.Batch() realizations (row stride u.Size() >= n_face, e.g. full solution vectors); the outputs are
+    /// in u's memory space: c_out u.Batch() x NumElements() (may be NULL), curve u.Batch() x NumReports(), the rest u.Batch()
+    void Run(const Vector& u, double* c_out, double* curve, double* stored, double* rate, double* t_reached, int32_t* nsteps,
+             int32_t* status);
+    /// Q (host, nbatch): curve[.][NumReports() - 1] (PMC_TRANSPORT_MASS_OUT) or stored (PMC_TRANSPORT_STORED)
+    void Reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace);
+    pmc_transport* Handle() const { return h_; }
+
+  private:
+    pmc_transport* h_ = nullptr;
+    int n_elem_ = 0, n_face_ = 0, n_outlet_ = 0, nreport_ = 0;
+};
+
 class DarcySolver : public PhysicalMLSolver {
   public:
     DarcySolver(pmc_ctx* ctx, pmc_darcy* handle) : ctx_(ctx), h_(handle) {}
+    /// Q of SolveFwd / SolveFwd_RtnPressure on ilevel becomes the transport QoI (kind: PMC_TRANSPORT_MASS_OUT | _STORED;
+    /// pmc_darcy_set_transport); nullptr detaches.  The gradient and Hessian entries keep <obs, x>.  A level holds a tracer or
+    /// a transport, not both.
+    void SetTransport(int ilevel, SoluteTransport* transport, int kind = PMC_TRANSPORT_MASS_OUT);
     /// Q of SolveFwd / SolveFwd_RtnPressure on ilevel becomes the tracer's travel-time QoI (kind: PMC_TRACER_MEAN | _MIN;
     /// pmc_darcy_set_tracer); nullptr detaches.  The gradient and Hessian entries keep <obs, x>.
     void SetTracer(int ilevel, ParticleTracer* tracer, int kind = PMC_TRACER_MEAN);
