@@ -317,7 +317,8 @@ static constexpr int kScalBlock = 1024;
 __device__ __forceinline__ double reduce_partials(const double* __restrict__ partial, int nblocks, int nb,
                                                   const double* __restrict__ partial2 = nullptr, int nblocks2 = 0) {
     __shared__ double lds[kScalBlock];
-    const int k = threadIdx.x % nb, q = threadIdx.x / nb, nq = kScalBlock / nb;
+    const int k = threadIdx.x % nb, q = threadIdx.x / nb, nq = kScalBlock / reduce_width(nb);
+    if (q >= nq) nblocks = nblocks2 = 0;   // nb = kGroup: the upper half of the threads adds nothing (see reduce_width)
     // eight independent chains keep the loads in flight (the partials of a 2 000-block launch are 36 values per thread)
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
     int b = q;
@@ -480,10 +481,10 @@ __global__ __launch_bounds__(256) void stage_partials_kernel(const double* __res
                                                              const double* __restrict__ pb2, int nbk2, int nb,
                                                              double* __restrict__ stage) {
     __shared__ double lds[2][256];
-    const int g = blockIdx.x, k = threadIdx.x % nb, q = threadIdx.x / nb, nq = 256 / nb;
+    const int g = blockIdx.x, k = threadIdx.x % nb, q = threadIdx.x / nb, nq = 256 / reduce_width(nb);
     auto chunk = [&](const double* __restrict__ p, int n) {
         const int per = (n + kStageBlocks - 1) / kStageBlocks;
-        const int lo = min(n, g * per), hi = min(n, lo + per);
+        const int lo = min(n, g * per), hi = q < nq ? min(n, lo + per) : lo;   // q >= nq: idle (see reduce_width)
         double a = 0.0, b = 0.0;
         int i = lo + q;
         for (; i + nq < hi; i += 2 * nq) {

@@ -25,6 +25,15 @@ __device__ __forceinline__ void sell_row_product(const int* __restrict__ slice_o
     sell_row_range<NB, BV, false, true, false, XT>(cols, vals, x, nullptr, off, width, lane, LD, acc);
 }
 
+// Row steps whose own-row reads an update pass (LZ 2 / 3) issues together: 64 B per lane and row step with v0 (LZ 2), 32 B
+// without (LZ 3), so both keep 128 B per lane in flight - what the gather loop does.  (gfx950, NB = 32, fp32 x: 150 VGPRs, no
+// scratch, 3 waves per SIMD; four row steps with v0 need 168 + 40 B of scratch)
+template <int NB, int LZ>
+constexpr int lz_batch() {
+    constexpr int H = LZ == 3 ? 4 : 2;
+    return Lay<NB>::T >= H ? H : Lay<NB>::T;
+}
+
 // MODE 0: y = Ax   1: y += Ax   2: y = r - Ax ; DOT: partial sums of <dot_with, result>.
 // Wavefronts stride over the slices (grid may be smaller than the slice count: bounded partial-sum count).
 // TAG only names the instantiation: 1 = the block saddle-point operator (K5) inside the solver, 2 = the same operator
@@ -89,6 +98,15 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
     double p[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) p[c] = 0.0;
+    // update passes: the lane's coefficients depend on the column group and t only - read once per wavefront, not behind
+    // every row step's stores (which the compiler must assume to alias them)
+    constexpr bool LZU = LZ == 2 || LZ == 3;
+    double cz0[LZU ? C : 1], cz1[LZU ? C : 1], cz2[LZU ? C : 1];
+    if constexpr (LZU) {
+        load_c<C>(lz.c0 + t * C, cz0);
+        load_c<C>(lz.c1 + t * C, cz1);
+        load_c<C>(lz.c2 + t * C, cz2);
+    }
     const SliceWalk sw = slice_walk(nslices);
     for (int si = sw.begin; si < sw.end; si += sw.stride) {
         const int slice = sched ? sched[si] : si;   // optional processing order (locality), see Sell::sched
@@ -108,6 +126,39 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
             sell_row_range<NB, BV, false, true, true, XT>(cols, vals, x, nullptr, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
         } else {
             sell_row_product<NB, BV, XT>(slice_off, cols, vals, x, slice, lane, LD, acc);
+        }
+        if constexpr (LZU) {
+            // row steps in batches of H: the own rows of v1 and v0 of the whole batch are in flight together, then the batch
+            // is combined and stored - rows past the end re-read the last row and store nothing
+            constexpr int H = lz_batch<NB, LZ>();
+#pragma unroll
+            for (int h0 = 0; h0 < T; h0 += H) {
+                double bv[H][C], yv[H][C];
+                size_t at[H];
+                bool ok[H];
+#pragma unroll
+                for (int u = 0; u < H; ++u) {
+                    const int row = slice * kWave + (h0 + u) * G + g;
+                    ok[u] = row < nrows;
+                    at[u] = (size_t)(ok[u] ? row : nrows - 1) * LD + t * C;
+                    load_c_nt<NT, C>(lz.v1 + at[u], bv[u]);
+                    if constexpr (LZ == 2) {
+                        load_c_nt<NT, C>(y + at[u], yv[u]);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) yv[u][c] = 0.0;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < H; ++u) {
+                    lanczos_combine<C>(cz0, cz1, cz2, acc[h0 + u], bv[u], yv[u]);
+                    if (ok[u]) {
+                        store_c<C>(y + at[u], yv[u]);          // gathered by the next kernels
+                        store_v<C>(lz.y32 + at[u], yv[u]);
+                    }
+                }
+            }
+            continue;
         }
 #pragma unroll
         for (int rs = 0; rs < T; ++rs) {
@@ -135,18 +186,6 @@ __global__ __launch_bounds__(kBlock, (NB >= 32 && BV == 0 && sizeof(XT) == 4 ? 3
                         if constexpr (SM == 2) tv = exp(tv);
                         y[(size_t)(t * C + c) * nrows + row] = tv;
                     }
-                } else if constexpr (LZ >= 2) {
-                    double bv[C], yv[C];
-                    load_c_nt<NT, C>(lz.v1 + at, bv);
-                    if constexpr (LZ == 2) {
-                        load_c_nt<NT, C>(y + at, yv);
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < C; ++c) yv[c] = 0.0;
-                    }
-                    lanczos_combine<C>(lz.c0, lz.c1, lz.c2, t * C, acc[rs], bv, yv);
-                    store_c<C>(y + at, yv);          // gathered by the next kernels
-                    store_v<C>(lz.y32 + at, yv);
                 } else if constexpr (LZ == 1) {      // the product only feeds the dot
                 } else if constexpr (sizeof(YT) == 8) store_c_stream<NT, C>(y + at, acc[rs]);
                 else store_v<C>(y + at, acc[rs]);
@@ -397,8 +436,11 @@ __device__ __forceinline__ void split_row_sums(double (&acc)[T][C], int sl) {
 // (index, value) pairs come from L1 / L2 the second time instead of being fetched again by another workgroup at another time
 // (what `traffic` showed as 1.34 x the algorithmic bytes) - gridDim.y is 1 and the partial sums keep their layout.
 // PT: storage type of padd_x (the coarse correction: fp64, or fp32 with fp32 inter-level vectors), widened on load
+// EPS: the optional operands of the epilogue are compile-time facts - xadd is there iff XA, the coarse correction (padd_idx,
+// padd_x) iff PA, dot_with iff DOT - so that a pair of row steps is one basic block: with run-time pointers every
+// `if (ptr)` is a branch the compiler moves no load across, and the pair drained the memory counter three times
 template <int NB, typename XT, typename OT, typename AT, bool DOT, bool NT = false, int BV = 0, int DEEP = 1, bool SPL = false,
-          bool GIB = false, typename PT = double>
+          bool GIB = false, typename PT = double, bool EPS = false, bool XA = false, bool PA = false>
 __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc_poly2_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                           const int* __restrict__ cols, const double* __restrict__ vals_scaled,
                                                           const double* __restrict__ dinv, const XT* __restrict__ r, OT* xout,
@@ -409,6 +451,7 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
                                                           int ld, int sl = 0) {
     static_assert(!SPL || (NB <= 8 && BV == 0 && DEEP == 1), "row-split instantiations: narrow launches, shared values");
     static_assert(!GIB || (NB == kGroup && BV == 0 && DEEP == 1 && !SPL), "both column groups in one workgroup: 64 wide, shared values");
+    static_assert(!EPS || (BV == 0 && DEEP == 1 && !SPL && !GIB), "static epilogue: the plain shared-value form");
     constexpr int C = Lay<NB>::C, T = Lay<NB>::T, G = Lay<NB>::G;
     constexpr int NG = GIB ? 2 : 1;
     const int LD = row_ld<NB>(ld);
@@ -416,9 +459,9 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
         const int g0 = col0<NB>();
         r += g0; xout += g0;
         if constexpr (BV != 0) { vals_scaled = shift_bv<BV>(vals_scaled, g0); dinv += g0; }
-        if (xadd) xadd += g0;
-        if (dot_with) dot_with += g0;
-        if (padd_x) padd_x += g0;
+        if (EPS ? XA : xadd != nullptr) xadd += g0;
+        if (EPS ? DOT : dot_with != nullptr) dot_with += g0;
+        if (EPS ? PA : padd_x != nullptr) padd_x += g0;
         if constexpr (DOT) partial += g0;
     }
     const int lane = threadIdx.x & (kWave - 1);
@@ -431,14 +474,22 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
       const int go = grp * NB;                         // 0 unless GIB
       const XT* rg = r + go;
       OT* xg = xout + go;
-      const AT* xa = xadd ? xadd + go : nullptr;
-      const double* dw = dot_with ? dot_with + go : nullptr;
-      const PT* px = padd_x ? padd_x + go : nullptr;
+      const AT* xa = (EPS ? XA : xadd != nullptr) ? xadd + go : nullptr;
+      const double* dw = (EPS ? DOT : dot_with != nullptr) ? dot_with + go : nullptr;
+      const PT* px = (EPS ? PA : padd_x != nullptr) ? padd_x + go : nullptr;
       double p[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) p[c] = 0.0;
       for (int slice = sw.begin; slice < sw.end; slice += sw.stride) {
         double acc[T][C];
+        // static epilogue with a coarse correction: the slice's parent indices are read ahead of the gather loop (T registers),
+        // so that xc[parent] is gathered together with the own-row reads and not one round trip behind them
+        constexpr bool PAR_AHEAD = EPS && PA;
+        int parv[PAR_AHEAD ? T : 1];
+        if constexpr (PAR_AHEAD) {
+#pragma unroll
+            for (int rs = 0; rs < T; ++rs) parv[rs] = padd_idx[min(slice * kWave + rs * G + g, nrows - 1)];
+        }
         const int off = slice_off[slice];
         sell_row_range_t<NB, XT, NT, BV, DEEP>(cols, vals_scaled, rg, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
         if constexpr (SPL) split_row_sums<NB, C, T>(acc, sl);
@@ -446,7 +497,9 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
         // either is consumed - rows past the end re-read the last row and store nothing
         // (pairs only where the gathers above leave the registers for it - the fp32-gather instantiations; the fp64-gather
         // ones, with sixteen 16-byte gathers in flight, would drop from three to two waves per SIMD)
-        constexpr int H = (T >= 2 && sizeof(XT) == 4) ? 2 : 1;
+        // (the static form that adds nothing - pre-smoothing - reads 24 B per lane and row step and takes four at a time: 124
+        // registers and four waves per SIMD either way at NB = 32)
+        constexpr int H = (T >= 2 && sizeof(XT) == 4) ? ((EPS && !XA && !PA && T >= 4) ? 4 : 2) : 1;
 #pragma unroll
         for (int h0 = 0; h0 < T; h0 += H) {
             double rv[H][C], di[H][C], x0[H][C], pc[H][C], wv[H][C];
@@ -468,11 +521,12 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
 #pragma unroll
                     for (int c = 0; c < C; ++c) di[u][c] = sdi;
                 }
-                if (xa) load_v<C>(xa + at[u], x0[u]);
-                if (padd_idx) par[u] = padd_idx[rowc];
+                if (EPS ? XA : xa != nullptr) load_v<C>(xa + at[u], x0[u]);
+                if constexpr (PAR_AHEAD) par[u] = parv[h0 + u];
+                else if (EPS ? PA : padd_idx != nullptr) par[u] = padd_idx[rowc];
                 if constexpr (DOT) load_c<C>(dw + at[u], wv[u]);
             }
-            if (padd_idx) {
+            if (EPS ? PA : padd_idx != nullptr) {
 #pragma unroll
                 for (int u = 0; u < H; ++u) load_v<C>(px + (size_t)par[u] * LD + t * C, pc[u]);
             }
@@ -481,11 +535,11 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
                 double xv[C];
 #pragma unroll
                 for (int c = 0; c < C; ++c) xv[c] = di[u][c] * (c0 * rv[u][c] - c1 * acc[h0 + u][c]);
-                if (xa) {
+                if (EPS ? XA : xa != nullptr) {
 #pragma unroll
                     for (int c = 0; c < C; ++c) xv[c] += x0[u][c];
                 }
-                if (padd_idx) {
+                if (EPS ? PA : padd_idx != nullptr) {
 #pragma unroll
                     for (int c = 0; c < C; ++c) xv[c] += pc[u][c];
                 }
@@ -679,7 +733,8 @@ static constexpr int kCompressBlocks = 256;   // dot_capacity() reserves this ma
 __global__ __launch_bounds__(256) void compress_partials_kernel(const double* __restrict__ in, int nblocks, int nb,
                                                                 double* __restrict__ out) {
     __shared__ double lds[256];
-    const int k = threadIdx.x % nb, q = threadIdx.x / nb, nq = 256 / nb;
+    const int k = threadIdx.x % nb, q = threadIdx.x / nb, nq = 256 / reduce_width(nb);
+    if (q >= nq) nblocks = 0;   // nb = kGroup: the upper half of the threads adds nothing (see reduce_width)
     double s0 = 0.0, s1 = 0.0;
     int b = blockIdx.x + kCompressBlocks * q;
     for (; b + kCompressBlocks * nq < nblocks; b += 2 * kCompressBlocks * nq) {
@@ -1043,10 +1098,12 @@ static void vc_presmooth32_t(hipStream_t st, int nb, const SellView& As, const d
         return;
     }
     PMC_DISPATCH_NB(nb, {
+        // (the 32-wide fp32 forms - the finest level of a cycle - know at compile time that the epilogue adds nothing)
+        constexpr bool EPS = NB == kGroup && sizeof(RT) == 4;
         if (nt_poly(As, NB))
-            vc_poly2_kernel<NB, RT, float, float, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+            vc_poly2_kernel<NB, RT, float, float, false, true, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
         else
-            vc_poly2_kernel<NB, RT, float, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+            vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
     });
     check_launch();
 }
@@ -1183,16 +1240,21 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
         check_launch();
         return dot_partial ? (int)g.x : 0;
     }
+    // (the 32-wide forms - the finest level of a cycle - know their epilogue at compile time: the iterate and the coarse
+    // correction are added, the dot is taken with r iff there is one)
+    if (!x || !parent || !xc || (dot_partial && !r))
+        throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: iterate, parent table, coarse correction and the dot's vector expected");
     PMC_DISPATCH_NB(nb, {
+        constexpr bool EPS = NB == kGroup;
         if (nt_poly(As, NB)) {
             if (dot_partial)
-                vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+                vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
             else
-                vc_poly2_kernel<NB, float, OT, float, false, true, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+                vc_poly2_kernel<NB, float, OT, float, false, true, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
         } else if (dot_partial)
-            vc_poly2_kernel<NB, float, OT, float, true, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
+            vc_poly2_kernel<NB, float, OT, float, true, false, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
         else
-            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
     });
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;

@@ -279,6 +279,17 @@ __device__ __forceinline__ void lanczos_combine(const double* __restrict__ c0, c
     for (int c = 0; c < C; ++c) y[c] = c0[k0 + c] * a[c] + c1[k0 + c] * b[c] + c2[k0 + c] * y[c];
 }
 
+// the same with the lane's coefficients in registers (read once per wavefront: the operator pass, whose stores the compiler
+// must assume to alias c0 / c1 / c2 and would reload them behind).  The contraction is written out: the expression above
+// compiles to c1 b, then fma(c0, a, .), then fma(c2, y, .), but which product stays the plain multiply is the backend's choice
+// per call site - with a (the row sums) ready before b arrives it took c0 a here, one rounding apart from the flat kernel.
+template <int C>
+__device__ __forceinline__ void lanczos_combine(const double (&c0)[C], const double (&c1)[C], const double (&c2)[C],
+                                                const double (&a)[C], const double (&b)[C], double (&y)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) y[c] = fma(c2[c], y[c], fma(c0[c], a[c], c1[c] * b[c]));
+}
+
 template <bool NT, int C>
 __device__ __forceinline__ void store_v_stream(double* __restrict__ p, const double (&v)[C]) { store_c_stream<NT, C>(p, v); }
 template <bool NT, int C>
@@ -376,6 +387,12 @@ __device__ __forceinline__ void reduce_flat_store(double (&p)[Lay<NB>::C], doubl
     }
     reduce_cols_store<NB>(p, partial);
 }
+
+// Second-stage sums of the per-block partials (the scalar kernels, their staging and compression kernels) deal the blocks
+// of a column over blockDim / nb threads.  A launch of kGroup columns deals them as a launch of two column groups does (half
+// of its threads stay idle), so a realization's dots - and with them its solve - are the same bits in one launch of 64 and
+// in a launch of 32.  The first-stage partials of the slice kernels do not depend on the number of groups.
+__device__ __forceinline__ int reduce_width(int nb) { return nb == kGroup ? 2 * kGroup : nb; }
 
 // XCD-aware slice assignment.  The dispatcher deals workgroups round-robin over the 8 XCDs (block b runs on XCD b % 8),
 // and each XCD has its own 4 MiB L2.  XCD x owns one CONTIGUOUS eighth of the slices (in processing order), so the x
