@@ -112,6 +112,13 @@ $(ABIBIN)/condition_smoke: tests/c/condition_smoke.c tests/c/kl_io.h include/pmc
 test-condition: $(ABIBIN)/condition_smoke
 .PHONY: test-condition
 
+# the tangent and adjoint of the conditioning map from C (tests/test_gpu_condition_derivatives.py builds and runs it)
+$(ABIBIN)/condition_derivatives_smoke: tests/c/condition_derivatives_smoke.c tests/c/kl_io.h include/pmc.h | $(LIB)
+	@mkdir -p $(ABIBIN)
+	gcc -std=c11 -O1 -Wall -Wextra -Werror -Iinclude -Itests/c -o $@ tests/c/condition_derivatives_smoke.c -Lparelagmc_amd/lib -lpmc -lm -Wl,-rpath,'$$ORIGIN/../../../parelagmc_amd/lib'
+test-condition-derivatives: $(ABIBIN)/condition_derivatives_smoke
+.PHONY: test-condition-derivatives
+
 # the adjoint gradients through the mirror classes of parelagmc.hpp (tests/test_gpu_darcy_gradient.py builds and runs it)
 $(ABIBIN)/gradient_smoke: tests/c/gradient_smoke.cpp tests/c/prob_io.h parelagmc_amd/host/parelagmc.hpp include/pmc.h include/pmc_host.h | $(HOSTLIB)
 	@mkdir -p $(ABIBIN)

@@ -386,10 +386,15 @@ int pmc_sampler_eval(pmc_sampler* s, int level, int xi_level, int nbatch, const 
  *   s_out   : in, NULL or Eval's output for the same xi: v is multiplied by it (f' of the exp() of a lognormal handle).
  *             NULL for callers that hold dJ/dlog s_out already (wrt_log of the Darcy gradients) and on Gaussian handles
  *   grad_xi : out, nbatch x xi_size(xi_level)
+ * Conditioned handles: with a conditioner attached that has pmc_conditioner_enable_derivatives on, the
+ * entry differentiates the CONDITIONAL field: per launch, w = pmc_conditioner_apply_adjoint(v, s_out) in a buffer of the
+ * conditioner, then the path above with v := w, s_out := NULL (the same solve, reported in stats as before; s_out is the
+ * conditional field Eval returned).  For nbatch <= pmc_sampler_batch_width(level) the result is bit for bit the composition
+ * of the public pieces: detach, w = pmc_conditioner_apply_adjoint(v, s_out) at the same nbatch, pmc_sampler_eval_adjoint(w,
+ * NULL).
  * PMC_ERR_INVALID: level outside [0, number of Monte Carlo levels), xi_level outside [0, level], nbatch < 1, NULL v or
- * grad_xi, s_out != NULL on a handle that is not lognormal, a handle with a conditioner attached.  Conditioned fields are
- * out of scope here: their adjoint adds (I - K A^-1 H)^T in front of f', and K is n x nobs column-major like Phi, so the KL
- * adjoint kernel can serve it in a later change. */
+ * grad_xi, s_out != NULL on a handle that is not lognormal, a handle with a conditioner attached that has not been opted in
+ * with pmc_conditioner_enable_derivatives. */
 int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
                              double* grad_xi, int memspace, pmc_stats* stats);
 /* Tangent of Eval (an extension): ds_out = (d Eval(level, xi_level) / d xi) v = f' o (L v), with L the
@@ -401,7 +406,12 @@ int pmc_sampler_eval_adjoint(pmc_sampler* s, int level, int xi_level, int nbatch
  *             for callers that want the direction in log s_out (wrt_log of the Darcy entries) and on Gaussian handles,
  *             where the result is Eval of v bit for bit
  *   ds_out  : out, nbatch x sample_size(level)
- * PMC_ERR_INVALID: as pmc_sampler_eval_adjoint (NULL v or ds_out, s_out on a handle that is not lognormal, a conditioner). */
+ * Conditioned handles, with pmc_conditioner_enable_derivatives on: Eval's linear part of v, then per
+ * launch the homogeneous conditioning update dg - K A^-1 H dg (y = 0, no exp), then o s_out.  For nbatch <=
+ * pmc_sampler_batch_width(level) bit for bit the composition: detach, pmc_sampler_eval_tangent(v, NULL),
+ * pmc_conditioner_apply_tangent(., s_out) at the same nbatch.
+ * PMC_ERR_INVALID: as pmc_sampler_eval_adjoint (NULL v or ds_out, s_out on a handle that is not lognormal, a conditioner
+ * without pmc_conditioner_enable_derivatives). */
 int pmc_sampler_eval_tangent(pmc_sampler* s, int level, int xi_level, int nbatch, const double* v, const double* s_out,
                              double* ds_out, int memspace, pmc_stats* stats);
 /* 1 if Eval applies exp() (the lognormal flag of the create call), 0 if not */
@@ -493,12 +503,30 @@ int pmc_conditioner_level(const pmc_conditioner* c, int level, int* n, int64_t* 
  * given for exact data), a level out of range, nbatch < 1, a NULL g / out. */
 int pmc_conditioner_apply(pmc_conditioner* c, int level, int nbatch, const double* g, const double* zeta, double* out,
                           int apply_exp, int memspace);
+/* The derivative of that map in g and its transpose, Gamma_l = I - K_l A_l^-1 H_l, for nbatch >= 1
+ * columns of n_s(level) entries in `memspace`.  Both work on any conditioner, attached or not, derivatives enabled or not.
+ * Every sum has a fixed order: a column's bits do not depend on nbatch or on how a call was split among pieces wider than 4;
+ * calls of more than 4 columns run fp64 MFMA kernels, narrower ones VALU kernels (a column's bits may differ between the two).
+ * PMC_ERR_INVALID: a level out of range, nbatch < 1, a NULL dg / v / out, a bad memspace, out aliasing s_out, and for the
+ * adjoint out aliasing v.  Nothing is written then. */
+/* out = f' o (dg - K_l A_l^-1 H_l dg); f' = s_out, or 1 when s_out == NULL.  Independent of y, sigma2 and zeta, so it is
+ * valid for noisy conditioners too.  out may alias dg. */
+int pmc_conditioner_apply_tangent(pmc_conditioner* c, int level, int nbatch, const double* dg, const double* s_out,
+                                  double* out, int memspace);
+/* out = u - H_l^T A_l^-1 K_l^T u,  u = v o s_out (u = v when s_out == NULL).  out must not alias v or s_out. */
+int pmc_conditioner_apply_adjoint(pmc_conditioner* c, int level, int nbatch, const double* v, const double* s_out,
+                                  double* out, int memspace);
+/* on != 0: while c is attached, pmc_sampler_eval_tangent / _eval_adjoint (and with them the pmc_bayes_* derivative entries
+ * and pmc_bayes_map) differentiate the CONDITIONAL field instead of refusing the handle.  Default off. */
+int pmc_conditioner_enable_derivatives(pmc_conditioner* c, int on);
+int pmc_conditioner_derivatives_enabled(const pmc_conditioner* c);
 /* Eval hook: with a conditioner set, pmc_sampler_eval (and with it the managers, pmc_field_stats_run and the farm) returns
  * conditional fields - exp() AFTER conditioning on a lognormal handle; embed_s_out keeps the PRIOR Gaussian field (it is the
  * finer level's warm start).  NULL detaches; without a conditioner Eval takes exactly the path it took before.
  * PMC_ERR_INVALID: a conditioner with any sigma2 > 0 (Eval receives no realization id, so it has no independent noise to
  * draw: such callers use pmc_conditioner_apply), a conditioner created on another handle.  While one is attached
- * pmc_sampler_set_projection is refused. */
+ * pmc_sampler_set_projection is refused, and so are pmc_sampler_eval_tangent / _eval_adjoint and everything built on them
+ * unless the conditioner has pmc_conditioner_enable_derivatives on. */
 int pmc_sampler_set_conditioner(pmc_sampler* s, pmc_conditioner* c);
 
 /* invA[level]->Mult(rhs, sol) (src/PDESampler.cpp:397,521), the narrowest seam of the reference: the whole linear solve

@@ -198,6 +198,10 @@ SYMBOLS = {
                                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double)]),
     "pmc_conditioner_apply": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.c_int]),
+    "pmc_conditioner_apply_tangent": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
+    "pmc_conditioner_apply_adjoint": (C.c_int, [_VP, C.c_int, C.c_int, _DP, _DP, _DP, C.c_int]),
+    "pmc_conditioner_enable_derivatives": (C.c_int, [_VP, C.c_int]),
+    "pmc_conditioner_derivatives_enabled": (C.c_int, [_VP]),
     "pmc_sampler_set_conditioner": (C.c_int, [_VP, _VP]),
     "pmc_field_stats_create": (C.c_int, [_VP, C.c_int, _DP, C.c_int, C.POINTER(_VP)]),
     "pmc_field_stats_destroy": (None, [_VP]),
@@ -1070,6 +1074,47 @@ class Conditioner:
         po, _ = _addr(out)
         _check(self.ctx.lib.pmc_conditioner_apply(self.h, level, nbatch, pg, pz, po, 1 if exp else 0, ms))
         return out
+
+    def _derivative(self, fn, level, x, s_out, out, in_place):
+        if isinstance(x, np.ndarray):
+            x = _f64(np.atleast_2d(x))
+            nbatch = x.shape[0]
+            if s_out is not None:
+                s_out = _f64(np.atleast_2d(s_out))
+                if s_out.shape != x.shape:
+                    raise PmcError(-1, "Conditioner: s_out must have the shape of the input")
+            if out is None:
+                out = np.empty_like(x)
+        else:
+            nbatch = _batch_of(x, self.sampler.xi_size(level))
+            if out is None:
+                if not in_place:
+                    raise PmcError(-1, "Conditioner.apply_adjoint: device arrays need out (it must not alias v)")
+                out = x
+        px, ms = _addr(x)
+        ps, _ = _addr(s_out)
+        po, _ = _addr(out)
+        _check(fn(self.h, level, nbatch, px, ps, po, ms))
+        return out
+
+    def apply_tangent(self, level, dg, s_out=None, out=None):
+        """f' o (dg - K A^-1 H dg), f' = s_out or 1: the derivative of apply in g (pmc_conditioner_apply_tangent).  Arrays as
+        for apply; out defaults to a new array (numpy) or to dg itself (device arrays)"""
+        return self._derivative(self.ctx.lib.pmc_conditioner_apply_tangent, level, dg, s_out, out, True)
+
+    def apply_adjoint(self, level, v, s_out=None, out=None):
+        """u - H^T A^-1 K^T u, u = v o s_out: the transpose of apply_tangent (pmc_conditioner_apply_adjoint).  out must not
+        alias v or s_out; device arrays must pass it"""
+        return self._derivative(self.ctx.lib.pmc_conditioner_apply_adjoint, level, v, s_out, out, False)
+
+    def enable_derivatives(self, on=True):
+        """while attached, EvalTangent / EvalAdjoint and what is built on them differentiate the conditional field"""
+        _check(self.ctx.lib.pmc_conditioner_enable_derivatives(self.h, 1 if on else 0))
+        return self
+
+    @property
+    def derivatives_enabled(self):
+        return bool(self.ctx.lib.pmc_conditioner_derivatives_enabled(self.h))
 
     def close(self):
         if getattr(self, "h", None):

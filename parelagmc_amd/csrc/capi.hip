@@ -498,6 +498,27 @@ int pmc_conditioner_apply(pmc_conditioner* c, int level, int nbatch, const doubl
         c->impl.apply(level, nbatch, g, zeta, out, apply_exp != 0, memspace);
     });
 }
+int pmc_conditioner_apply_tangent(pmc_conditioner* c, int level, int nbatch, const double* dg, const double* s_out,
+                                  double* out, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr, "conditioner is NULL");
+        c->impl.apply_tangent(level, nbatch, dg, s_out, out, memspace);
+    });
+}
+int pmc_conditioner_apply_adjoint(pmc_conditioner* c, int level, int nbatch, const double* v, const double* s_out,
+                                  double* out, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr, "conditioner is NULL");
+        c->impl.apply_adjoint(level, nbatch, v, s_out, out, memspace);
+    });
+}
+int pmc_conditioner_enable_derivatives(pmc_conditioner* c, int on) {
+    return guarded([&] {
+        PMC_REQUIRE(c != nullptr, "conditioner is NULL");
+        c->impl.derivs = on != 0;
+    });
+}
+int pmc_conditioner_derivatives_enabled(const pmc_conditioner* c) { return c ? (c->impl.derivs ? 1 : 0) : PMC_ERR_INVALID; }
 int pmc_sampler_set_conditioner(pmc_sampler* s, pmc_conditioner* c) {
     return guarded([&] {
         PMC_REQUIRE(s != nullptr, "sampler is NULL");

@@ -12,6 +12,16 @@
 //                       one is multiplied.  A lane reads exactly the entries of g it later writes: out may alias g.
 //   cond_update_gemv    nb <= 4: one field row per lane, the observations split over the 4 waves of a workgroup.
 // A column's bits may differ between the two update kernels (different summation order), as for the KL sampler.
+//
+// Derivatives of the map in g, Gamma = I - K A^-1 H:
+//   tangent  f' o (Gamma dg): the kernels above with y = 0 (cond_coef_kernel's homogeneous mode) and exp() off, then o s_out.
+//   adjoint  w = Gamma^T u = u - H^T A^-1 K^T u, u = v o s_out formed in the load (one rounding):
+//     cond_adjoint_mfma / _gemv   t = K^T u as partials over chunks of kl_adjoint_chunk_rows(n) field rows, a function of n
+//                       alone; the operand maps and LDS staging of kl_adjoint_mfma_kernel with K's leading dimension.  The
+//                       workgroups of the first mode block store u to w while they stage it: u is read once.
+//     cond_adjoint_finish_kernel  one workgroup per realization: the partials summed in ascending chunk order, c = A^-1 t
+//                       (the mirror of cond_coef_kernel), then w -= H^T c at the touched columns only, each column's entries
+//                       in ascending row order.  No atomics anywhere.
 #include "handles.hpp"
 #include "kernels.hpp"
 
@@ -46,7 +56,7 @@ __global__ __launch_bounds__(kCoefThreads) void cond_coef_kernel(int n, int nobs
     for (int j = threadIdx.x; j < nobs; j += kCoefThreads) {
         double hg = 0.0;
         for (int p = hrp[j]; p < hrp[j + 1]; ++p) hg = fma(hv[p], gb[hci[p]], hg);
-        double v = y[j];
+        double v = y ? y[j] : 0.0;   // y == NULL: the homogeneous map (the tangent)
         if (zeta) v = fma(sig[j], zeta[b * nobs + j], v);
         d[j] = v - hg;
     }
@@ -179,6 +189,184 @@ __global__ __launch_bounds__(64 * kWaves) void cond_update_gemv(int n, int ld, i
         v += g[o];
         out[o] = apply_exp ? exp(v) : v;
     }
+}
+
+// ---- adjoint -------------------------------------------------------------------------------------------------------------------
+constexpr int kAdjModes = 16 * kWaves;   // observations per MFMA workgroup: 16 per wave
+constexpr int kAdjRows = 32;             // field rows per LDS stage
+constexpr int kAdjLd = kAdjRows + 2;     // row stride of the LDS tiles in doubles: conflict-free as kLd of kl_adjoint.hip
+constexpr int kAdjMaxLaunch = 256;       // realizations per launch (bounds the partials: chunks x 256 x nobs doubles)
+
+// part[(chunk nb + b) m + k] = sum over the chunk's rows i of K[k ld + i] u[b n + i], u = v o sv (u = v when sv == NULL).
+// A = U (rows: realizations, reduction: field rows), B = K (columns: observations): lane l, register r of tile t holds
+// D[realization 16 t + (l >> 4) + 4 r][observation l & 15].  Rows past the chunk, observations past m and realizations past nb
+// are staged as zeros: they add +0 products.  The workgroups of mode block 0 write u to w as they load it.
+template <int NT>
+__global__ __launch_bounds__(64 * kWaves) void cond_adjoint_mfma(int n, int ld, int m, int nb, int chunk_rows,
+                                                                  const double* __restrict__ K, const double* __restrict__ v,
+                                                                  const double* __restrict__ sv, double* __restrict__ w,
+                                                                  double* __restrict__ part) {
+    constexpr int kThreads = 64 * kWaves;
+    constexpr int kP = kAdjModes * kAdjRows / kThreads;   // K entries each thread stages per step
+    constexpr int kV = 16 * NT * kAdjRows / kThreads;     // U entries
+    __shared__ double ps[kAdjModes][kAdjLd];
+    __shared__ double vs[16 * NT][kAdjLd];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kq = lane >> 4;
+    const int k0 = blockIdx.x * kAdjModes;
+    const int chunk = blockIdx.y;
+    const int b0 = blockIdx.z * 16 * NT;
+    const int r0 = chunk * chunk_rows, r1 = min(n, r0 + chunk_rows);
+    const bool store_u = blockIdx.x == 0;
+    f64x4 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double pr[kP], vr[kV];
+    auto load_tile = [&](int i0) {
+        const int i = i0 + (threadIdx.x & (kAdjRows - 1));
+        const bool row_ok = i < r1;
+#pragma unroll
+        for (int j = 0; j < kP; ++j) {
+            const int k = k0 + (threadIdx.x + j * kThreads) / kAdjRows;
+            pr[j] = (row_ok && k < m) ? K[(size_t)k * ld + i] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < kV; ++j) {
+            const int b = b0 + (threadIdx.x + j * kThreads) / kAdjRows;
+            double x = 0.0;
+            if (row_ok && b < nb) {
+                const size_t o = (size_t)b * n + i;
+                x = sv ? v[o] * sv[o] : v[o];
+            }
+            vr[j] = x;
+        }
+    };
+    load_tile(r0);
+    for (int i0 = r0; i0 < r1; i0 += kAdjRows) {
+#pragma unroll
+        for (int j = 0; j < kP; ++j) {
+            const int e = threadIdx.x + j * kThreads;
+            ps[e / kAdjRows][e % kAdjRows] = pr[j];
+        }
+        // u goes to w here, where the staged values are consumed anyway: a store inside load_tile would wait for the loads
+        // that are meant to stay in flight while the previous stage is multiplied
+        const int iu = i0 + (threadIdx.x & (kAdjRows - 1));
+#pragma unroll
+        for (int j = 0; j < kV; ++j) {
+            const int e = threadIdx.x + j * kThreads;
+            vs[e / kAdjRows][e % kAdjRows] = vr[j];
+            const int b = b0 + e / kAdjRows;
+            if (store_u && iu < r1 && b < nb) w[(size_t)b * n + iu] = vr[j];
+        }
+        __syncthreads();
+        if (i0 + kAdjRows < r1) load_tile(i0 + kAdjRows);   // in flight while this stage is multiplied
+#pragma unroll
+        for (int kk = 0; kk < kAdjRows / 4; ++kk) {
+            const double b = ps[wave * 16 + (lane & 15)][4 * kk + kq];
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[t * 16 + (lane & 15)][4 * kk + kq], b, acc[t], 0, 0, 0);
+        }
+        __syncthreads();   // every wave has read the tiles before the next stage overwrites them
+    }
+    const int k = k0 + wave * 16 + (lane & 15);
+    if (k >= m) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = b0 + 16 * t + kq + 4 * r;
+            if (b < nb) part[((size_t)chunk * nb + b) * m + k] = acc[t][r];
+        }
+    }
+}
+
+// nb <= 4: one observation per wave, the chunk's rows over the lanes, a fixed butterfly; the wave of observation 0 stores u
+template <int NB>
+__global__ __launch_bounds__(64 * kWaves) void cond_adjoint_gemv(int n, int ld, int m, int chunk_rows,
+                                                                  const double* __restrict__ K, const double* __restrict__ v,
+                                                                  const double* __restrict__ sv, double* __restrict__ w,
+                                                                  double* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (k >= m) return;   // whole waves; the kernel has no barrier
+    const int chunk = blockIdx.y;
+    const int r0 = chunk * chunk_rows, r1 = min(n, r0 + chunk_rows);
+    const double* __restrict__ col = K + (size_t)k * ld;
+    const bool store_u = k == 0;
+    double acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 0.0;
+#pragma unroll 4
+    for (int i = r0 + lane; i < r1; i += 64) {
+        const double p = col[i];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const size_t o = (size_t)b * n + i;
+            const double x = sv ? v[o] * sv[o] : v[o];
+            if (store_u) w[o] = x;
+            acc[b] = fma(p, x, acc[b]);
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        double a = acc[b];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
+        if (lane == 0) part[((size_t)chunk * NB + b) * m + k] = a;
+    }
+}
+
+// realization b = blockIdx.x: t[j] = sum over the chunks, ascending, of part[(chunk nb + b) nobs + j]; c = Ainv t (Ainv is
+// exactly symmetric: thread j reads column j); w[b n + tcol[q]] -= sum_p tval[p] c[trow[p]], p in column q of H^T's
+// compressed form, ascending.  Only the touched entries of w are read and written again.
+__global__ __launch_bounds__(kCoefThreads) void cond_adjoint_finish_kernel(int n, int nobs, int nb, int nchunks, int tcols,
+                                                                           const double* __restrict__ part,
+                                                                           const double* __restrict__ ainv,
+                                                                           const int* __restrict__ tcol, const int* __restrict__ tptr,
+                                                                           const int* __restrict__ trow,
+                                                                           const double* __restrict__ tval, double* __restrict__ w) {
+    __shared__ double t[kCondMaxObs];
+    __shared__ double c[kCondMaxObs];
+    const size_t b = blockIdx.x;
+    for (int j = threadIdx.x; j < nobs; j += kCoefThreads) {
+        double a = part[b * nobs + j];
+        for (int ch = 1; ch < nchunks; ++ch) a += part[((size_t)ch * nb + b) * nobs + j];
+        t[j] = a;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < nobs; j += kCoefThreads) {
+        double a = 0.0;
+        for (int k = 0; k < nobs; ++k) a = fma(ainv[(size_t)k * nobs + j], t[k], a);
+        c[j] = a;
+    }
+    __syncthreads();
+    double* wb = w + b * n;
+    for (int q = threadIdx.x; q < tcols; q += kCoefThreads) {
+        double a = 0.0;
+        for (int p = tptr[q]; p < tptr[q + 1]; ++p) a = fma(tval[p], c[trow[p]], a);
+        wb[tcol[q]] -= a;
+    }
+}
+
+template <int NT>
+void launch_adjoint_mfma(hipStream_t st, int n, int ld, int m, int nb, int chunk_rows, int nchunks, const double* K,
+                         const double* v, const double* sv, double* w, double* part) {
+    const dim3 grid((unsigned)((m + kAdjModes - 1) / kAdjModes), (unsigned)nchunks, (unsigned)((nb + 16 * NT - 1) / (16 * NT)));
+    cond_adjoint_mfma<NT><<<grid, 64 * kWaves, 0, st>>>(n, ld, m, nb, chunk_rows, K, v, sv, w, part);
+}
+
+template <int NB>
+void launch_adjoint_gemv(hipStream_t st, int n, int ld, int m, int chunk_rows, int nchunks, const double* K, const double* v,
+                         const double* sv, double* w, double* part) {
+    const dim3 grid((unsigned)((m + kWaves - 1) / kWaves), (unsigned)nchunks);
+    cond_adjoint_gemv<NB><<<grid, 64 * kWaves, 0, st>>>(n, ld, m, chunk_rows, K, v, sv, w, part);
+}
+
+// out[i] *= s[i]: the f' = s_out of a lognormal field on the tangent
+__global__ void cond_mul_inplace_kernel(size_t total, const double* __restrict__ s, double* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < total) out[t] *= s[t];
 }
 
 // ---- setup kernels ----------------------------------------------------------------------------------------------------------
@@ -320,6 +508,30 @@ Conditioner::Conditioner(Sampler& s, int nobs_, const pmc_csr* H0, const double*
         L.hrp.upload(H.rowptr, st);
         L.hci.upload(H.colind, st);
         L.hv.upload(H.vals, st);
+        {   // H_l^T compressed: the touched columns ascending, each column's entries in ascending row order
+            std::vector<int> order((size_t)H.nnz()), rowof((size_t)H.nnz());
+            for (int r = 0; r < nobs; ++r)
+                for (int p = H.rowptr[r]; p < H.rowptr[r + 1]; ++p) rowof[(size_t)p] = r;
+            for (size_t p = 0; p < order.size(); ++p) order[p] = (int)p;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return H.colind[a] < H.colind[b]; });
+            std::vector<int> tcol, tptr, trow;
+            std::vector<double> tval;
+            for (int p : order) {
+                if (tcol.empty() || tcol.back() != H.colind[p]) {
+                    tcol.push_back(H.colind[p]);
+                    tptr.push_back((int)trow.size());
+                }
+                trow.push_back(rowof[(size_t)p]);
+                tval.push_back(H.vals[p]);
+            }
+            tptr.push_back((int)trow.size());
+            L.tcols = (int)tcol.size();
+            L.tcol.upload(tcol, st);
+            L.tptr.upload(tptr, st);
+            L.trow.upload(trow, st);
+            L.tval.upload(tval, st);
+            PMC_HIP(hipStreamSynchronize(st));   // the host vectors end here
+        }
         L.K.alloc((size_t)L.ld * mp);
         L.K.zero(st);
         if (smp.kl) build_K_kl(l);
@@ -390,19 +602,21 @@ void Conditioner::build_K_kl(int level) {
     PMC_HIP(hipStreamSynchronize(st));
 }
 
-void Conditioner::apply_device(int level, int nbatch, const double* g_d, const double* zeta_d, double* out_d, bool apply_exp) {
+void Conditioner::apply_device(int level, int nbatch, const double* g_d, const double* zeta_d, double* out_d, bool apply_exp,
+                               bool homogeneous, int call_width) {
     const Level& L = lv[level];
     hipStream_t st = smp.ctx.stream;
     const int n = L.n;
     coef.ensure((size_t)std::min(nbatch, kLaunchCols) * mp);
-    const bool wide = nbatch > 4;   // chosen per call, not per launch: the last launch of a long call stays on the MFMA path
+    // chosen per call, not per launch: the last launch of a long call stays on the MFMA path
+    const bool wide = (call_width > 0 ? call_width : nbatch) > 4;
     for (int done = 0; done < nbatch; done += kLaunchCols) {
         const int nb = std::min(kLaunchCols, nbatch - done);
         const double* g = g_d + (size_t)done * n;
         double* out = out_d + (size_t)done * n;
-        cond_coef_kernel<<<(unsigned)nb, kCoefThreads, 0, st>>>(n, nobs, mp, L.hrp.p, L.hci.p, L.hv.p, y.p, sqrt_sigma2.p,
-                                                               L.Ainv.p, g, zeta_d ? zeta_d + (size_t)done * nobs : nullptr,
-                                                               coef.p);
+        cond_coef_kernel<<<(unsigned)nb, kCoefThreads, 0, st>>>(n, nobs, mp, L.hrp.p, L.hci.p, L.hv.p, homogeneous ? nullptr : y.p,
+                                                               sqrt_sigma2.p, L.Ainv.p, g,
+                                                               zeta_d ? zeta_d + (size_t)done * nobs : nullptr, coef.p);
         if (wide) {
             const int tiles = (std::min(nb, 16 * kMaxTiles) + 15) / 16;
             if (tiles <= 1) launch_mfma<1>(st, n, L.ld, mp, nb, L.K.p, coef.p, g, out, apply_exp);
@@ -443,6 +657,98 @@ void Conditioner::apply(int level, int nbatch, const double* g, const double* ze
     }
     apply_device(level, nbatch, stage_g.p, zeta ? stage_z.p : nullptr, stage_g.p, apply_exp);
     PMC_HIP(hipMemcpyAsync(out, stage_g.p, sizeof(double) * n * nbatch, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+void Conditioner::apply_tangent(int level, int nbatch, const double* dg, const double* s_out, double* out, int memspace) {
+    PMC_REQUIRE(level >= 0 && level < (int)lv.size(), "conditioner apply_tangent: level out of range");
+    PMC_REQUIRE(nbatch >= 1 && dg != nullptr && out != nullptr, "conditioner apply_tangent: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "conditioner apply_tangent: bad memspace");
+    PMC_REQUIRE(out != s_out, "conditioner apply_tangent: out must not alias s_out");
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    const size_t total = (size_t)lv[level].n * nbatch;
+    if (memspace == PMC_MEM_DEVICE) {
+        apply_device(level, nbatch, dg, nullptr, out, false, true);
+        if (s_out) {
+            cond_mul_inplace_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(total, s_out, out);
+            PMC_HIP(hipGetLastError());
+            count_kernel_launches(1);
+        }
+        return;
+    }
+    stage_g.ensure(total);
+    PMC_HIP(hipMemcpyAsync(stage_g.p, dg, sizeof(double) * total, hipMemcpyHostToDevice, st));
+    apply_device(level, nbatch, stage_g.p, nullptr, stage_g.p, false, true);
+    PMC_HIP(hipMemcpyAsync(out, stage_g.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+    if (s_out)   // host arrays are staged, so the product is the host's (the same single rounding)
+        for (size_t i = 0; i < total; ++i) out[i] *= s_out[i];
+}
+
+void Conditioner::apply_adjoint_device(int level, int nbatch, const double* v_d, const double* s_d, double* out_d,
+                                       int call_width) {
+    const Level& L = lv[level];
+    hipStream_t st = smp.ctx.stream;
+    const int n = L.n;
+    const int cr = kl_adjoint_chunk_rows(n);
+    const int nchunks = (n + cr - 1) / cr;
+    adj_part.ensure((size_t)nchunks * (size_t)std::min(nbatch, kAdjMaxLaunch) * (size_t)nobs);
+    const bool wide = (call_width > 0 ? call_width : nbatch) > 4;   // decided by the CALL, as everywhere in this file
+    for (int done = 0; done < nbatch; done += kAdjMaxLaunch) {
+        const int nb = std::min(kAdjMaxLaunch, nbatch - done);
+        const double* v = v_d + (size_t)done * n;
+        const double* sv = s_d ? s_d + (size_t)done * n : nullptr;
+        double* w = out_d + (size_t)done * n;
+        if (wide) {
+            // Realization tiles per workgroup: 2 per mode block of kAdjModes observations, at most kMaxTiles.  The grid is
+            // (mode blocks) x (chunks, at most 32) x (tiles / NT): with up to 64 observations, 8 tiles per workgroup leave
+            // 32 - 64 workgroups for 256 CUs (measured at n = 262 144, nobs = 64: 0.99 ms for 256 realizations against 0.47 ms
+            // with 2 tiles); K is re-read once per workgroup row of tiles, which more mode blocks (a larger K) make rarer.
+            // A column's bits do not depend on NT.
+            const int cap = std::min(kMaxTiles, 2 * ((nobs + kAdjModes - 1) / kAdjModes));
+            const int tiles = (std::min(nb, 16 * cap) + 15) / 16;
+            if (tiles <= 1) launch_adjoint_mfma<1>(st, n, L.ld, nobs, nb, cr, nchunks, L.K.p, v, sv, w, adj_part.p);
+            else if (tiles <= 2) launch_adjoint_mfma<2>(st, n, L.ld, nobs, nb, cr, nchunks, L.K.p, v, sv, w, adj_part.p);
+            else if (tiles <= 4) launch_adjoint_mfma<4>(st, n, L.ld, nobs, nb, cr, nchunks, L.K.p, v, sv, w, adj_part.p);
+            else launch_adjoint_mfma<8>(st, n, L.ld, nobs, nb, cr, nchunks, L.K.p, v, sv, w, adj_part.p);
+        } else {
+            switch (nb) {
+                case 1: launch_adjoint_gemv<1>(st, n, L.ld, nobs, cr, nchunks, L.K.p, v, sv, w, adj_part.p); break;
+                case 2: launch_adjoint_gemv<2>(st, n, L.ld, nobs, cr, nchunks, L.K.p, v, sv, w, adj_part.p); break;
+                case 3: launch_adjoint_gemv<3>(st, n, L.ld, nobs, cr, nchunks, L.K.p, v, sv, w, adj_part.p); break;
+                default: launch_adjoint_gemv<4>(st, n, L.ld, nobs, cr, nchunks, L.K.p, v, sv, w, adj_part.p); break;
+            }
+        }
+        PMC_HIP(hipGetLastError());
+        cond_adjoint_finish_kernel<<<(unsigned)nb, kCoefThreads, 0, st>>>(n, nobs, nb, nchunks, L.tcols, adj_part.p, L.Ainv.p,
+                                                                         L.tcol.p, L.tptr.p, L.trow.p, L.tval.p, w);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(2);
+    }
+}
+
+void Conditioner::apply_adjoint(int level, int nbatch, const double* v, const double* s_out, double* out, int memspace) {
+    PMC_REQUIRE(level >= 0 && level < (int)lv.size(), "conditioner apply_adjoint: level out of range");
+    PMC_REQUIRE(nbatch >= 1 && v != nullptr && out != nullptr, "conditioner apply_adjoint: bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "conditioner apply_adjoint: bad memspace");
+    PMC_REQUIRE(out != v && out != s_out, "conditioner apply_adjoint: out must not alias v or s_out");
+    smp.ctx.activate();
+    hipStream_t st = smp.ctx.stream;
+    if (memspace == PMC_MEM_DEVICE) {
+        apply_adjoint_device(level, nbatch, v, s_out, out);
+        return;
+    }
+    const size_t total = (size_t)lv[level].n * nbatch;
+    stage_g.ensure(total);
+    stage_w.ensure(total);
+    PMC_HIP(hipMemcpyAsync(stage_g.p, v, sizeof(double) * total, hipMemcpyHostToDevice, st));
+    if (s_out) {
+        stage_s.ensure(total);
+        PMC_HIP(hipMemcpyAsync(stage_s.p, s_out, sizeof(double) * total, hipMemcpyHostToDevice, st));
+    }
+    apply_adjoint_device(level, nbatch, stage_g.p, s_out ? stage_s.p : nullptr, stage_w.p);
+    PMC_HIP(hipMemcpyAsync(out, stage_w.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
     PMC_HIP(hipStreamSynchronize(st));
 }
 

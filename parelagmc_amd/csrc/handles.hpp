@@ -70,6 +70,9 @@ struct Sampler {
     // pmc_sampler_set_conditioner (condition.hip): when set, Eval conditions its Gaussian field before the output map (the
     // exp() of a lognormal handle then happens in the conditioner's store); embed_s_out keeps the prior field
     Conditioner* cond = nullptr;
+    // set by eval_tangent around its Eval when the conditioner has derivatives enabled: the hook then applies the
+    // homogeneous map (y = 0), its kernel chosen by the width of the whole call (0 outside such a call)
+    int cond_tangent_width = 0;
     // ComputeL2Error / ComputeMaxError (field_stats.hip): diag(W) of level 0 as handed over, and the hierarchy of the output
     // space of the embedded / L2-projected variants (pmc_sampler_set_output_hierarchy: out_P[l] maps sample_size(l + 1) ->
     // sample_size(l), out_w0 the P0 mass of the original mesh's level 0; empty = not set)
@@ -172,15 +175,33 @@ struct Conditioner {
         DevBuf<int> hrp, hci;
         DevBuf<double> hv, K, Ainv;
         std::vector<double> A;        // nobs x nobs, as inverted
+        // H_l^T in compressed-column form, the touched columns only (the adjoint's correction): column tcol[q] holds the
+        // entries tptr[q] .. tptr[q + 1], (trow, tval) in ascending row order
+        int tcols = 0;
+        DevBuf<int> tcol, tptr, trow;
+        DevBuf<double> tval;
     };
     std::vector<Level> lv;
     DevBuf<double> y, sqrt_sigma2, coef, stage_g, stage_z;
+    // derivatives of the map: partials of the adjoint's split reduction, the staging of a host call's
+    // s_out and result, and w = Gamma^T (v o f') of the EvalAdjoint hook; grown at the first use, never shrunk
+    DevBuf<double> adj_part, stage_s, stage_w, hook_w;
+    bool derivs = false;              // pmc_conditioner_enable_derivatives
     Conditioner(Sampler& s, int nobs, const pmc_csr* H0, const double* y, const double* sigma2);
     ~Conditioner() { if (smp.cond == this) smp.cond = nullptr; }
     // out = f(g + K_l A_l^-1 (y + sqrt(sigma2) zeta - H_l g)), f = exp or the identity; out may alias g
     void apply(int level, int nbatch, const double* g, const double* zeta, double* out, bool apply_exp, int memspace);
-    // the same on device arrays, enqueued on the handle's stream (the Eval hook)
-    void apply_device(int level, int nbatch, const double* g_d, const double* zeta_d, double* out_d, bool apply_exp);
+    // the same on device arrays, enqueued on the handle's stream (the Eval hook).  homogeneous: y = 0 and no noise, the linear
+    // part of the map (its tangent); call_width: the realizations of the CALL this launch is a piece of (0 = nbatch) - more
+    // than 4 select the MFMA kernel
+    void apply_device(int level, int nbatch, const double* g_d, const double* zeta_d, double* out_d, bool apply_exp,
+                      bool homogeneous = false, int call_width = 0);
+    // out = f' o (dg - K_l A_l^-1 H_l dg), f' = s_out or 1; out may alias dg
+    void apply_tangent(int level, int nbatch, const double* dg, const double* s_out, double* out, int memspace);
+    // out = u - H_l^T A_l^-1 K_l^T u, u = v o s_out (s_out may be NULL); out aliases neither v nor s_out
+    void apply_adjoint(int level, int nbatch, const double* v, const double* s_out, double* out, int memspace);
+    // the same on device arrays, enqueued on the handle's stream (the EvalAdjoint hook); call_width as for apply_device
+    void apply_adjoint_device(int level, int nbatch, const double* v_d, const double* s_d, double* out_d, int call_width = 0);
     void export_level(int level, int* n, int64_t* nnz, double* K, double* A, int32_t* rowptr, int32_t* colind,
                       double* vals) const;
 
@@ -252,6 +273,8 @@ void kl_eval(hipStream_t st, int n, int m, int nb, const double* phi, const doub
 // over i is split into chunks that depend on n alone and summed in a fixed order: column b has the same bits for every
 // nb > 4 and every split of a call into pieces wider than 4 (narrower calls take the VALU kernel, whose bits may differ).
 size_t kl_adjoint_partials(int n, int m, int nb);
+// rows of one reduction chunk of a field of n rows (the conditioner's adjoint cuts its reduction by the same rule)
+int kl_adjoint_chunk_rows(int n);
 void kl_eval_adjoint(hipStream_t st, int n, int m, int nb, const double* phi, const double* v, const double* sv, int n_xi,
                      double* grad, double* part);
 

@@ -295,7 +295,8 @@ void Sampler::eval_kl(int level, int xi_level, int nbatch, const double* xi, dou
         ctx.phase_mark(1);
     }
     kl_eval(st, n, kl_m, nbatch, kl_phi[level].p, xi_d, n_xi, s_d, emb_d, lognormal && !cond);
-    if (cond) cond->apply_device(level, nbatch, s_d, nullptr, s_d, lognormal);   // exp() in the conditioner's store
+    // exp() in the conditioner's store; inside EvalTangent the homogeneous map
+    if (cond) cond->apply_device(level, nbatch, s_d, nullptr, s_d, lognormal, cond_tangent_width > 0, cond_tangent_width);
     if (stats) {
         ctx.phase_mark(2);
         ctx.phase_report(stats, nbatch);

@@ -173,6 +173,8 @@ void launch_gemv(hipStream_t st, int n, int m, int chunk_rows, int nchunks, cons
 
 }  // namespace
 
+int kl_adjoint_chunk_rows(int n) { return adjoint_chunk_rows(n); }
+
 size_t kl_adjoint_partials(int n, int m, int nb) {
     const int cr = adjoint_chunk_rows(n);
     return (size_t)((n + cr - 1) / cr) * (size_t)std::min(nb, kMaxLaunch) * (size_t)m;
@@ -230,6 +232,12 @@ void Sampler::eval_adjoint_kl(int level, int xi_level, int nbatch, const double*
         g_d = stage_out.p;
     }
     adj_part.ensure(kl_adjoint_partials(n, kl_m, nbatch));
+    if (cond) {   // w = Gamma^T (v o f') of the whole call, then the unconditioned product with v := w, s_out := NULL
+        cond->hook_w.ensure((size_t)n * nbatch);
+        cond->apply_adjoint_device(level, nbatch, v_d, s_d, cond->hook_w.p);
+        v_d = cond->hook_w.p;
+        s_d = nullptr;
+    }
     if (stats) {
         ctx.phase_mark(0);
         ctx.phase_mark(1);

@@ -638,7 +638,7 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
     if (d.proj == PMC_PROJ_NONE) {
         // with a conditioner the Gaussian field lands in s_d and is updated in place, exp() fused into that kernel's store
         k::deinterleave(st, nb, n_s, sol_s, nullptr, nullptr, lognormal && !cond, s_d);
-        if (cond) cond->apply_device(level, nb, s_d, nullptr, s_d, lognormal);
+        if (cond) cond->apply_device(level, nb, s_d, nullptr, s_d, lognormal, cond_tangent_width > 0, cond_tangent_width);
     } else if (d.proj == PMC_PROJ_GATHER) {
         k::deinterleave(st, nb, d.out_size, sol_s, d.gather.p, nullptr, lognormal, s_d);
     } else {

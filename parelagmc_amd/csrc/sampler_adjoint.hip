@@ -11,6 +11,11 @@
 // Tangent of Eval (pmc_sampler_eval_tangent): ds_out = f' o (O S R D v), the linear part of Eval applied
 // to the direction - Eval itself with the exp() of its stores switched off, so the same solve from a zero guess at the same
 // launch widths on every handle kind - times s_out, the f' of a lognormal handle, when the caller hands it over.
+//
+// Conditioned handles: with a conditioner attached that has derivatives enabled, Gamma = I - K A^-1 H
+// stands between L = O S R D and f.  The tangent runs Eval's hook on its homogeneous map (Sampler::cond_tangent_width); the
+// adjoint forms w = Gamma^T (v o f') per launch (Conditioner::apply_adjoint_device) and takes the path above with v := w,
+// s_out := NULL.  Without the opt-in both entries refuse the handle, as they always did.
 #include "handles.hpp"
 
 namespace pmc {
@@ -56,8 +61,9 @@ void Sampler::eval_tangent(int level, int xi_level, int nbatch, const double* v,
     PMC_REQUIRE(nbatch >= 1 && v != nullptr && ds_out != nullptr, "EvalTangent: bad arguments");
     PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "EvalTangent: bad memspace");
     PMC_REQUIRE(s_out == nullptr || lognormal, "EvalTangent: s_out given on a handle that is not lognormal");
-    PMC_REQUIRE(cond == nullptr, "EvalTangent: a conditioner is attached (pmc_sampler_set_conditioner); the tangent of the "
-                                 "conditional field is not implemented");
+    PMC_REQUIRE(cond == nullptr || cond->derivs,
+                "EvalTangent: a conditioner is attached (pmc_sampler_set_conditioner) without derivatives enabled; call "
+                "pmc_conditioner_enable_derivatives for the tangent of the conditional field");
     // Eval of v with the exp() of the stores off: the flag is a plain argument of every store Eval ends in
     struct FlagOff {
         bool& f;
@@ -65,8 +71,15 @@ void Sampler::eval_tangent(int level, int xi_level, int nbatch, const double* v,
         explicit FlagOff(bool& flag) : f(flag), keep(flag) { f = false; }
         ~FlagOff() { f = keep; }
     };
+    // ... and with the conditioner's hook on its homogeneous map dg - K A^-1 H dg, launch by launch as in Eval
+    struct WidthSet {
+        int& w;
+        WidthSet(int& width, int value) : w(width) { w = value; }
+        ~WidthSet() { w = 0; }
+    };
     {
         FlagOff off(lognormal);
+        WidthSet hom(cond_tangent_width, cond ? nbatch : 0);
         eval(level, xi_level, nbatch, v, ds_out, nullptr, 0, false, nullptr, memspace, stats);
     }
     if (!s_out) return;
@@ -264,8 +277,9 @@ void Sampler::eval_adjoint(int level, int xi_level, int nbatch, const double* v,
     PMC_REQUIRE(nbatch >= 1 && v != nullptr && grad_xi != nullptr, "EvalAdjoint: bad arguments");
     PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "EvalAdjoint: bad memspace");
     PMC_REQUIRE(s_out == nullptr || lognormal, "EvalAdjoint: s_out given on a handle that is not lognormal");
-    PMC_REQUIRE(cond == nullptr, "EvalAdjoint: a conditioner is attached (pmc_sampler_set_conditioner); the adjoint of the "
-                                 "conditional field is not implemented");
+    PMC_REQUIRE(cond == nullptr || cond->derivs,
+                "EvalAdjoint: a conditioner is attached (pmc_sampler_set_conditioner) without derivatives enabled; call "
+                "pmc_conditioner_enable_derivatives for the adjoint of the conditional field");
     if (kl) {
         eval_adjoint_kl(level, xi_level, nbatch, v, s_out, grad_xi, memspace, stats);
         return;
@@ -285,8 +299,17 @@ void Sampler::eval_adjoint(int level, int xi_level, int nbatch, const double* v,
             ensure(level, nb);
             PMC_HIP(hipMemcpyAsync(stage_in.p, v_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
             if (s_d) PMC_HIP(hipMemcpyAsync(stage_emb.p, s_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
-            eval_adjoint_chunk(level, xi_level, nb, stage_in.p, s_d ? stage_emb.p : nullptr, stage_out.p,
-                               stats ? stats + done : nullptr);
+            v_d = stage_in.p;
+            if (s_d) s_d = stage_emb.p;
+        }
+        if (cond) {   // w = Gamma^T (v o f') per launch, then the unconditioned path with v := w, s_out := NULL
+            cond->hook_w.ensure((size_t)n_out * nb);
+            cond->apply_adjoint_device(level, nb, v_d, s_d, cond->hook_w.p, nbatch);
+            v_d = cond->hook_w.p;
+            s_d = nullptr;
+        }
+        if (memspace == PMC_MEM_HOST) {
+            eval_adjoint_chunk(level, xi_level, nb, v_d, s_d, stage_out.p, stats ? stats + done : nullptr);
             PMC_HIP(hipMemcpyAsync(g_d, stage_out.p, sizeof(double) * n_xi * nb, hipMemcpyDeviceToHost, st));
             PMC_HIP(hipStreamSynchronize(st));
         } else {

@@ -72,14 +72,35 @@ def apply_affine(K, A, H, y, sigma2, g, zeta=None, exp=False):
     d = np.asarray(y)[None, :] - (H @ g.T).T
     if noisy:
         d = d + np.sqrt(sigma2)[None, :] * np.atleast_2d(zeta)
-    # one step of iterative refinement with the residual in long double: a plain float64 Cholesky solve carries cond(A) eps,
-    # which at cond(A) = 3.5e3 is 2e-12 in exp() of fields of size 25 (tests/gemm_depth_cases.py)
-    chol = (np.linalg.cholesky(A), True)
-    c = sla.cho_solve(chol, d.T)
-    r = np.asarray(d.T, dtype=np.longdouble) - np.asarray(A, dtype=np.longdouble) @ np.asarray(c, dtype=np.longdouble)
-    c = c + sla.cho_solve(chol, np.asarray(r, dtype=np.float64))
-    out = g + (K @ c).T
+    out = g + (K @ _refined_solve(A, d.T)).T
     return np.exp(out) if exp else out
+
+
+def _refined_solve(A, d):
+    """A^-1 d for columns d (nobs, nbatch): Cholesky and one step of iterative refinement with the residual in long double.  A
+    plain float64 Cholesky solve carries cond(A) eps, which at cond(A) = 3.5e3 is 2e-12 in exp() of fields of size 25
+    (tests/gemm_depth_cases.py)"""
+    chol = (np.linalg.cholesky(A), True)
+    c = sla.cho_solve(chol, d)
+    r = np.asarray(d, dtype=np.longdouble) - np.asarray(A, dtype=np.longdouble) @ np.asarray(c, dtype=np.longdouble)
+    return c + sla.cho_solve(chol, np.asarray(r, dtype=np.float64))
+
+
+def apply_tangent(K, A, H, dg, s_out=None):
+    """The derivative of apply_affine in g applied to a batch dg (nbatch, n): f' o (dg - K A^-1 H dg), f' = s_out (the
+    conditional lognormal field of the linearization point) or 1.  Independent of y, sigma2 and zeta."""
+    dg = np.atleast_2d(np.asarray(dg, dtype=np.float64))
+    out = dg - (K @ _refined_solve(A, np.asarray(H @ dg.T))).T
+    return out if s_out is None else out * np.atleast_2d(np.asarray(s_out, dtype=np.float64))
+
+
+def apply_adjoint(K, A, H, v, s_out=None):
+    """The transpose of apply_tangent applied to a batch v (nbatch, n): u - H^T A^-1 K^T u, u = v o s_out (u = v without
+    s_out).  <apply_tangent(dg, s), v> = <dg, apply_adjoint(v, s)>."""
+    u = np.atleast_2d(np.asarray(v, dtype=np.float64))
+    if s_out is not None:
+        u = u * np.atleast_2d(np.asarray(s_out, dtype=np.float64))
+    return u - np.asarray(H.T @ _refined_solve(A, K.T @ u.T)).T
 
 
 class _Gaussian:
@@ -153,6 +174,14 @@ class Conditioner:
         normals, required iff some sigma2 > 0; exp: return exp() of it"""
         return apply_affine(self.K[level], self.A[level], self.H[level], self.y, self.sigma2 if self.noisy else None, g, zeta,
                             exp)
+
+    def apply_tangent(self, level, dg, s_out=None):
+        """f' o (dg - K_l A_l^-1 H_l dg) for a batch dg (nbatch, n_s(level)): the derivative of apply in g; f' = s_out or 1"""
+        return apply_tangent(self.K[level], self.A[level], self.H[level], dg, s_out)
+
+    def apply_adjoint(self, level, v, s_out=None):
+        """u - H_l^T A_l^-1 K_l^T u, u = v o s_out, for a batch v (nbatch, n_s(level)): the transpose of apply_tangent"""
+        return apply_adjoint(self.K[level], self.A[level], self.H[level], v, s_out)
 
 
 def pick_observation_elements(hierarchy, nobs: int, seed: int = 0) -> np.ndarray:

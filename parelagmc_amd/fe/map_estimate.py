@@ -165,19 +165,21 @@ def map_newton_cg(logpost_grad, hessvec, xi0, **opts):
     return xi, res
 
 
-def map_estimate(sampler_problem, darcy_problem, level, xi0, Gobs, data, noise, xi_level=None, projection=None, **opts):
+def map_estimate(sampler_problem, darcy_problem, level, xi0, Gobs, data, noise, xi_level=None, projection=None, conditioner=None,
+                 **opts):
     """map_newton_cg over the twins of the library's two entries, with direct solves: logpost_gradient and
-    logpost_gn_hessvec of sampler_adjoint, column by column (Gobs: the observation functionals, data: the observed values)."""
+    logpost_gn_hessvec of sampler_adjoint, column by column (Gobs: the observation functionals, data: the observed values).
+    conditioner: an fe.condition.Conditioner with exact data - the MAP point of the conditional prior."""
     cache = {}
 
     def logpost_grad(X):
         out = [sampler_adjoint.logpost_gradient(sampler_problem, darcy_problem, level, x, Gobs, data, noise, xi_level,
-                                                projection, cache) for x in X]
+                                                projection, cache, conditioner) for x in X]
         return np.array([a for a, _ in out]), np.array([g for _, g in out])
 
     def hessvec(X, V):
         return np.array([sampler_adjoint.logpost_gn_hessvec(sampler_problem, darcy_problem, level, x, v, Gobs, noise, xi_level,
-                                                            projection, cache) if np.any(v) else np.zeros_like(v)
+                                                            projection, cache, conditioner) if np.any(v) else np.zeros_like(v)
                          for x, v in zip(X, V)])
 
     return map_newton_cg(logpost_grad, hessvec, xi0, **opts)

@@ -181,7 +181,9 @@ class PDESampler : public MLSampler {
     int GetNumAdjointIters() const { return last_adj_iters_; }
     bool IsLognormal() const { return pmc_sampler_is_lognormal(h_) == 1; }
     /// Eval returns fields conditioned on the data of `c` (pmc_conditioner_create on this handle, exact data); nullptr
-    /// detaches (pmc_sampler_set_conditioner).  The caller keeps ownership of `c`.
+    /// detaches (pmc_sampler_set_conditioner).  The caller keeps ownership of `c`.  EvalAdjoint / EvalTangent, the
+    /// BayesianInverseProblem derivative entries and ComputeMAP refuse the handle while `c` is attached unless the caller
+    /// has opted in with pmc_conditioner_enable_derivatives(c, 1): they then differentiate the conditional field.
     void SetConditioner(pmc_conditioner* c);
     pmc_sampler* Handle() const { return h_; }
     pmc_ctx* Context() const { return ctx_; }
