@@ -935,6 +935,49 @@ int pmc_transport_reduce(pmc_transport* t, int nbatch, const double* curve, cons
  * created on another context's device, a kind other than the two, a tracer attached to the level. */
 int pmc_darcy_set_transport(pmc_darcy* d, int level, pmc_transport* t, int kind);
 
+/* ---- The adjoint of the solute transport: gradients of breakthrough data (an extension)
+ * For J = <curve_bar, curve> + stored_bar stored + <c_bar, c> per column, pmc_transport_run_adjoint returns u_bar = dJ/du
+ * (the first n_face entries of the row at u_bar + b * ld_bar; nothing else of the row is written) and c0_bar = dJ/dc0 (nbatch
+ * x n_elem, may be NULL), the discrete adjoint of the scheme above with three decisions of the forward pass held fixed: the
+ * step count, the sign of every g_l (g_l == 0 contributes nothing) and the branch out_e >= in_e of r_e.  Seeds: curve_bar
+ * (nbatch x nreport), stored_bar (nbatch), c_bar (nbatch x n_elem); each may be NULL and then counts as zero, at least one must
+ * be given.  The forward outputs curve, stored, nsteps (each may be NULL) and status are those of pmc_transport_run bit for
+ * bit.  A column whose status is not PMC_TRANSPORT_OK is not differentiated: its u_bar and c0_bar are zero.  All arrays in
+ * `memspace`.
+ *   history: the sweep needs every state c^n.  The forward pass keeps every K-th one and the sweep recomputes a segment of K
+ *            states at a time, with the forward bits.  K = ceil(sqrt(largest step count of the launch)) unless
+ *            pmc_transport_set_adjoint_segment sets one (0: automatic again); scratch about (N / K + K) n_elem nbatch doubles.
+ * A column's results have the same bits at every nbatch, in every split into calls, in either memory space, at every K and
+ * in repeated calls; pmc_transport_run is not disturbed.
+ * Refused with PMC_ERR_INVALID (nothing is written, the handle stays usable): all three seeds NULL; NULL u, u_bar or status;
+ * ld or ld_bar < n_face; nbatch < 1; a bad memspace; K < 0. */
+int pmc_transport_run_adjoint(pmc_transport* t, int nbatch, const double* u, int64_t ld,
+                              const double* curve_bar /* nbatch x nreport | NULL */, const double* stored_bar /* nbatch | NULL */,
+                              const double* c_bar /* nbatch x n_elem | NULL */, double* u_bar, int64_t ld_bar /* >= n_face */,
+                              double* c0_bar /* nbatch x n_elem | NULL */, double* curve /* | NULL */, double* stored /* | NULL */,
+                              int32_t* nsteps /* | NULL */, int32_t* status, int memspace);
+int pmc_transport_set_adjoint_segment(pmc_transport* t, int K);   /* 0: automatic */
+/* dJ/dk (wrt_log: dJ/dlog k) of J = <curve_bar, curve> + stored_bar stored of the transport t on the flux of the level's
+ * Darcy solution, per realization: forward solve, the transport and its adjoint on the solver's internal solution, u_bar as the
+ * u rows of the adjoint right-hand side (p rows and essential rows zero), adjoint solve, pmc_darcy_mass_sensitivity - the
+ * pipeline of pmc_darcy_solve_gradient, saddle-point path on every handle, whose sol_out / adj_out / stats these are.  t is
+ * given with the call: what pmc_darcy_set_transport or pmc_darcy_set_tracer attached is neither read nor changed.  k,
+ * curve_bar (nbatch x nreport | NULL), stored_bar (nbatch | NULL; one of the two must be given), grad (nbatch x n_p), curve
+ * (nbatch x nreport | NULL), stored (nbatch | NULL), sol_out and adj_out (| NULL) in `memspace`; status (nbatch) on the host.  A
+ * column whose status is not PMC_TRANSPORT_OK has a zero gradient.
+ * pmc_darcy_transport_loglik_gradient: loglik[b] = -|curve_b - data|^2 / (2 noise) (host) and its gradient, the seed
+ * curve_bar = -(curve - data) / noise formed on the device; data (nreport), loglik, curve (| NULL) and status on the host.
+ * Refused with PMC_ERR_INVALID: a level out of range, t NULL, of other sizes than the level (n_face != n_u or n_elem != n_p) or
+ * created on another device, nbatch < 1, NULL k, grad, status or data, both seeds NULL, noise <= 0, a bad memspace. */
+int pmc_darcy_transport_gradient(pmc_darcy* d, int level, pmc_transport* t, int nbatch, const double* k,
+                                 const double* curve_bar, const double* stored_bar, int wrt_log, double* curve, double* stored,
+                                 int32_t* status, double* grad, double* sol_out, double* adj_out, int memspace,
+                                 pmc_stats* stats_fwd, pmc_stats* stats_adj);
+int pmc_darcy_transport_loglik_gradient(pmc_darcy* d, int level, pmc_transport* t, int nbatch, const double* k,
+                                        const double* data /* host, nreport */, double noise, int wrt_log, double* loglik /* host */,
+                                        double* curve /* host, nbatch x nreport | NULL */, int32_t* status, double* grad, int memspace,
+                                        pmc_stats* stats_adj);
+
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */
 int pmc_comm_unique_id(void* id128);                                        /* 128 bytes    */

@@ -282,6 +282,15 @@ SYMBOLS = {
     "pmc_transport_run": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _DP, _DP, _DP, _DP, _VP, _VP, C.c_int]),
     "pmc_transport_reduce": (C.c_int, [_VP, C.c_int, _DP, _DP, C.c_int, C.POINTER(C.c_double), C.c_int]),
     "pmc_darcy_set_transport": (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
+    "pmc_transport_run_adjoint": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _DP, _DP, _DP, C.c_int64, _DP, _DP, _DP, _VP, _VP,
+                                            C.c_int]),
+    "pmc_transport_set_adjoint_segment": (C.c_int, [_VP, C.c_int]),
+    "pmc_darcy_transport_gradient": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _DP, _DP, _DP, C.c_int, _DP, _DP,
+                                               C.POINTER(C.c_int32), _DP, _DP, _DP, C.c_int, C.POINTER(pmc_stats),
+                                               C.POINTER(pmc_stats)]),
+    "pmc_darcy_transport_loglik_gradient": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _DP, C.POINTER(C.c_double), C.c_double, C.c_int,
+                                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _DP,
+                                                      C.c_int, C.POINTER(pmc_stats)]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -1531,6 +1540,55 @@ class DarcySolver:
                                                       _addr(grad)[0], ms, None))
         return ll, G, grad
 
+    # ---- gradients of breakthrough data through a transport's adjoint ---------------------------
+    def TransportGradient(self, level, transport, k, curve_bar=None, stored_bar=None, wrt_log=False, nbatch=None, grad_out=None,
+                          want_solution=False, return_stats=False):
+        """dJ/dk (dJ/dlog k) of J = <curve_bar, curve> + stored_bar stored of `transport` (a capi.Transport of the level's
+        sizes) on the flux of the Darcy solution (pmc_darcy_transport_gradient).  k and the seeds numpy, or all on the device
+        with nbatch and grad_out.  Returns a dict of grad, curve (nbatch x nreport), stored and status (numpy int32) - plus sol
+        and adj with want_solution, plus stats (forward, adjoint) with return_stats."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        host = ms == PMC_MEM_HOST
+        nr, n = (transport.nreport if transport is not None else 1), self.GetGlobalNumberOfDofs(level)   # None: the library refuses
+        if host and transport is not None:
+            curve_bar = None if curve_bar is None else _f64(np.atleast_2d(curve_bar))
+            stored_bar = None if stored_bar is None else _f64(np.atleast_1d(stored_bar))
+            if (curve_bar is not None and curve_bar.shape != (nbatch, nr)) or (stored_bar is not None and stored_bar.shape != (nbatch,)):
+                raise ValueError("curve_bar must be nbatch x nreport and stored_bar nbatch")
+        new = (lambda *shape: np.empty(shape)) if host else (lambda *shape: DeviceArray(self.ctx, int(np.prod(shape))))
+        curve, stored = new(nbatch, nr), new(nbatch)
+        sol, adj = (new(nbatch, n), new(nbatch, n)) if want_solution else (None, None)
+        for a in (curve_bar, stored_bar):
+            if a is not None and _addr(a)[1] != ms:
+                raise ValueError("all arrays of a call must share a memory space")
+        status = np.empty(nbatch, np.int32)
+        sf, sa = (pmc_stats * nbatch)(), (pmc_stats * nbatch)()
+        _check(self.ctx.lib.pmc_darcy_transport_gradient(
+            self.h, level, None if transport is None else transport.h, nbatch, pk, _addr(curve_bar)[0], _addr(stored_bar)[0],
+            1 if wrt_log else 0, _addr(curve)[0], _addr(stored)[0], _ptr(status, C.c_int32), _addr(grad)[0], _addr(sol)[0],
+            _addr(adj)[0], ms, sf, sa))
+        out = dict(grad=grad, curve=curve, stored=stored, status=status)
+        if want_solution:
+            out.update(sol=sol, adj=adj)
+        if return_stats:
+            out["stats"] = [[(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in st] for st in (sf, sa)]
+        return out
+
+    def TransportLoglikGradient(self, level, transport, k, data, noise, wrt_log=False, nbatch=None, grad_out=None):
+        """loglik = -|curve - data|^2 / (2 noise) of the breakthrough curve of `transport` and its gradient in k
+        (pmc_darcy_transport_loglik_gradient): returns (loglik (nbatch,), curve (nbatch, nreport), status, grad)."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        data = None if data is None else _f64(np.asarray(data, dtype=np.float64).ravel())
+        if data is not None and data.size != transport.nreport:
+            raise ValueError("data must hold one value per report time")
+        ll, curve, status = np.empty(nbatch), np.empty((nbatch, transport.nreport)), np.empty(nbatch, np.int32)
+        _check(self.ctx.lib.pmc_darcy_transport_loglik_gradient(
+            self.h, level, transport.h, nbatch, pk, None if data is None else _ptr(data, C.c_double), float(noise),
+            1 if wrt_log else 0, _ptr(ll, C.c_double), _ptr(curve, C.c_double), _ptr(status, C.c_int32), _addr(grad)[0], ms, None))
+        return ll, curve, status, grad
+
     # ---- Gauss-Newton Hessian-vector products in k (DESIGN.md section 18) ----------------------------------------------
     def mass_tangent_time(self):
         """the tangent right-hand side kernel under set_operator_timing: (bracket ms, launches, empty-bracket ms)"""
@@ -1826,6 +1884,48 @@ class Transport:
         if not want_c:
             del out["c"]
         return out
+
+    def run_adjoint(self, u, curve_bar=None, stored_bar=None, c_bar=None, nbatch=None, ld=None, ld_bar=None, want_c0_bar=True):
+        """u_bar = dJ/du and c0_bar = dJ/dc0 of J = <curve_bar, curve> + stored_bar stored + <c_bar, c> per column
+        (pmc_transport_run_adjoint).  u and the seeds: numpy (u: nbatch x ld >= n_face), or DeviceArrays /
+        device tensors with nbatch (and ld, default n_face).  Returns a dict of u_bar (nbatch x ld_bar, default n_face; only the
+        first n_face entries of a row are written), c0_bar (unless want_c0_bar is False), curve, stored, nsteps and status."""
+        ne, nr = self.n_elem, self.nreport
+        seeds = [curve_bar, stored_bar, c_bar]
+        if isinstance(u, np.ndarray):
+            u = _f64(np.atleast_2d(u))
+            nbatch, ld = u.shape
+            ld_bar = self.n_face if ld_bar is None else int(ld_bar)
+            shapes = [(nbatch, nr), (nbatch,), (nbatch, ne)]
+            for i, (a, shape) in enumerate(zip(seeds, shapes)):
+                if a is not None:
+                    seeds[i] = _f64(a).reshape(shape)
+            out = dict(u_bar=np.zeros((nbatch, max(ld_bar, 0))), c0_bar=np.empty((nbatch, ne)) if want_c0_bar else None,
+                       curve=np.empty((nbatch, nr)), stored=np.empty(nbatch), nsteps=np.empty(nbatch, np.int32),
+                       status=np.empty(nbatch, np.int32))
+            pu, ms = u.ctypes.data, PMC_MEM_HOST
+            addr = lambda a: None if a is None else a.ctypes.data
+        else:
+            assert nbatch is not None
+            ld = self.n_face if ld is None else int(ld)
+            ld_bar = self.n_face if ld_bar is None else int(ld_bar)
+            pu, ms = _addr(u)
+            assert ms == PMC_MEM_DEVICE and all(a is None or _addr(a)[1] == ms for a in seeds)
+            dev = lambda n: DeviceArray(self.ctx, n)
+            out = dict(u_bar=dev(nbatch * max(ld_bar, 1)), c0_bar=dev(nbatch * ne) if want_c0_bar else None, curve=dev(nbatch * nr),
+                       stored=dev(nbatch), nsteps=DeviceInt32Array(self.ctx, nbatch), status=DeviceInt32Array(self.ctx, nbatch))
+            addr = lambda a: None if a is None else (a.ptr if isinstance(a, DeviceArray) else _addr(a)[0])
+        _check(self.ctx.lib.pmc_transport_run_adjoint(self.h, int(nbatch), pu, int(ld), *[addr(a) for a in seeds], addr(out["u_bar"]),
+                                                      int(ld_bar), *[addr(out[k]) for k in ("c0_bar", "curve", "stored", "nsteps",
+                                                                                            "status")], ms))
+        if not want_c0_bar:
+            del out["c0_bar"]
+        return out
+
+    def set_adjoint_segment(self, K=0):
+        """the number of steps between two kept states of run_adjoint; 0: ceil(sqrt(largest step count)).  The results do
+        not depend on it."""
+        _check(self.ctx.lib.pmc_transport_set_adjoint_segment(self.h, int(K)))
 
     def Reduce(self, curve, stored, kind=0):
         """Q per realization: the mass that left through the outlet (MASS_OUT) or the weighted mass in place (STORED)"""

@@ -848,6 +848,38 @@ int pmc_darcy_set_transport(pmc_darcy* d, int level, pmc_transport* t, int kind)
         d->impl.set_transport(level, t ? &t->impl : nullptr, kind);
     });
 }
+int pmc_transport_run_adjoint(pmc_transport* t, int nbatch, const double* u, int64_t ld, const double* curve_bar,
+                              const double* stored_bar, const double* c_bar, double* u_bar, int64_t ld_bar, double* c0_bar,
+                              double* curve, double* stored, int32_t* nsteps, int32_t* status, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_transport_run_adjoint: transport is NULL");
+        t->impl.run_adjoint(nbatch, u, ld, curve_bar, stored_bar, c_bar, u_bar, ld_bar, c0_bar, curve, stored, nsteps, status, memspace);
+    });
+}
+int pmc_transport_set_adjoint_segment(pmc_transport* t, int K) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_transport_set_adjoint_segment: transport is NULL");
+        t->impl.set_adjoint_segment(K);
+    });
+}
+int pmc_darcy_transport_gradient(pmc_darcy* d, int level, pmc_transport* t, int nbatch, const double* k, const double* curve_bar,
+                                 const double* stored_bar, int wrt_log, double* curve, double* stored, int32_t* status, double* grad,
+                                 double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_transport_gradient: darcy is NULL");
+        d->impl.transport_gradient(level, t ? &t->impl : nullptr, nbatch, k, curve_bar, stored_bar, wrt_log != 0, curve, stored, status,
+                                   grad, sol_out, adj_out, memspace, stats_fwd, stats_adj);
+    });
+}
+int pmc_darcy_transport_loglik_gradient(pmc_darcy* d, int level, pmc_transport* t, int nbatch, const double* k, const double* data,
+                                        double noise, int wrt_log, double* loglik, double* curve, int32_t* status, double* grad,
+                                        int memspace, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_transport_loglik_gradient: darcy is NULL");
+        d->impl.transport_loglik_gradient(level, t ? &t->impl : nullptr, nbatch, k, data, noise, wrt_log != 0, loglik, curve, status,
+                                          grad, memspace, stats_adj);
+    });
+}
 
 int pmc_darcy_num_dofs(const pmc_darcy* d, int level) {
     if (!d || level < 0 || level >= d->impl.nlevels) return PMC_ERR_INVALID;

@@ -392,6 +392,19 @@ void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSp
                                                            obs_data.p, -1.0 / adj.noise, adj_rhs.p + (size_t)n_u * nb);
         PMC_HIP(hipGetLastError());
         count_kernel_launches(2);
+    } else if (adj.transport) {
+        // J of the breakthrough data: the transport and its adjoint on the interleaved solution (minres_solve has synchronised
+        // the stream, as Transport::qoi_interleaved requires), u_bar straight into the u rows, zero p rows and essential rows
+        Transport& T = *adj.transport;
+        T.adjoint_forward(st, nb, sol.p, nb, 1, adj.curve_d, adj.stored_d);
+        for (int kcol = 0; kcol < nb; ++kcol) adj.status_h[kcol] = T.h_status[kcol];
+        const double* cb_d = adj.tdata_d ? T.loglik_seed(st, nb, adj.curve_d, adj.tdata_d, adj.noise) : adj.curve_bar_d;
+        T.adjoint_backward(st, nb, sol.p, nb, 1, cb_d, adj.tdata_d ? nullptr : adj.stored_bar_d, nullptr, adj_rhs.p, nb, 1, nullptr);
+        k::fill(st, (size_t)n_p * nb, adj_rhs.p + (size_t)n_u * nb, 0.0);
+        const size_t tu = (size_t)n_u * nb;
+        zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
     } else {
         if (adj.rhs_d) k::interleave(st, nb, n, adj.rhs_d, nullptr, 1.0, adj_rhs.p);
         else k::broadcast(st, nb, n, d.obs.p, adj_rhs.p);
@@ -570,6 +583,136 @@ void Darcy::loglik_gradient(int level, int nbatch, const double* kf, const doubl
                 if (G) G[(size_t)(done + b) * nobs + i] = gh[(size_t)b * nobs + i];
             }
             if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;      // log of BayesianInverseProblem::ComputeLikelihood
+        }
+        done += nb;
+    }
+}
+
+void Darcy::check_transport(int level, const Transport* t, const char* who) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, std::string(who) + ": level out of range");
+    PMC_REQUIRE(t != nullptr, std::string(who) + ": transport is NULL");
+    PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
+                std::string(who) + ": the transport's mesh does not match the level (n_face != n_u or n_elem != n_p)");
+    PMC_REQUIRE(t->ctx.device == ctx.device, std::string(who) + ": the transport was created on another device");
+}
+
+void Darcy::transport_gradient(int level, Transport* t, int nbatch, const double* kf, const double* curve_bar,
+                               const double* stored_bar, bool wrt_log, double* curve, double* stored, int32_t* status, double* grad,
+                               double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj) {
+    const char* who = "pmc_darcy_transport_gradient";
+    check_transport(level, t, who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr, std::string(who) + ": bad arguments");
+    PMC_REQUIRE(curve_bar != nullptr || stored_bar != nullptr, std::string(who) + ": curve_bar or stored_bar must be given");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, nr = (size_t)t->nreport;
+    const bool host = memspace == PMC_MEM_HOST;
+    std::vector<double> q(kMaxBatch);
+    DevBuf<double> stage_out;
+    int done = 0;
+    while (done < nbatch) {
+        int nb = batch_width(n, true, ctx.device);
+        while (nb > nbatch - done) nb >>= 1;
+        struct { const double *k_d, *cb_d, *sb_d; double *grad_d, *sol_d, *adj_d; } s{
+            kf + done * np, curve_bar ? curve_bar + done * nr : nullptr, stored_bar ? stored_bar + done : nullptr, grad + done * np,
+            sol_out ? sol_out + done * n : nullptr, adj_out ? adj_out + done * n : nullptr};
+        tr_curve.ensure(nr * nb);
+        tr_stored.ensure(nb);
+        if (host) {
+            ensure(level, nb);
+            stage_grad.ensure(np * nb);
+            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
+            s.k_d = stage_k.p;
+            if (s.cb_d) {
+                tr_cb.upload(s.cb_d, nr * nb, st);
+                s.cb_d = tr_cb.p;
+            }
+            if (s.sb_d) {
+                tr_sb.upload(s.sb_d, nb, st);
+                s.sb_d = tr_sb.p;
+            }
+            s.grad_d = stage_grad.p;
+            if (s.sol_d) s.sol_d = stage_sol.p;
+            if (s.adj_d) {
+                stage_out.ensure(n * nb);
+                s.adj_d = stage_out.p;
+            }
+        }
+        AdjointSpec adj;
+        adj.transport = t;
+        adj.curve_bar_d = s.cb_d;
+        adj.stored_bar_d = s.sb_d;
+        adj.curve_d = tr_curve.p;
+        adj.stored_d = tr_stored.p;
+        adj.status_h = status + done;
+        gradient_chunk(level, nb, s.k_d, adj, wrt_log, q.data(), nullptr, s.grad_d, s.sol_d, s.adj_d,
+                       stats_fwd ? stats_fwd + done : nullptr, stats_adj ? stats_adj + done : nullptr);
+        const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (curve) PMC_HIP(hipMemcpyAsync(curve + done * nr, tr_curve.p, sizeof(double) * nr * nb, back, st));
+        if (stored) PMC_HIP(hipMemcpyAsync(stored + done, tr_stored.p, sizeof(double) * nb, back, st));
+        if (host) {
+            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
+            if (sol_out) PMC_HIP(hipMemcpyAsync(sol_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
+            if (adj_out) PMC_HIP(hipMemcpyAsync(adj_out + done * n, stage_out.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
+        }
+        PMC_HIP(hipStreamSynchronize(st));
+        done += nb;
+    }
+}
+
+void Darcy::transport_loglik_gradient(int level, Transport* t, int nbatch, const double* kf, const double* data, double noise,
+                                      bool wrt_log, double* loglik, double* curve, int32_t* status, double* grad, int memspace,
+                                      pmc_stats* stats_adj) {
+    const char* who = "pmc_darcy_transport_loglik_gradient";
+    check_transport(level, t, who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && status != nullptr, std::string(who) + ": bad arguments");
+    PMC_REQUIRE(noise > 0.0, std::string(who) + ": the noise variance must be positive");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
+    const int nr = t->nreport;
+    const bool host = memspace == PMC_MEM_HOST;
+    std::vector<double> q(kMaxBatch), ch((size_t)nr * kMaxBatch);
+    tr_data.upload(data, (size_t)nr, st);
+    int done = 0;
+    while (done < nbatch) {
+        int nb = batch_width(n, true, ctx.device);
+        while (nb > nbatch - done) nb >>= 1;
+        const double* k_d = kf + done * np;
+        double* grad_d = grad + done * np;
+        tr_curve.ensure((size_t)nr * nb);
+        tr_stored.ensure(nb);
+        if (host) {
+            ensure(level, nb);
+            stage_grad.ensure(np * nb);
+            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
+            k_d = stage_k.p;
+            grad_d = stage_grad.p;
+        }
+        AdjointSpec adj;
+        adj.transport = t;
+        adj.tdata_d = tr_data.p;
+        adj.noise = noise;
+        adj.curve_d = tr_curve.p;
+        adj.stored_d = tr_stored.p;
+        adj.status_h = status + done;
+        gradient_chunk(level, nb, k_d, adj, wrt_log, q.data(), nullptr, grad_d, nullptr, nullptr, nullptr,
+                       stats_adj ? stats_adj + done : nullptr);
+        PMC_HIP(hipMemcpyAsync(ch.data(), tr_curve.p, sizeof(double) * nr * nb, hipMemcpyDeviceToHost, st));
+        if (host) PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < nb; ++b) {
+            double s = 0.0;
+            for (int i = 0; i < nr; ++i) {
+                const double dd = ch[(size_t)b * nr + i] - data[i];
+                s += dd * dd;
+                if (curve) curve[(size_t)(done + b) * nr + i] = ch[(size_t)b * nr + i];
+            }
+            if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;
         }
         done += nb;
     }

@@ -319,8 +319,33 @@ struct Transport {
     DevBuf<double> cbuf, acc, snap, col_rate, col_dt, stage_u, out_c, out_curve, out_stored;
     DevBuf<int32_t> col_steps;
     std::vector<double> h_rate, h_dt, h_treached;   // the plan of the last launch, per column
-    std::vector<int32_t> h_steps, h_status;
+    std::vector<int32_t> h_steps, h_status, h_steps_adj;
+    // the adjoint (pmc_transport_run_adjoint): per dof its one or two elements and its outlet index;
+    // the checkpoints, one recomputed segment, the final states, the (lam, w lam) pairs, beta per (step, column), the time
+    // sums P, X, O and the branch of r_e; the staging of a host call.  Scratch of their own: a pmc_transport_run after an
+    // adjoint call finds its buffers as it left them.
+    DevBuf<int32_t> side, col_steps_adj;
+    DevBuf<double> adj_ck, adj_seg, adj_tmp, adj_fin, adj_lam, adj_wlam, adj_beta, adj_P, adj_X, adj_O;
+    DevBuf<unsigned char> adj_sig;
+    DevBuf<double> stage_cb, stage_sb, stage_eb, stage_ubar, stage_c0bar, seed_cb;
+    int adj_segment = 0;           // K of pmc_transport_set_adjoint_segment; 0: ceil(sqrt(longest step count))
+    int adj_K = 1, adj_nck = 1, adj_longest = 0, adj_longest_fwd = 0;   // of the last adjoint_forward
     Transport(Ctx& c, const pmc_transport_mesh& m, const pmc_transport_params& p);
+    void run_adjoint(int nbatch, const double* u, int64_t ld, const double* curve_bar, const double* stored_bar, const double* c_bar,
+                     double* u_bar, int64_t ld_bar, double* c0_bar, double* curve, double* stored, int32_t* nsteps, int32_t* status,
+                     int memspace);
+    void set_adjoint_segment(int K);
+    // The two halves of an adjoint launch of nb columns on stream st, the flux read through (stride_face, stride_batch):
+    // the forward pass with checkpoints (curve_d nb x nreport, stored_d nb; the plan in h_*), then the sweep from the
+    // seeds (device, sample-major, each may be NULL) to u_bar, written through (stride_face_out, stride_batch_out), and
+    // c0_bar (nb x n_elem, may be NULL).  Columns whose status is not PMC_TRANSPORT_OK get zeros.
+    void adjoint_forward(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
+                         double* stored_d);
+    void adjoint_backward(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch,
+                          const double* curve_bar_d, const double* stored_bar_d, const double* c_bar_d, double* ubar_d,
+                          int64_t stride_face_out, int64_t stride_batch_out, double* c0_bar_d);
+    // curve_bar = -(curve - data) / noise into seed_cb (data: device, nreport); returns seed_cb.p
+    const double* loglik_seed(hipStream_t st, int nb, const double* curve_d, const double* data_d, double noise);
     void run(int nbatch, const double* u, int64_t ld, double* c_out, double* curve, double* stored, double* rate,
              double* t_reached, int32_t* nsteps, int32_t* status, int memspace);
     void reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace);
@@ -329,6 +354,9 @@ struct Transport {
 
   private:
     int nnz_ = 0;
+    template <class F>
+    void by_width(F&& launch) const;   // transport.hip only
+    int plan_columns(hipStream_t st, int nb, const double* q_d);
     void compute(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
                  double* stored_d, int kind, double* q_d);
 };
@@ -496,6 +524,15 @@ struct Darcy {
                         pmc_stats* stats_adj);
     void loglik_gradient(int level, int nbatch, const double* k, const double* data, double noise, bool wrt_log,
                          double* loglik, double* G, double* grad, int memspace, pmc_stats* stats_adj);
+    // Gradients in k of the breakthrough data of a transport on the level's flux (pmc_darcy_transport_gradient /
+    // _transport_loglik_gradient): gradient_chunk with the transport's adjoint in front of the adjoint
+    // solve.  t is given with the call; what set_transport / set_tracer attached is neither read nor changed.
+    void transport_gradient(int level, Transport* t, int nbatch, const double* k, const double* curve_bar, const double* stored_bar,
+                            bool wrt_log, double* curve, double* stored, int32_t* status, double* grad, double* sol_out,
+                            double* adj_out, int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj);
+    void transport_loglik_gradient(int level, Transport* t, int nbatch, const double* k, const double* data, double noise,
+                                   bool wrt_log, double* loglik, double* curve, int32_t* status, double* grad, int memspace,
+                                   pmc_stats* stats_adj);
     // Tangent right-hand side and Gauss-Newton Hessian action (pmc_darcy_mass_tangent / _gn_hessvec, darcy_hessian.hip);
     // the saddle-point path on every handle, as the gradients
     void mass_tangent(int level, int nbatch, const double* k, const double* x, const double* dk, bool wrt_log, double* t_out,
@@ -534,7 +571,17 @@ struct Darcy {
         bool loglik = false;              // right-hand side of the Gaussian log-likelihood, formed on the device
         const double* data = nullptr;     // loglik: observed values (host, n_gobs)
         double noise = 1.0;
+        // third mode: dJ/du of a transport's J on the internal solution, written straight into the u rows
+        Transport* transport = nullptr;
+        const double* curve_bar_d = nullptr;   // seeds: device, sample-major (NULL: zero); ignored with tdata_d
+        const double* stored_bar_d = nullptr;
+        const double* tdata_d = nullptr;       // breakthrough data (device, nreport): curve_bar = -(curve - data) / noise
+        double* curve_d = nullptr;             // forward outputs of the launch: device, nb x nreport and nb
+        double* stored_d = nullptr;
+        int32_t* status_h = nullptr;           // host, nb
     };
+    void check_transport(int level, const Transport* t, const char* who) const;
+    DevBuf<double> tr_curve, tr_stored, tr_cb, tr_sb, tr_data;
     void ensure_gradient(int level, bool tangent = false);   // tangent: the face-major copy as well
     void ensure_loglik(int level);
     // darcy_hessian.hip

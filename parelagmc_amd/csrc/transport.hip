@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -110,23 +111,13 @@ __global__ __launch_bounds__(kTransportThreads) void transport_rate_max_kernel(i
     }
 }
 
-// step s of every column that has one: buf holds the two concentration buffers (n_elem * nb each)
-template <int W>
-__global__ __launch_bounds__(kTransportThreads) void transport_step_kernel(TransportView v, int nb, int s, const double* __restrict__ u,
-                                                                           int64_t stride_face, int64_t stride_batch,
-                                                                           const double* __restrict__ dtcol,
-                                                                           const int32_t* __restrict__ ncol, double* buf,
-                                                                           double* __restrict__ acc, double* __restrict__ snap) {
-    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
-    const unsigned e = gid / (unsigned)nb, b = gid % (unsigned)nb;
-    if (e >= (unsigned)v.n_elem) return;
-    const int nsteps = ncol[b];
-    if (s >= nsteps) return;
-    const size_t len = (size_t)v.n_elem * nb;
-    const double* src = buf + (s & 1) * len;
-    double* dst = buf + ((s + 1) & 1) * len;
-    const double* ub = u + (int64_t)b * stride_batch;
-    const double dt = dtcol[b];
+// the arithmetic of step s for element e of column b: c^{s+1}_e from the state src.  kOutlet: also the accumulators of the
+// element's outlet dofs and the report times that fall into this step.  The forward kernel, the checkpointed forward pass of
+// the adjoint and its recomputation all go through here, so a recomputed state has the forward bits.
+template <int W, bool kOutlet>
+__device__ __forceinline__ double step_value(const TransportView& v, int nb, int s, int nsteps, unsigned gid, unsigned e, unsigned b,
+                                             const double* ub, int64_t stride_face, double dt, const double* __restrict__ src,
+                                             double* __restrict__ acc, double* __restrict__ snap) {
     const double w = dt / v.vol[e];
     const double ce = src[gid];
     double out = 0.0, in = 0.0, sacc = 0.0;
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(kTransportThreads) void transport_step_kernel(Trans
         in += gi;
         const double cn = nbr >= 0 ? src[(size_t)nbr * nb + b] : v.cin[dof_id(enc)];
         sacc += gi * cn;
-        if (nbr <= -2) {
+        if (kOutlet && nbr <= -2) {
             // an outlet dof of this element: its accumulator and the report times that fall into this step
             const int j = -2 - nbr;
             const size_t jb = (size_t)j * nb + b;
@@ -157,7 +148,25 @@ __global__ __launch_bounds__(kTransportThreads) void transport_step_kernel(Trans
     });
     const double r = fmax(out, in);
     const double d = 1.0 - w * r;
-    dst[gid] = d * ce + w * sacc;
+    return d * ce + w * sacc;
+}
+
+// step s of every column that has one: buf holds the two concentration buffers (n_elem * nb each)
+template <int W>
+__global__ __launch_bounds__(kTransportThreads) void transport_step_kernel(TransportView v, int nb, int s, const double* __restrict__ u,
+                                                                           int64_t stride_face, int64_t stride_batch,
+                                                                           const double* __restrict__ dtcol,
+                                                                           const int32_t* __restrict__ ncol, double* buf,
+                                                                           double* __restrict__ acc, double* __restrict__ snap) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned e = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (e >= (unsigned)v.n_elem) return;
+    const int nsteps = ncol[b];
+    if (s >= nsteps) return;
+    const size_t len = (size_t)v.n_elem * nb;
+    const double* src = buf + (s & 1) * len;
+    double* dst = buf + ((s + 1) & 1) * len;
+    dst[gid] = step_value<W, true>(v, nb, s, nsteps, gid, e, b, u + (int64_t)b * stride_batch, stride_face, dtcol[b], src, acc, snap);
 }
 
 __device__ __forceinline__ double block_sum(double acc, double* wsum) {
@@ -170,9 +179,10 @@ __device__ __forceinline__ double block_sum(double acc, double* wsum) {
 }
 
 // blockIdx.x < nreport: curve[b][x] = sum_j snap[x][j][b] (0 for a column that took no step); blockIdx.x == nreport:
-// stored[b] = sum_e wgt_e c_e in the column's final buffer.  q (may be NULL) receives the QoI of `kind`.
+// stored[b] = sum_e wgt_e c_e in the column's final buffer, buf + (nsteps & 1) * half (half 0: one buffer of final states).
+// q (may be NULL) receives the QoI of `kind`.
 __global__ __launch_bounds__(kTransportThreads) void transport_finish_kernel(TransportView v, int nb, const int32_t* __restrict__ ncol,
-                                                                             const double* __restrict__ buf,
+                                                                             const double* __restrict__ buf, size_t half,
                                                                              const double* __restrict__ snap, double* __restrict__ curve,
                                                                              double* __restrict__ stored, int kind, double* __restrict__ q) {
     __shared__ double wsum[kTransportThreads / 64];
@@ -183,7 +193,7 @@ __global__ __launch_bounds__(kTransportThreads) void transport_finish_kernel(Tra
         if (nsteps > 0)
             for (int j = threadIdx.x; j < v.n_outlet; j += kTransportThreads) acc += snap[((size_t)x * v.n_outlet + j) * nb + b];
     } else {
-        const double* c = buf + (size_t)(nsteps & 1) * v.n_elem * nb;
+        const double* c = buf + (size_t)(nsteps & 1) * half;
         for (int e = threadIdx.x; e < v.n_elem; e += kTransportThreads) acc += v.wgt[e] * c[(size_t)e * nb + b];
     }
     const double s = block_sum(acc, wsum);
@@ -204,6 +214,185 @@ __global__ __launch_bounds__(kTransportThreads) void transport_copy_out_kernel(i
     const unsigned b = gid / (unsigned)n_elem, e = gid % (unsigned)n_elem;
     if (b >= (unsigned)nb) return;
     c_out[gid] = buf[(size_t)(ncol[b] & 1) * n_elem * nb + (size_t)e * nb + b];
+}
+
+// ---- the discrete adjoint (pmc_transport_run_adjoint) ----------------------------------------------
+// J = <curve_bar, curve> + stored_bar stored + <c_bar, c^N> per column, differentiated in u with three decisions of the forward
+// pass held fixed: the step count, the sign of every g and the branch sigma_e = (out_e >= in_e) of r_e.  The forward pass
+// keeps every K-th state; the backward sweep recomputes one segment of K states at a time with step_value and walks it
+// backwards, one launch per step:
+//     lam^n_e = d_e lam^{n+1}_e + sum_l go_l y_l,   y_l = w_nbr lam^{n+1}_nbr | beta^n on an outlet dof | 0
+// while the element's thread accumulates P_e = sum_n c^n_e lam^{n+1}_e, X_f = sum_n cn^n_f lam^{n+1}_e for the dofs f through
+// which it takes inflow (a dof is the inflow of at most one element: X is kept per dof, no atomics) and
+// O_j = sum_n beta^n c^n_e for its outlet dofs.  The sweep stores w_e lam_e beside lam_e so that a neighbour reads the
+// product instead of dividing.  One thread per (dof, column) then assembles u_bar.
+
+// step s from src to dst; cfin (may be NULL) receives the state after a column's last step
+template <int W, bool kOutlet>
+__global__ __launch_bounds__(kTransportThreads) void transport_step_to_kernel(TransportView v, int nb, int s, const double* __restrict__ u,
+                                                                              int64_t stride_face, int64_t stride_batch,
+                                                                              const double* __restrict__ dtcol,
+                                                                              const int32_t* __restrict__ ncol,
+                                                                              const double* __restrict__ src, double* __restrict__ dst,
+                                                                              double* __restrict__ acc, double* __restrict__ snap,
+                                                                              double* __restrict__ cfin) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned e = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (e >= (unsigned)v.n_elem) return;
+    const int nsteps = ncol[b];
+    if (s >= nsteps) return;
+    const double c1 = step_value<W, kOutlet>(v, nb, s, nsteps, gid, e, b, u + (int64_t)b * stride_batch, stride_face, dtcol[b], src, acc, snap);
+    dst[gid] = c1;
+    if (cfin && s == nsteps - 1) cfin[gid] = c1;
+}
+
+// beta[n * nb + b] = dt sum_{r: n_r > n} curve_bar[b][r] + sum_{r: n_r == n} tau_r curve_bar[b][r], r ascending in both sums
+__global__ __launch_bounds__(kTransportThreads) void transport_beta_kernel(int nb, int nreport, int longest, const int32_t* __restrict__ ncol,
+                                                                           const double* __restrict__ dtcol,
+                                                                           const double* __restrict__ curve_bar, double* __restrict__ beta) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned n = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (n >= (unsigned)longest) return;
+    const int64_t R = nreport, N = ncol[b];
+    if (!curve_bar || (int64_t)n >= N) {
+        beta[gid] = 0.0;
+        return;
+    }
+    const double dt = dtcol[b];
+    const double* cb = curve_bar + (size_t)b * nreport;
+    double s1 = 0.0;
+    for (int64_t r = 1; r <= R; ++r) {
+        const int64_t at = (r * N) / R, nr = at < N - 1 ? at : N - 1;
+        if (nr > (int64_t)n) s1 += cb[r - 1];
+    }
+    double be = dt * s1;
+    for (int64_t r = 1; r <= R; ++r) {
+        const int64_t at = (r * N) / R, nr = at < N - 1 ? at : N - 1;
+        if (nr == (int64_t)n) be += (((double)(r * N - nr * R) / (double)R) * dt) * cb[r - 1];
+    }
+    beta[gid] = be;
+}
+
+// lam^N_e = stored_bar wgt_e + c_bar_e and w_e lam^N_e into both buffers of the pair: a column's first sweep step n = N - 1
+// reads the buffer (n + 1) & 1, whatever its N.  stored_bar (nb) and c_bar (nb x n_elem) may be NULL: zero.
+__global__ __launch_bounds__(kTransportThreads) void transport_adjoint_init_kernel(TransportView v, int nb, const double* __restrict__ dtcol,
+                                                                                   const double* __restrict__ stored_bar,
+                                                                                   const double* __restrict__ c_bar, double* __restrict__ lam,
+                                                                                   double* __restrict__ wlam) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned e = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (e >= (unsigned)v.n_elem) return;
+    const size_t len = (size_t)v.n_elem * nb;
+    const double sb = stored_bar ? stored_bar[b] : 0.0;
+    const double cb = c_bar ? c_bar[(size_t)b * v.n_elem + e] : 0.0;
+    const double l = sb * v.wgt[e] + cb;
+    const double wl = (dtcol[b] / v.vol[e]) * l;
+    lam[gid] = l;
+    lam[len + gid] = l;
+    wlam[gid] = wl;
+    wlam[len + gid] = wl;
+}
+
+// sweep step n of every column that has one: c holds c^n, (lam1, wlam1) the pair of step n + 1, (lam0, wlam0) receives step n
+template <int W>
+__global__ __launch_bounds__(kTransportThreads) void transport_adjoint_step_kernel(
+    TransportView v, int nb, int n, const double* __restrict__ u, int64_t stride_face, int64_t stride_batch,
+    const double* __restrict__ dtcol, const int32_t* __restrict__ ncol, const double* __restrict__ beta, const double* __restrict__ c,
+    const double* __restrict__ lam1, const double* __restrict__ wlam1, double* __restrict__ lam0, double* __restrict__ wlam0,
+    double* __restrict__ P, double* __restrict__ X, double* __restrict__ O, uint8_t* __restrict__ sig) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned e = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (e >= (unsigned)v.n_elem) return;
+    if (n >= ncol[b]) return;
+    const double* ub = u + (int64_t)b * stride_batch;
+    const double w = dtcol[b] / v.vol[e];
+    const double ce = c[gid], l1 = lam1[gid], bn = beta[(size_t)n * nb + b];
+    double out = 0.0, in = 0.0, sacc = 0.0;
+    for_row<W>(v, (int)e, [&](int32_t enc, int32_t nbr) {
+        const double g = outward(v, ub, stride_face, enc);
+        const double go = fmax(g, 0.0), gi = fmax(-g, 0.0);
+        out += go;
+        in += gi;
+        double y = 0.0;
+        if (nbr >= 0) {
+            y = wlam1[(size_t)nbr * nb + b];
+        } else if (nbr <= -2) {
+            const size_t jb = (size_t)(-2 - nbr) * nb + b;
+            y = bn;
+            O[jb] += bn * ce;
+        }
+        sacc += go * y;
+        if (g < 0.0) {
+            const int f = dof_id(enc);
+            const double cn = nbr >= 0 ? c[(size_t)nbr * nb + b] : v.cin[f];
+            X[(size_t)f * nb + b] += cn * l1;
+        }
+    });
+    const double r = fmax(out, in);
+    const double d = 1.0 - w * r;
+    const double l0 = d * l1 + sacc;
+    lam0[gid] = l0;
+    wlam0[gid] = w * l0;
+    P[gid] += ce * l1;
+    if (n == 0) sig[gid] = out >= in ? 1 : 0;
+}
+
+// u_bar of dof f, column b, written to ubar[f * stride_face_out + b * stride_batch_out]; side: per dof the element of its
+// first entry and of its second (INT32_MIN: none), ~e where B[e, f] < 0, and its outlet index or -1.  Zero for a column
+// that was not differentiated (ncol 0).
+__global__ __launch_bounds__(kTransportThreads) void transport_adjoint_assemble_kernel(
+    TransportView v, int n_face, const int32_t* __restrict__ side, int nb, const double* __restrict__ u, int64_t stride_face,
+    int64_t stride_batch, const double* __restrict__ dtcol, const int32_t* __restrict__ ncol, const double* __restrict__ P,
+    const double* __restrict__ X, const double* __restrict__ O, const uint8_t* __restrict__ sig, double* __restrict__ ubar,
+    int64_t stride_face_out, int64_t stride_batch_out) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned f = gid / (unsigned)nb, b = gid % (unsigned)nb;
+    if (f >= (unsigned)n_face) return;
+    double* dst = ubar + (int64_t)f * stride_face_out + (int64_t)b * stride_batch_out;
+    if (ncol[b] == 0) {
+        *dst = 0.0;
+        return;
+    }
+    const double af = v.a[f];
+    const double gf = af * u[(int64_t)b * stride_batch + (int64_t)f * stride_face];
+    const double dt = dtcol[b];
+    const int j = side[3 * (size_t)f + 2];
+    double sum = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const int32_t enc = side[3 * (size_t)f + k];
+        if (enc == INT32_MIN) break;
+        const bool neg = enc < 0;
+        const size_t eb = (size_t)(neg ? ~enc : enc) * nb + b;
+        const double g = neg ? -gf : gf;
+        const double w = dt / v.vol[neg ? ~enc : enc];
+        const double t1 = w * P[eb];
+        const bool sg = sig[eb] != 0;
+        double G = 0.0;
+        if (g > 0.0 && sg) G = -t1;
+        else if (g < 0.0 && !sg) G = t1;
+        if (g < 0.0) G = G - w * X[gid];
+        if (j >= 0 && g > 0.0) G = G + O[(size_t)j * nb + b];
+        sum += neg ? -G : G;
+    }
+    *dst = af * sum;
+}
+
+// c0_bar[b][e] = lam^0, zero for a column that was not differentiated
+__global__ __launch_bounds__(kTransportThreads) void transport_adjoint_c0_kernel(int n_elem, int nb, const int32_t* __restrict__ ncol,
+                                                                                 const double* __restrict__ lam, double* __restrict__ c0_bar) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    const unsigned b = gid / (unsigned)n_elem, e = gid % (unsigned)n_elem;
+    if (b >= (unsigned)nb) return;
+    c0_bar[gid] = ncol[b] ? lam[(size_t)e * nb + b] : 0.0;
+}
+
+// curve_bar[b][r] = -(curve[b][r] - data[r]) / noise: the seed of loglik = -|curve - data|^2 / (2 noise)
+__global__ __launch_bounds__(kTransportThreads) void transport_loglik_seed_kernel(int nb, int nreport, const double* __restrict__ curve,
+                                                                                  const double* __restrict__ data, double noise,
+                                                                                  double* __restrict__ curve_bar) {
+    const unsigned gid = blockIdx.x * kTransportThreads + threadIdx.x;
+    if (gid >= (unsigned)nb * (unsigned)nreport) return;
+    curve_bar[gid] = -(curve[gid] - data[gid % (unsigned)nreport]) / noise;
 }
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + kTransportThreads - 1) / kTransportThreads); }
@@ -279,12 +468,21 @@ Transport::Transport(Ctx& c, const pmc_transport_mesh& m, const pmc_transport_pa
             rec_h[at_nbr] = other;
         }
     nnz_ = nnz;
+    // per dof for the adjoint's assembly: its elements in ascending order (~e where B[e, f] < 0) and its outlet index
+    std::vector<int32_t> side_h(3 * (size_t)n_face);
+    for (int f = 0; f < n_face; ++f) {
+        const auto enc_of = [&](int32_t q) { return m.val[q] > 0.0 ? row_of[q] : ~row_of[q]; };
+        side_h[3 * (size_t)f] = enc_of(first[f]);
+        side_h[3 * (size_t)f + 1] = second[f] >= 0 ? enc_of(second[f]) : INT32_MIN;
+        side_h[3 * (size_t)f + 2] = outlet_of[f];
+    }
     std::vector<double> c0_h(n_elem, 0.0);
     if (m.c0) std::copy(m.c0, m.c0 + n_elem, c0_h.begin());
     const double* wsrc = m.weight ? m.weight : m.pore_volume;
     ctx.activate();
     hipStream_t st = ctx.stream;
     rec.upload(rec_h, st);
+    side.upload(side_h, st);
     rowptr.upload(m.rowptr, (size_t)n_elem + 1, st);
     a.upload(a_h, st);
     cin.upload(cin_h, st);
@@ -294,35 +492,24 @@ Transport::Transport(Ctx& c, const pmc_transport_mesh& m, const pmc_transport_pa
     PMC_HIP(hipStreamSynchronize(st));
 }
 
-// the whole computation for nb columns on stream st; the results stay in cbuf / curve_d / stored_d and the h_* vectors
-void Transport::compute(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
-                        double* stored_d, int kind, double* q_d) {
-    PMC_REQUIRE((int64_t)n_elem * nb < (int64_t(1) << 31), "pmc_transport: n_elem x nbatch of one launch must stay below 2^31");
-    const size_t len = (size_t)n_elem * nb;
-    cbuf.ensure(2 * len);
-    acc.ensure((size_t)std::max(n_outlet, 1) * nb);
-    snap.ensure((size_t)nreport * std::max(n_outlet, 1) * nb);
-    col_rate.ensure(nb);
-    col_dt.ensure(nb);
-    col_steps.ensure(nb);
-    const TransportView v{n_elem, n_outlet, nreport, nnz_, rec.p, rowptr.p, a.p, cin.p, vol.p, c0.p, wgt.p};
-    const unsigned grid = blocks_for(len);
-    auto by_width = [&](auto&& launch) {
-        switch (width) {
-            case 3: launch(std::integral_constant<int, 3>{}); break;
-            case 4: launch(std::integral_constant<int, 4>{}); break;
-            case 6: launch(std::integral_constant<int, 6>{}); break;
-            default: launch(std::integral_constant<int, 0>{}); break;
-        }
-        PMC_HIP(hipGetLastError());
-        count_kernel_launches(1);
-    };
-    // c = c0 into buffer 0, r_e / V_e into buffer 1 (which step 0 overwrites), their maximum per column
-    by_width([&](auto W) {
-        transport_rates_kernel<decltype(W)::value><<<grid, kTransportThreads, 0, st>>>(v, nb, u_d, stride_face, stride_batch, cbuf.p,
-                                                                                       cbuf.p + len);
-    });
-    transport_rate_max_kernel<<<(unsigned)nb, kTransportThreads, 0, st>>>(n_elem, nb, cbuf.p + len, col_rate.p);
+// one launch of a kernel templated on the row form: launch(std::integral_constant<int, W>) with W = 3 | 4 | 6 for the register
+// forms, 0 for the general form
+template <class F>
+void Transport::by_width(F&& launch) const {
+    switch (width) {
+        case 3: launch(std::integral_constant<int, 3>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 6: launch(std::integral_constant<int, 6>{}); break;
+        default: launch(std::integral_constant<int, 0>{}); break;
+    }
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+}
+
+// rate[b] = max_e q[e * nb + b] and from it, on the host, the step count, step size and status of every column (h_*), uploaded
+// into col_dt / col_steps.  Returns the largest step count.
+int Transport::plan_columns(hipStream_t st, int nb, const double* q_d) {
+    transport_rate_max_kernel<<<(unsigned)nb, kTransportThreads, 0, st>>>(n_elem, nb, q_d, col_rate.p);
     PMC_HIP(hipGetLastError());
     count_kernel_launches(1);
     h_rate.resize(nb);
@@ -359,12 +546,34 @@ void Transport::compute(hipStream_t st, int nb, const double* u_d, int64_t strid
     }
     col_dt.upload(h_dt, st);
     col_steps.upload(h_steps, st);
+    return longest;
+}
+
+// the whole computation for nb columns on stream st; the results stay in cbuf / curve_d / stored_d and the h_* vectors
+void Transport::compute(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
+                        double* stored_d, int kind, double* q_d) {
+    PMC_REQUIRE((int64_t)n_elem * nb < (int64_t(1) << 31), "pmc_transport: n_elem x nbatch of one launch must stay below 2^31");
+    const size_t len = (size_t)n_elem * nb;
+    cbuf.ensure(2 * len);
+    acc.ensure((size_t)std::max(n_outlet, 1) * nb);
+    snap.ensure((size_t)nreport * std::max(n_outlet, 1) * nb);
+    col_rate.ensure(nb);
+    col_dt.ensure(nb);
+    col_steps.ensure(nb);
+    const TransportView v{n_elem, n_outlet, nreport, nnz_, rec.p, rowptr.p, a.p, cin.p, vol.p, c0.p, wgt.p};
+    const unsigned grid = blocks_for(len);
+    // c = c0 into buffer 0, r_e / V_e into buffer 1 (which step 0 overwrites), their maximum per column
+    by_width([&](auto W) {
+        transport_rates_kernel<decltype(W)::value><<<grid, kTransportThreads, 0, st>>>(v, nb, u_d, stride_face, stride_batch, cbuf.p,
+                                                                                       cbuf.p + len);
+    });
+    const int longest = plan_columns(st, nb, cbuf.p + len);
     for (int s = 0; s < longest; ++s)
         by_width([&](auto W) {
             transport_step_kernel<decltype(W)::value><<<grid, kTransportThreads, 0, st>>>(v, nb, s, u_d, stride_face, stride_batch, col_dt.p,
                                                                                           col_steps.p, cbuf.p, acc.p, snap.p);
         });
-    transport_finish_kernel<<<dim3((unsigned)nreport + 1, (unsigned)nb), kTransportThreads, 0, st>>>(v, nb, col_steps.p, cbuf.p, snap.p,
+    transport_finish_kernel<<<dim3((unsigned)nreport + 1, (unsigned)nb), kTransportThreads, 0, st>>>(v, nb, col_steps.p, cbuf.p, len, snap.p,
                                                                                                       curve_d, stored_d, kind, q_d);
     PMC_HIP(hipGetLastError());
     count_kernel_launches(1);
@@ -415,6 +624,197 @@ void Transport::run(int nbatch, const double* u, int64_t ld, double* c_out, doub
         PMC_HIP(hipMemcpyAsync(rate + b0, h_rate.data(), sizeof(double) * n, scal, st));
         PMC_HIP(hipMemcpyAsync(t_reached + b0, h_treached.data(), sizeof(double) * n, scal, st));
         PMC_HIP(hipMemcpyAsync(nsteps + b0, h_steps.data(), sizeof(int32_t) * n, scal, st));
+        PMC_HIP(hipMemcpyAsync(status + b0, h_status.data(), sizeof(int32_t) * n, scal, st));
+        PMC_HIP(hipStreamSynchronize(st));
+    }
+}
+
+void Transport::set_adjoint_segment(int K) {
+    PMC_REQUIRE(K >= 0, "pmc_transport_set_adjoint_segment: K must not be negative");
+    adj_segment = K;
+}
+
+// plan, then the forward pass: state s of the pass lives in checkpoint s / K where K divides s (and the sweep will want it),
+// else in a pair of buffers by parity; every column's final state is copied to adj_fin by the thread that forms it
+void Transport::adjoint_forward(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch, double* curve_d,
+                                double* stored_d) {
+    PMC_REQUIRE((int64_t)std::max(n_elem, n_face) * nb < (int64_t(1) << 31),
+                "pmc_transport: n_elem x nbatch and n_face x nbatch of one launch must stay below 2^31");
+    const size_t len = (size_t)n_elem * nb;
+    adj_tmp.ensure(2 * len);
+    adj_fin.ensure(len);
+    acc.ensure((size_t)std::max(n_outlet, 1) * nb);
+    snap.ensure((size_t)nreport * std::max(n_outlet, 1) * nb);
+    col_rate.ensure(nb);
+    col_dt.ensure(nb);
+    col_steps.ensure(nb);
+    const TransportView v{n_elem, n_outlet, nreport, nnz_, rec.p, rowptr.p, a.p, cin.p, vol.p, c0.p, wgt.p};
+    const unsigned grid = blocks_for(len);
+    // c^0 into the final states (a column without a step ends there), r_e / V_e into the pair
+    by_width([&](auto W) {
+        transport_rates_kernel<decltype(W)::value><<<grid, kTransportThreads, 0, st>>>(v, nb, u_d, stride_face, stride_batch, adj_fin.p,
+                                                                                       adj_tmp.p);
+    });
+    adj_longest_fwd = plan_columns(st, nb, adj_tmp.p);
+    // only columns whose status is OK are differentiated: the others take no part in the recomputation and the sweep
+    h_steps_adj.resize(nb);
+    adj_longest = 0;
+    for (int b = 0; b < nb; ++b) {
+        h_steps_adj[b] = h_status[b] == PMC_TRANSPORT_OK ? h_steps[b] : 0;
+        adj_longest = std::max(adj_longest, h_steps_adj[b]);
+    }
+    col_steps_adj.upload(h_steps_adj, st);
+    adj_K = adj_segment ? adj_segment : (int)std::ceil(std::sqrt((double)adj_longest));
+    adj_K = std::max(1, std::min(adj_K, std::max(adj_longest, 1)));
+    while ((int64_t)adj_K * adj_K < adj_longest && !adj_segment) ++adj_K;
+    adj_nck = std::max(1, (adj_longest + adj_K - 1) / adj_K);
+    adj_ck.ensure((size_t)adj_nck * len);
+    PMC_HIP(hipMemcpyAsync(adj_ck.p, adj_fin.p, sizeof(double) * len, hipMemcpyDeviceToDevice, st));
+    auto loc = [&](int s) {
+        return (s % adj_K == 0 && s / adj_K < adj_nck) ? adj_ck.p + (size_t)(s / adj_K) * len : adj_tmp.p + (size_t)(s & 1) * len;
+    };
+    for (int s = 0; s < adj_longest_fwd; ++s)
+        by_width([&](auto W) {
+            transport_step_to_kernel<decltype(W)::value, true><<<grid, kTransportThreads, 0, st>>>(
+                v, nb, s, u_d, stride_face, stride_batch, col_dt.p, col_steps.p, loc(s), loc(s + 1), acc.p, snap.p, adj_fin.p);
+        });
+    transport_finish_kernel<<<dim3((unsigned)nreport + 1, (unsigned)nb), kTransportThreads, 0, st>>>(v, nb, col_steps.p, adj_fin.p, 0, snap.p,
+                                                                                                      curve_d, stored_d, 0, nullptr);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+}
+
+void Transport::adjoint_backward(hipStream_t st, int nb, const double* u_d, int64_t stride_face, int64_t stride_batch,
+                                 const double* curve_bar_d, const double* stored_bar_d, const double* c_bar_d, double* ubar_d,
+                                 int64_t stride_face_out, int64_t stride_batch_out, double* c0_bar_d) {
+    const size_t len = (size_t)n_elem * nb, flen = (size_t)n_face * nb, olen = (size_t)std::max(n_outlet, 1) * nb;
+    const int K = adj_K, N = adj_longest;
+    adj_seg.ensure((size_t)std::max(K - 1, 1) * len);
+    adj_lam.ensure(2 * len);
+    adj_wlam.ensure(2 * len);
+    adj_beta.ensure((size_t)std::max(N, 1) * nb);
+    adj_P.ensure(len);
+    adj_X.ensure(flen);
+    adj_O.ensure(olen);
+    adj_sig.ensure(len);
+    const TransportView v{n_elem, n_outlet, nreport, nnz_, rec.p, rowptr.p, a.p, cin.p, vol.p, c0.p, wgt.p};
+    const unsigned grid = blocks_for(len);
+    PMC_HIP(hipMemsetAsync(adj_P.p, 0, sizeof(double) * len, st));
+    PMC_HIP(hipMemsetAsync(adj_X.p, 0, sizeof(double) * flen, st));
+    PMC_HIP(hipMemsetAsync(adj_O.p, 0, sizeof(double) * olen, st));
+    PMC_HIP(hipMemsetAsync(adj_sig.p, 0, len, st));
+    if (N > 0) {
+        transport_beta_kernel<<<blocks_for((size_t)N * nb), kTransportThreads, 0, st>>>(nb, nreport, N, col_steps_adj.p, col_dt.p, curve_bar_d,
+                                                                                        adj_beta.p);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
+    }
+    transport_adjoint_init_kernel<<<grid, kTransportThreads, 0, st>>>(v, nb, col_dt.p, stored_bar_d, c_bar_d, adj_lam.p, adj_wlam.p);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    for (int i = adj_nck - 1; i >= 0 && N > 0; --i) {
+        const int n0 = i * K, n1 = std::min(n0 + K, N);
+        auto state = [&](int n) { return n == n0 ? adj_ck.p + (size_t)i * len : adj_seg.p + (size_t)(n - n0 - 1) * len; };
+        // the states n0 + 1 .. n1 - 1 of the segment, with the forward bits
+        for (int n = n0; n + 1 < n1; ++n)
+            by_width([&](auto W) {
+                transport_step_to_kernel<decltype(W)::value, false><<<grid, kTransportThreads, 0, st>>>(
+                    v, nb, n, u_d, stride_face, stride_batch, col_dt.p, col_steps_adj.p, state(n), state(n + 1), nullptr, nullptr, nullptr);
+            });
+        for (int n = n1 - 1; n >= n0; --n) {
+            const size_t from = (size_t)((n + 1) & 1) * len, to = (size_t)(n & 1) * len;
+            by_width([&](auto W) {
+                transport_adjoint_step_kernel<decltype(W)::value><<<grid, kTransportThreads, 0, st>>>(
+                    v, nb, n, u_d, stride_face, stride_batch, col_dt.p, col_steps_adj.p, adj_beta.p, state(n), adj_lam.p + from,
+                    adj_wlam.p + from, adj_lam.p + to, adj_wlam.p + to, adj_P.p, adj_X.p, adj_O.p, adj_sig.p);
+            });
+        }
+    }
+    transport_adjoint_assemble_kernel<<<blocks_for(flen), kTransportThreads, 0, st>>>(
+        v, n_face, side.p, nb, u_d, stride_face, stride_batch, col_dt.p, col_steps_adj.p, adj_P.p, adj_X.p, adj_O.p, adj_sig.p, ubar_d,
+        stride_face_out, stride_batch_out);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    if (c0_bar_d) {
+        transport_adjoint_c0_kernel<<<grid, kTransportThreads, 0, st>>>(n_elem, nb, col_steps_adj.p, adj_lam.p, c0_bar_d);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
+    }
+}
+
+const double* Transport::loglik_seed(hipStream_t st, int nb, const double* curve_d, const double* data_d, double noise) {
+    seed_cb.ensure((size_t)nb * nreport);
+    transport_loglik_seed_kernel<<<blocks_for((size_t)nb * nreport), kTransportThreads, 0, st>>>(nb, nreport, curve_d, data_d, noise,
+                                                                                                 seed_cb.p);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    return seed_cb.p;
+}
+
+void Transport::run_adjoint(int nbatch, const double* u, int64_t ld, const double* curve_bar, const double* stored_bar,
+                            const double* c_bar, double* u_bar, int64_t ld_bar, double* c0_bar, double* curve, double* stored,
+                            int32_t* nsteps, int32_t* status, int memspace) {
+    PMC_REQUIRE(nbatch >= 1, "pmc_transport_run_adjoint: nbatch must be at least 1");
+    PMC_REQUIRE(u && u_bar && status, "pmc_transport_run_adjoint: NULL array");
+    PMC_REQUIRE(curve_bar || stored_bar || c_bar, "pmc_transport_run_adjoint: at least one of curve_bar, stored_bar and c_bar must be given");
+    PMC_REQUIRE(ld >= n_face && ld_bar >= n_face, "pmc_transport_run_adjoint: ld or ld_bar is smaller than the number of flux dofs");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "pmc_transport_run_adjoint: bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const bool host = memspace == PMC_MEM_HOST;
+    const int per = (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t(1) << 24) / std::max(n_face, n_elem)));
+    out_curve.ensure((size_t)per * nreport);
+    out_stored.ensure(per);
+    if (host) {
+        stage_u.ensure((size_t)per * n_face);
+        stage_ubar.ensure((size_t)per * n_face);
+        if (curve_bar) stage_cb.ensure((size_t)per * nreport);
+        if (stored_bar) stage_sb.ensure(per);
+        if (c_bar) stage_eb.ensure((size_t)per * n_elem);
+        if (c0_bar) stage_c0bar.ensure((size_t)per * n_elem);
+    }
+    const hipMemcpyKind scal = host ? hipMemcpyHostToHost : hipMemcpyHostToDevice;
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (int b0 = 0; b0 < nbatch; b0 += per) {
+        const int n = std::min(per, nbatch - b0);
+        const double* u_d = u + (size_t)b0 * ld;
+        const double* cb_d = curve_bar ? curve_bar + (size_t)b0 * nreport : nullptr;
+        const double* sb_d = stored_bar ? stored_bar + b0 : nullptr;
+        const double* eb_d = c_bar ? c_bar + (size_t)b0 * n_elem : nullptr;
+        double* ubar_d = u_bar + (size_t)b0 * ld_bar;
+        double* c0bar_d = c0_bar ? c0_bar + (size_t)b0 * n_elem : nullptr;
+        int64_t stride_batch = ld, stride_out = ld_bar;
+        if (host) {
+            PMC_HIP(hipMemcpy2DAsync(stage_u.p, sizeof(double) * n_face, u_d, sizeof(double) * ld, sizeof(double) * n_face, n,
+                                     hipMemcpyHostToDevice, st));
+            u_d = stage_u.p;
+            stride_batch = n_face;
+            if (cb_d) {
+                PMC_HIP(hipMemcpyAsync(stage_cb.p, cb_d, sizeof(double) * n * nreport, hipMemcpyHostToDevice, st));
+                cb_d = stage_cb.p;
+            }
+            if (sb_d) {
+                PMC_HIP(hipMemcpyAsync(stage_sb.p, sb_d, sizeof(double) * n, hipMemcpyHostToDevice, st));
+                sb_d = stage_sb.p;
+            }
+            if (eb_d) {
+                PMC_HIP(hipMemcpyAsync(stage_eb.p, eb_d, sizeof(double) * n * n_elem, hipMemcpyHostToDevice, st));
+                eb_d = stage_eb.p;
+            }
+            ubar_d = stage_ubar.p;
+            stride_out = n_face;
+            if (c0bar_d) c0bar_d = stage_c0bar.p;
+        }
+        adjoint_forward(st, n, u_d, 1, stride_batch, out_curve.p, out_stored.p);
+        adjoint_backward(st, n, u_d, 1, stride_batch, cb_d, sb_d, eb_d, ubar_d, 1, stride_out, c0bar_d);
+        if (host) {
+            PMC_HIP(hipMemcpy2DAsync(u_bar + (size_t)b0 * ld_bar, sizeof(double) * ld_bar, stage_ubar.p, sizeof(double) * n_face,
+                                     sizeof(double) * n_face, n, hipMemcpyDeviceToHost, st));
+            if (c0_bar) PMC_HIP(hipMemcpyAsync(c0_bar + (size_t)b0 * n_elem, stage_c0bar.p, sizeof(double) * n * n_elem, hipMemcpyDeviceToHost, st));
+        }
+        if (curve) PMC_HIP(hipMemcpyAsync(curve + (size_t)b0 * nreport, out_curve.p, sizeof(double) * n * nreport, back, st));
+        if (stored) PMC_HIP(hipMemcpyAsync(stored + b0, out_stored.p, sizeof(double) * n, back, st));
+        if (nsteps) PMC_HIP(hipMemcpyAsync(nsteps + b0, h_steps.data(), sizeof(int32_t) * n, scal, st));
         PMC_HIP(hipMemcpyAsync(status + b0, h_status.data(), sizeof(int32_t) * n, scal, st));
         PMC_HIP(hipStreamSynchronize(st));
     }

@@ -18,3 +18,4 @@ from .kl import (KLLevel, KLProblem, analytic_exponential_eigs, build_kl_sampler
 from .output import (compute_l2_error, compute_max_error, prolongate_to_fine_grid, read_gridfunction_p0,  # noqa: F401
                      save_field_glvis, save_mesh_glvis, write_mfem_mesh)
 from .statistics import chi_center_of_mass, restrict_chi  # noqa: F401
+from .transport import advance_adjoint, advance_tangent  # noqa: F401

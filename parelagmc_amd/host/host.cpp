@@ -272,6 +272,17 @@ void SoluteTransport::Run(const Vector& u, double* c_out, double* curve, double*
 void SoluteTransport::Reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace) {
     check_arg(pmc_transport_reduce(h_, nbatch, curve, stored, kind, Q, memspace), "SoluteTransport::Reduce");
 }
+void SoluteTransport::RunAdjoint(const Vector& u, const double* curve_bar, const double* stored_bar, const double* c_bar, Vector& u_bar,
+                                 double* c0_bar, double* curve, double* stored, int32_t* nsteps, int32_t* status) {
+    if (u_bar.MemSpace() != u.MemSpace()) throw std::invalid_argument("SoluteTransport::RunAdjoint: u and u_bar must share a memory space");
+    u_bar.SetSize(u.Size(), u.Batch());
+    check_arg(pmc_transport_run_adjoint(h_, u.Batch(), u.GetData(), u.Size(), curve_bar, stored_bar, c_bar, u_bar.GetData(), u.Size(),
+                                        c0_bar, curve, stored, nsteps, status, u.MemSpace()),
+              "SoluteTransport::RunAdjoint");
+}
+void SoluteTransport::SetAdjointSegment(int K) {
+    check_arg(pmc_transport_set_adjoint_segment(h_, K), "SoluteTransport::SetAdjointSegment");
+}
 
 // ---- DarcySolver ------------------------------------------------------------------------------
 void DarcySolver::SetTransport(int ilevel, SoluteTransport* transport, int kind) {
@@ -307,6 +318,34 @@ void DarcySolver::SolveFwd_Gradient(int ilevel, Vector& k, double* Q, double* C,
                                    nullptr, k.MemSpace(), st.data(), sta.data()),
           "DarcySolver::SolveFwd_Gradient");
     record(ilevel, st);
+    record(ilevel, sta);
+}
+void DarcySolver::SolveFwd_TransportGradient(int ilevel, SoluteTransport& transport, Vector& k, const double* curve_bar,
+                                             const double* stored_bar, double* curve, double* stored, int32_t* status, Vector& grad,
+                                             bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::SolveFwd_TransportGradient: level");
+    if (grad.MemSpace() != k.MemSpace())
+        throw std::invalid_argument("SolveFwd_TransportGradient: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    std::vector<pmc_stats> st(k.Batch()), sta(k.Batch());
+    check(pmc_darcy_transport_gradient(h_, ilevel, transport.Handle(), k.Batch(), k.GetData(), curve_bar, stored_bar, wrt_log ? 1 : 0,
+                                       curve, stored, status, grad.GetData(), nullptr, nullptr, k.MemSpace(), st.data(), sta.data()),
+          "DarcySolver::SolveFwd_TransportGradient");
+    record(ilevel, st);
+    record(ilevel, sta);
+}
+void DarcySolver::ComputeGradTransportLogLikelihood(int ilevel, SoluteTransport& transport, Vector& k, const double* data, double noise,
+                                                    double* loglik, double* curve, int32_t* status, Vector& grad, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::ComputeGradTransportLogLikelihood: level");
+    if (grad.MemSpace() != k.MemSpace())
+        throw std::invalid_argument("ComputeGradTransportLogLikelihood: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    std::vector<pmc_stats> sta(k.Batch());
+    check(pmc_darcy_transport_loglik_gradient(h_, ilevel, transport.Handle(), k.Batch(), k.GetData(), data, noise, wrt_log ? 1 : 0,
+                                              loglik, curve, status, grad.GetData(), k.MemSpace(), sta.data()),
+          "DarcySolver::ComputeGradTransportLogLikelihood");
     record(ilevel, sta);
 }
 void DarcySolver::SolveFwd_GNHessVec(int ilevel, Vector& k, const Vector& dk, double noise, Vector& x, bool x_given, Vector& hv,

@@ -307,6 +307,14 @@ class SoluteTransport {
              int32_t* status);
     /// Q (host, nbatch): curve[.][NumReports() - 1] (PMC_TRANSPORT_MASS_OUT) or stored (PMC_TRANSPORT_STORED)
     void Reduce(int nbatch, const double* curve, const double* stored, int kind, double* Q, int memspace);
+    /// The discrete adjoint (pmc_transport_run_adjoint): u_bar = dJ/du and c0_bar = dJ/dc0 (may be NULL) of
+    /// J = <curve_bar, curve> + stored_bar stored + <c_bar, c> per realization.  Seeds (each may be NULL, not all) and outputs in
+    /// u's memory space; u_bar is sized to u.Size() x u.Batch() and only the first NumFluxDofs() entries of a row are written.
+    /// curve, stored, nsteps may be NULL; status may not.
+    void RunAdjoint(const Vector& u, const double* curve_bar, const double* stored_bar, const double* c_bar, Vector& u_bar,
+                    double* c0_bar, double* curve, double* stored, int32_t* nsteps, int32_t* status);
+    /// steps between two kept states of RunAdjoint; 0: automatic.  The results do not depend on it.
+    void SetAdjointSegment(int K);
     pmc_transport* Handle() const { return h_; }
 
   private:
@@ -332,6 +340,19 @@ class DarcySolver : public PhysicalMLSolver {
     /// GetSizeOfStochasticData(ilevel) x k.Batch() in k's memory space (pmc_darcy_solve_gradient; an extension, the
     /// reference has no gradients).  Q, C: host arrays of k.Batch(), may be NULL.
     void SolveFwd_Gradient(int ilevel, Vector& k_over_k_ref, double* Q, double* C, Vector& grad, bool wrt_log = false);
+    /// Forward solve plus the gradient in k (wrt_log: in log k) of J = <curve_bar, curve> + stored_bar stored of `transport` on
+    /// the solution's flux (pmc_darcy_transport_gradient; an extension).  The transport is given with the call: what
+    /// SetTransport / SetTracer attached is neither read nor changed.  curve_bar (k.Batch() x NumReports()), stored_bar
+    /// (k.Batch()), one of them may be NULL, and the outputs curve, stored (may be NULL) in k's memory space; status: host,
+    /// k.Batch().  grad is sized like k.
+    void SolveFwd_TransportGradient(int ilevel, SoluteTransport& transport, Vector& k_over_k_ref, const double* curve_bar,
+                                    const double* stored_bar, double* curve, double* stored, int32_t* status, Vector& grad,
+                                    bool wrt_log = false);
+    /// loglik = -|curve - data|^2 / (2 noise) of the breakthrough curve of `transport` and its gradient in k
+    /// (pmc_darcy_transport_loglik_gradient).  data: host, NumReports(); loglik, curve (may be NULL) and status: host.
+    void ComputeGradTransportLogLikelihood(int ilevel, SoluteTransport& transport, Vector& k_over_k_ref, const double* data,
+                                           double noise, double* loglik, double* curve, int32_t* status, Vector& grad,
+                                           bool wrt_log = false);
     /// Gauss-Newton Hessian action hv = J^T (1/noise) J dk of the negative log-likelihood of the handle's observation
     /// functionals, J = dG/dk (wrt_log: in log k), for every realization (pmc_darcy_gn_hessvec; an extension).  x: the forward
     /// solutions, GetNumberOfDofs(ilevel) x k.Batch() - x_given false: solved inside and written to x; true: read, and no
