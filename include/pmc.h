@@ -50,7 +50,10 @@ typedef struct pmc_ctx pmc_ctx;
 typedef struct pmc_sampler pmc_sampler;
 typedef struct pmc_darcy pmc_darcy;
 
-/* CSR matrix, host pointers, sorted or unsorted column indices. */
+/* CSR matrix, host pointers, sorted or unsorted column indices.  The entries of a row may come in any order (ascending,
+ * the diagonal first, unordered) and may include stored zeros - an eliminated coupling left in the pattern, or an entry of
+ * M_pattern with an empty contribution list.  A column may appear only ONCE in a row: every call that takes a pmc_csr
+ * returns PMC_ERR_INVALID (-1) with a message naming the matrix and the row if one appears twice; sum duplicates first. */
 typedef struct pmc_csr {
     int32_t nrows, ncols;
     const int32_t* rowptr; /* nrows+1 */

@@ -20,7 +20,10 @@ class DarcyOracle:
         L = self.p.levels[level]
         c = (1.0 / k) if self.p.k_divides else k
         contrib = c[L.c_elem] * L.c_val
-        data = np.add.reduceat(contrib, L.c_ptr[:-1])
+        # a stored entry with an empty list (a structural zero of the caller's pattern) is 0; reduceat would not say so
+        full = np.flatnonzero(np.diff(L.c_ptr) > 0)
+        data = np.zeros(len(L.c_ptr) - 1)
+        data[full] = np.add.reduceat(contrib, L.c_ptr[:-1][full])
         return sp.csr_matrix((data, L.M_pattern.indices, L.M_pattern.indptr), shape=L.M_pattern.shape)
 
     def assemble(self, level, k):

@@ -107,7 +107,6 @@ ElementInverses element_inverses(const HostCsr& Mp, const HostCsr& B, const int3
     // (face a, face b) of the u-mass matrix
     const int m = nfe_max;
     std::vector<double> Me((size_t)ns * m * m, 0.0);
-    const int64_t nnzM = Mp.nnz();
     PMC_REQUIRE(c_ptr[0] == 0, w + ": c_ptr[0] != 0");
     // rows of M are independent of each other only per ELEMENT pair, and two rows may write the same element block (at
     // different (a, b)): writes never collide, so rows can be split over threads
@@ -129,7 +128,7 @@ ElementInverses element_inverses(const HostCsr& Mp, const HostCsr& B, const int3
                 }
             }
     });
-    PMC_REQUIRE(c_ptr[nnzM] >= nnzM, w + ": fewer contributions than stored entries");
+    // (a list may be empty: a stored zero of the caller's pattern)
     // local inverses
     ElementInverses out;
     out.m = m;

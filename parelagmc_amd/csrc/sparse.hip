@@ -25,6 +25,15 @@ HostCsr csr_from_c(const pmc_csr& c, bool need_vals, const char* what) {
     a.colind.assign(c.colind, c.colind + nnz);
     for (int64_t p = 0; p < nnz; ++p)
         PMC_REQUIRE(a.colind[p] >= 0 && a.colind[p] < c.ncols, std::string(what) + ": column index out of range");
+    // one stored entry per (row, column): the setup reads "the" entry of a position (the diagonal slot of a row, the
+    // single entry of an injection row, the contribution list of a mass entry), and a second one would be dropped silently
+    std::vector<int> seen_in(c.ncols, -1);
+    for (int i = 0; i < c.nrows; ++i)
+        for (int p = a.rowptr[i]; p < a.rowptr[i + 1]; ++p) {
+            PMC_REQUIRE(seen_in[a.colind[p]] != i, std::string(what) + ": a column index appears twice in row " +
+                                                       std::to_string(i) + " (sum duplicate entries before the call)");
+            seen_in[a.colind[p]] = i;
+        }
     if (need_vals) {
         PMC_REQUIRE(nnz == 0 || c.vals != nullptr, std::string(what) + ": vals is NULL");
         a.vals.assign(c.vals, c.vals + nnz);

@@ -93,7 +93,9 @@ def assemble(problem, level, k):
     L = problem.levels[level]
     k = np.asarray(k, dtype=np.float64)
     c = (1.0 / k) if problem.k_divides else k
-    data = np.add.reduceat(c[L.c_elem] * L.c_val, L.c_ptr[:-1])
+    full = np.flatnonzero(np.diff(L.c_ptr) > 0)                 # entries with an empty list are stored zeros
+    data = np.zeros(len(L.c_ptr) - 1)
+    data[full] = np.add.reduceat(c[L.c_elem] * L.c_val, L.c_ptr[:-1][full])
     M = sp.csr_matrix((data, L.M_pattern.indices, L.M_pattern.indptr), shape=L.M_pattern.shape)
     A = sp.bmat([[M, L.B.T], [L.B, None]], format="csr")
     n = L.n_u + L.n_p

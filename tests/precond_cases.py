@@ -61,13 +61,19 @@ def sampler_problem(name):
 
 
 class Handle:
-    """one sampler handle with what the tests read from it; **opts: solver options beyond the storage and mg_coarsening"""
+    """one sampler handle with what the tests read from it; **opts: solver options beyond the storage and mg_coarsening.
+    problem: the handle is created on this problem instead of the registered one of `name` (then only a label) - another
+    layout of it, say (test_gpu_input_layouts.py); mg_coarsening 0"""
 
-    def __init__(self, ctx, name, storage, **opts):
+    def __init__(self, ctx, name, storage, problem=None, **opts):
         from parelagmc_amd import capi
-        cfg = SOLVE_HANDLES[name]
+        if problem is None:
+            cfg = SOLVE_HANDLES[name]
+            self.prob = sampler_problem(name)
+        else:
+            cfg = dict(kind="hybrid" if hasattr(problem.levels[0], "n_lambda") else "saddle", coarsening=0)
+            self.prob = problem
         self.hybrid = cfg["kind"] == "hybrid"
-        self.prob = sampler_problem(name)
         st = capi.PMC_STORAGE_FP64 if storage == "fp64" else capi.PMC_STORAGE_FP32
         self.opts = capi.solver_opts(precond_storage=st, mg_coarsening=cfg["coarsening"], **opts)
         self.smp = capi.PDESampler(ctx, self.prob, self.opts)
