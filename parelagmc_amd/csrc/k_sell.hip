@@ -571,9 +571,38 @@ __global__ __launch_bounds__(kBlock, (vc_min_waves<NB, XT, BV, DEEP>())) void vc
 // SPL: rows stored in 2^sl pieces, see vc_poly2_kernel
 // CT: storage type of `coarse` (fp64, or fp32 with fp32 inter-level vectors: the fp64 sums are rounded once, on store)
 // TAG only names the instantiation: 1 = res - (S P) xc (in place), so that profiles show that pass on a row of its own
+// ROWS AHEAD (vc_rows_ahead: the 32-wide shared-value forms with an fp32 gathered vector and an fp32 r, not row-split, not
+// deep, no groups of 8 - the finest levels of a cycle): a wavefront handles one slice and its life was a chain - slice_off, the
+// first (index, value) pair, the gather columns, and only then the own rows of r in two batches of four row steps, two more
+// round trips with nothing else in flight.  The own rows depend on nothing the gather loop produces: they are requested BEFORE
+// the loop (rows past the end re-read the last row and store nothing) and pinned as one point of use behind it - all T row
+// steps (32 registers) in the plain forms, T / 2 ahead and T / 2 behind the loop with RAGG, where all T spill.  With RAGG the
+// slice's segment range and the lane group's first (position, coarse row) pair travel with them, so that behind the wave
+// barrier only LDS reads and the coarse store remain.  The in-place form (TAG 1, r == y) keeps every load of a slice ahead
+// of that slice's stores; a wavefront owns its rows.  Same operations in the same order (LAB_NOTES 10.32).
+#ifndef PMC_RES_ROWS_AHEAD
+#define PMC_RES_ROWS_AHEAD 1   // laboratory macro: 0 = the own rows behind the gather loop, as every other form reads them
+#endif
+#ifndef PMC_RES_SEG_AHEAD
+#define PMC_RES_SEG_AHEAD 1    // laboratory macro: 0 = the segment tables behind the wave barrier
+#endif
+template <int NB, typename XT, typename RT, bool R8, int BV, int DEEP, bool SPL>
+constexpr bool vc_rows_ahead() {
+    return PMC_RES_ROWS_AHEAD != 0 && NB == kGroup && sizeof(XT) == 4 && sizeof(RT) == 4 && !R8 && BV == 0 && DEEP == 1 && !SPL;
+}
+// (0: no occupancy request, as before; the forms with 32 more registers in flight are held to three waves per SIMD)
+template <int NB, typename XT, typename RT, bool R8, int BV, int DEEP, bool SPL>
+constexpr int vc_res_min_waves() {
+    return vc_rows_ahead<NB, XT, RT, R8, BV, DEEP, SPL>() ? 3 : 0;
+}
+__device__ __forceinline__ void pin_rows(pmc_f4 (&q)[8]) {
+    asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7]));
+}
+__device__ __forceinline__ void pin_rows(pmc_f4 (&q)[4]) { asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3])); }
+__device__ __forceinline__ void pin_rows(pmc_f4 (&)[1]) {}
 template <int NB, typename XT, typename RT, typename YT, bool R8, int BV = 0, bool STORE = true, int DEEP = 1, bool RAGG = false,
           bool SPL = false, typename CT = double, int TAG = 0>
-__global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
+__global__ __launch_bounds__(kBlock, (vc_res_min_waves<NB, XT, RT, R8, BV, DEEP, SPL>())) void vc_residual_kernel(int nrows, int nslices, const int* __restrict__ slice_off,
                                                              const int* __restrict__ cols, const double* __restrict__ vals,
                                                              const XT* __restrict__ x, const RT* r, YT* y,
                                                              typename ident<CT>::type* __restrict__ coarse, int ld,
@@ -597,11 +626,60 @@ __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nsli
     __shared__ float tile_all[RAGG ? (kBlock / kWave) * kWave * NB : 1];
     float* tile = tile_all + (RAGG ? (threadIdx.x / kWave) * kWave * NB : 0);
     const SliceWalk sw = slice_walk(nslices);
+    constexpr bool AHEAD = vc_rows_ahead<NB, XT, RT, R8, BV, DEEP, SPL>();
+    constexpr bool SEGA = AHEAD && RAGG && PMC_RES_SEG_AHEAD != 0;
+    // row steps read ahead: all T; T / 2 with the fused restriction, whose tile addressing and segment pair leave no room for
+    // 32 registers at three waves per SIMD (all T: 168 VGPRs and 20-24 B of scratch)
+    constexpr int AH = RAGG ? T / 2 : T;
     for (int slice = sw.begin; slice < sw.end; slice += sw.stride) {
         double acc[T][C];
-        const int off = slice_off[slice];
-        sell_row_range_t<NB, XT, false, BV, DEEP>(cols, vals, x, off, (slice_off[slice + 1] - off) >> 6, lane, LD, acc);
+        pmc_f4 own[AHEAD ? AH : 1];
+        int s0 = 0, s1 = 0, pos0 = 0, cid0 = 0;
+        if constexpr (AHEAD) {
+#pragma unroll
+            for (int u = 0; u < AH; ++u)
+                own[u] = *reinterpret_cast<const pmc_f4*>(r + (size_t)min(slice * kWave + u * G + g, nrows - 1) * LD + t * C);
+            if constexpr (SEGA) {
+                s0 = seg_ptr[slice];
+                s1 = seg_ptr[slice + 1];
+            }
+        }
+        const int off = slice_off[slice], width = (slice_off[slice + 1] - off) >> 6;
+        if constexpr (SEGA) {
+            // (behind the request for slice_off: the segment range's round trip then runs beside that one, not ahead of it)
+            if (s0 + g < s1) {
+                pos0 = seg_pos[s0 + g];
+                cid0 = seg_cid[s0 + g];
+            }
+        }
+        sell_row_range_t<NB, XT, false, BV, DEEP>(cols, vals, x, off, width, lane, LD, acc);
         if constexpr (SPL) split_row_sums<NB, C, T>(acc, sl);
+        if constexpr (AHEAD) {
+#pragma unroll
+            for (int h0 = 0; h0 < T; h0 += AH) {
+                if (h0 > 0) {
+                    // (the rest, where all T ahead do not fit: one batch, once the rows read ahead are consumed)
+#pragma unroll
+                    for (int u = 0; u < AH; ++u)
+                        own[u] = *reinterpret_cast<const pmc_f4*>(r + (size_t)min(slice * kWave + (h0 + u) * G + g, nrows - 1) * LD + t * C);
+                }
+                pin_rows(own);
+#pragma unroll
+                for (int u = 0; u < AH; ++u) {
+                    const int rs = h0 + u, row = slice * kWave + rs * G + g;
+                    if (row < nrows) {
+                        const size_t at = (size_t)row * LD + t * C;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) acc[rs][c] = (double)own[u][c] - acc[rs][c];
+                        if constexpr (STORE) store_v<C>(y + at, acc[rs]);
+                        if constexpr (RAGG) {
+#pragma unroll
+                            for (int c = 0; c < C; ++c) tile[(rs * G + g) * NB + t * C + c] = (float)acc[rs][c];
+                        }
+                    }
+                }
+            }
+        } else {
         // the own-row reads of H row steps are issued together (rows past the end re-read the last row): one latency per
         // batch instead of one per row step - these launches are single occupancy rounds of dependent loads
         constexpr int H = T >= 4 ? 4 : T;
@@ -643,11 +721,31 @@ __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nsli
                 if ((g & 7) == 0 && row < nrows) store_v<C>(coarse + (size_t)(row >> 3) * LD + t * C, s);
             }
         }
+        }
         if constexpr (RAGG) {
             // the tile is private to this wavefront: its own LDS writes are complete once the wait below has passed
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if constexpr (SEGA) {
+                // the first trip's pair was read ahead of the gather loop; later trips (sg += G) load theirs here
+                int pos = pos0, cid = cid0;
+                for (int sg = s0 + g; sg < s1;) {
+                    const int first = pos >> 8, len = pos & 255;
+                    double sum[C];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) sum[c] = 0.0;
+                    for (int q = 0; q < len; ++q)
+#pragma unroll
+                        for (int c = 0; c < C; ++c) sum[c] += (double)tile[(first + q) * NB + t * C + c];
+                    store_v<C>(coarse + (size_t)cid * LD + t * C, sum);
+                    sg += G;
+                    if (sg < s1) {
+                        pos = seg_pos[sg];
+                        cid = seg_cid[sg];
+                    }
+                }
+            } else {
             const int s0 = seg_ptr[slice], s1 = seg_ptr[slice + 1];
             for (int sg = s0 + g; sg < s1; sg += G) {
                 const int pos = seg_pos[sg], first = pos >> 8, len = pos & 255;
@@ -658,6 +756,7 @@ __global__ __launch_bounds__(kBlock) void vc_residual_kernel(int nrows, int nsli
 #pragma unroll
                     for (int c = 0; c < C; ++c) sum[c] += (double)tile[(first + q) * NB + t * C + c];
                 store_v<C>(coarse + (size_t)seg_cid[sg] * LD + t * C, sum);
+            }
             }
             __builtin_amdgcn_wave_barrier();    // the next slice overwrites the tile
         }
