@@ -206,7 +206,14 @@ uint64_t pmc_fused_field_evals(void);
  * solve on PMC_PATH_GRAPH that ends within its first, eager pair of iterations (or whose max_iter is 1: only the eager tail
  * runs) never replays a graph.  Two further values count events, not solves: PMC_COUNT_GRAPH_REPLAYS the graph launches, and
  * PMC_COUNT_POLLS the convergence polls (device-to-host reads of the active-column count) of all solves - a solve that starts
- * polling late, at the iteration count its predecessor on the handle needed, shows fewer.  Another value returns 0. */
+ * polling late, at the iteration count its predecessor on the handle needed, shows fewer.  Six more count launches that took a
+ * size-gated form, bumped on the host next to the launch (under graph capture: the capture, not its replays), so that a test can
+ * tell that its shape reached the gate: PMC_COUNT_NT_OPERATOR block-operator products with non-temporal matrix / result streams;
+ * PMC_COUNT_NT_POLY one-pass polynomial (smoother) launches with them; PMC_COUNT_NT_FLAT flat vector kernels (lincomb3, the w / x
+ * updates, the Darcy element-gather operator and polynomial) with them; PMC_COUNT_BOUNDED_GRID fused-dot launches whose grid the
+ * workgroup bound actually cut (their workgroups loop); PMC_COUNT_TWO_STAGE_DOT block-operator products whose partial blocks
+ * were folded by a second kernel; PMC_COUNT_TRACER_SPLIT tracer walks or flux uploads issued in more than one piece.  Another
+ * value returns 0. */
 enum pmc_solve_path {
     PMC_PATH_MINI = 0,
     PMC_PATH_GRAPH = 1,
@@ -215,7 +222,13 @@ enum pmc_solve_path {
     PMC_PATH_WINDOW = 4,
     PMC_PATH_PLAIN = 5,
     PMC_COUNT_GRAPH_REPLAYS = 6,
-    PMC_COUNT_POLLS = 7
+    PMC_COUNT_POLLS = 7,
+    PMC_COUNT_NT_OPERATOR = 8,
+    PMC_COUNT_NT_POLY = 9,
+    PMC_COUNT_NT_FLAT = 10,
+    PMC_COUNT_BOUNDED_GRID = 11,
+    PMC_COUNT_TWO_STAGE_DOT = 12,
+    PMC_COUNT_TRACER_SPLIT = 13
 };
 uint64_t pmc_solve_path_count(int path);
 const char* pmc_last_error(void);

@@ -44,6 +44,10 @@ PMC_STORAGE_FP32, PMC_STORAGE_FP64 = 0, 1
 # enum pmc_solve_path: the loops pmc_solve_path_count counts
 PMC_PATH_MINI, PMC_PATH_GRAPH, PMC_PATH_LATE, PMC_PATH_INDEXED, PMC_PATH_WINDOW, PMC_PATH_PLAIN = range(6)
 PMC_COUNT_GRAPH_REPLAYS, PMC_COUNT_POLLS = 6, 7     # ... events, not solves: graph launches, convergence polls
+# ... launches that took a size-gated form: non-temporal operator / polynomial / flat kernels, a fused-dot grid the bound cut,
+# the block operator's two-stage dot, a tracer walk or upload in more than one piece
+(PMC_COUNT_NT_OPERATOR, PMC_COUNT_NT_POLY, PMC_COUNT_NT_FLAT, PMC_COUNT_BOUNDED_GRID, PMC_COUNT_TWO_STAGE_DOT,
+ PMC_COUNT_TRACER_SPLIT) = range(8, 14)
 
 
 class pmc_stats(C.Structure):

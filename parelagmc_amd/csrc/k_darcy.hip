@@ -418,6 +418,7 @@ static int eg_pair_spmm_t(hipStream_t st, int nb, const EgView& M, const double*
     const dim3 g = grid_bounded(grid_slices(M.nslices), dot_partial != nullptr);
     PMC_DISPATCH_NB(nb, {
         if (nt_flat((size_t)M.nrows * NB * 2)) {   // from 4 MiB per vector on
+            count_solve_path(PMC_COUNT_NT_FLAT);
             if (dot_partial)
                 eg_pair_spmm_kernel<NB, true, true, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y, dot_with, dot_partial, nb);
             else
@@ -451,6 +452,7 @@ static int eg_poly2_t(hipStream_t st, int nb, const EgView& M, const double* coe
     const dim3 g = grid_bounded(grid_slices(M.nslices), dot_partial != nullptr);
     PMC_DISPATCH_NB(nb, {
         if (nt_flat((size_t)M.nrows * NB * 2)) {
+            count_solve_path(PMC_COUNT_NT_FLAT);
             if (dot_partial)
                 eg_poly2_kernel<NB, true, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, dot_partial, nb);
             else

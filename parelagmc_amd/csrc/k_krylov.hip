@@ -593,6 +593,7 @@ void lincomb3(hipStream_t st, int nb, int n, const double* c0, const double* a, 
     // non-temporal loads on large levels (one lane 1104 -> 1129, four lanes 1400 -> 1412 samples/s); PMC_NT_LINCOMB=0: off
     static const bool nt_on = [] { const char* e = lab_env("PMC_NT_LINCOMB"); return !e || atoi(e) != 0; }();
     const bool nt = nt_on && nt_flat((size_t)n * nb);
+    if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
     PMC_DISPATCH_NB(nb, {
         if (nt) lincomb3_kernel<NB, true><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, a, c1, b, c2, y, nb, y32);
         else lincomb3_kernel<NB><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, a, c1, b, c2, y, nb, y32);
@@ -604,6 +605,7 @@ template <typename UT>
 static void minres_wx_t(hipStream_t st, int nb, int n, const double* c0, const UT* u, const double* c1, double* w0,
                         const double* c2, const double* w1, const double* c3, double* x) {
     const bool nt = nt_flat((size_t)n * nb);
+    if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
     PMC_DISPATCH_NB(nb, {
         if (nt) minres_wx_kernel<NB, true, UT><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, u, c1, w0, c2, w1, c3, x, nb);
         else minres_wx_kernel<NB, false, UT><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, u, c1, w0, c2, w1, c3, x, nb);
@@ -622,6 +624,7 @@ void minres_wx_deferred(hipStream_t st, int nb, int n, const MinresState* s, con
     if (B.cnt < 0 || B.cnt > kWxWindow) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: bad count");
     const double* cW = reinterpret_cast<const double*>(reinterpret_cast<const char*>(s) + offsetof(MinresState, cW));
     const bool nt = nt_flat((size_t)n * nb);
+    if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
     // the entries of one thread share their columns (see the kernel): kBlock * C flat values are whole rows
     if ((kBlock * lay_c(nb)) % nb != 0) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: row stride does not divide a workgroup's step");
     const size_t nf = flat_count(n, nb);

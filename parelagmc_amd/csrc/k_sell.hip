@@ -891,6 +891,7 @@ static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const
             if (lz_mode) {
                 // the matrix streams of both passes are those of the in-loop product (its launch carries the dot)
                 const bool ntl = nt_streams(A, NB, true);
+                if (ntl) count_solve_path(PMC_COUNT_NT_OPERATOR);
                 constexpr bool kDl = Lay<NB>::T > 1;
                 if (lz_mode == 1) {
                     if (ntl) { if (dl) PMC_SPMM_LZ(true, kDl, 1); else PMC_SPMM_LZ(true, false, 1); }
@@ -905,6 +906,7 @@ static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const
         }
         const bool nt = TAG != 0 && nt_streams(A, NB, dot_partial != nullptr);
         if (nt) {
+            count_solve_path(PMC_COUNT_NT_OPERATOR);
             if (dot_partial && dl)
                 sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1), XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
             else if (dot_partial)
@@ -936,6 +938,7 @@ static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const
         else
             sell_spmm_kernel<NB, true, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
     } else if (TAG != 0 && nt_streams(A, NB, dot_partial != nullptr)) {
+        count_solve_path(PMC_COUNT_NT_OPERATOR);
         if (dot_partial && dl)
             sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1)><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
         else if (dot_partial)
@@ -962,15 +965,15 @@ static int spmm_t(hipStream_t st, int nb, const SellView& A, const XT* x, double
     check_offsets32(A, nb);
     if (A.nrows == 0) return 0;
     if (dot_partial && !dot_with) throw Error(PMC_ERR_INTERNAL, "spmm: fused dot without its second vector");
-    dim3 g = grid_bounded(grid_slices(A.nslices), dot_partial != nullptr);
     // The block operator keeps one slice per wavefront also with a fused dot (a bounded grid of looping workgroups cost
     // 22 us of 450 at 4.7 M rows); its partial blocks - more than the single-block consumers should read - are first
     // compressed to kCompressBlocks.  They are written behind the compressed ones: dot_capacity() leaves the room.
-    const bool two_stage = dot_partial && A.tag != 0 && !A.bv && grid_slices(A.nslices).x > g.x;
+    const bool two_stage = dot_partial && A.tag != 0 && !A.bv && grid_slices(A.nslices).x > dot_grid_bound();
+    const dim3 g = two_stage ? grid_slices(A.nslices) : grid_bounded(grid_slices(A.nslices), dot_partial != nullptr);
     double* kernel_partial = dot_partial;
     if (two_stage) {
-        g = grid_slices(A.nslices);
         kernel_partial = dot_partial + (size_t)kCompressBlocks * nb;
+        count_solve_path(PMC_COUNT_TWO_STAGE_DOT);
     }
     PMC_DISPATCH_NB(nb, {
         if (A.tag == 1) spmm_launch<NB, 1, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with, lz_mode, lz);
@@ -1130,6 +1133,7 @@ static int poly2_t(hipStream_t st, int nb, const SellView& As, const double* din
             else
                 sell_poly2_kernel<NB, 1, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
         } else if (nt_poly(As, NB)) {
+            count_solve_path(PMC_COUNT_NT_POLY);
             if (dot_partial)
                 sell_poly2_kernel<NB, 0, true, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
             else
@@ -1199,9 +1203,10 @@ static void vc_presmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     PMC_DISPATCH_NB(nb, {
         // (the 32-wide fp32 forms - the finest level of a cycle - know at compile time that the epilogue adds nothing)
         constexpr bool EPS = NB == kGroup && sizeof(RT) == 4;
-        if (nt_poly(As, NB))
+        if (nt_poly(As, NB)) {
+            count_solve_path(PMC_COUNT_NT_POLY);
             vc_poly2_kernel<NB, RT, float, float, false, true, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
-        else
+        } else
             vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
     });
     check_launch();
@@ -1332,6 +1337,7 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     // product: one lane 2 870 -> 2 815 samples/s, four lanes 3 745 -> 3 757 (LAB_NOTES 10.19); laboratory switch PMC_GIB=1
     static const bool gib = [] { const char* e = lab_env("PMC_GIB"); return e && atoi(e) != 0; }();
     if (gib && nb == 2 * kGroup && nt_poly(As, kGroup) && !xcd_layout(g, nb)) {
+        count_solve_path(PMC_COUNT_NT_POLY);
         if (dot_partial)
             vc_poly2_kernel<kGroup, float, OT, float, true, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
         else
@@ -1346,6 +1352,7 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     PMC_DISPATCH_NB(nb, {
         constexpr bool EPS = NB == kGroup;
         if (nt_poly(As, NB)) {
+            count_solve_path(PMC_COUNT_NT_POLY);
             if (dot_partial)
                 vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
             else

@@ -104,6 +104,9 @@ int dot_capacity(int nrows, int nb);
 // kernels this process has launched through the library so far (all handles, all threads): launch-rate diagnostics
 uint64_t kernel_launch_count();
 void count_kernel_launches(int n);
+// ---- solver.hip
+// one more solve on `path`, or one more event of enum pmc_solve_path (the launchers count the size-gated forms they take)
+void count_solve_path(int path);
 
 namespace k {
 

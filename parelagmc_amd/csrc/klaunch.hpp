@@ -67,7 +67,12 @@ static inline unsigned dot_grid_bound() {
 
 namespace k {
 
-static inline dim3 grid_bounded(dim3 g, bool bounded) { return bounded ? dim3(std::min(g.x, dot_grid_bound())) : g; }
+// (called once per launch, next to it: a grid the bound actually cuts is counted as PMC_COUNT_BOUNDED_GRID)
+static inline dim3 grid_bounded(dim3 g, bool bounded) {
+    if (!bounded || g.x <= dot_grid_bound()) return g;
+    count_solve_path(PMC_COUNT_BOUNDED_GRID);
+    return dim3(dot_grid_bound());
+}
 
 // non-temporal matrix / result streams for the block operator once its operands no longer fit the Infinity Cache.  Inside
 // the MINRES loop (in_loop: the launch with the fused dot) they never are cache-resident from half that size on - the rest

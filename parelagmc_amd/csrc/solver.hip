@@ -597,9 +597,9 @@ static bool fused_lanczos_on() {
 static std::atomic<uint64_t> g_adopted_rhs_solves{0};
 uint64_t adopted_rhs_solve_count() { return g_adopted_rhs_solves.load(std::memory_order_relaxed); }
 
-static std::atomic<uint64_t> g_path_solves[PMC_COUNT_POLLS + 1];
+static std::atomic<uint64_t> g_path_solves[PMC_COUNT_TRACER_SPLIT + 1];
 uint64_t solve_path_count(int path) {
-    return path >= 0 && path <= PMC_COUNT_POLLS ? g_path_solves[path].load(std::memory_order_relaxed) : 0;
+    return path >= 0 && path <= PMC_COUNT_TRACER_SPLIT ? g_path_solves[path].load(std::memory_order_relaxed) : 0;
 }
 void count_solve_path(int path) { g_path_solves[path].fetch_add(1, std::memory_order_relaxed); }
 

@@ -367,9 +367,8 @@ uint64_t fused_lanczos_solve_count();
 // ... that adopted their right-hand side from its producer (RhsFn) instead of copying a stored b
 uint64_t adopted_rhs_solve_count();
 // ... by the loop they selected, and the graph replays / convergence polls of all solves (enum pmc_solve_path);
-// count_solve_path: one more solve on `path`, or one more such event
+// count_solve_path (kernels.hpp): one more solve on `path`, or one more such event
 uint64_t solve_path_count(int path);
-void count_solve_path(int path);
 
 struct MinresResult {
     pmc_stats col[kMaxBatch];

@@ -437,6 +437,7 @@ void Tracer::launch_walk(hipStream_t st, int nb, bool by_batch, const double* u_
                          double* T_d, int32_t* face_d, int32_t* status_d, int32_t* steps_d, double* x_d) {
     // blockIdx.y carries the realization of the sample-major layout: at most 32768 per launch
     const int per = by_batch ? nb : std::min(nb, 32768);
+    if (per < nb) count_solve_path(PMC_COUNT_TRACER_SPLIT);
     for (int b0 = 0; b0 < nb; b0 += per) {
         const int n = std::min(per, nb - b0);
         const int64_t threads = by_batch ? (int64_t)npart * n : npart;
@@ -479,6 +480,7 @@ void Tracer::run(int nbatch, const double* u, int64_t ld, double* T, int32_t* ex
     // host memory: the flux rows are staged in pieces of at most 2^24 values
     const int per = (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t(1) << 24) / n_face));
     const size_t cnt = (size_t)per * npart;
+    if (per < nbatch) count_solve_path(PMC_COUNT_TRACER_SPLIT);
     stage_u.ensure((size_t)per * n_face);
     out_T.ensure(cnt);
     out_x.ensure(3 * cnt);

@@ -145,10 +145,11 @@ def _took(before, after):
     return {nm: after[nm] - before[nm] for nm in after if after[nm] != before[nm]}
 
 
-def _check_replays(case, replays, issued):
+def _check_replays(case, replays, issued, cases=None):
     """pmc_solve_path_count says which loop a solve SELECTED; that the graph path really replayed is read from the replay
-    count: `issued` iterations (an even number, or max_iter) = one eager pair, the replays, the eager tail of an odd max_iter"""
-    if SAMPLER_CASES[case]["path"] == "GRAPH":
+    count: `issued` iterations (an even number, or max_iter) = one eager pair, the replays, the eager tail of an odd max_iter.
+    cases: another case table than SAMPLER_CASES (test_gpu_minres_full_width.py)"""
+    if (cases or SAMPLER_CASES)[case]["path"] == "GRAPH":
         assert replays == max(issued // 2 - 1, 0), (case, replays, issued)
     else:
         assert replays == 0, (case, replays)
@@ -324,15 +325,17 @@ def _operator(hd):
 
 
 class _Batch:
-    """the mixed batch of a (handle, storage, width) with the reference of its compared columns"""
+    """the mixed batch of a (handle, storage, width) with the reference of its compared columns.  pos: the places of the
+    eight scaled columns and the ninth one, copy_at: the place of the copy of column 0, seed: the label the generator is
+    seeded from (defaults: the places and the seed of this file's cases; test_gpu_minres_full_width.py passes its own)"""
 
-    def __init__(self, hd, handle, storage, width):
+    def __init__(self, hd, handle, storage, width, pos=None, copy_at=None, seed=None):
         self.hd, self.width, self.storage = hd, width, storage
         self.narrow = hd.narrow(width)
         self.A = _operator(hd)
         self.Binv = lambda r: hd.oracle.apply(r, self.narrow)
-        self.rng = np.random.Generator(np.random.PCG64(zlib.crc32(f"{handle}/{width}".encode())))
-        self.pos = _positions(width) + ([EXTRA_AT] if width > 8 else [])
+        self.rng = np.random.Generator(np.random.PCG64(zlib.crc32((seed or f"{handle}/{width}").encode())))
+        self.pos = list(pos) if pos is not None else _positions(width) + ([EXTRA_AT] if width > 8 else [])
         self.scales = SCALES + ((EXTRA_SCALE,) if width > 8 else ())
         rhs = self.rng.standard_normal((width, hd.n))
         unit = [j for j in range(width) if j not in self.pos[2:]]
@@ -341,7 +344,7 @@ class _Batch:
         self.abs_tol = 1e-9 * self.beta_ref
         for p, s in zip(self.pos, self.scales):
             rhs[p] *= s
-        self.copy_at = COPY_AT if width > 8 else None
+        self.copy_at = (COPY_AT if copy_at is None else copy_at) if width > 8 else None
         if self.copy_at is not None:
             assert self.copy_at not in self.pos and len(set(self.pos)) == len(self.pos)
             rhs[self.copy_at] = rhs[0]
@@ -389,25 +392,26 @@ def _batch(base, case, storage, width):
     return _REFS[key]
 
 
-def _open(ctx, base, case, storage, **opts):
+def _open(ctx, base, case, storage, cases=None, **opts):
     """a fresh handle of the case with the given tolerances; its setup must be the one the reference was built from"""
-    cfg = SAMPLER_CASES[case]
+    cfg = (cases or SAMPLER_CASES)[case]
     hd = Handle(ctx, cfg["handle"], storage, **cfg["opts"], **opts)
     b = base(cfg["handle"], storage)
     assert hd.setup == b.setup and all((p != q).nnz == 0 for p, q in zip(hd.P, b.P)), "the options changed the preconditioner"
     return hd
 
 
-def _expected_path(case, hd, storage, width):
+def _expected_path(case, hd, storage, width, cases=None):
     """the counters one solve of the case must move, from the case table and the handle's own report of its cycle"""
     from oracle.precond_oracle import ROLE_DESCEND, ROLE_EXACT
-    want = {SAMPLER_CASES[case]["path"]: 1}
+    cases = cases or SAMPLER_CASES
+    want = {cases[case]["path"]: 1}
     if hd.hybrid:
         narrow = hd.narrow(width)
         m0 = hd.setup[0]
         top_on_kernels = not (m0["tail_narrow"] if narrow else m0["tail_wide"])
         assert int(m0["role_wide"]) == ROLE_DESCEND
-        if case == "hex12-hybrid":
+        if cases[case]["handle"] == "hex12-hybrid":
             # narrow: level 0 on kernels, the exact dense solve on level 1; wide: the whole cycle inside the tail
             assert top_on_kernels == narrow and int(hd.setup[1]["role_narrow"]) == ROLE_EXACT
         else:
@@ -415,7 +419,7 @@ def _expected_path(case, hd, storage, width):
             assert storage == "fp64" or (hd.info[0]["fused_restriction"] and hd.info[1]["narrow_pieces"] > 1)
         if top_on_kernels and storage == "fp32":
             want["FUSED"] = 1          # the two operator passes need the fp32 copy of the Lanczos vector (r32)
-    elif SAMPLER_CASES[case]["path"] == "MINI":
+    elif cases[case]["path"] == "MINI":
         assert hd.n <= hd.opts.mini_max_rows and hd.info[0]["in_tail"]
     else:
         assert hd.n > hd.opts.mini_max_rows
@@ -580,7 +584,10 @@ DARCY_COLUMNS = 8
 
 
 class _DarcyBatch:
-    def __init__(self, ctx, hex_hierarchy, hybrid, storage):
+    """ncols realizations of darcy_fields with the systems of the `compared` ones (default: DARCY_COLUMNS, all compared, the
+    last a twin of column 1; test_gpu_minres_full_width.py passes a full launch and the columns it compares)"""
+
+    def __init__(self, ctx, hex_hierarchy, hybrid, storage, ncols=DARCY_COLUMNS, compared=None):
         from oracle.darcy_oracle import DarcyOracle
         from oracle.precond_oracle import DarcyChainPrecondOracle, DarcyPrecondOracle, chebyshev, vcycle
         from parelagmc_amd import capi
@@ -590,8 +597,10 @@ class _DarcyBatch:
         L = dp.levels[0]
         self.L = L
         self.rng = np.random.Generator(np.random.PCG64(zlib.crc32(f"darcy/{hybrid}".encode())))
-        self.k = darcy_fields(self.rng, DARCY_COLUMNS, L.n_p)
-        self.k[7] = self.k[1]          # (both are k == 1 already: columns 1 and 7 are bitwise twins)
+        self.k = darcy_fields(self.rng, ncols, L.n_p)
+        if compared is None:
+            self.k[7] = self.k[1]      # (both are k == 1 already: columns 1 and 7 are bitwise twins)
+        self.compared = list(range(ncols)) if compared is None else list(compared)
         st = capi.PMC_STORAGE_FP64 if storage == "fp64" else capi.PMC_STORAGE_FP32
         self.make = lambda **kw: capi.DarcySolver(ctx, dp, capi.solver_opts(precond_storage=st, cheb_degree_M=0, **kw),
                                                   hybrid=hybrid)
@@ -604,7 +613,7 @@ class _DarcyBatch:
             P = [ds.vcycle_prolongator(0, v) for v in range(len(setup) - 1)]
             oc = DarcyChainPrecondOracle(dp, 0, setup, P, hl)
             deg, ratio = int(setup[0]["smooth_degree"]), setup[0]["smooth_ratio"]
-            for j in range(DARCY_COLUMNS):
+            for j in self.compared:
                 kappa = self.k[j] if dp.k_divides else 1.0 / self.k[j]
                 lv = oc.levels(self.k[j])
                 self.systems.append((hl.operator(kappa).tocsr(), (lambda r, lv=lv: vcycle(lv, r, deg, ratio)), hl.rhs(kappa),
@@ -613,7 +622,7 @@ class _DarcyBatch:
             do = DarcyOracle(dp)
             po = DarcyPrecondOracle(dp, o.mg_smooth_degree, o.mg_smooth_ratio, o.mg_coarse_degree, o.mg_coarse_ratio)
             ratio_M, deg_M = setup[0]["ratio_M"], int(setup[0]["degree_M"])
-            for j in range(DARCY_COLUMNS):
+            for j in self.compared:
                 A, rhs = do.assemble(0, self.k[j])
                 M, _ = po.mass(0, self.k[j])
                 l1inv = 1.0 / np.asarray(abs(M).sum(axis=1)).ravel()
