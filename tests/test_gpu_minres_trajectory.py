@@ -42,6 +42,9 @@ its solve capped at 1, which runs the eager tail alone; the blind runs read PMC_
   hex16-graph    ... use_graph = 1, check_every = 2: graph replay, per-iteration minres_wx, eager tail of an odd max_iter
   hex8-mini      hex 4^3 refined once (2 240 rows): mini_sampler_kernel (the second copy of the recurrences)
   tet-mini       tet-saddle of the preconditioner tests: mini_sampler_kernel on tetrahedra
+  hex8-mini-deg3     hex 4^3 refined once at corlen 2 under the deg3 options of precond_cases.py (smoothers of degree 3 on
+                     [lmax / 5, lmax], bottom of degree 2): mini_sampler_kernel with the tail's general loop
+  hex16-saddle-deg3  hex16-saddle under the full deg3 set: the window loop, the same tail, M-block of degree 3 (cheb_step_z)
   hex12-hybrid   8 columns: level 0 on kernels, fused Lanczos update + r32 (fp32 storage), dense_apply; 32: cycle in the tail, stored q
   hex24-hybrid   43 200 multipliers: fused Lanczos update, r32_top, fused aggregate restriction, row-split narrow levels
   darcy-hex      per-realization operators; window update (solution wanted) and minres_wx_idx (Q only)
@@ -121,6 +124,13 @@ SAMPLER_CASES = {
     "tet-mini": dict(handle="tet-saddle", opts={}, path="MINI", widths=(32,)),
     "hex12-hybrid": dict(handle="hex12-hybrid", opts={}, path="WINDOW", widths=(8, 32)),
     "hex24-hybrid": dict(handle="hex24-hybrid", opts={}, path="WINDOW", widths=(8, 32)),
+    # whole solves under the deg3 option set of precond_cases.OPTION_SETS (the handles carry the options, so that the
+    # reference preconditioner is exported under them): the tail's general smoothing loop and one-pass bottom inside
+    # mini_sampler_kernel (degree-2 M-block, which that kernel requires; hex 4^3 refined once at corlen 2, where the cycle
+    # descends), and in the window loop the same tail beside an M-block of degree 3 through cheb_apply_z's unfused loop
+    # (cheb_step_z into the typed z)
+    "hex8-mini-deg3": dict(handle="hex8-long-deg3", opts={}, path="MINI", widths=(32,)),
+    "hex16-saddle-deg3": dict(handle="hex16-saddle-deg3", opts=dict(mini_max_rows=0), path="WINDOW", widths=(32,)),
 }
 CASE_WIDTHS = [(c, w) for c, cfg in SAMPLER_CASES.items() for w in cfg["widths"]]
 CASE_IDS = [f"{c}-{w}" for c, w in CASE_WIDTHS]
