@@ -994,6 +994,62 @@ int pmc_darcy_transport_loglik_gradient(pmc_darcy* d, int level, pmc_transport* 
                                         double* curve /* host, nbatch x nreport | NULL */, int32_t* status, double* grad, int memspace,
                                         pmc_stats* stats_adj);
 
+/* ---- The adjoint of the particle tracer: gradients of travel times (an extension)
+ * For J = <T_bar, T> + <x_exit_bar, x_exit> per column, pmc_tracer_run_adjoint returns u_bar = dJ/du (the first n_face entries
+ * of the row at u_bar + b * ld_bar; nothing else of the row is written) and x0_bar = dJ/dx0 (nbatch x nparticles x 3, may be
+ * NULL): the derivative of the walk above with its decisions held at their forward values - the element sequence and the
+ * step count, the chosen exit of every step (for a box the side of its axis) and the series / closed-form branch of L and E.
+ * Clamps count as the identity; a coordinate that the walk sets exactly (the exit plane, the entry face's barycentric
+ * coordinate) has a zero derivative.  Seeds: T_bar (nbatch x nparticles), x_exit_bar (nbatch x nparticles x 3); each may be
+ * NULL and then counts as zero, at least one must be given.  The forward outputs T, exit_face, nsteps (each may be NULL) and
+ * status are those of pmc_tracer_run bit for bit.  A particle whose status is not PMC_TRACER_EXITED is not differentiated:
+ * it adds nothing to u_bar and its x0_bar is zero (its T is a censored time so far).  All arrays in `memspace`.
+ *   order:   u_bar[f] is summed from 0.0 over the (at most two) elements of face_elem[f] in that order and, within an element,
+ *            over the visits of the column's particles in ascending (particle index in the caller's order, step).
+ *   records: the sweep needs, per (column, particle, step), the element, the entry coordinates and the chosen exit; a second
+ *            walk stores them, sized by the largest step count of the call, about (16 + 8 (n_c + n_fe)) bytes each (n_c = 3 |
+ *            4 coordinates, n_fe = 6 | 4 faces).  Columns are processed in chunks whose records stay under 256 MiB (at least
+ *            one column); pmc_tracer_set_adjoint_scratch sets another cap in bytes (0: the default) and
+ *            pmc_tracer_adjoint_chunks returns the chunks of the last launch.  No result depends on the chunking.
+ * A column's u_bar, x0_bar and forward outputs have the same bits at every nbatch, beside any other columns, in every split
+ * into calls, in either memory space, at every ld / ld_bar, under any chunking and in repeated calls; pmc_tracer_run is not
+ * disturbed.
+ * pmc_tracer_reduce_seed: T_bar = dQ/dT of the Q of pmc_tracer_reduce, in `memspace` like T and status - PMC_TRACER_MEAN:
+ * 1 / nparticles on the particles that exited, 0 elsewhere; PMC_TRACER_MIN: 1 on the lowest-index particle attaining the
+ * minimum, if it exited, 0 elsewhere.
+ * Refused with PMC_ERR_INVALID (nothing is written, the handle stays usable): both seeds NULL; NULL u, u_bar or status (T,
+ * status or T_bar of the seed); ld or ld_bar < n_face; nbatch < 1; a bad memspace; a kind other than the two; bytes < 0. */
+int pmc_tracer_run_adjoint(pmc_tracer* t, int nbatch, const double* u, int64_t ld,
+                           const double* T_bar /* nbatch x nparticles | NULL */,
+                           const double* x_exit_bar /* nbatch x nparticles x 3 | NULL; at least one seed */,
+                           double* u_bar, int64_t ld_bar /* >= n_face; only the first n_face of each row written */,
+                           double* x0_bar /* nbatch x nparticles x 3 | NULL */, double* T /* | NULL */,
+                           int32_t* exit_face /* | NULL */, int32_t* status, int32_t* nsteps /* | NULL */, int memspace);
+int pmc_tracer_reduce_seed(pmc_tracer* t, int nbatch, const double* T, const int32_t* status, int kind, double* T_bar,
+                           int memspace);
+int pmc_tracer_set_adjoint_scratch(pmc_tracer* t, int64_t bytes);   /* 0: 256 MiB */
+int pmc_tracer_adjoint_chunks(const pmc_tracer* t);
+/* dJ/dk (wrt_log: dJ/dlog k) of J = <T_bar, T> of the tracer t on the flux of the level's Darcy solution, per realization:
+ * forward solve, the walk and its adjoint on the solver's internal solution, u_bar as the u rows of the adjoint right-hand
+ * side (p rows and essential rows zero), adjoint solve, pmc_darcy_mass_sensitivity - the pipeline of
+ * pmc_darcy_solve_gradient, saddle-point path on every handle, whose sol_out / adj_out / stats these are.  t is given with the
+ * call: what pmc_darcy_set_tracer or pmc_darcy_set_transport attached is neither read nor changed.  k, T_bar (nbatch x
+ * nparticles), grad (nbatch x n_p), T (nbatch x nparticles | NULL), status (nbatch x nparticles), sol_out and adj_out (| NULL)
+ * in `memspace`.  Particles that did not exit add nothing to the gradient.
+ * pmc_darcy_tracer_loglik_gradient: loglik[b] = -|T_b - data|^2 / (2 noise) over all particles (host) and its gradient, the
+ * seed T_bar = -(T - data) / noise formed on the device; data (nparticles), loglik, T (| NULL) and not_exited (nbatch, the
+ * particles of the column that did not exit) on the host.  A column with not_exited[b] > 0 has a zero gradient.
+ * Refused with PMC_ERR_INVALID: a level out of range, t NULL, of other sizes than the level (n_face != n_u or n_elem != n_p) or
+ * created on another device, nbatch < 1, NULL k, grad, T_bar, status, not_exited or data, noise <= 0, a bad memspace. */
+int pmc_darcy_tracer_gradient(pmc_darcy* d, int level, pmc_tracer* t, int nbatch, const double* k,
+                              const double* T_bar /* nbatch x nparticles */, int wrt_log, double* T,
+                              int32_t* status /* nbatch x nparticles */, double* grad, double* sol_out, double* adj_out,
+                              int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj);
+int pmc_darcy_tracer_loglik_gradient(pmc_darcy* d, int level, pmc_tracer* t, int nbatch, const double* k,
+                                     const double* data /* host, nparticles */, double noise, int wrt_log,
+                                     double* loglik /* host */, double* T /* host | NULL */,
+                                     int32_t* not_exited /* host, nbatch */, double* grad, int memspace, pmc_stats* stats_adj);
+
 /* ---- MLMC accumulators across GPUs (new: the reference's manager is serial,
  *      src/MLMC_Manager.hpp:24) ----------------------------------------------------------- */
 int pmc_comm_unique_id(void* id128);                                        /* 128 bytes    */

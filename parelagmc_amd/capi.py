@@ -295,6 +295,15 @@ SYMBOLS = {
     "pmc_darcy_transport_loglik_gradient": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _DP, C.POINTER(C.c_double), C.c_double, C.c_int,
                                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _DP,
                                                       C.c_int, C.POINTER(pmc_stats)]),
+    "pmc_tracer_run_adjoint": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, _DP, _DP, _DP, C.c_int64, _DP, _DP, _VP, _VP, _VP, C.c_int]),
+    "pmc_tracer_reduce_seed": (C.c_int, [_VP, C.c_int, _DP, _VP, C.c_int, _DP, C.c_int]),
+    "pmc_tracer_set_adjoint_scratch": (C.c_int, [_VP, C.c_int64]),
+    "pmc_tracer_adjoint_chunks": (C.c_int, [_VP]),
+    "pmc_darcy_tracer_gradient": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _DP, _DP, C.c_int, _DP, _VP, _DP, _DP, _DP, C.c_int,
+                                            C.POINTER(pmc_stats), C.POINTER(pmc_stats)]),
+    "pmc_darcy_tracer_loglik_gradient": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _DP, C.POINTER(C.c_double), C.c_double, C.c_int,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _DP,
+                                                   C.c_int, C.POINTER(pmc_stats)]),
     "pmc_comm_unique_id": (C.c_int, [_VP]),
     "pmc_comm_init": (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
     "pmc_comm_destroy": (C.c_int, [_VP]),
@@ -1593,6 +1602,53 @@ class DarcySolver:
             1 if wrt_log else 0, _ptr(ll, C.c_double), _ptr(curve, C.c_double), _ptr(status, C.c_int32), _addr(grad)[0], ms, None))
         return ll, curve, status, grad
 
+    # ---- gradients of travel times through a tracer's adjoint -------------------------------------
+    def tracer_gradient(self, level, tracer, k, T_bar, wrt_log=False, nbatch=None, grad_out=None, want_solution=False,
+                        return_stats=False):
+        """dJ/dk (dJ/dlog k) of J = <T_bar, T> of `tracer` (a capi.Tracer of the level's sizes) on the flux of the Darcy solution
+        (pmc_darcy_tracer_gradient).  k and T_bar (nbatch x nparticles) numpy, or both on the device with nbatch and grad_out.
+        Returns a dict of grad, T and status (nbatch x nparticles) - plus sol and adj with want_solution, plus stats (forward,
+        adjoint) with return_stats."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        host = ms == PMC_MEM_HOST
+        npart, n = (tracer.nparticles if tracer is not None else 1), self.GetGlobalNumberOfDofs(level)   # None: the library refuses
+        if host and T_bar is not None:
+            T_bar = _f64(np.atleast_2d(T_bar))
+            if tracer is not None and T_bar.shape != (nbatch, npart):
+                raise ValueError("T_bar must be nbatch x nparticles")
+        if T_bar is not None and _addr(T_bar)[1] != ms:
+            raise ValueError("all arrays of a call must share a memory space")
+        new = (lambda *shape: np.empty(shape)) if host else (lambda *shape: DeviceArray(self.ctx, int(np.prod(shape))))
+        T = new(nbatch, npart)
+        status = np.empty((nbatch, npart), np.int32) if host else DeviceInt32Array(self.ctx, nbatch * npart)
+        sol, adj = (new(nbatch, n), new(nbatch, n)) if want_solution else (None, None)
+        sf, sa = (pmc_stats * nbatch)(), (pmc_stats * nbatch)()
+        _check(self.ctx.lib.pmc_darcy_tracer_gradient(
+            self.h, level, None if tracer is None else tracer.h, nbatch, pk, _addr(T_bar)[0], 1 if wrt_log else 0, _addr(T)[0],
+            status.ctypes.data if host else status.ptr, _addr(grad)[0], _addr(sol)[0], _addr(adj)[0], ms, sf, sa))
+        out = dict(grad=grad, T=T, status=status)
+        if want_solution:
+            out.update(sol=sol, adj=adj)
+        if return_stats:
+            out["stats"] = [[(s.iterations, s.converged, s.initial_norm, s.final_norm) for s in st] for st in (sf, sa)]
+        return out
+
+    def tracer_loglik_gradient(self, level, tracer, k, data, noise, wrt_log=False, nbatch=None, grad_out=None):
+        """loglik = -|T - data|^2 / (2 noise) of the travel times of `tracer` and its gradient in k
+        (pmc_darcy_tracer_loglik_gradient): returns (loglik (nbatch,), T (nbatch, nparticles), not_exited (nbatch,), grad).  A
+        column with not_exited > 0 has a zero gradient."""
+        k, nbatch, grad = self._grad_out(level, k, nbatch, grad_out)
+        pk, ms = _addr(k)
+        data = None if data is None else _f64(np.asarray(data, dtype=np.float64).ravel())
+        if data is not None and data.size != tracer.nparticles:
+            raise ValueError("data must hold one value per particle")
+        ll, T, nex = np.empty(nbatch), np.empty((nbatch, tracer.nparticles)), np.empty(nbatch, np.int32)
+        _check(self.ctx.lib.pmc_darcy_tracer_loglik_gradient(
+            self.h, level, tracer.h, nbatch, pk, None if data is None else _ptr(data, C.c_double), float(noise),
+            1 if wrt_log else 0, _ptr(ll, C.c_double), _ptr(T, C.c_double), _ptr(nex, C.c_int32), _addr(grad)[0], ms, None))
+        return ll, T, nex, grad
+
     # ---- Gauss-Newton Hessian-vector products in k (DESIGN.md section 18) ----------------------------------------------
     def mass_tangent_time(self):
         """the tangent right-hand side kernel under set_operator_timing: (bracket ms, launches, empty-bracket ms)"""
@@ -1802,6 +1858,69 @@ class Tracer:
         if want_x:
             out["x_exit"] = x
         return out
+
+    def run_adjoint(self, u, T_bar=None, x_exit_bar=None, nbatch=None, ld=None, ld_bar=None, want_x0_bar=True):
+        """u_bar = dJ/du and x0_bar = dJ/dx0 of J = <T_bar, T> + <x_exit_bar, x_exit> per column, the decisions of the walk held
+        (pmc_tracer_run_adjoint).  u and the seeds: numpy (u: nbatch x ld >= n_face), or DeviceArrays /
+        device tensors with nbatch (and ld, default n_face).  Returns a dict of u_bar (nbatch x ld_bar, default n_face; only the
+        first n_face entries of a row are written), x0_bar (nbatch x nparticles x 3, unless want_x0_bar is False), T,
+        exit_face, status and nsteps.  Particles that did not exit contribute nothing."""
+        npart = self.nparticles
+        seeds = [T_bar, x_exit_bar]
+        if isinstance(u, np.ndarray):
+            u = _f64(np.atleast_2d(u))
+            nbatch, ld = u.shape
+            ld_bar = self.n_face if ld_bar is None else int(ld_bar)
+            for i, (a, shape) in enumerate(zip(seeds, [(nbatch, npart), (nbatch, npart, 3)])):
+                if a is not None:
+                    seeds[i] = _f64(a).reshape(shape)
+            out = dict(u_bar=np.zeros((nbatch, max(ld_bar, 0))), x0_bar=np.empty((nbatch, npart, 3)) if want_x0_bar else None,
+                       T=np.empty((nbatch, npart)), exit_face=np.empty((nbatch, npart), np.int32),
+                       status=np.empty((nbatch, npart), np.int32), nsteps=np.empty((nbatch, npart), np.int32))
+            pu, ms = u.ctypes.data, PMC_MEM_HOST
+            addr = lambda a: None if a is None else a.ctypes.data
+        else:
+            assert nbatch is not None
+            ld = self.n_face if ld is None else int(ld)
+            ld_bar = self.n_face if ld_bar is None else int(ld_bar)
+            pu, ms = _addr(u)
+            assert ms == PMC_MEM_DEVICE and all(a is None or _addr(a)[1] == ms for a in seeds)
+            dev = lambda n: DeviceArray(self.ctx, n)
+            idev = lambda: DeviceInt32Array(self.ctx, nbatch * npart)
+            out = dict(u_bar=dev(nbatch * max(ld_bar, 1)), x0_bar=dev(nbatch * npart * 3) if want_x0_bar else None,
+                       T=dev(nbatch * npart), exit_face=idev(), status=idev(), nsteps=idev())
+            addr = lambda a: None if a is None else (a.ptr if isinstance(a, (DeviceArray, DeviceInt32Array)) else _addr(a)[0])
+        _check(self.ctx.lib.pmc_tracer_run_adjoint(self.h, int(nbatch), pu, int(ld), addr(seeds[0]), addr(seeds[1]),
+                                                   addr(out["u_bar"]), int(ld_bar), *[addr(out[k]) for k in
+                                                                                      ("x0_bar", "T", "exit_face", "status", "nsteps")], ms))
+        if not want_x0_bar:
+            del out["x0_bar"]
+        return out
+
+    def reduce_seed(self, T, status, kind=0):
+        """T_bar = dQ/dT of the Q of Reduce (pmc_tracer_reduce_seed): numpy (nbatch x nparticles) for numpy inputs, a DeviceArray
+        for the device buffers of Run"""
+        if isinstance(T, np.ndarray):
+            T = _f64(np.atleast_2d(T))
+            status = _i32(np.atleast_2d(status))
+            nbatch = T.shape[0]
+            out = np.empty(T.shape)
+            pT, ps, po, ms = T.ctypes.data, status.ctypes.data, out.ctypes.data, PMC_MEM_HOST
+        else:
+            nbatch = T.n // self.nparticles
+            out = DeviceArray(self.ctx, nbatch * self.nparticles)
+            pT, ps, po, ms = T.ptr, status.ptr, out.ptr, PMC_MEM_DEVICE
+        _check(self.ctx.lib.pmc_tracer_reduce_seed(self.h, nbatch, pT, ps, int(kind), po, ms))
+        return out
+
+    def set_adjoint_scratch(self, nbytes=0):
+        """the cap in bytes on the records of one chunk of columns of run_adjoint; 0: 256 MiB.  The results do not depend on
+        it."""
+        _check(self.ctx.lib.pmc_tracer_set_adjoint_scratch(self.h, int(nbytes)))
+
+    def adjoint_chunks(self):
+        """column chunks of the last adjoint launch"""
+        return int(self.ctx.lib.pmc_tracer_adjoint_chunks(self.h))
 
     def Reduce(self, T, status, kind=0):
         """(Q, not_exited) per realization: the mean (MEAN) or minimum (MIN) travel time and the particles that did not exit"""

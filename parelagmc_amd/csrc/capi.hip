@@ -806,6 +806,45 @@ int pmc_darcy_set_tracer(pmc_darcy* d, int level, pmc_tracer* t, int kind) {
         d->impl.set_tracer(level, t ? &t->impl : nullptr, kind);
     });
 }
+int pmc_tracer_run_adjoint(pmc_tracer* t, int nbatch, const double* u, int64_t ld, const double* T_bar, const double* x_exit_bar,
+                           double* u_bar, int64_t ld_bar, double* x0_bar, double* T, int32_t* exit_face, int32_t* status,
+                           int32_t* nsteps, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_tracer_run_adjoint: tracer is NULL");
+        t->impl.run_adjoint(nbatch, u, ld, T_bar, x_exit_bar, u_bar, ld_bar, x0_bar, T, exit_face, status, nsteps, memspace);
+    });
+}
+int pmc_tracer_reduce_seed(pmc_tracer* t, int nbatch, const double* T, const int32_t* status, int kind, double* T_bar, int memspace) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_tracer_reduce_seed: tracer is NULL");
+        t->impl.reduce_seed(nbatch, T, status, kind, T_bar, memspace);
+    });
+}
+int pmc_tracer_set_adjoint_scratch(pmc_tracer* t, int64_t bytes) {
+    return guarded([&] {
+        PMC_REQUIRE(t != nullptr, "pmc_tracer_set_adjoint_scratch: tracer is NULL");
+        t->impl.set_adjoint_scratch(bytes);
+    });
+}
+int pmc_tracer_adjoint_chunks(const pmc_tracer* t) { return t ? t->impl.adj_chunks : PMC_ERR_INVALID; }
+int pmc_darcy_tracer_gradient(pmc_darcy* d, int level, pmc_tracer* t, int nbatch, const double* k, const double* T_bar, int wrt_log,
+                              double* T, int32_t* status, double* grad, double* sol_out, double* adj_out, int memspace,
+                              pmc_stats* stats_fwd, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_tracer_gradient: darcy is NULL");
+        d->impl.tracer_gradient(level, t ? &t->impl : nullptr, nbatch, k, T_bar, wrt_log != 0, T, status, grad, sol_out, adj_out,
+                                memspace, stats_fwd, stats_adj);
+    });
+}
+int pmc_darcy_tracer_loglik_gradient(pmc_darcy* d, int level, pmc_tracer* t, int nbatch, const double* k, const double* data,
+                                     double noise, int wrt_log, double* loglik, double* T, int32_t* not_exited, double* grad,
+                                     int memspace, pmc_stats* stats_adj) {
+    return guarded([&] {
+        PMC_REQUIRE(d != nullptr, "pmc_darcy_tracer_loglik_gradient: darcy is NULL");
+        d->impl.tracer_loglik_gradient(level, t ? &t->impl : nullptr, nbatch, k, data, noise, wrt_log != 0, loglik, T, not_exited,
+                                       grad, memspace, stats_adj);
+    });
+}
 
 // ---- upwind solute transport (transport.hip) ----
 int pmc_transport_create(pmc_ctx* ctx, const pmc_transport_mesh* mesh, const pmc_transport_params* params, pmc_transport** out) {

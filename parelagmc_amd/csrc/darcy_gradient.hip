@@ -405,6 +405,19 @@ void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSp
         zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
         PMC_HIP(hipGetLastError());
         count_kernel_launches(1);
+    } else if (adj.tracer) {
+        // J of the travel times: the walk and its adjoint on the interleaved solution, u_bar straight into the u rows, zero
+        // p rows and essential rows
+        Tracer& T = *adj.tracer;
+        const size_t cnt = (size_t)nb * T.npart;
+        trc_i.ensure(2 * cnt);
+        T.adjoint_launch(st, nb, true, sol.p, nb, 1, adj.tbar_d, nullptr, adj_rhs.p, nb, 1, nullptr, adj.trT_d, trc_i.p,
+                         adj.trstatus_d, trc_i.p + cnt, adj.trdata_d, adj.noise);
+        k::fill(st, (size_t)n_p * nb, adj_rhs.p + (size_t)n_u * nb, 0.0);
+        const size_t tu = (size_t)n_u * nb;
+        zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(1);
     } else {
         if (adj.rhs_d) k::interleave(st, nb, n, adj.rhs_d, nullptr, 1.0, adj_rhs.p);
         else k::broadcast(st, nb, n, d.obs.p, adj_rhs.p);
@@ -711,6 +724,128 @@ void Darcy::transport_loglik_gradient(int level, Transport* t, int nbatch, const
                 const double dd = ch[(size_t)b * nr + i] - data[i];
                 s += dd * dd;
                 if (curve) curve[(size_t)(done + b) * nr + i] = ch[(size_t)b * nr + i];
+            }
+            if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;
+        }
+        done += nb;
+    }
+}
+
+void Darcy::check_tracer(int level, const Tracer* t, const char* who) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, std::string(who) + ": level out of range");
+    PMC_REQUIRE(t != nullptr, std::string(who) + ": tracer is NULL");
+    PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
+                std::string(who) + ": the tracer's mesh does not match the level (n_face != n_u or n_elem != n_p)");
+    PMC_REQUIRE(t->ctx.device == ctx.device, std::string(who) + ": the tracer was created on another device");
+}
+
+void Darcy::tracer_gradient(int level, Tracer* t, int nbatch, const double* kf, const double* T_bar, bool wrt_log, double* T,
+                            int32_t* status, double* grad, double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd,
+                            pmc_stats* stats_adj) {
+    const char* who = "pmc_darcy_tracer_gradient";
+    check_tracer(level, t, who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr && T_bar != nullptr,
+                std::string(who) + ": bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, npt = (size_t)t->npart;
+    const bool host = memspace == PMC_MEM_HOST;
+    std::vector<double> q(kMaxBatch);
+    DevBuf<double> stage_out;
+    int done = 0;
+    while (done < nbatch) {
+        int nb = batch_width(n, true, ctx.device);
+        while (nb > nbatch - done) nb >>= 1;
+        struct { const double *k_d, *tb_d; double *grad_d, *sol_d, *adj_d; } s{
+            kf + done * np, T_bar + done * npt, grad + done * np, sol_out ? sol_out + done * n : nullptr,
+            adj_out ? adj_out + done * n : nullptr};
+        trc_T.ensure(npt * nb);
+        trc_i.ensure(3 * npt * nb);
+        if (host) {
+            ensure(level, nb);
+            stage_grad.ensure(np * nb);
+            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
+            s.k_d = stage_k.p;
+            trc_tb.upload(s.tb_d, npt * nb, st);
+            s.tb_d = trc_tb.p;
+            s.grad_d = stage_grad.p;
+            if (s.sol_d) s.sol_d = stage_sol.p;
+            if (s.adj_d) {
+                stage_out.ensure(n * nb);
+                s.adj_d = stage_out.p;
+            }
+        }
+        AdjointSpec adj;
+        adj.tracer = t;
+        adj.tbar_d = s.tb_d;
+        adj.trT_d = trc_T.p;
+        adj.trstatus_d = trc_i.p + 2 * npt * nb;
+        gradient_chunk(level, nb, s.k_d, adj, wrt_log, q.data(), nullptr, s.grad_d, s.sol_d, s.adj_d,
+                       stats_fwd ? stats_fwd + done : nullptr, stats_adj ? stats_adj + done : nullptr);
+        const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (T) PMC_HIP(hipMemcpyAsync(T + done * npt, trc_T.p, sizeof(double) * npt * nb, back, st));
+        PMC_HIP(hipMemcpyAsync(status + done * npt, adj.trstatus_d, sizeof(int32_t) * npt * nb, back, st));
+        if (host) {
+            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
+            if (sol_out) PMC_HIP(hipMemcpyAsync(sol_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
+            if (adj_out) PMC_HIP(hipMemcpyAsync(adj_out + done * n, stage_out.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
+        }
+        PMC_HIP(hipStreamSynchronize(st));
+        done += nb;
+    }
+}
+
+void Darcy::tracer_loglik_gradient(int level, Tracer* t, int nbatch, const double* kf, const double* data, double noise,
+                                   bool wrt_log, double* loglik, double* T, int32_t* not_exited, double* grad, int memspace,
+                                   pmc_stats* stats_adj) {
+    const char* who = "pmc_darcy_tracer_loglik_gradient";
+    check_tracer(level, t, who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && not_exited != nullptr,
+                std::string(who) + ": bad arguments");
+    PMC_REQUIRE(noise > 0.0, std::string(who) + ": the noise variance must be positive");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    DarcyLevel& d = lv[level];
+    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, npt = (size_t)t->npart;
+    const bool host = memspace == PMC_MEM_HOST;
+    std::vector<double> q(kMaxBatch), th(npt * kMaxBatch);
+    trc_data.upload(data, npt, st);
+    int done = 0;
+    while (done < nbatch) {
+        int nb = batch_width(n, true, ctx.device);
+        while (nb > nbatch - done) nb >>= 1;
+        const double* k_d = kf + done * np;
+        double* grad_d = grad + done * np;
+        trc_T.ensure(npt * nb);
+        trc_i.ensure(3 * npt * nb);
+        if (host) {
+            ensure(level, nb);
+            stage_grad.ensure(np * nb);
+            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
+            k_d = stage_k.p;
+            grad_d = stage_grad.p;
+        }
+        AdjointSpec adj;
+        adj.tracer = t;
+        adj.trdata_d = trc_data.p;
+        adj.noise = noise;
+        adj.trT_d = trc_T.p;
+        adj.trstatus_d = trc_i.p + 2 * npt * nb;
+        gradient_chunk(level, nb, k_d, adj, wrt_log, q.data(), nullptr, grad_d, nullptr, nullptr, nullptr,
+                       stats_adj ? stats_adj + done : nullptr);
+        PMC_HIP(hipMemcpyAsync(th.data(), trc_T.p, sizeof(double) * npt * nb, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipMemcpyAsync(not_exited + done, t->nex.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+        if (host) PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < nb; ++b) {
+            double s = 0.0;
+            for (size_t i = 0; i < npt; ++i) {
+                const double dd = th[(size_t)b * npt + i] - data[i];
+                s += dd * dd;
+                if (T) T[(size_t)(done + b) * npt + i] = th[(size_t)b * npt + i];
             }
             if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;
         }

@@ -280,8 +280,8 @@ void kl_eval_adjoint(hipStream_t st, int n, int m, int nb, const double* phi, co
 
 // Particle travel times on the RT0 flux (tracer.hip, pmc_tracer_*): per element one packed record
 // (faces with the sign folded in, neighbours, porosity, geometry), the particles sorted by start element, and the output
-// buffers of the hooked SolveFwd / the staging of host-memory callers.  Work on ctx's stream, except qoi_interleaved, which
-// runs on the stream of the Darcy handle it is attached to: attach a tracer to one handle at a time.
+// buffers of the hooked SolveFwd / the staging of host-memory callers.  Work on ctx's stream, except qoi_interleaved and
+// adjoint_launch, which run on the stream the Darcy handle passes: a tracer serves one handle at a time.
 struct Tracer {
     Ctx& ctx;
     int kind, n_elem, n_face, npart, max_steps = 0;
@@ -297,6 +297,29 @@ struct Tracer {
     void reduce(int nbatch, const double* T, const int32_t* status, int kind, double* Q, int32_t* not_exited, int memspace);
     // Q of a launch of the Darcy solver: walk on its interleaved solution sol[row * nb + col], reduce into q_d (device, nb)
     void qoi_interleaved(hipStream_t st, int nb, const double* sol, int kind, double* q_d);
+    // the adjoint (pmc_tracer_run_adjoint): per face its elements, local faces and signs; the records
+    // of a launch - per (step, thread) the element, the chosen exit, the entry coordinates, the adjoints of the outward
+    // fluxes and the link of the element's visit list - the list heads per (element, column), and the staging of a host
+    // call.  Scratch of its own: a pmc_tracer_run after an adjoint call finds its buffers as it left them.
+    DevBuf<int32_t> side, adj_elem, adj_code, adj_link, adj_head, adj_i;
+    DevBuf<double> adj_c, adj_fbar, adj_T, adj_stage_u, adj_stage_ubar, adj_stage_tb, adj_stage_xb, adj_stage_x0b, seed_tb;
+    std::vector<int32_t> h_steps;
+    int64_t adj_cap = 0;           // bytes of records per chunk of columns (pmc_tracer_set_adjoint_scratch); 0: 256 MiB
+    int adj_chunks = 0;            // column chunks of the last adjoint_launch
+    void run_adjoint(int nbatch, const double* u, int64_t ld, const double* T_bar, const double* x_exit_bar, double* u_bar,
+                     int64_t ld_bar, double* x0_bar, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps, int memspace);
+    void reduce_seed(int nbatch, const double* T, const int32_t* status, int kind, double* T_bar, int memspace);
+    void set_adjoint_scratch(int64_t bytes);
+    // nb columns on stream st, the flux read through (stride_face, stride_batch): the forward outputs (device, nb x npart,
+    // the caller's particle order), u_bar written through (stride_face_out, stride_batch_out), x0_bar (nb x npart x 3 | NULL)
+    // from the seeds (device, sample-major, each may be NULL)
+    void adjoint_launch(hipStream_t st, int nb, bool by_batch, const double* u_d, int64_t stride_face, int64_t stride_batch,
+                        const double* Tbar_d, const double* xbar_d, double* ubar_d, int64_t stride_face_out,
+                        int64_t stride_batch_out, double* x0bar_d, double* T_d, int32_t* face_d, int32_t* status_d,
+                        int32_t* steps_d, const double* data_d = nullptr, double noise = 1.0);
+    // T_bar = -(T - data) / noise, zero on the columns with nex > 0, into seed_tb (data: device, npart); returns seed_tb.p.
+    // adjoint_launch forms it after its walk when data_d is given (Tbar_d is then ignored) and leaves the counts in nex.
+    const double* loglik_seed(hipStream_t st, int nb, const double* T_d, const double* data_d, double noise);
 
   private:
     void launch_walk(hipStream_t st, int nb, bool by_batch, const double* u_d, int64_t stride_face, int64_t stride_batch,
@@ -530,6 +553,13 @@ struct Darcy {
     void transport_gradient(int level, Transport* t, int nbatch, const double* k, const double* curve_bar, const double* stored_bar,
                             bool wrt_log, double* curve, double* stored, int32_t* status, double* grad, double* sol_out,
                             double* adj_out, int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj);
+    // Gradients in k of the travel times of a tracer on the level's flux (pmc_darcy_tracer_gradient / _tracer_loglik_gradient;
+    // DESIGN.md section 25): gradient_chunk with the tracer's adjoint in front of the adjoint solve.  t is given with the call.
+    void tracer_gradient(int level, Tracer* t, int nbatch, const double* k, const double* T_bar, bool wrt_log, double* T,
+                         int32_t* status, double* grad, double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd,
+                         pmc_stats* stats_adj);
+    void tracer_loglik_gradient(int level, Tracer* t, int nbatch, const double* k, const double* data, double noise, bool wrt_log,
+                                double* loglik, double* T, int32_t* not_exited, double* grad, int memspace, pmc_stats* stats_adj);
     void transport_loglik_gradient(int level, Transport* t, int nbatch, const double* k, const double* data, double noise,
                                    bool wrt_log, double* loglik, double* curve, int32_t* status, double* grad, int memspace,
                                    pmc_stats* stats_adj);
@@ -579,9 +609,18 @@ struct Darcy {
         double* curve_d = nullptr;             // forward outputs of the launch: device, nb x nreport and nb
         double* stored_d = nullptr;
         int32_t* status_h = nullptr;           // host, nb
+        // fourth mode: dJ/du of the travel times of a tracer on the internal solution
+        Tracer* tracer = nullptr;
+        const double* tbar_d = nullptr;        // seed: device, nb x nparticles; ignored with trdata_d
+        const double* trdata_d = nullptr;      // travel-time data (device, nparticles): T_bar = -(T - data) / noise
+        double* trT_d = nullptr;               // forward outputs of the launch: device, nb x nparticles
+        int32_t* trstatus_d = nullptr;
     };
     void check_transport(int level, const Transport* t, const char* who) const;
+    void check_tracer(int level, const Tracer* t, const char* who) const;
     DevBuf<double> tr_curve, tr_stored, tr_cb, tr_sb, tr_data;
+    DevBuf<double> trc_T, trc_tb, trc_data;
+    DevBuf<int32_t> trc_i;
     void ensure_gradient(int level, bool tangent = false);   // tangent: the face-major copy as well
     void ensure_loglik(int level);
     // darcy_hessian.hip

@@ -18,6 +18,7 @@
 #include "handles.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <numeric>
 
@@ -108,8 +109,17 @@ struct Path {
     int32_t exit_face, status, nsteps;
 };
 
+// What a walk leaves behind for the adjoint sweep.  The plain walk keeps nothing: its policy is empty
+// and the kernel of pmc_tracer_run compiles to the code it had before the policy existed.
+struct NoHist {
+    __device__ __forceinline__ void box_step(int, int, const BoxRec&, const Path&, const Pick&) {}
+    __device__ __forceinline__ void tet_step(int, int, double, double, double, double, const Pick&) {}
+    __device__ __forceinline__ void tet_enter(const TetRec&, int) {}
+};
+
+template <class Hist>
 __device__ __forceinline__ void walk(const BoxRec* __restrict__ recs, const double* __restrict__ ub, int64_t stride_face,
-                                     int max_steps, int e, Path& o) {
+                                     int max_steps, int e, Path& o, Hist& hist) {
     {
         const BoxRec& r = recs[e];
         o.x = clampd(o.x, r.lo[0], r.hi[0]);
@@ -128,6 +138,7 @@ __device__ __forceinline__ void walk(const BoxRec* __restrict__ recs, const doub
             o.status = PMC_TRACER_STAGNANT;
             break;
         }
+        hist.box_step(s, e, r, o, p);
         o.T += r.phi * p.dt;
         o.nsteps += 1;
         o.x = box_advance<0>(r, p, o.x, vx, gx);
@@ -158,8 +169,9 @@ __device__ __forceinline__ double tet_advance(const Pick& p, double lam, double 
     return p.which == I ? 0.0 : c;
 }
 
+template <class Hist>
 __device__ __forceinline__ void walk(const TetRec* __restrict__ recs, const double* __restrict__ ub, int64_t stride_face,
-                                     int max_steps, int e, Path& o) {
+                                     int max_steps, int e, Path& o, Hist& hist) {
     double l0, l1, l2, l3;
     {
         const TetRec& r = recs[e];
@@ -185,6 +197,7 @@ __device__ __forceinline__ void walk(const TetRec* __restrict__ recs, const doub
             o.status = PMC_TRACER_STAGNANT;
             break;
         }
+        hist.tet_step(s, e, l0, l1, l2, l3, p);
         o.T += r.phi * p.dt;
         o.nsteps += 1;
         const double eb = tracer_E(b * p.dt);
@@ -206,6 +219,7 @@ __device__ __forceinline__ void walk(const TetRec* __restrict__ recs, const doub
         e = p.nbr;
         const TetRec& q = recs[e];
         const int f = face_id(p.face);
+        hist.tet_enter(q, f);
         // barycentric coordinates in the neighbour; the entry face's is zero exactly
         l0 = face_id(q.face[0]) == f ? 0.0 : tet_lambda<0>(q, o.x, o.y, o.z);
         l1 = face_id(q.face[1]) == f ? 0.0 : tet_lambda<1>(q, o.x, o.y, o.z);
@@ -228,7 +242,8 @@ __global__ __launch_bounds__(kTracerThreads) void tracer_walk_kernel(
     if (part >= npart) return;
     const int p = (int)part;
     Path o{0.0, x0[3 * p], x0[3 * p + 1], x0[3 * p + 2], -1, PMC_TRACER_MAX_STEPS, 0};
-    walk(recs, u + (int64_t)b * stride_batch, stride_face, max_steps, e0[p], o);
+    NoHist none;
+    walk(recs, u + (int64_t)b * stride_batch, stride_face, max_steps, e0[p], o, none);
     const int64_t at = (int64_t)b * npart + orig[p];
     T[at] = o.T;
     exit_face[at] = o.exit_face;
@@ -277,6 +292,434 @@ __global__ __launch_bounds__(kTracerThreads) void tracer_reduce_kernel(int npart
         Q[blockIdx.x] = kind == PMC_TRACER_MEAN ? s / (double)npart : m;
         not_exited[blockIdx.x] = c;
     }
+}
+
+// ---- the adjoint (pmc_tracer_run_adjoint; twin: trace_adjoint) ------------------------------------
+// Three kernels on records of their own.  A second forward walk keeps, per (step, thread), the element, the entry
+// coordinates and the chosen exit; the sweep, one thread per (particle, column), goes through its steps last to first,
+// carrying the adjoints of the time and of the position, and leaves the adjoint of the element's outward fluxes in the
+// record; the assembly, one thread per (face, column), adds them in the fixed order of the contract.  Every array of the
+// records is indexed s * N + tid (N threads of the launch), so a wave reads and writes contiguous runs.
+//
+// The visits of one (element, column) are found through a linked list: the sweep threads push their record index with an
+// integer exchange on the list's head.  The order of the links is arbitrary and never reaches a sum: the assembly picks
+// the visits in ascending (particle in the caller's order, step), kAsmKeys of them per traversal of the list.
+constexpr double kDSeries = 0x1p-3;   // |argument| below which L' and E' are summed as series
+constexpr int kLpTerms = 19, kEpTerms = 11;
+constexpr int kAsmKeys = 32;
+
+constexpr double factorial(int n) { return n <= 1 ? 1.0 : (double)n * factorial(n - 1); }
+
+// The series' coefficients, highest power last: L'(rho) = sum_k (-1)^k k rho^(k - 1) / (k + 1), E'(z) = sum_k k z^(k - 1) /
+// (k + 1)!.  Tables in constant memory and rolled Horner loops: unrolled, the 30 constants are hoisted out of the step loop
+// into scalar registers and the sweep spills them.
+struct SeriesTables {
+    double lp[kLpTerms], ep[kEpTerms];
+};
+constexpr SeriesTables make_series() {
+    SeriesTables t{};
+    for (int k = 1; k <= kLpTerms; ++k) t.lp[k - 1] = (double)((k & 1) ? -k : k) / (double)(k + 1);
+    for (int k = 1; k <= kEpTerms; ++k) t.ep[k - 1] = (double)k / factorial(k + 1);
+    return t;
+}
+__constant__ SeriesTables kSeriesTab = make_series();
+
+__device__ __forceinline__ double tracer_Lp_series(double rho) {
+    double acc = kSeriesTab.lp[kLpTerms - 1];
+#pragma unroll 1
+    for (int k = kLpTerms - 2; k >= 0; --k) acc = kSeriesTab.lp[k] + rho * acc;
+    return acc;
+}
+__device__ __forceinline__ double tracer_Ep_series(double z) {
+    double acc = kSeriesTab.ep[kEpTerms - 1];
+#pragma unroll 1
+    for (int k = kEpTerms - 2; k >= 0; --k) acc = kSeriesTab.ep[k] + z * acc;
+    return acc;
+}
+
+struct HistView {
+    int64_t N, SN;        // threads of the launch; S * N
+    int S;                // steps a record holds: the largest step count of the launch
+    int32_t* elem;
+    int32_t* code;        // box: axis | up << 2; tet: local exit face | (1 + local entry face, 0 at the start) << 2
+    double* c;            // entry coordinates, c[k * SN + s * N + tid]: x, y, z of a box, lambda_0..3 of a tetrahedron
+};
+
+struct KeepHist {
+    HistView h;
+    int64_t tid;
+    int entry;
+    __device__ __forceinline__ void box_step(int s, int e, const BoxRec& r, const Path& o, const Pick& p) {
+        if (s >= h.S) return;
+        const int64_t i = (int64_t)s * h.N + tid;
+        const double hi = p.which == 0 ? r.hi[0] : p.which == 1 ? r.hi[1] : r.hi[2];
+        h.elem[i] = e;
+        h.code[i] = p.which | (p.bound == hi ? 4 : 0);
+        h.c[i] = o.x;
+        h.c[h.SN + i] = o.y;
+        h.c[2 * h.SN + i] = o.z;
+    }
+    __device__ __forceinline__ void tet_step(int s, int e, double l0, double l1, double l2, double l3, const Pick& p) {
+        if (s >= h.S) return;
+        const int64_t i = (int64_t)s * h.N + tid;
+        h.elem[i] = e;
+        h.code[i] = p.which | (entry << 2);
+        h.c[i] = l0;
+        h.c[h.SN + i] = l1;
+        h.c[2 * h.SN + i] = l2;
+        h.c[3 * h.SN + i] = l3;
+    }
+    __device__ __forceinline__ void tet_enter(const TetRec& q, int f) {
+        entry = face_id(q.face[0]) == f ? 1 : face_id(q.face[1]) == f ? 2 : face_id(q.face[2]) == f ? 3 : 4;
+    }
+};
+
+// thread -> (particle in sorted order, column of the launch, record slot), the mapping of tracer_walk_kernel
+__device__ __forceinline__ bool adjoint_thread(int npart, int nb, int by_batch, int& p, int& b, int64_t& tid) {
+    const int64_t gid = (int64_t)blockIdx.x * kTracerThreads + threadIdx.x;
+    const int64_t part = by_batch ? gid / nb : gid;
+    b = by_batch ? (int)(gid % nb) : (int)blockIdx.y;
+    if (part >= npart) return false;
+    p = (int)part;
+    tid = by_batch ? gid : (int64_t)b * npart + part;
+    return true;
+}
+
+template <class Rec>
+__global__ __launch_bounds__(kTracerThreads) void tracer_history_kernel(
+    const Rec* __restrict__ recs, int npart, int nb, int by_batch, const double* __restrict__ x0,
+    const int32_t* __restrict__ e0, int max_steps, const double* __restrict__ u, int64_t stride_face, int64_t stride_batch,
+    HistView h) {
+    int p, b;
+    int64_t tid;
+    if (!adjoint_thread(npart, nb, by_batch, p, b, tid)) return;
+    Path o{0.0, x0[3 * p], x0[3 * p + 1], x0[3 * p + 2], -1, PMC_TRACER_MAX_STEPS, 0};
+    KeepHist keep{h, tid, 0};
+    walk(recs, u + (int64_t)b * stride_batch, stride_face, max_steps, e0[p], o, keep);
+}
+
+struct BoxAxis {
+    double lo, h, area, vlo, vhi, g, v, x;
+};
+template <int A, int LO, int HI>
+__device__ __forceinline__ BoxAxis box_axis_values(const BoxRec& r, const double* __restrict__ ub, int64_t stride_face,
+                                                   double vol, double x) {
+    BoxAxis a;
+    a.lo = r.lo[A];
+    a.h = r.hi[A] - a.lo;
+    a.area = vol / a.h;
+    a.vlo = -face_flux(ub, stride_face, r.face[LO]) / a.area;
+    a.vhi = face_flux(ub, stride_face, r.face[HI]) / a.area;
+    a.g = (a.vhi - a.vlo) / a.h;
+    a.v = a.vlo + a.g * (x - a.lo);
+    a.x = x;
+    return a;
+}
+// E(z) and E'(z) = (e^z - E) / z from one expm1; L(rho) and L'(rho) = (1 / (1 + rho) - L) / rho from one log1p
+__device__ __forceinline__ void tracer_E_both(double z, double& E, double& Ep) {
+    const double az = fabs(z);
+    const double em = expm1(z);
+    E = az < kSeries ? (1.0 + z / 2.0) + z * z / 6.0 : em / z;
+    Ep = az < kDSeries ? tracer_Ep_series(z) : ((em + 1.0) - em / z) / z;
+}
+__device__ __forceinline__ void tracer_L_both(double rho, double& L, double& Lp) {
+    const double ar = fabs(rho);
+    const double lg = log1p(rho);
+    L = ar < kSeries ? (1.0 - rho / 2.0) + rho * rho / 3.0 : lg / rho;
+    Lp = ar < kDSeries ? tracer_Lp_series(rho) : (1.0 / (1.0 + rho) - lg / rho) / rho;
+}
+
+// a coordinate that is not the exit's: c = x + (v dt) E(g dt)
+__device__ __forceinline__ void box_axis_back(double g, double v, double cb, double dt, double& dtb, double& vb, double& gb) {
+    const double z = g * dt;
+    double E, Ep;
+    tracer_E_both(z, E, Ep);
+    const double mb = cb * E;
+    const double zb = (cb * (v * dt)) * Ep;
+    vb = mb * dt;
+    gb = zb * dt;
+    dtb = dtb + mb * v;
+    dtb = dtb + zb * g;
+}
+__device__ __forceinline__ void box_axis_flux(const BoxAxis& a, bool is_exit, bool up, double vexb, double vb, double gb,
+                                              double& xin, double& fb_lo, double& fb_hi) {
+    const double gba = gb + vb * (a.x - a.lo);
+    xin = xin + vb * a.g;
+    double vlob = vb - gba / a.h;
+    double vhib = gba / a.h;
+    if (is_exit) {
+        if (up) vhib = vhib + vexb;
+        else vlob = vlob + vexb;
+    }
+    fb_lo = -vlob / a.area;
+    fb_hi = vhib / a.area;
+}
+
+// One step backwards (twin: _step_adjoint): xb0..2 holds the adjoint of the position after the step and receives that of
+// the position at its entry; the adjoints of the outward fluxes go to fb[l * SN]
+__device__ __forceinline__ void sweep_step(const BoxRec& r, const double* __restrict__ ub, int64_t stride_face,
+                                           const double* __restrict__ c, int64_t SN, int code, double Tbar, double& xb0,
+                                           double& xb1, double& xb2, double* __restrict__ fb) {
+    const double vol = ((r.hi[0] - r.lo[0]) * (r.hi[1] - r.lo[1])) * (r.hi[2] - r.lo[2]);
+    const BoxAxis a0 = box_axis_values<0, 4, 2>(r, ub, stride_face, vol, c[0]);
+    const BoxAxis a1 = box_axis_values<1, 1, 3>(r, ub, stride_face, vol, c[SN]);
+    const BoxAxis a2 = box_axis_values<2, 0, 5>(r, ub, stride_face, vol, c[2 * SN]);
+    const int A = code & 3;
+    const bool up = (code & 4) != 0;
+#define PMC_SEL(m) (A == 0 ? a0.m : A == 1 ? a1.m : a2.m)
+    const double vA = PMC_SEL(v), xA = PMC_SEL(x), loA = PMC_SEL(lo);
+    const double vex = up ? PMC_SEL(vhi) : PMC_SEL(vlo);
+#undef PMC_SEL
+    const double hiA = A == 0 ? r.hi[0] : A == 1 ? r.hi[1] : r.hi[2];
+    const double dist = up ? hiA - xA : loA - xA;
+    const double q = dist / vA;
+    const double rho = (vex - vA) / vA;
+    double Lr, Lpr;
+    tracer_L_both(rho, Lr, Lpr);
+    const double dt = q * Lr;
+    double dtb = r.phi * Tbar;
+    // the two coordinates that are not the exit's, in ascending order
+    const bool pf = A == 0, qf = A == 2;             // the first is axis 1 instead of 0; the second is axis 1 instead of 2
+    double vbp, gbp, vbq, gbq;
+    box_axis_back(pf ? a1.g : a0.g, pf ? a1.v : a0.v, pf ? xb1 : xb0, dt, dtb, vbp, gbp);
+    box_axis_back(qf ? a1.g : a2.g, qf ? a1.v : a2.v, qf ? xb1 : xb2, dt, dtb, vbq, gbq);
+    const double qb = dtb * Lr;
+    const double rb = (dtb * q) * Lpr;
+    const double vexb = rb / vA;
+    const double vbA = -(qb * q) / vA - (rb * (1.0 + rho)) / vA;
+    const double xinA = -(qb / vA);
+    double xin0 = A == 0 ? xinA : xb0, xin1 = A == 1 ? xinA : xb1, xin2 = A == 2 ? xinA : xb2;
+    const double vb0 = A == 0 ? vbA : vbp, vb1 = A == 1 ? vbA : A == 0 ? vbp : vbq, vb2 = A == 2 ? vbA : vbq;
+    const double gb0 = A == 0 ? 0.0 : gbp, gb1 = A == 1 ? 0.0 : A == 0 ? gbp : gbq, gb2 = A == 2 ? 0.0 : gbq;
+    double f0, f1, f2, f3, f4, f5;
+    box_axis_flux(a0, A == 0, up, vexb, vb0, gb0, xin0, f4, f2);
+    box_axis_flux(a1, A == 1, up, vexb, vb1, gb1, xin1, f1, f3);
+    box_axis_flux(a2, A == 2, up, vexb, vb2, gb2, xin2, f0, f5);
+    fb[0] = f0;
+    fb[SN] = f1;
+    fb[2 * SN] = f2;
+    fb[3 * SN] = f3;
+    fb[4 * SN] = f4;
+    fb[5 * SN] = f5;
+    xb0 = xin0;
+    xb1 = xin1;
+    xb2 = xin2;
+}
+
+__device__ __forceinline__ void sweep_step(const TetRec& r, const double* __restrict__ ub, int64_t stride_face,
+                                           const double* __restrict__ c, int64_t SN, int code, double Tbar, double& xb0,
+                                           double& xb1, double& xb2, double* __restrict__ fb) {
+    const int A = code & 3, entry = (code >> 2) - 1;
+    double F[4], lam[4], w[4], v[4], lnb[4], lamb[4], vb[4], wb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        F[i] = face_flux(ub, stride_face, r.face[i]);
+        lam[i] = c[i * SN];
+    }
+    const double c3 = 3.0 * r.vol;
+    const double b = (((F[0] + F[1]) + F[2]) + F[3]) / c3;
+    double lamA = 0.0, vA = 0.0, wA = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        w[i] = F[i] / c3;
+        v[i] = b * lam[i] - w[i];
+        if (i == A) {
+            lamA = lam[i];
+            vA = v[i];
+            wA = w[i];
+        }
+    }
+    const double q = -lamA / vA;
+    const double rho = (-wA - vA) / vA;
+    double Lr, Lpr, eb, ebp;
+    tracer_L_both(rho, Lr, Lpr);
+    const double dt = q * Lr;
+    const double z = b * dt;
+    tracer_E_both(z, eb, ebp);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) lnb[j] = (r.edge[j][0] * xb0 + r.edge[j][1] * xb1) + r.edge[j][2] * xb2;
+    lnb[3] = 0.0;
+    double dtb = r.phi * Tbar, ebb = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i == A) lnb[i] = 0.0;
+        const double mb = lnb[i] * eb;
+        ebb = ebb + lnb[i] * (v[i] * dt);
+        lamb[i] = lnb[i];
+        vb[i] = mb * dt;
+        wb[i] = 0.0;
+        dtb = dtb + mb * v[i];
+    }
+    const double zb = ebb * ebp;
+    double bb = zb * dt;
+    dtb = dtb + zb * b;
+    const double qb = dtb * Lr;
+    const double rb = (dtb * q) * Lpr;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i == A) {
+            lamb[i] = lamb[i] - qb / vA;
+            vb[i] = (vb[i] - (qb * q) / vA) - (rb * (1.0 + rho)) / vA;
+            wb[i] = -(rb / vA);
+        }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        bb = bb + vb[i] * lam[i];
+        lamb[i] = lamb[i] + vb[i] * b;
+        wb[i] = wb[i] - vb[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        fb[i * SN] = (wb[i] + bb) / c3;
+        if (i == entry) lamb[i] = 0.0;                 // the entry face's coordinate was set, not computed
+    }
+    xb0 = ((r.row[0][0] * lamb[0] + r.row[1][0] * lamb[1]) + r.row[2][0] * lamb[2]) + r.row[3][0] * lamb[3];
+    xb1 = ((r.row[0][1] * lamb[0] + r.row[1][1] * lamb[1]) + r.row[2][1] * lamb[2]) + r.row[3][1] * lamb[3];
+    xb2 = ((r.row[0][2] * lamb[0] + r.row[1][2] * lamb[1]) + r.row[2][2] * lamb[2]) + r.row[3][2] * lamb[3];
+}
+
+// link[i] = (the record pushed before i on the list of its (element, column), the particle's index in the caller's order)
+template <class Rec>
+__global__ __launch_bounds__(kTracerThreads) void tracer_sweep_kernel(
+    const Rec* __restrict__ recs, int npart, int nb, int by_batch, const int32_t* __restrict__ orig,
+    const double* __restrict__ u, int64_t stride_face, int64_t stride_batch, HistView h, const int32_t* __restrict__ status,
+    const int32_t* __restrict__ nsteps, const double* __restrict__ T_bar, const double* __restrict__ xe_bar,
+    double* __restrict__ fbar, int2* __restrict__ link, int32_t* __restrict__ head, double* __restrict__ x0_bar) {
+    int p, b;
+    int64_t tid;
+    if (!adjoint_thread(npart, nb, by_batch, p, b, tid)) return;
+    const int32_t op = orig[p];
+    const int64_t at = (int64_t)b * npart + op;
+    double xb0 = 0.0, xb1 = 0.0, xb2 = 0.0;
+    if (status[at] == PMC_TRACER_EXITED) {
+        const double Tb = T_bar ? T_bar[at] : 0.0;
+        if (xe_bar) {
+            xb0 = xe_bar[3 * at];
+            xb1 = xe_bar[3 * at + 1];
+            xb2 = xe_bar[3 * at + 2];
+        }
+        const double* ub = u + (int64_t)b * stride_batch;
+        const int ns = min(nsteps[at], h.S);
+        for (int s = ns - 1; s >= 0; --s) {
+            const int64_t i = (int64_t)s * h.N + tid;
+            const int e = h.elem[i];
+            sweep_step(recs[e], ub, stride_face, h.c + i, h.SN, h.code[i], Tb, xb0, xb1, xb2, fbar + i);
+            const int prev = atomicExch(&head[(int64_t)e * nb + b], (int)i);
+            link[i] = make_int2(prev, op);
+        }
+    }
+    if (x0_bar) {
+        x0_bar[3 * at] = xb0;
+        x0_bar[3 * at + 1] = xb1;
+        x0_bar[3 * at + 2] = xb2;
+    }
+}
+
+// u_bar of one (face, column): from 0.0, over the (at most two) elements of the face in the order of face_elem, within an
+// element over its visits in ascending (particle in the caller's order, step).  side[2 f + k] = element << 4 | local face
+// << 1 | (outward normal against the global one), -1 for no element.  A key is particle << 32 | record index: for one
+// particle of one column the record index ascends with the step.
+__global__ __launch_bounds__(kTracerThreads) void tracer_assemble_kernel(
+    int n_face, int nb, int by_batch, const int32_t* __restrict__ side, const int32_t* __restrict__ head,
+    const int2* __restrict__ link, const double* __restrict__ fbar, int64_t SN, double* __restrict__ u_bar,
+    int64_t stride_face, int64_t stride_batch) {
+    const int64_t gid = (int64_t)blockIdx.x * kTracerThreads + threadIdx.x;
+    const int64_t f = by_batch ? gid / nb : gid;
+    const int b = by_batch ? (int)(gid % nb) : (int)blockIdx.y;
+    if (f >= n_face) return;
+    constexpr int64_t kNone = INT64_MAX;
+    double acc = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const int32_t enc = side[2 * f + k];
+        if (enc < 0) continue;
+        const int hd = head[(int64_t)(enc >> 4) * nb + b];
+        if (hd < 0) continue;
+        const double* fb = fbar + (int64_t)((enc >> 1) & 7) * SN;
+        const bool neg = (enc & 1) != 0;
+        int64_t last = -1;
+        for (;;) {
+            int64_t key[kAsmKeys];
+#pragma unroll
+            for (int j = 0; j < kAsmKeys; ++j) key[j] = kNone;
+            for (int n = hd; n >= 0;) {
+                const int2 l = link[n];
+                int64_t cand = ((int64_t)l.y << 32) | (int64_t)n;
+                n = l.x;
+                if (cand <= last || cand >= key[kAsmKeys - 1]) continue;
+#pragma unroll
+                for (int j = 0; j < kAsmKeys; ++j)       // insert into the ascending keys
+                    if (cand < key[j]) {
+                        const int64_t t = key[j];
+                        key[j] = cand;
+                        cand = t;
+                    }
+            }
+#pragma unroll
+            for (int j = 0; j < kAsmKeys; ++j)
+                if (key[j] != kNone) {
+                    const double v = fb[key[j] & 0x7fffffff];
+                    acc = acc + (neg ? -v : v);
+                    last = key[j];
+                }
+            if (key[kAsmKeys - 1] == kNone) break;
+        }
+    }
+    u_bar[f * stride_face + (int64_t)b * stride_batch] = acc;
+}
+
+// T_bar of the QoI of tracer_reduce_kernel: MEAN 1 / npart on the particles that exited; MIN 1 on the lowest-index particle
+// attaining the minimum, if it exited.  One workgroup per column.
+__global__ __launch_bounds__(kTracerThreads) void tracer_seed_kernel(int npart, const double* __restrict__ T,
+                                                                     const int32_t* __restrict__ status, int kind,
+                                                                     double* __restrict__ T_bar) {
+    __shared__ double wmin[kTracerThreads / 64];
+    __shared__ int widx[kTracerThreads / 64];
+    __shared__ int arg;
+    const int64_t base = (int64_t)blockIdx.x * npart;
+    if (kind == PMC_TRACER_MIN) {
+        double mn = INFINITY;
+        int at = INT_MAX;
+        for (int i = threadIdx.x; i < npart; i += kTracerThreads) {
+            const double t = T[base + i];
+            if (t < mn) {
+                mn = t;
+                at = i;
+            }
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double om = __shfl_xor(mn, off, 64);
+            const int oa = __shfl_xor(at, off, 64);
+            if (om < mn || (om == mn && oa < at)) {
+                mn = om;
+                at = oa;
+            }
+        }
+        if ((threadIdx.x & 63) == 0) {
+            wmin[threadIdx.x >> 6] = mn;
+            widx[threadIdx.x >> 6] = at;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < kTracerThreads / 64; ++w)
+                if (wmin[w] < mn || (wmin[w] == mn && widx[w] < at)) {
+                    mn = wmin[w];
+                    at = widx[w];
+                }
+            arg = at;
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < npart; i += kTracerThreads) {
+        const bool ok = status[base + i] == PMC_TRACER_EXITED;
+        T_bar[base + i] = !ok ? 0.0 : kind == PMC_TRACER_MEAN ? 1.0 / (double)npart : i == arg ? 1.0 : 0.0;
+    }
+}
+
+// T_bar = -(T - data) / noise (the seed of the travel-time log-likelihood); zero on a column that has a censored particle
+__global__ void tracer_loglik_seed_kernel(int64_t total, int npart, const double* __restrict__ T, const double* __restrict__ data,
+                                          const int32_t* __restrict__ not_exited, double noise, double* __restrict__ T_bar) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) T_bar[i] = not_exited[i / npart] > 0 ? 0.0 : -(T[i] - data[i % npart]) / noise;
 }
 
 // ---- host: setup ------------------------------------------------------------------------------------------------------
@@ -424,12 +867,24 @@ Tracer::Tracer(Ctx& c, const pmc_tracer_mesh& m, int nparticles, const double* x
         es[p] = elem0[order[p]];
         for (int d = 0; d < 3; ++d) xs[3 * (size_t)p + d] = x0_in[3 * (size_t)order[p] + d];
     }
+    // the adjoint's assembly: per face its (at most two) elements in the order of face_elem, with the local face and the sign
+    std::vector<int32_t> side_h(2 * (size_t)n_face, -1);
+    if (n_elem < (1 << 27))
+        for (int f = 0; f < n_face; ++f)
+            for (int k = 0; k < 2; ++k) {
+                const int32_t e = m.face_elem[2 * (size_t)f + k];
+                if (e < 0) continue;
+                for (int l = 0; l < nfe; ++l)
+                    if (m.elem_face[(size_t)e * nfe + l] == f)
+                        side_h[2 * (size_t)f + k] = (e << 4) | (l << 1) | (m.elem_sign[(size_t)e * nfe + l] > 0 ? 0 : 1);
+            }
     ctx.activate();
     hipStream_t st = ctx.stream;
     recs.upload(rec_h, st);
     x0.upload(xs, st);
     e0.upload(es, st);
     orig.upload(order, st);
+    side.upload(side_h, st);
     PMC_HIP(hipStreamSynchronize(st));
 }
 
@@ -537,6 +992,176 @@ void Tracer::qoi_interleaved(hipStream_t st, int nb, const double* sol, int qkin
     nex.ensure(nb);
     launch_walk(st, nb, true, sol, nb, 1, out_T.p, out_i.p, out_i.p + cnt, out_i.p + 2 * cnt, nullptr);
     launch_reduce(st, nb, out_T.p, out_i.p + cnt, qkind, q_d, nex.p);
+}
+
+// ---- host: the adjoint --------------------------------------------------------------------------------------------------
+void Tracer::set_adjoint_scratch(int64_t bytes) {
+    PMC_REQUIRE(bytes >= 0, "pmc_tracer_set_adjoint_scratch: bytes must not be negative");
+    adj_cap = bytes;
+}
+
+// One adjoint launch of nb columns on stream st: the plain walk (the forward outputs, pmc_tracer_run's), then per chunk of
+// columns the walk with history, the sweep and the assembly.  A chunk is as many columns as keep the records of the largest
+// step count under the cap (at least one).  Nothing a column receives depends on its chunk: a thread meets only its own
+// records, and the assembly orders a list by (particle, step).  Synchronises st once, for the step counts.
+void Tracer::adjoint_launch(hipStream_t st, int nb, bool by_batch, const double* u_d, int64_t stride_face, int64_t stride_batch,
+                            const double* Tbar_d, const double* xbar_d, double* ubar_d, int64_t stride_face_out,
+                            int64_t stride_batch_out, double* x0bar_d, double* T_d, int32_t* face_d, int32_t* status_d,
+                            int32_t* steps_d, const double* data_d, double noise) {
+    PMC_REQUIRE(n_elem < (1 << 27), "pmc_tracer_run_adjoint: more than 2^27 elements");
+    launch_walk(st, nb, by_batch, u_d, stride_face, stride_batch, T_d, face_d, status_d, steps_d, nullptr);
+    if (data_d) {
+        // the seed of the log-likelihood, zero on a column with a particle that did not exit (nex: their count per column)
+        q.ensure(nb);
+        nex.ensure(nb);
+        launch_reduce(st, nb, T_d, status_d, PMC_TRACER_MEAN, q.p, nex.p);
+        Tbar_d = loglik_seed(st, nb, T_d, data_d, noise);
+    }
+    const size_t cnt = (size_t)nb * npart;
+    h_steps.resize(cnt);
+    PMC_HIP(hipMemcpyAsync(h_steps.data(), steps_d, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+    const int S = std::max(1, *std::max_element(h_steps.begin(), h_steps.end()));
+    const bool box = kind == PMC_TRACER_BOX;
+    const int nc = box ? 3 : 4, nf = box ? 6 : 4;
+    const size_t per_visit = 16 + 8 * (size_t)(nc + nf);          // element, code, link; coordinates and flux adjoints
+    const size_t per_col = per_visit * (size_t)S * npart + sizeof(int32_t) * (size_t)n_elem;
+    const size_t cap = adj_cap > 0 ? (size_t)adj_cap : (size_t)256 << 20;
+    int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)nb, cap / per_col));
+    // record indices and the sample-major grid: 2^31 records and 32768 columns per chunk at the most
+    while (per > 1 && (size_t)S * npart * per >= ((size_t)1 << 31)) per >>= 1;
+    PMC_REQUIRE((size_t)S * npart * per < ((size_t)1 << 31), "pmc_tracer_run_adjoint: the records of one column pass 2^31");
+    if (!by_batch) per = std::min(per, 32768);
+    adj_chunks = (nb + per - 1) / per;
+    const size_t SNmax = (size_t)S * npart * per;
+    adj_elem.ensure(SNmax);
+    adj_code.ensure(SNmax);
+    adj_link.ensure(2 * SNmax);
+    adj_c.ensure(nc * SNmax);
+    adj_fbar.ensure(nf * SNmax);
+    adj_head.ensure((size_t)n_elem * per);
+    for (int b0 = 0; b0 < nb; b0 += per) {
+        const int n = std::min(per, nb - b0);
+        const int64_t N = (int64_t)npart * n, SN = N * S;
+        const HistView h{N, SN, S, adj_elem.p, adj_code.p, adj_c.p};
+        const int64_t o = (int64_t)b0 * npart;
+        const double* ub = u_d + (int64_t)b0 * stride_batch;
+        const dim3 grid((unsigned)(((by_batch ? N : (int64_t)npart) + kTracerThreads - 1) / kTracerThreads), by_batch ? 1u : (unsigned)n);
+        const dim3 agrid((unsigned)(((by_batch ? (int64_t)n_face * n : (int64_t)n_face) + kTracerThreads - 1) / kTracerThreads),
+                         by_batch ? 1u : (unsigned)n);
+        PMC_HIP(hipMemsetAsync(adj_head.p, 0xff, sizeof(int32_t) * (size_t)n_elem * n, st));
+        int2* link = reinterpret_cast<int2*>(adj_link.p);
+        const double* tb = Tbar_d ? Tbar_d + o : nullptr;
+        const double* xb = xbar_d ? xbar_d + 3 * o : nullptr;
+        double* x0b = x0bar_d ? x0bar_d + 3 * o : nullptr;
+        if (box) {
+            const BoxRec* R = reinterpret_cast<const BoxRec*>(recs.p);
+            tracer_history_kernel<BoxRec><<<grid, kTracerThreads, 0, st>>>(R, npart, n, by_batch ? 1 : 0, x0.p, e0.p, max_steps, ub,
+                                                                           stride_face, stride_batch, h);
+            tracer_sweep_kernel<BoxRec><<<grid, kTracerThreads, 0, st>>>(R, npart, n, by_batch ? 1 : 0, orig.p, ub, stride_face,
+                                                                         stride_batch, h, status_d + o, steps_d + o, tb, xb,
+                                                                         adj_fbar.p, link, adj_head.p, x0b);
+        } else {
+            const TetRec* R = reinterpret_cast<const TetRec*>(recs.p);
+            tracer_history_kernel<TetRec><<<grid, kTracerThreads, 0, st>>>(R, npart, n, by_batch ? 1 : 0, x0.p, e0.p, max_steps, ub,
+                                                                           stride_face, stride_batch, h);
+            tracer_sweep_kernel<TetRec><<<grid, kTracerThreads, 0, st>>>(R, npart, n, by_batch ? 1 : 0, orig.p, ub, stride_face,
+                                                                         stride_batch, h, status_d + o, steps_d + o, tb, xb,
+                                                                         adj_fbar.p, link, adj_head.p, x0b);
+        }
+        tracer_assemble_kernel<<<agrid, kTracerThreads, 0, st>>>(n_face, n, by_batch ? 1 : 0, side.p, adj_head.p, link, adj_fbar.p, SN,
+                                                                 ubar_d + (int64_t)b0 * stride_batch_out, stride_face_out,
+                                                                 stride_batch_out);
+        PMC_HIP(hipGetLastError());
+        count_kernel_launches(3);
+    }
+}
+
+void Tracer::run_adjoint(int nbatch, const double* u, int64_t ld, const double* T_bar, const double* x_exit_bar, double* u_bar,
+                         int64_t ld_bar, double* x0_bar, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps,
+                         int memspace) {
+    PMC_REQUIRE(nbatch >= 1, "pmc_tracer_run_adjoint: nbatch must be at least 1");
+    PMC_REQUIRE(u && u_bar && status, "pmc_tracer_run_adjoint: NULL array");
+    PMC_REQUIRE(T_bar || x_exit_bar, "pmc_tracer_run_adjoint: T_bar or x_exit_bar must be given");
+    PMC_REQUIRE(ld >= n_face && ld_bar >= n_face, "pmc_tracer_run_adjoint: ld or ld_bar is smaller than the number of faces");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "pmc_tracer_run_adjoint: bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const bool host = memspace == PMC_MEM_HOST;
+    // pieces as in run: at most 2^24 staged flux values
+    const int per = host ? (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t(1) << 24) / n_face)) : nbatch;
+    const size_t cnt = (size_t)per * npart;
+    adj_T.ensure(cnt);
+    adj_i.ensure(3 * cnt);
+    if (host) {
+        adj_stage_u.ensure((size_t)per * n_face);
+        adj_stage_ubar.ensure((size_t)per * n_face);
+        if (T_bar) adj_stage_tb.ensure(cnt);
+        if (x_exit_bar) adj_stage_xb.ensure(3 * cnt);
+        if (x0_bar) adj_stage_x0b.ensure(3 * cnt);
+    }
+    for (int b0 = 0; b0 < nbatch; b0 += per) {
+        const int n = std::min(per, nbatch - b0);
+        const size_t c = (size_t)n * npart, o = (size_t)b0 * npart;
+        // forward outputs the caller did not ask for go to scratch
+        double* T_d = !host && T ? T + o : adj_T.p;
+        int32_t* face_d = !host && exit_face ? exit_face + o : adj_i.p;
+        int32_t* status_d = !host ? status + o : adj_i.p + cnt;
+        int32_t* steps_d = !host && nsteps ? nsteps + o : adj_i.p + 2 * cnt;
+        if (!host) {
+            adjoint_launch(st, n, false, u + (size_t)b0 * ld, 1, ld, T_bar ? T_bar + o : nullptr, x_exit_bar ? x_exit_bar + 3 * o : nullptr,
+                           u_bar + (size_t)b0 * ld_bar, 1, ld_bar, x0_bar ? x0_bar + 3 * o : nullptr, T_d, face_d, status_d, steps_d);
+            PMC_HIP(hipStreamSynchronize(st));
+            continue;
+        }
+        PMC_HIP(hipMemcpy2DAsync(adj_stage_u.p, sizeof(double) * n_face, u + (size_t)b0 * ld, sizeof(double) * ld,
+                                 sizeof(double) * n_face, n, hipMemcpyHostToDevice, st));
+        if (T_bar) PMC_HIP(hipMemcpyAsync(adj_stage_tb.p, T_bar + o, sizeof(double) * c, hipMemcpyHostToDevice, st));
+        if (x_exit_bar) PMC_HIP(hipMemcpyAsync(adj_stage_xb.p, x_exit_bar + 3 * o, sizeof(double) * 3 * c, hipMemcpyHostToDevice, st));
+        adjoint_launch(st, n, false, adj_stage_u.p, 1, n_face, T_bar ? adj_stage_tb.p : nullptr, x_exit_bar ? adj_stage_xb.p : nullptr,
+                       adj_stage_ubar.p, 1, n_face, x0_bar ? adj_stage_x0b.p : nullptr, T_d, face_d, status_d, steps_d);
+        PMC_HIP(hipMemcpy2DAsync(u_bar + (size_t)b0 * ld_bar, sizeof(double) * ld_bar, adj_stage_ubar.p, sizeof(double) * n_face,
+                                 sizeof(double) * n_face, n, hipMemcpyDeviceToHost, st));
+        if (x0_bar) PMC_HIP(hipMemcpyAsync(x0_bar + 3 * o, adj_stage_x0b.p, sizeof(double) * 3 * c, hipMemcpyDeviceToHost, st));
+        if (T) PMC_HIP(hipMemcpyAsync(T + o, T_d, sizeof(double) * c, hipMemcpyDeviceToHost, st));
+        if (exit_face) PMC_HIP(hipMemcpyAsync(exit_face + o, face_d, sizeof(int32_t) * c, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipMemcpyAsync(status + o, status_d, sizeof(int32_t) * c, hipMemcpyDeviceToHost, st));
+        if (nsteps) PMC_HIP(hipMemcpyAsync(nsteps + o, steps_d, sizeof(int32_t) * c, hipMemcpyDeviceToHost, st));
+        PMC_HIP(hipStreamSynchronize(st));
+    }
+}
+
+void Tracer::reduce_seed(int nbatch, const double* T, const int32_t* status, int qkind, double* T_bar, int memspace) {
+    PMC_REQUIRE(nbatch >= 1, "pmc_tracer_reduce_seed: nbatch must be at least 1");
+    PMC_REQUIRE(T && status && T_bar, "pmc_tracer_reduce_seed: NULL array");
+    PMC_REQUIRE(qkind == PMC_TRACER_MEAN || qkind == PMC_TRACER_MIN, "pmc_tracer_reduce_seed: kind must be PMC_TRACER_MEAN or _MIN");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, "pmc_tracer_reduce_seed: bad memspace");
+    ctx.activate();
+    hipStream_t st = ctx.stream;
+    const size_t cnt = (size_t)nbatch * npart;
+    const bool host = memspace == PMC_MEM_HOST;
+    if (host) {
+        red_T.ensure(cnt);
+        red_s.ensure(cnt);
+        seed_tb.ensure(cnt);
+        PMC_HIP(hipMemcpyAsync(red_T.p, T, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        PMC_HIP(hipMemcpyAsync(red_s.p, status, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, st));
+    }
+    tracer_seed_kernel<<<(unsigned)nbatch, kTracerThreads, 0, st>>>(npart, host ? red_T.p : T, host ? red_s.p : status, qkind,
+                                                                    host ? seed_tb.p : T_bar);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    if (host) PMC_HIP(hipMemcpyAsync(T_bar, seed_tb.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+    PMC_HIP(hipStreamSynchronize(st));
+}
+
+const double* Tracer::loglik_seed(hipStream_t st, int nb, const double* T_d, const double* data_d, double noise) {
+    const int64_t total = (int64_t)nb * npart;
+    seed_tb.ensure((size_t)total);
+    tracer_loglik_seed_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(total, npart, T_d, data_d, nex.p, noise, seed_tb.p);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+    return seed_tb.p;
 }
 
 }  // namespace pmc

@@ -311,3 +311,442 @@ def reduce(T, status, kind=MEAN):
     T = np.atleast_2d(T)
     q = T.mean(axis=1) if kind == MEAN else T.min(axis=1)
     return q, (np.atleast_2d(status) != EXITED).sum(axis=1).astype(np.int32)
+
+
+# ---- tangent and adjoint of the walk (the kernels of pmc_tracer_run_adjoint follow them) ----------
+# The walk is differentiated with its decisions held: the element sequence, the step count, the chosen exit of every step
+# and, for a box, the side of the exit axis.  Clamps are the identity, a coordinate set exactly (the exit plane, the entry
+# face's barycentric coordinate) has a zero derivative.
+#
+# L'(rho) = (1 / (1 + rho) - L) / rho and E'(z) = (e^z - E) / z cancel near zero: below |argument| < 2^-3 they are summed
+# as series (Horner), 19 terms of L' = sum_k (-1)^k k rho^(k - 1) / (k + 1) and 11 of E' = sum_k k z^(k - 1) / (k + 1)!.
+# At the switch the closed forms lose three bits and the truncated tails are below 2^-56
+# (tests/tracer_adjoint_cases.py::derivative_branch_agreement measures both against long double).
+_DSERIES = 2.0 ** -3
+_LP_TERMS = 19
+_EP_TERMS = 11
+
+
+def _fact(n):
+    out = 1
+    for i in range(2, n + 1):
+        out *= i
+    return out
+
+
+def _Lp(rho):
+    """L'(rho) of one scalar, in rho's precision"""
+    t = type(rho)
+    if abs(rho) < _DSERIES:
+        acc = t((-1) ** _LP_TERMS * _LP_TERMS) / t(_LP_TERMS + 1)
+        for k in range(_LP_TERMS - 1, 0, -1):
+            acc = t((-1) ** k * k) / t(k + 1) + rho * acc
+        return acc
+    return (1 / (1 + rho) - np.log1p(rho) / rho) / rho
+
+
+def _Ep(z):
+    """E'(z) of one scalar, in z's precision"""
+    t = type(z)
+    if abs(z) < _DSERIES:
+        acc = t(_EP_TERMS) / t(_fact(_EP_TERMS + 1))
+        for k in range(_EP_TERMS - 1, 0, -1):
+            acc = t(k) / t(_fact(k + 1)) + z * acc
+        return acc
+    em = np.expm1(z)
+    return ((em + 1) - em / z) / z
+
+
+def _Ls(rho):
+    return (1 - rho / 2) + rho * rho / 3 if abs(rho) < _SERIES else np.log1p(rho) / rho
+
+
+def _Es(z):
+    return (1 + z / 2) + z * z / 6 if abs(z) < _SERIES else np.expm1(z) / z
+
+
+class _Tables:
+    """the per-element data of a mesh in one precision"""
+
+    def __init__(self, mesh, dtype):
+        self.box = mesh.kind == BOX
+        self.nfe = 6 if self.box else 4
+        self.face = mesh.elem_face.astype(np.int64)
+        self.sgn = mesh.elem_sign.astype(dtype)
+        fe = mesh.face_elem.astype(np.int64)
+        self.nbr = np.where(fe[self.face, 0] == np.arange(mesh.n_elem)[:, None], fe[self.face, 1], fe[self.face, 0])
+        self.phi = np.ones(mesh.n_elem, dtype) if mesh.porosity is None else mesh.porosity.astype(dtype)
+        self.geom = mesh.geom.astype(dtype)
+        if not self.box:
+            self.rows, self.vol = simplex_rows(mesh.geom, dtype)
+
+
+def _box_velocities(tb, e, F, x):
+    lo, hi = tb.geom[e, :3], tb.geom[e, 3:]
+    h = hi - lo
+    vol = (h[0] * h[1]) * h[2]
+    area, vlo, vhi, g, v = [], [], [], [], []
+    for a in range(3):
+        area.append(vol / h[a])
+        vlo.append(-F[_BOX_LO[a]] / area[a])
+        vhi.append(F[_BOX_HI[a]] / area[a])
+        g.append((vhi[a] - vlo[a]) / h[a])
+        v.append(vlo[a] + g[a] * (x[a] - lo[a]))
+    return lo, hi, h, area, vlo, vhi, g, v
+
+
+def _tet_lambda(tb, e, x, dtype):
+    r = tb.rows[e]
+    return [min(max(((r[i, 0] * x[0] + r[i, 1] * x[1]) + r[i, 2] * x[2]) + r[i, 3], dtype(0)), dtype(1)) for i in range(4)]
+
+
+def _walk_one(tb, ucol, x0, e0, max_steps, dtype, forced=None):
+    """One particle in scalar arithmetic, the operations of `trace` in its order.  Returns (tape, T, x, status, exit_face):
+    tape[s] = (element, entry coordinates, exit, side): exit is the axis (box) or the local face (simplex); side is the `up`
+    of the exit axis (box) or the local entry face, -1 on the first step (simplex).  forced = (tape, status) of another run
+    imposes its decisions (the long-double twin on the float64 path)."""
+    inf = dtype(np.inf)
+    e = int(e0)
+    x = [dtype(c) for c in x0]
+    T = dtype(0)
+    tape = []
+    status, exit_face = MAX_STEPS, -1
+    entry = -1
+    if tb.box:
+        x = [min(max(x[a], tb.geom[e, a]), tb.geom[e, 3 + a]) for a in range(3)]
+    else:
+        lam = _tet_lambda(tb, e, x, dtype)
+    nmax = max_steps if forced is None else len(forced[0])
+    for s in range(nmax):
+        F = tb.sgn[e] * ucol[tb.face[e]]
+        best, which, side = inf, -1, 0
+        if tb.box:
+            lo, hi, h, area, vlo, vhi, g, v = _box_velocities(tb, e, F, x)
+            if forced is None:
+                for a in range(3):
+                    up = bool(v[a] > 0 and vhi[a] > 0)
+                    if up or (v[a] < 0 and vlo[a] < 0):
+                        d = hi[a] - x[a] if up else lo[a] - x[a]
+                        vex = vhi[a] if up else vlo[a]
+                        dt = (d / v[a]) * _Ls((vex - v[a]) / v[a])
+                        if dt < best:
+                            best, which, side = dt, a, int(up)
+            else:
+                which, side = forced[0][s][2], forced[0][s][3]
+                d = hi[which] - x[which] if side else lo[which] - x[which]
+                vex = vhi[which] if side else vlo[which]
+                best = (d / v[which]) * _Ls((vex - v[which]) / v[which])
+            coords = tuple(x)
+        else:
+            c3 = 3 * tb.vol[e]
+            b = (((F[0] + F[1]) + F[2]) + F[3]) / c3
+            w = [F[i] / c3 for i in range(4)]
+            vl = [b * lam[i] - w[i] for i in range(4)]
+            if forced is None:
+                for i in range(4):
+                    if F[i] > 0 and vl[i] < 0:
+                        dt = (-lam[i] / vl[i]) * _Ls((-w[i] - vl[i]) / vl[i])
+                        if dt < best:
+                            best, which = dt, i
+            else:
+                which = forced[0][s][2]
+                best = (-lam[which] / vl[which]) * _Ls((-w[which] - vl[which]) / vl[which])
+            side = entry
+            coords = tuple(lam)
+        if which < 0:
+            status = STAGNANT
+            break
+        tape.append((e, coords, which, side))
+        T = T + tb.phi[e] * best
+        if tb.box:
+            for a in range(3):
+                c = x[a] + (v[a] * best) * _Es(g[a] * best)
+                c = min(max(c, lo[a]), hi[a])
+                if a == which:
+                    c = hi[a] if side else lo[a]
+                x[a] = c
+            lf = (_BOX_HI if side else _BOX_LO)[which]
+        else:
+            eb = _Es(b * best)
+            ln = [min(max(lam[i] + (vl[i] * best) * eb, dtype(0)), dtype(1)) for i in range(4)]
+            ln[which] = dtype(0)
+            V = tb.geom[e]
+            x = [V[3, d] + ((ln[0] * (V[0, d] - V[3, d]) + ln[1] * (V[1, d] - V[3, d])) + ln[2] * (V[2, d] - V[3, d]))
+                 for d in range(3)]
+            lf = which
+        f, en = int(tb.face[e, lf]), int(tb.nbr[e, lf])
+        if en < 0:
+            status, exit_face = EXITED, f
+            break
+        e = en
+        if not tb.box:
+            lam = _tet_lambda(tb, e, x, dtype)
+            entry = int(np.nonzero(tb.face[e] == f)[0][0])
+            lam[entry] = dtype(0)
+    if forced is not None:
+        status = forced[1]
+    return tape, T, x, status, exit_face
+
+
+def _step_values(tb, step, F):
+    """the forward values of one recorded step that its derivatives need"""
+    e, c, which, side = step
+    if tb.box:
+        lo, hi, h, area, vlo, vhi, g, v = _box_velocities(tb, e, F, c)
+        d = hi[which] - c[which] if side else lo[which] - c[which]
+        vex = vhi[which] if side else vlo[which]
+        q = d / v[which]
+        rho = (vex - v[which]) / v[which]
+        Lr = _Ls(rho)
+        return dict(lo=lo, h=h, area=area, g=g, v=v, q=q, rho=rho, Lr=Lr, dt=q * Lr)
+    c3 = 3 * tb.vol[e]
+    b = (((F[0] + F[1]) + F[2]) + F[3]) / c3
+    w = [F[i] / c3 for i in range(4)]
+    v = [b * c[i] - w[i] for i in range(4)]
+    q = -c[which] / v[which]
+    rho = (-w[which] - v[which]) / v[which]
+    Lr = _Ls(rho)
+    dt = q * Lr
+    return dict(c3=c3, b=b, v=v, q=q, rho=rho, Lr=Lr, dt=dt, z=b * dt, eb=_Es(b * dt))
+
+
+def _step_adjoint(tb, step, F, Tbar, xbar, dtype):
+    """One step backwards: from the adjoints of T and of the position after the step to (Fbar (nfe), the adjoint of the
+    entry coordinates).  csrc/tracer.hip performs these operations in this order."""
+    e, c, A, side = step
+    m = _step_values(tb, step, F)
+    zero = dtype(0)
+    dt, q, rho, Lr, v = m["dt"], m["q"], m["rho"], m["Lr"], m["v"]
+    dtb = tb.phi[e] * Tbar
+    if tb.box:
+        g, lo, h, area = m["g"], m["lo"], m["h"], m["area"]
+        vb, gb, xin = [zero] * 3, [zero] * 3, [zero] * 3
+        for a in range(3):
+            if a == A:
+                continue
+            z = g[a] * dt
+            cb = xbar[a]
+            mb = cb * _Es(z)
+            zb = (cb * (v[a] * dt)) * _Ep(z)
+            xin[a] = cb
+            vb[a] = mb * dt
+            gb[a] = zb * dt
+            dtb = dtb + mb * v[a]
+            dtb = dtb + zb * g[a]
+        qb = dtb * Lr
+        rb = (dtb * q) * _Lp(rho)
+        vexb = rb / v[A]
+        vb[A] = -(qb * q) / v[A] - (rb * (1 + rho)) / v[A]
+        xin[A] = -(qb / v[A])
+        Fb = [zero] * 6
+        for a in range(3):
+            gba = gb[a] + vb[a] * (c[a] - lo[a])
+            xin[a] = xin[a] + vb[a] * g[a]
+            vlob = vb[a] - gba / h[a]
+            vhib = gba / h[a]
+            if a == A:
+                if side:
+                    vhib = vhib + vexb
+                else:
+                    vlob = vlob + vexb
+            Fb[_BOX_LO[a]] = -vlob / area[a]
+            Fb[_BOX_HI[a]] = vhib / area[a]
+        return Fb, xin
+    V = tb.geom[e]
+    b, eb, z, c3 = m["b"], m["eb"], m["z"], m["c3"]
+    lnb = [(((V[j, 0] - V[3, 0]) * xbar[0] + (V[j, 1] - V[3, 1]) * xbar[1]) + (V[j, 2] - V[3, 2]) * xbar[2]) for j in range(3)]
+    lnb.append(zero)
+    lnb[A] = zero
+    lamb, vb, wb = [zero] * 4, [zero] * 4, [zero] * 4
+    ebb = zero
+    for i in range(4):
+        mb = lnb[i] * eb
+        ebb = ebb + lnb[i] * (v[i] * dt)
+        lamb[i] = lnb[i]
+        vb[i] = mb * dt
+        dtb = dtb + mb * v[i]
+    zb = ebb * _Ep(z)
+    bb = zb * dt
+    dtb = dtb + zb * b
+    qb = dtb * Lr
+    rb = (dtb * q) * _Lp(rho)
+    lamb[A] = lamb[A] - qb / v[A]
+    vb[A] = (vb[A] - (qb * q) / v[A]) - (rb * (1 + rho)) / v[A]
+    wb[A] = -(rb / v[A])
+    for i in range(4):
+        bb = bb + vb[i] * c[i]
+        lamb[i] = lamb[i] + vb[i] * b
+        wb[i] = wb[i] - vb[i]
+    return [(wb[i] + bb) / c3 for i in range(4)], lamb
+
+
+def _rows_transpose(tb, e, lamb, skip):
+    """adjoint of lambda_k = row_k . x + d_k over the faces k != skip"""
+    r = tb.rows[e]
+    lb = [lamb[k] if k != skip else type(lamb[k])(0) for k in range(4)]
+    return [((r[0, d] * lb[0] + r[1, d] * lb[1]) + r[2, d] * lb[2]) + r[3, d] * lb[3] for d in range(3)]
+
+
+def _step_tangent(tb, step, F, dF, dc, dtype):
+    """One step forwards: from the tangents of the outward fluxes and of the entry coordinates to (d dt, the tangent of the
+    position (box) / of the position through the barycentric coordinates (simplex))"""
+    e, c, A, side = step
+    m = _step_values(tb, step, F)
+    dt, q, rho, Lr, v = m["dt"], m["q"], m["rho"], m["Lr"], m["v"]
+    zero = dtype(0)
+    if tb.box:
+        g, lo, h, area = m["g"], m["lo"], m["h"], m["area"]
+        dv, dg, dvlo, dvhi = [], [], [], []
+        for a in range(3):
+            dvlo.append(-dF[_BOX_LO[a]] / area[a])
+            dvhi.append(dF[_BOX_HI[a]] / area[a])
+            dg.append((dvhi[a] - dvlo[a]) / h[a])
+            dv.append(dvlo[a] + dg[a] * (c[a] - lo[a]) + g[a] * dc[a])
+        dvex = dvhi[A] if side else dvlo[A]
+        dq = (-dc[A] - q * dv[A]) / v[A]
+        drho = (dvex - (1 + rho) * dv[A]) / v[A]
+        ddt = dq * Lr + q * _Lp(rho) * drho
+        out = []
+        for a in range(3):
+            z = g[a] * dt
+            out.append(zero if a == A else dc[a] + (dv[a] * dt + v[a] * ddt) * _Es(z)
+                       + (v[a] * dt) * _Ep(z) * (dg[a] * dt + g[a] * ddt))
+        return ddt, out
+    b, eb, z, c3 = m["b"], m["eb"], m["z"], m["c3"]
+    db = (((dF[0] + dF[1]) + dF[2]) + dF[3]) / c3
+    dv = [db * c[i] + b * dc[i] - dF[i] / c3 for i in range(4)]
+    dq = (-dc[A] - q * dv[A]) / v[A]
+    drho = (-dF[A] / c3 - (1 + rho) * dv[A]) / v[A]
+    ddt = dq * Lr + q * _Lp(rho) * drho
+    deb = _Ep(z) * (db * dt + b * ddt)
+    dln = [zero if i == A else dc[i] + (dv[i] * dt + v[i] * ddt) * eb + (v[i] * dt) * deb for i in range(4)]
+    V = tb.geom[e]
+    return ddt, [(dln[0] * (V[0, d] - V[3, d]) + dln[1] * (V[1, d] - V[3, d])) + dln[2] * (V[2, d] - V[3, d]) for d in range(3)]
+
+
+def _prepare(mesh, u, x0, elem0, max_steps, dtype, decisions):
+    u2 = np.atleast_2d(np.asarray(u, dtype=dtype))
+    if max_steps == 0:
+        max_steps = default_max_steps(mesh.n_elem)
+    tb = _Tables(mesh, dtype)
+    x0 = np.asarray(x0, dtype=dtype).reshape(-1, 3)
+    paths = []
+    for b in range(u2.shape[0]):
+        for p in range(len(elem0)):
+            forced = None if decisions is None else decisions[b][p]
+            paths.append(_walk_one(tb, u2[b], x0[p], elem0[p], max_steps, dtype, forced))
+    return u2, tb, paths
+
+
+def _forward_dict(paths, nb, npart, dtype, squeeze):
+    res = dict(T=np.array([p[1] for p in paths], dtype).reshape(nb, npart),
+               exit_face=np.array([p[4] for p in paths], np.int32).reshape(nb, npart),
+               status=np.array([p[3] for p in paths], np.int32).reshape(nb, npart),
+               nsteps=np.array([len(p[0]) for p in paths], np.int32).reshape(nb, npart),
+               x_exit=np.array([p[2] for p in paths], dtype).reshape(nb, npart, 3))
+    res["decisions"] = [[(paths[b * npart + p][0], paths[b * npart + p][3]) for p in range(npart)] for b in range(nb)]
+    if squeeze:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def trace_tangent(mesh: TracerMesh, u, du, x0, elem0, max_steps=0, dtype=np.float64, dx0=None, decisions=None):
+    """Directional derivative of `trace` for the flux direction du (the shape of u) and, optionally, the start-point
+    direction dx0 (nparticles, 3), the decisions of the walk held.  Returns trace's forward outputs (without the margin) and
+    dT, dx_exit; particles that did not exit get zeros.  decisions: the "decisions" entry of another call's result (always
+    with the batch axis) imposes that call's path - the long-double reference on the float64 path."""
+    u2, tb, paths = _prepare(mesh, u, x0, elem0, max_steps, dtype, decisions)
+    du2 = np.atleast_2d(np.asarray(du, dtype=dtype))
+    nb, npart = u2.shape[0], len(elem0)
+    dx0 = np.zeros((npart, 3), dtype) if dx0 is None else np.asarray(dx0, dtype=dtype).reshape(npart, 3)
+    dT = np.zeros((nb, npart), dtype)
+    dxe = np.zeros((nb, npart, 3), dtype)
+    for b in range(nb):
+        for p in range(npart):
+            tape, _, _, status, _ = paths[b * npart + p]
+            if status != EXITED:
+                continue
+            acc = dtype(0)
+            dx = [dx0[p, d] for d in range(3)]
+            for s, step in enumerate(tape):
+                e = step[0]
+                F = tb.sgn[e] * u2[b, tb.face[e]]
+                dF = tb.sgn[e] * du2[b, tb.face[e]]
+                if tb.box:
+                    dc = dx
+                else:
+                    r = tb.rows[e]
+                    dc = [dtype(0) if k == step[3] else (r[k, 0] * dx[0] + r[k, 1] * dx[1]) + r[k, 2] * dx[2] for k in range(4)]
+                ddt, dx = _step_tangent(tb, step, F, dF, dc, dtype)
+                acc = acc + tb.phi[e] * ddt
+            dT[b, p] = acc
+            dxe[b, p] = dx
+    res = _forward_dict(paths, nb, npart, dtype, False)
+    res.update(dT=dT, dx_exit=dxe)
+    if np.ndim(u) == 1:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def trace_adjoint(mesh: TracerMesh, u, x0, elem0, T_bar=None, x_exit_bar=None, max_steps=0, dtype=np.float64, decisions=None):
+    """Numpy twin of pmc_tracer_run_adjoint: u_bar (nbatch, n_face) and x0_bar (nbatch, nparticles, 3) of
+    J = <T_bar, T> + <x_exit_bar, x_exit> per column, the decisions of the walk held, with trace's forward outputs (T,
+    exit_face, status, nsteps, x_exit: the same bits).  Particles that did not exit contribute nothing.
+
+    u_bar[f] is summed from 0.0 over the elements of face_elem[f] in that order and, within an element, over the visits in
+    ascending (particle, step)."""
+    u2, tb, paths = _prepare(mesh, u, x0, elem0, max_steps, dtype, decisions)
+    nb, npart = u2.shape[0], len(elem0)
+    Tb = np.zeros((nb, npart), dtype) if T_bar is None else np.asarray(T_bar, dtype=dtype).reshape(nb, npart)
+    xb = np.zeros((nb, npart, 3), dtype) if x_exit_bar is None else np.asarray(x_exit_bar, dtype=dtype).reshape(nb, npart, 3)
+    ubar = np.zeros((nb, mesh.n_face), dtype)
+    x0bar = np.zeros((nb, npart, 3), dtype)
+    local = {}
+    for e in range(mesh.n_elem):
+        for l in range(tb.nfe):
+            local[e, int(tb.face[e, l])] = l
+    for b in range(nb):
+        visits = {}                                        # element -> [(particle, step, Fbar)]
+        for p in range(npart):
+            tape, _, _, status, _ = paths[b * npart + p]
+            if status != EXITED:
+                continue
+            xbar = [xb[b, p, d] for d in range(3)]
+            for s in range(len(tape) - 1, -1, -1):
+                step = tape[s]
+                e = step[0]
+                F = tb.sgn[e] * u2[b, tb.face[e]]
+                Fb, cin = _step_adjoint(tb, step, F, Tb[b, p], xbar, dtype)
+                visits.setdefault(e, []).append((p, s, Fb))
+                xbar = cin if tb.box else _rows_transpose(tb, e, cin, step[3])
+            x0bar[b, p] = xbar
+        for e in visits:
+            visits[e].sort(key=lambda t: (t[0], t[1]))
+        for f in range(mesh.n_face):
+            acc = dtype(0)
+            for e in mesh.face_elem[f]:
+                if e < 0 or int(e) not in visits:
+                    continue
+                l = local[int(e), f]
+                for _, _, Fb in visits[int(e)]:
+                    acc = acc + tb.sgn[e, l] * Fb[l]
+            ubar[b, f] = acc
+    res = _forward_dict(paths, nb, npart, dtype, False)
+    res.update(u_bar=ubar, x0_bar=x0bar)
+    if np.ndim(u) == 1:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def reduce_seed(T, status, kind=MEAN):
+    """Twin of pmc_tracer_reduce_seed: T_bar = dQ/dT of the Q of `reduce`.  MEAN: 1 / nparticles on the particles that exited;
+    MIN: 1 on the lowest-index particle attaining the minimum, if it exited; 0 elsewhere."""
+    T, status = np.atleast_2d(T), np.atleast_2d(status)
+    out = np.zeros(T.shape)
+    if kind == MEAN:
+        out[status == EXITED] = 1.0 / T.shape[1]
+    else:
+        j = T.argmin(axis=1)
+        r = np.arange(T.shape[0])
+        out[r, j] = (status[r, j] == EXITED).astype(np.float64)
+    return out

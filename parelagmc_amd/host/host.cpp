@@ -257,6 +257,20 @@ void ParticleTracer::Reduce(int nbatch, const double* T, const int32_t* status, 
                             int memspace) {
     check_arg(pmc_tracer_reduce(h_, nbatch, T, status, kind, Q, not_exited, memspace), "ParticleTracer::Reduce");
 }
+void ParticleTracer::RunAdjoint(const Vector& u, const double* T_bar, const double* x_exit_bar, Vector& u_bar, double* x0_bar,
+                                double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps) {
+    if (u_bar.MemSpace() != u.MemSpace()) throw std::invalid_argument("ParticleTracer::RunAdjoint: u and u_bar must share a memory space");
+    u_bar.SetSize(u.Size(), u.Batch());
+    check_arg(pmc_tracer_run_adjoint(h_, u.Batch(), u.GetData(), u.Size(), T_bar, x_exit_bar, u_bar.GetData(), u.Size(), x0_bar, T,
+                                     exit_face, status, nsteps, u.MemSpace()),
+              "ParticleTracer::RunAdjoint");
+}
+void ParticleTracer::ReduceSeed(int nbatch, const double* T, const int32_t* status, int kind, double* T_bar, int memspace) {
+    check_arg(pmc_tracer_reduce_seed(h_, nbatch, T, status, kind, T_bar, memspace), "ParticleTracer::ReduceSeed");
+}
+void ParticleTracer::SetAdjointScratch(int64_t bytes) {
+    check_arg(pmc_tracer_set_adjoint_scratch(h_, bytes), "ParticleTracer::SetAdjointScratch");
+}
 
 // ---- SoluteTransport --------------------------------------------------------------------------
 SoluteTransport::SoluteTransport(pmc_ctx* ctx, const pmc_transport_mesh& mesh, const pmc_transport_params& params) {
@@ -346,6 +360,32 @@ void DarcySolver::ComputeGradTransportLogLikelihood(int ilevel, SoluteTransport&
     check(pmc_darcy_transport_loglik_gradient(h_, ilevel, transport.Handle(), k.Batch(), k.GetData(), data, noise, wrt_log ? 1 : 0,
                                               loglik, curve, status, grad.GetData(), k.MemSpace(), sta.data()),
           "DarcySolver::ComputeGradTransportLogLikelihood");
+    record(ilevel, sta);
+}
+void DarcySolver::SolveFwd_TracerGradient(int ilevel, ParticleTracer& tracer, Vector& k, const double* T_bar, double* T,
+                                          int32_t* status, Vector& grad, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::SolveFwd_TracerGradient: level");
+    if (grad.MemSpace() != k.MemSpace()) throw std::invalid_argument("SolveFwd_TracerGradient: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    std::vector<pmc_stats> st(k.Batch()), sta(k.Batch());
+    check(pmc_darcy_tracer_gradient(h_, ilevel, tracer.Handle(), k.Batch(), k.GetData(), T_bar, wrt_log ? 1 : 0, T, status,
+                                    grad.GetData(), nullptr, nullptr, k.MemSpace(), st.data(), sta.data()),
+          "DarcySolver::SolveFwd_TracerGradient");
+    record(ilevel, st);
+    record(ilevel, sta);
+}
+void DarcySolver::ComputeGradTravelTimeLogLikelihood(int ilevel, ParticleTracer& tracer, Vector& k, const double* data, double noise,
+                                                     double* loglik, double* T, int32_t* not_exited, Vector& grad, bool wrt_log) {
+    const int np = pmc_darcy_num_pressure_dofs(h_, ilevel);
+    if (np < 0) throw std::out_of_range("DarcySolver::ComputeGradTravelTimeLogLikelihood: level");
+    if (grad.MemSpace() != k.MemSpace())
+        throw std::invalid_argument("ComputeGradTravelTimeLogLikelihood: k and grad must share a memory space");
+    grad.SetSize(np, k.Batch());
+    std::vector<pmc_stats> sta(k.Batch());
+    check(pmc_darcy_tracer_loglik_gradient(h_, ilevel, tracer.Handle(), k.Batch(), k.GetData(), data, noise, wrt_log ? 1 : 0, loglik,
+                                           T, not_exited, grad.GetData(), k.MemSpace(), sta.data()),
+          "DarcySolver::ComputeGradTravelTimeLogLikelihood");
     record(ilevel, sta);
 }
 void DarcySolver::SolveFwd_GNHessVec(int ilevel, Vector& k, const Vector& dk, double noise, Vector& x, bool x_given, Vector& hv,

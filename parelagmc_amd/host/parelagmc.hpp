@@ -281,6 +281,17 @@ class ParticleTracer {
     void Run(const Vector& u, double* T, int32_t* exit_face, int32_t* status, int32_t* nsteps, double* x_exit = nullptr);
     /// Q (host, nbatch): mean (PMC_TRACER_MEAN) or minimum (PMC_TRACER_MIN) of T per realization; not_exited (host) may be NULL
     void Reduce(int nbatch, const double* T, const int32_t* status, int kind, double* Q, int32_t* not_exited, int memspace);
+    /// The adjoint of the walk, its decisions held (pmc_tracer_run_adjoint): u_bar = dJ/du and x0_bar =
+    /// dJ/dx0 (u.Batch() x NumParticles() x 3, may be NULL) of J = <T_bar, T> + <x_exit_bar, x_exit> per realization.  Seeds
+    /// (u.Batch() x NumParticles() and x 3; each may be NULL, not both) and outputs in u's memory space; u_bar is sized to
+    /// u.Size() x u.Batch() and only the first n_face entries of a row are written.  T, exit_face, nsteps may be NULL; status
+    /// may not.  Particles that did not exit contribute nothing.
+    void RunAdjoint(const Vector& u, const double* T_bar, const double* x_exit_bar, Vector& u_bar, double* x0_bar, double* T,
+                    int32_t* exit_face, int32_t* status, int32_t* nsteps);
+    /// T_bar = dQ/dT of the Q of Reduce (pmc_tracer_reduce_seed), in the memory space of T and status
+    void ReduceSeed(int nbatch, const double* T, const int32_t* status, int kind, double* T_bar, int memspace);
+    /// cap in bytes on the records of one chunk of columns of RunAdjoint; 0: 256 MiB.  The results do not depend on it.
+    void SetAdjointScratch(int64_t bytes);
     pmc_tracer* Handle() const { return h_; }
 
   private:
@@ -353,6 +364,18 @@ class DarcySolver : public PhysicalMLSolver {
     void ComputeGradTransportLogLikelihood(int ilevel, SoluteTransport& transport, Vector& k_over_k_ref, const double* data,
                                            double noise, double* loglik, double* curve, int32_t* status, Vector& grad,
                                            bool wrt_log = false);
+    /// Forward solve plus the gradient in k (wrt_log: in log k) of J = <T_bar, T> of the travel times of `tracer` on the
+    /// solution's flux (pmc_darcy_tracer_gradient; an extension).  The tracer is given with the call: what SetTracer /
+    /// SetTransport attached is neither read nor changed.  T_bar, T (may be NULL) and status, k.Batch() x NumParticles(), in
+    /// k's memory space.  grad is sized like k.
+    void SolveFwd_TracerGradient(int ilevel, ParticleTracer& tracer, Vector& k_over_k_ref, const double* T_bar, double* T,
+                                 int32_t* status, Vector& grad, bool wrt_log = false);
+    /// loglik = -|T - data|^2 / (2 noise) of the travel times of `tracer` and its gradient in k
+    /// (pmc_darcy_tracer_loglik_gradient).  data: host, NumParticles(); loglik, T (may be NULL) and not_exited (k.Batch()): host.
+    /// A realization with not_exited > 0 has a zero gradient.
+    void ComputeGradTravelTimeLogLikelihood(int ilevel, ParticleTracer& tracer, Vector& k_over_k_ref, const double* data,
+                                            double noise, double* loglik, double* T, int32_t* not_exited, Vector& grad,
+                                            bool wrt_log = false);
     /// Gauss-Newton Hessian action hv = J^T (1/noise) J dk of the negative log-likelihood of the handle's observation
     /// functionals, J = dG/dk (wrt_log: in log k), for every realization (pmc_darcy_gn_hessvec; an extension).  x: the forward
     /// solutions, GetNumberOfDofs(ilevel) x k.Batch() - x_given false: solved inside and written to x; true: read, and no
