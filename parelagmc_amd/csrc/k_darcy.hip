@@ -417,16 +417,16 @@ static int eg_pair_spmm_t(hipStream_t st, int nb, const EgView& M, const double*
         throw Error(PMC_ERR_INVALID, "eg_pair_spmm: rows x batch width exceed 32-bit gather offsets");
     const dim3 g = grid_bounded(grid_slices(M.nslices), dot_partial != nullptr);
     PMC_DISPATCH_NB(nb, {
-        if (nt_flat((size_t)M.nrows * NB * 2)) {   // from 4 MiB per vector on
-            count_solve_path(PMC_COUNT_NT_FLAT);
-            if (dot_partial)
-                eg_pair_spmm_kernel<NB, true, true, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y, dot_with, dot_partial, nb);
-            else
-                eg_pair_spmm_kernel<NB, false, true, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y, nullptr, nullptr, nb);
-        } else if (dot_partial)
-            eg_pair_spmm_kernel<NB, true, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y, dot_with, dot_partial, nb);
-        else
-            eg_pair_spmm_kernel<NB, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y, nullptr, nullptr, nb);
+        const bool nt = nt_flat((size_t)M.nrows * NB * 2);   // from 4 MiB per vector on
+        if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
+        dispatch_bool(nt, [&](auto nt_c) {
+            dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+                constexpr bool DOT = decltype(dot)::value;
+                eg_pair_spmm_kernel<NB, DOT, decltype(nt_c)::value, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+                    M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, A2.slice_off, A2.cols, A2.vals, x1, x2, y,
+                    DOT ? dot_with : nullptr, DOT ? dot_partial : nullptr, nb);
+            });
+        });
     });
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
@@ -438,9 +438,7 @@ int eg_pair_spmm(hipStream_t st, int nb, const EgView& M, const double* coef, co
 }
 int eg_pair_spmm_z(hipStream_t st, int nb, const EgView& M, const double* coef, zvec x1, const SellView& A2,
                    zvec x2, double* y, double* dot_partial, zvec dot_with) {
-    if (x1.f32)
-        return eg_pair_spmm_t<float>(st, nb, M, coef, x1.as<float>(), A2, x2.as<float>(), y, dot_partial, dot_with.as<float>());
-    return eg_pair_spmm_t<double>(st, nb, M, coef, x1.as<double>(), A2, x2.as<double>(), y, dot_partial, dot_with.as<double>());
+    return dispatch_storage(x1, [&](auto* p1, auto* p2, auto* dw) { return eg_pair_spmm_t(st, nb, M, coef, p1, A2, p2, y, dot_partial, dw); }, x2, dot_with);
 }
 
 template <typename OT>
@@ -451,16 +449,15 @@ static int eg_poly2_t(hipStream_t st, int nb, const EgView& M, const double* coe
         throw Error(PMC_ERR_INVALID, "eg_poly2: rows x batch width exceed 32-bit gather offsets");
     const dim3 g = grid_bounded(grid_slices(M.nslices), dot_partial != nullptr);
     PMC_DISPATCH_NB(nb, {
-        if (nt_flat((size_t)M.nrows * NB * 2)) {
-            count_solve_path(PMC_COUNT_NT_FLAT);
-            if (dot_partial)
-                eg_poly2_kernel<NB, true, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, dot_partial, nb);
-            else
-                eg_poly2_kernel<NB, false, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, nullptr, nb);
-        } else if (dot_partial)
-            eg_poly2_kernel<NB, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, dot_partial, nb);
-        else
-            eg_poly2_kernel<NB, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, nullptr, nb);
+        const bool nt = nt_flat((size_t)M.nrows * NB * 2);
+        if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
+        dispatch_bool(nt, [&](auto nt_c) {
+            dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+                constexpr bool DOT = decltype(dot)::value;
+                eg_poly2_kernel<NB, DOT, decltype(nt_c)::value, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+                    M.nrows, M.nslices, M.gw, M.cols, M.w, M.e12, coef, dinv, r, xout, c0, c1, DOT ? dot_partial : nullptr, nb);
+            });
+        });
     });
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
@@ -472,8 +469,7 @@ int eg_poly2(hipStream_t st, int nb, const EgView& M, const double* coef, const 
 }
 int eg_poly2_z(hipStream_t st, int nb, const EgView& M, const double* coef, const double* dinv, const double* r, zvec xout,
                double c0, double c1, double* dot_partial) {
-    if (xout.f32) return eg_poly2_t<float>(st, nb, M, coef, dinv, r, xout.as<float>(), c0, c1, dot_partial);
-    return eg_poly2_t<double>(st, nb, M, coef, dinv, r, xout.as<double>(), c0, c1, dot_partial);
+    return dispatch_storage(xout, [&](auto* out) { return eg_poly2_t(st, nb, M, coef, dinv, r, out, c0, c1, dot_partial); });
 }
 
 void scale_cols_bv(hipStream_t st, int nb, int64_t nslots, const int* cols, const double* vals, const double* colscale,

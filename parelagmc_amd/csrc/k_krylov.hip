@@ -519,10 +519,9 @@ namespace k {
 void minres_wx_idx(hipStream_t st, int nb, int nsel, const int* rows, const double* c0, zvec u, const double* c1,
                    double* w0, const double* c2, const double* w1, const double* c3, double* x) {
     if (nsel == 0) return;
-    PMC_DISPATCH_NB(nb, {
-        if (u.f32) minres_wx_idx_kernel<NB, float><<<grid_flat(nsel, nb), kBlock, 0, st>>>(flat_count(nsel, nb), rows, c0, u.as<float>(), c1, w0, c2, w1, c3, x, nb);
-        else minres_wx_idx_kernel<NB, double><<<grid_flat(nsel, nb), kBlock, 0, st>>>(flat_count(nsel, nb), rows, c0, u.as<double>(), c1, w0, c2, w1, c3, x, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_storage(u, [&](auto* up) {
+        minres_wx_idx_kernel<NB><<<grid_flat(nsel, nb), kBlock, 0, st>>>(flat_count(nsel, nb), rows, c0, up, c1, w0, c2, w1, c3, x, nb);
+    }));
     check_launch();
 }
 
@@ -531,25 +530,19 @@ int cheb_first(hipStream_t st, int nb, int n, const double* dinv, bool dinv_bv, 
     if (n == 0) return 0;
     const size_t nf = flat_count(n, nb);
     const dim3 g = grid_bounded(grid_flat(n, nb), dot_partial != nullptr);
-    PMC_DISPATCH_NB(nb, {
-        if (dinv_bv) {
-            if (dot_partial) cheb_first_kernel<NB, true, true><<<g, kBlock, 0, st>>>(nf, dinv, r, d, x, b, dot_partial, nb);
-            else cheb_first_kernel<NB, true, false><<<g, kBlock, 0, st>>>(nf, dinv, r, d, x, b, nullptr, nb);
-        } else {
-            if (dot_partial) cheb_first_kernel<NB, false, true><<<g, kBlock, 0, st>>>(nf, dinv, r, d, x, b, dot_partial, nb);
-            else cheb_first_kernel<NB, false, false><<<g, kBlock, 0, st>>>(nf, dinv, r, d, x, b, nullptr, nb);
-        }
-    });
+    PMC_DISPATCH_NB(nb, dispatch_bool(dinv_bv, [&](auto bv) {
+        dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+            constexpr bool DOT = decltype(dot)::value;
+            cheb_first_kernel<NB, decltype(bv)::value, DOT><<<g, kBlock, 0, st>>>(nf, dinv, r, d, x, b, DOT ? dot_partial : nullptr, nb);
+        });
+    }));
     check_launch();
     return dot_partial ? (int)g.x : 0;
 }
 
 int dot_z(hipStream_t st, int nb, int n, const double* a, zvec b, double* partial) {
     const dim3 g = grid_dot(n, nb);
-    PMC_DISPATCH_NB(nb, {
-        if (b.f32) dot_kernel<NB, float><<<g, kBlock, 0, st>>>(flat_count(n, nb), a, b.as<float>(), partial, nb);
-        else dot_kernel<NB, double><<<g, kBlock, 0, st>>>(flat_count(n, nb), a, b.as<double>(), partial, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_storage(b, [&](auto* bp) { dot_kernel<NB><<<g, kBlock, 0, st>>>(flat_count(n, nb), a, bp, partial, nb); }));
     check_launch();
     return (int)g.x;
 }
@@ -557,15 +550,12 @@ int dot_z(hipStream_t st, int nb, int n, const double* a, zvec b, double* partia
 int convert_z(hipStream_t st, int nb, int n, const double* in, zvec out, const double* r, double* dot_partial) {
     if (n == 0) return 0;
     const dim3 g = grid_dot(n, nb);
-    PMC_DISPATCH_NB(nb, {
-        if (out.f32) {
-            if (dot_partial) convert_dot_kernel<NB, true, float><<<g, kBlock, 0, st>>>(flat_count(n, nb), in, out.as<float>(), r, dot_partial, nb);
-            else convert_dot_kernel<NB, false, float><<<g, kBlock, 0, st>>>(flat_count(n, nb), in, out.as<float>(), nullptr, nullptr, nb);
-        } else {
-            if (dot_partial) convert_dot_kernel<NB, true, double><<<g, kBlock, 0, st>>>(flat_count(n, nb), in, out.as<double>(), r, dot_partial, nb);
-            else convert_dot_kernel<NB, false, double><<<g, kBlock, 0, st>>>(flat_count(n, nb), in, out.as<double>(), nullptr, nullptr, nb);
-        }
-    });
+    PMC_DISPATCH_NB(nb, dispatch_storage(out, [&](auto* op) {
+        dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+            constexpr bool DOT = decltype(dot)::value;
+            convert_dot_kernel<NB, DOT><<<g, kBlock, 0, st>>>(flat_count(n, nb), in, op, DOT ? r : nullptr, DOT ? dot_partial : nullptr, nb);
+        });
+    }));
     check_launch();
     return dot_partial ? (int)g.x : 0;
 }
@@ -594,27 +584,21 @@ void lincomb3(hipStream_t st, int nb, int n, const double* c0, const double* a, 
     static const bool nt_on = [] { const char* e = lab_env("PMC_NT_LINCOMB"); return !e || atoi(e) != 0; }();
     const bool nt = nt_on && nt_flat((size_t)n * nb);
     if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
-    PMC_DISPATCH_NB(nb, {
-        if (nt) lincomb3_kernel<NB, true><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, a, c1, b, c2, y, nb, y32);
-        else lincomb3_kernel<NB><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, a, c1, b, c2, y, nb, y32);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_bool(nt, [&](auto nt_c) {
+        lincomb3_kernel<NB, decltype(nt_c)::value><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, a, c1, b, c2, y, nb, y32);
+    }));
     check_launch();
 }
 
-template <typename UT>
-static void minres_wx_t(hipStream_t st, int nb, int n, const double* c0, const UT* u, const double* c1, double* w0,
-                        const double* c2, const double* w1, const double* c3, double* x) {
-    const bool nt = nt_flat((size_t)n * nb);
-    if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
-    PMC_DISPATCH_NB(nb, {
-        if (nt) minres_wx_kernel<NB, true, UT><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, u, c1, w0, c2, w1, c3, x, nb);
-        else minres_wx_kernel<NB, false, UT><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, u, c1, w0, c2, w1, c3, x, nb);
-    });
-}
 void minres_wx(hipStream_t st, int nb, int n, const double* c0, zvec u, const double* c1, double* w0,
                const double* c2, const double* w1, const double* c3, double* x) {
-    if (u.f32) minres_wx_t<float>(st, nb, n, c0, u.as<float>(), c1, w0, c2, w1, c3, x);
-    else minres_wx_t<double>(st, nb, n, c0, u.as<double>(), c1, w0, c2, w1, c3, x);
+    const bool nt = nt_flat((size_t)n * nb);
+    if (nt) count_solve_path(PMC_COUNT_NT_FLAT);
+    PMC_DISPATCH_NB(nb, dispatch_storage(u, [&](auto* up) {
+        dispatch_bool(nt, [&](auto nt_c) {
+            minres_wx_kernel<NB, decltype(nt_c)::value><<<grid_flat(n, nb), kBlock, 0, st>>>(flat_count(n, nb), c0, up, c1, w0, c2, w1, c3, x, nb);
+        });
+    }));
     check_launch();
 }
 
@@ -628,17 +612,13 @@ void minres_wx_deferred(hipStream_t st, int nb, int n, const MinresState* s, con
     // the entries of one thread share their columns (see the kernel): kBlock * C flat values are whole rows
     if ((kBlock * lay_c(nb)) % nb != 0) throw Error(PMC_ERR_INTERNAL, "minres_wx_deferred: row stride does not divide a workgroup's step");
     const size_t nf = flat_count(n, nb);
-    PMC_DISPATCH_NB(nb, {
-        constexpr int C = Lay<NB>::C;
-        const dim3 g32(wx_deferred_blocks(nf, WxShape<float, C>::R)), g64(wx_deferred_blocks(nf, WxShape<double, C>::R));
-        if (B.f32) {
-            if (nt) minres_wx_deferred_kernel<NB, true, float><<<g32, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
-            else minres_wx_deferred_kernel<NB, false, float><<<g32, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
-        } else {
-            if (nt) minres_wx_deferred_kernel<NB, true, double><<<g64, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
-            else minres_wx_deferred_kernel<NB, false, double><<<g64, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
-        }
-    });
+    PMC_DISPATCH_NB(nb, dispatch_f32(B.f32, [&](auto t) {   // (the u vectors travel inside B)
+        dispatch_bool(nt, [&](auto nt_c) {
+            using UT = typename decltype(t)::type;
+            const dim3 g(wx_deferred_blocks(nf, WxShape<UT, Lay<NB>::C>::R));
+            minres_wx_deferred_kernel<NB, decltype(nt_c)::value, UT><<<g, kBlock, 0, st>>>(nf, B, cW, w0, w1, x, nb);
+        });
+    }));
     check_launch();
 }
 

@@ -864,99 +864,95 @@ int dot_capacity(int nrows, int nb) {
 // launchers
 namespace k {
 
-// the row-split instantiations (SellView::split_log2) exist for launches of at most 8 realizations
-#define PMC_DISPATCH_NARROW(nb, ...)                                      \
-    switch (nb) {                                                         \
-        case 1: { constexpr int NB = 1; __VA_ARGS__; } break;             \
-        case 2: { constexpr int NB = 2; __VA_ARGS__; } break;             \
-        case 4: { constexpr int NB = 4; __VA_ARGS__; } break;             \
-        case 8: { constexpr int NB = 8; __VA_ARGS__; } break;             \
-        default: throw Error(PMC_ERR_INTERNAL, "row-split level kernels serve launches of 1, 2, 4 or 8 realizations"); \
-    }
+// How these launchers are built (the dispatch helpers: klaunch.hpp).  Every kernel template above has ONE <<< site.  A kernel
+// that several public launchers start (sell_spmm_kernel, vc_poly2_kernel, vc_residual_kernel) has a launch_* function: it
+// takes the grid, the matrix view and the operands, fills the matrix arguments from the view and passes an optional operand
+// only if the form reads it, nullptr otherwise - a flag and its pointer cannot disagree.  The other kernels are started in
+// place by their one launcher, under the same rule.  A public launcher is the checks, the grid, the decision and a call;
+// the run-time facts of the decision become template arguments through dispatch_bool / dispatch_values / dispatch_storage /
+// dispatch_narrow and PMC_DISPATCH_NB.  The instantiations of the unit are exactly those the dispatches span, so each
+// dispatch names the forms that do not exist.
 
-// one Lanczos pass of the operator (sell_spmm_kernel's LZ forms) with the matrix streams and the dot of the in-loop product
-#define PMC_SPMM_LZ(NTF, DLF, LZF)                                                                                          \
-    sell_spmm_kernel<NB, false, 0, (LZF) == 1, TAG, NTF, false, DLF, XT, double, LZF><<<groups_xcd(g, nb), kBlock, 0, st>>>( \
-        A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb, *lz)
+// what one launch of sell_spmm_kernel computes: its MODE, R8, LZ and SM arguments, of which at most one differs from the
+// plain product
+enum class Spmm {
+    product,               // y = A x                                            MODE 0
+    accumulate,            // y += A x                                           MODE 1
+    residual,              // y = r - A x                                        MODE 2
+    residual_restrict8,    // ... with the fused restriction over groups of 8    MODE 2, R8
+    residual_samples,      // ... stored sample-major                            MODE 2, SM 1
+    residual_samples_exp,  // ... through exp()                                  MODE 2, SM 2
+    dot_only,              // <x, A x> alone (first Lanczos pass)                LZ 1
+    update,                // the next Lanczos vector from A x, v1 and v0        LZ 2
+    update_first,          // ... in the first iteration (v0 = 0)                LZ 3
+    product_store32        // y = A x with its fp32 copy                         LZ 4
+};
+// sell_spmm_kernel's TAG (SellView::tag)
+constexpr int kTagNone = 0, kTagOperator = 1, kTagApply = 2;
 
+template <int NB, int BV, Spmm OP, int TAG = kTagNone, bool DOT = false, bool NT = false, bool DL = false, typename XT, typename YT>
+static void launch_spmm(hipStream_t st, int nb, dim3 g, const SellView& A, const XT* x, YT* y, const double* r,
+                        const typename ident<XT>::type* dot_with, double* partial, const LanczosUpdate* lz = nullptr) {
+    constexpr bool RES = OP == Spmm::residual || OP == Spmm::residual_restrict8 || OP == Spmm::residual_samples ||
+                         OP == Spmm::residual_samples_exp;
+    constexpr int MODE = OP == Spmm::accumulate ? 1 : (RES ? 2 : 0);
+    constexpr bool R8 = OP == Spmm::residual_restrict8;
+    constexpr int SM = OP == Spmm::residual_samples ? 1 : (OP == Spmm::residual_samples_exp ? 2 : 0);
+    constexpr int LZ = OP == Spmm::dot_only ? 1 : OP == Spmm::update ? 2 : OP == Spmm::update_first ? 3 : OP == Spmm::product_store32 ? 4 : 0;
+    sell_spmm_kernel<NB, BV, MODE, DOT, TAG, NT, R8, DL, XT, YT, LZ, SM><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+        A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, RES ? r : nullptr, DOT ? dot_with : nullptr,
+        DOT || R8 ? partial : nullptr, nb, LZ != 0 ? *lz : LanczosUpdate{});
+}
+
+// the operator products: y = A x, y += A x, with a fused dot, and the Lanczos passes of the solver's operator (lz_mode 1 - 3)
 template <int NB, int TAG, typename XT>
 static void spmm_launch(hipStream_t st, int nb, dim3 g, const SellView& A, const XT* x, double* y, bool accumulate,
                         double* dot_partial, const XT* dot_with, int lz_mode = 0, const LanczosUpdate* lz = nullptr) {
+    constexpr bool F32 = !std::is_same<XT, double>::value;   // fp32-stored input: the preconditioned Krylov vectors
+    constexpr bool LANCZOS = F32 && TAG == kTagOperator;      // where the Lanczos passes exist (lz_mode != 0 comes with both)
+    constexpr bool DL_ROWS = Lay<NB>::T > 1;
+    if (!LANCZOS && lz_mode != 0) throw Error(PMC_ERR_INTERNAL, "spmm: Lanczos pass outside the solver's fp32 operator product");
     // <x, Ax> with a diagonal-last matrix: x_i is what the row's last slice column gathers
-    const bool dl = TAG == 1 && Lay<NB>::T > 1 && A.diag_last && dot_with == x;
-    if constexpr (!std::is_same<XT, double>::value) {
-        // fp32-stored input (the preconditioned Krylov vectors): the operator products of the solver loop only
+    const bool dl = TAG == kTagOperator && DL_ROWS && A.diag_last && dot_with == x;
+    if constexpr (F32) {
+        // the operator products of the solver loop only
         if (A.bv || accumulate) throw Error(PMC_ERR_INTERNAL, "spmm: fp32 input with per-realization values / accumulation");
-        if constexpr (TAG == 1) {
-            if (lz_mode) {
-                // the matrix streams of both passes are those of the in-loop product (its launch carries the dot)
-                const bool ntl = nt_streams(A, NB, true);
-                if (ntl) count_solve_path(PMC_COUNT_NT_OPERATOR);
-                constexpr bool kDl = Lay<NB>::T > 1;
-                if (lz_mode == 1) {
-                    if (ntl) { if (dl) PMC_SPMM_LZ(true, kDl, 1); else PMC_SPMM_LZ(true, false, 1); }
-                    else { if (dl) PMC_SPMM_LZ(false, kDl, 1); else PMC_SPMM_LZ(false, false, 1); }
-                } else if (lz_mode == 2) {
-                    if (ntl) PMC_SPMM_LZ(true, false, 2); else PMC_SPMM_LZ(false, false, 2);
-                } else {
-                    if (ntl) PMC_SPMM_LZ(true, false, 3); else PMC_SPMM_LZ(false, false, 3);
+    }
+    // non-temporal streams: the matrix streams of the Lanczos passes are those of the in-loop product (its launch carries the dot)
+    const bool nt = !A.bv && TAG != kTagNone && nt_streams(A, NB, lz_mode != 0 || dot_partial != nullptr);
+    if (nt) count_solve_path(PMC_COUNT_NT_OPERATOR);
+    dispatch_values<!F32>(A, [&](auto bv) {
+        constexpr int BV = decltype(bv)::value;
+        constexpr bool SHARED = BV == kSharedValues;   // non-temporal and diagonal-last forms: shared values only
+        dispatch_bool<SHARED>(nt, [&](auto nt_c) {
+            constexpr bool NT = decltype(nt_c)::value;
+            if constexpr (LANCZOS) {
+                if (lz_mode != 0 && lz_mode != 1) {   // the update passes: 2, and 3 in the first iteration
+                    dispatch_bool(lz_mode != 2, [&](auto first) {
+                        constexpr Spmm OP = decltype(first)::value ? Spmm::update_first : Spmm::update;
+                        launch_spmm<NB, BV, OP, TAG, false, NT>(st, nb, g, A, x, y, nullptr, nullptr, nullptr, lz);
+                    });
+                    return;
                 }
+            }
+            if (dot_partial || lz_mode == 1) {
+                dispatch_bool<SHARED && DL_ROWS>(dl, [&](auto dl_c) {
+                    dispatch_bool<LANCZOS>(lz_mode == 1, [&](auto only) {
+                        constexpr Spmm OP = decltype(only)::value ? Spmm::dot_only : Spmm::product;
+                        launch_spmm<NB, BV, OP, TAG, true, NT, decltype(dl_c)::value>(st, nb, g, A, x, y, nullptr, dot_with, dot_partial, lz);
+                    });
+                });
                 return;
             }
-        }
-        const bool nt = TAG != 0 && nt_streams(A, NB, dot_partial != nullptr);
-        if (nt) {
-            count_solve_path(PMC_COUNT_NT_OPERATOR);
-            if (dot_partial && dl)
-                sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1), XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-            else if (dot_partial)
-                sell_spmm_kernel<NB, false, 0, true, TAG, true, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-            else
-                sell_spmm_kernel<NB, false, 0, false, TAG, true, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        } else {
-            if (dot_partial && dl)
-                sell_spmm_kernel<NB, false, 0, true, TAG, false, false, (Lay<NB>::T > 1), XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-            else if (dot_partial)
-                sell_spmm_kernel<NB, false, 0, true, TAG, false, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-            else
-                sell_spmm_kernel<NB, false, 0, false, TAG, false, false, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        }
-        return;
-    } else
-    if (A.bv && A.f32) {
-        if (dot_partial)
-            sell_spmm_kernel<NB, 2, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (accumulate)
-            sell_spmm_kernel<NB, 2, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, 2, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-    } else if (A.bv) {
-        if (dot_partial)
-            sell_spmm_kernel<NB, true, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (accumulate)
-            sell_spmm_kernel<NB, true, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, true, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-    } else if (TAG != 0 && nt_streams(A, NB, dot_partial != nullptr)) {
-        count_solve_path(PMC_COUNT_NT_OPERATOR);
-        if (dot_partial && dl)
-            sell_spmm_kernel<NB, false, 0, true, TAG, true, false, (Lay<NB>::T > 1)><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (dot_partial)
-            sell_spmm_kernel<NB, false, 0, true, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (accumulate)
-            sell_spmm_kernel<NB, false, 1, false, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, false, 0, false, TAG, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-    } else {
-        if (dot_partial && dl)
-            sell_spmm_kernel<NB, false, 0, true, TAG, false, false, (Lay<NB>::T > 1)><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (dot_partial)
-            sell_spmm_kernel<NB, false, 0, true, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, dot_with, dot_partial, nb);
-        else if (accumulate)
-            sell_spmm_kernel<NB, false, 1, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, false, 0, false, TAG><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb);
-    }
+            if constexpr (!F32) {
+                if (accumulate) {
+                    launch_spmm<NB, BV, Spmm::accumulate, TAG, false, NT>(st, nb, g, A, x, y, nullptr, nullptr, nullptr);
+                    return;
+                }
+            }
+            launch_spmm<NB, BV, Spmm::product, TAG, false, NT>(st, nb, g, A, x, y, nullptr, nullptr, nullptr);
+        });
+    });
 }
 
 template <typename XT>
@@ -976,9 +972,9 @@ static int spmm_t(hipStream_t st, int nb, const SellView& A, const XT* x, double
         count_solve_path(PMC_COUNT_TWO_STAGE_DOT);
     }
     PMC_DISPATCH_NB(nb, {
-        if (A.tag == 1) spmm_launch<NB, 1, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with, lz_mode, lz);
-        else if (A.tag == 2) spmm_launch<NB, 2, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
-        else spmm_launch<NB, 0, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
+        if (A.tag == kTagOperator) spmm_launch<NB, kTagOperator, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with, lz_mode, lz);
+        else if (A.tag == kTagApply) spmm_launch<NB, kTagApply, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
+        else spmm_launch<NB, kTagNone, XT>(st, nb, g, A, x, y, accumulate, kernel_partial, dot_with);
     });
     check_launch();
     if (two_stage) {
@@ -993,8 +989,7 @@ int spmm(hipStream_t st, int nb, const SellView& A, const double* x, double* y, 
     return spmm_t<double>(st, nb, A, x, y, accumulate, dot_partial, dot_with);
 }
 int spmm_z(hipStream_t st, int nb, const SellView& A, zvec x, double* y, double* dot_partial, zvec dot_with) {
-    if (x.f32) return spmm_t<float>(st, nb, A, x.as<float>(), y, false, dot_partial, dot_with.as<float>());
-    return spmm_t<double>(st, nb, A, x.as<double>(), y, false, dot_partial, dot_with.as<double>());
+    return dispatch_storage(x, [&](auto* xp, auto* dw) { return spmm_t(st, nb, A, xp, y, false, dot_partial, dw); }, dot_with);
 }
 
 static void check_lanczos_pass(const SellView& A, zvec x) {
@@ -1019,14 +1014,9 @@ void residual_restrict8(hipStream_t st, int nb, const SellView& A, const double*
     if (A.nrows == 0) return;
     if (A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "residual_restrict8: rows are not groups of 8");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        if (A.bv && A.f32)
-            sell_spmm_kernel<NB, 2, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
-        else if (A.bv)
-            sell_spmm_kernel<NB, true, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
-        else
-            sell_spmm_kernel<NB, false, 2, false, 0, false, true><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, coarse, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_values(A, [&](auto bv) {
+        launch_spmm<NB, decltype(bv)::value, Spmm::residual_restrict8>(st, nb, g, A, x, out, r, nullptr, coarse);
+    }));
     check_launch();
 }
 
@@ -1037,9 +1027,7 @@ void spmm_store32(hipStream_t st, int nb, const SellView& A, const double* x, do
     const dim3 g = grid_slices(A.nslices);
     LanczosUpdate lz{};
     lz.y32 = y32;
-    PMC_DISPATCH_NB(nb, {
-        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, double, double, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, y, nullptr, nullptr, nullptr, nb, lz);
-    });
+    PMC_DISPATCH_NB(nb, { launch_spmm<NB, kSharedValues, Spmm::product_store32>(st, nb, g, A, x, y, nullptr, nullptr, nullptr, &lz); });
     check_launch();
 }
 
@@ -1048,12 +1036,10 @@ void residual_samples(hipStream_t st, int nb, const SellView& A, const double* r
     if (A.bv) throw Error(PMC_ERR_INTERNAL, "residual_samples: shared values only");
     if (A.nrows == 0) return;
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        if (do_exp)
-            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, false, 2, false, 0, false, false, false, double, double, 0, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_bool(do_exp, [&](auto e) {
+        constexpr Spmm OP = decltype(e)::value ? Spmm::residual_samples_exp : Spmm::residual_samples;
+        launch_spmm<NB, kSharedValues, OP>(st, nb, g, A, x, out, r, nullptr, nullptr);
+    }));
     check_launch();
 }
 
@@ -1061,14 +1047,9 @@ void residual(hipStream_t st, int nb, const SellView& A, const double* r, const 
     check_offsets32(A, nb);
     if (A.nrows == 0) return;
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        if (A.bv && A.f32)
-            sell_spmm_kernel<NB, 2, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
-        else if (A.bv)
-            sell_spmm_kernel<NB, true, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
-        else
-            sell_spmm_kernel<NB, false, 2, false, 0><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, x, out, r, nullptr, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_values(A, [&](auto bv) {
+        launch_spmm<NB, decltype(bv)::value, Spmm::residual>(st, nb, g, A, x, out, r, nullptr, nullptr);
+    }));
     check_launch();
 }
 
@@ -1079,24 +1060,13 @@ static int cheb_step_t(hipStream_t st, int nb, const SellView& A, const double* 
     if (A.nrows == 0) return 0;
     if (A.bv != dinv_bv) throw Error(PMC_ERR_INTERNAL, "cheb_step: value/diagonal batching mismatch");
     const dim3 g = grid_bounded(grid_slices(A.nslices), dot_partial != nullptr);
-    PMC_DISPATCH_NB(nb, {
-        if (A.bv && A.f32) {
-            if (dot_partial)
-                sell_cheb_kernel<NB, 2, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
-            else
-                sell_cheb_kernel<NB, 2, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
-        } else if (A.bv) {
-            if (dot_partial)
-                sell_cheb_kernel<NB, 1, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
-            else
-                sell_cheb_kernel<NB, 1, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
-        } else {
-            if (dot_partial)
-                sell_cheb_kernel<NB, 0, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, dot_partial, nb);
-            else
-                sell_cheb_kernel<NB, 0, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, nullptr, nb);
-        }
-    });
+    PMC_DISPATCH_NB(nb, dispatch_values(A, [&](auto bv) {
+        dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+            constexpr bool DOT = decltype(dot)::value;
+            sell_cheb_kernel<NB, decltype(bv)::value, DOT, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+                A.nrows, A.nslices, A.slice_off, A.sched, A.cols, A.vals, dinv, r, xin, d, xout, a, b, DOT ? dot_partial : nullptr, nb);
+        });
+    }));
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
@@ -1109,8 +1079,7 @@ int cheb_step(hipStream_t st, int nb, const SellView& A, const double* dinv, boo
 // fp64 storage: the iterate of the last step goes straight to zout, d is left as it was (as the typed kernel does)
 int cheb_step_z(hipStream_t st, int nb, const SellView& A, const double* dinv, bool dinv_bv, const double* r,
                 const double* xin, double* d, zvec zout, double a, double b, double* dot_partial) {
-    if (zout.f32) return cheb_step_t<float>(st, nb, A, dinv, dinv_bv, r, xin, d, zout.as<float>(), a, b, dot_partial);
-    return cheb_step_t<double>(st, nb, A, dinv, dinv_bv, r, xin, d, zout.as<double>(), a, b, dot_partial);
+    return dispatch_storage(zout, [&](auto* out) { return cheb_step_t(st, nb, A, dinv, dinv_bv, r, xin, d, out, a, b, dot_partial); });
 }
 
 template <typename OT>
@@ -1121,30 +1090,20 @@ static int poly2_t(hipStream_t st, int nb, const SellView& As, const double* din
     if (As.nrows == 0) return 0;
     if (As.bv != dinv_bv) throw Error(PMC_ERR_INTERNAL, "poly2: value/diagonal batching mismatch");
     const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
-    PMC_DISPATCH_NB(nb, {
-        if (As.bv && As.f32) {
-            if (dot_partial)
-                sell_poly2_kernel<NB, 2, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
-            else
-                sell_poly2_kernel<NB, 2, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
-        } else if (As.bv) {
-            if (dot_partial)
-                sell_poly2_kernel<NB, 1, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
-            else
-                sell_poly2_kernel<NB, 1, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
-        } else if (nt_poly(As, NB)) {
-            count_solve_path(PMC_COUNT_NT_POLY);
-            if (dot_partial)
-                sell_poly2_kernel<NB, 0, true, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
-            else
-                sell_poly2_kernel<NB, 0, false, true, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
-        } else {
-            if (dot_partial)
-                sell_poly2_kernel<NB, 0, true, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x, nb);
-            else
-                sell_poly2_kernel<NB, 0, false, false, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, xadd, dot_with, padd_idx, padd_x, nb);
-        }
-    });
+    PMC_DISPATCH_NB(nb, dispatch_values(As, [&](auto bv) {
+        constexpr int BV = decltype(bv)::value;
+        constexpr bool SHARED = BV == kSharedValues;   // the non-temporal form: shared values only
+        const bool nt = SHARED && nt_poly(As, NB);
+        if (nt) count_solve_path(PMC_COUNT_NT_POLY);
+        dispatch_bool<SHARED>(nt, [&](auto nt_c) {
+            dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+                constexpr bool DOT = decltype(dot)::value;
+                sell_poly2_kernel<NB, BV, DOT, decltype(nt_c)::value, OT><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+                    As.nrows, As.nslices, As.slice_off, As.sched, As.cols, As.vals, dinv, r, xout, c0, c1,
+                    DOT ? dot_partial : nullptr, xadd, dot_with, padd_idx, padd_x, nb);
+            });
+        });
+    }));
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
@@ -1158,9 +1117,9 @@ int poly2(hipStream_t st, int nb, const SellView& As, const double* dinv, bool d
 int poly2_z(hipStream_t st, int nb, const SellView& As, const double* dinv, bool dinv_bv, const double* r, zvec xout,
             double c0, double c1, double* dot_partial, const double* xadd, const double* dot_with, const int* padd_idx,
             const double* padd_x) {
-    if (xout.f32)
-        return poly2_t<float>(st, nb, As, dinv, dinv_bv, r, xout.as<float>(), c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
-    return poly2_t<double>(st, nb, As, dinv, dinv_bv, r, xout.as<double>(), c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
+    return dispatch_storage(xout, [&](auto* out) {
+        return poly2_t(st, nb, As, dinv, dinv_bv, r, out, c0, c1, dot_partial, xadd, dot_with, padd_idx, padd_x);
+    });
 }
 
 // a level runs the deep gather loop (sell_row_range_deep) when its launch has at most this many wavefronts - about two per
@@ -1173,11 +1132,69 @@ static inline bool deep_level(const SellView& A, int nb) {
     return nb >= kGroup && !A.bv && (long)A.nslices * (nb / kGroup) <= limit;
 }
 
-// the launchers below take the right-hand side and the inter-level vectors (coarse right-hand side, coarse correction) of a
-// shared-value level in either storage: T names the element type inside the braces
-#define PMC_DISPATCH_F32(is_f32, T, ...)                \
-    if (is_f32) { using T = float; __VA_ARGS__; }       \
-    else { using T = double; __VA_ARGS__; }
+// how a V-cycle kernel walks a level: its NT, DEEP, SPL and GIB arguments, of which at most one path is taken
+enum class Walk {
+    lean,        // the lean gather loop
+    lean_nt,     // ... with non-temporal matrix / result streams                                   NT
+    deep2,       // sell_row_range_deep, 2 slice columns per trip (small 32-wide levels)            DEEP 2
+    deep4,       // ... 4 slice columns per trip                                                    DEEP 4
+    split,       // rows stored as 2^split_log2 pieces: narrow launches, grid and row count differ  SPL
+    both_groups  // both column groups of a 64-wide launch in one workgroup, non-temporal           GIB, NT
+};
+template <Walk W>
+struct WalkArgs {
+    static constexpr bool NT = W == Walk::lean_nt || W == Walk::both_groups;
+    static constexpr int DEEP = W == Walk::deep2 ? 2 : (W == Walk::deep4 ? 4 : 1);
+    static constexpr bool SPL = W == Walk::split, GIB = W == Walk::both_groups;
+    // the row-split and the two-group forms carry the column groups inside the workgroup
+    static dim3 grid(dim3 g, int nb) { return SPL || GIB ? g : groups_xcd(g, nb); }
+    static int nrows(const SellView& A) { return SPL ? A.nrows >> A.split_log2 : A.nrows; }
+    static int sl(const SellView& A) { return SPL ? A.split_log2 : 0; }
+};
+
+// the epilogue of vc_poly2_kernel (EPS, XA, PA): operands found at run time by their pointers, or known at compile time
+enum class Epilogue {
+    dynamic,  // xadd / the coarse correction are added where their pointers are set
+    nothing,  // compile time: nothing is added (pre-smoothing)                       EPS
+    full      // compile time: the iterate and the coarse correction are added        EPS, XA, PA
+};
+
+// xadd is the level's fp32 iterate; a launch without coarse correction passes a typed null (PT = double)
+template <int NB, Walk W, bool DOT, int BV = kSharedValues, Epilogue E = Epilogue::dynamic, typename XT, typename OT, typename PT>
+static void launch_vc_poly2(hipStream_t st, int nb, dim3 g, const SellView& As, const double* dinv, const XT* r, OT* xout,
+                            double c0, double c1, double* partial, const float* xadd, const double* dot_with,
+                            const int* padd_idx, const PT* padd_x) {
+    using WA = WalkArgs<W>;
+    constexpr bool EPS = E != Epilogue::dynamic, ADD = E != Epilogue::nothing;
+    vc_poly2_kernel<NB, XT, OT, float, DOT, WA::NT, BV, WA::DEEP, WA::SPL, WA::GIB, PT, EPS, EPS && ADD, EPS && ADD>
+        <<<WA::grid(g, nb), kBlock, 0, st>>>(
+        WA::nrows(As), As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, DOT ? partial : nullptr,
+        ADD ? xadd : nullptr, DOT ? dot_with : nullptr, ADD ? padd_idx : nullptr, ADD ? padd_x : nullptr, nb, WA::sl(As));
+}
+constexpr const double* kNoCoarse = nullptr;
+
+// what leaves vc_residual_kernel besides (or instead of) the residual: its R8, STORE and RAGG arguments
+enum class Restrict {
+    none,         // the residual alone
+    groups8,      // ... and its sums over groups of 8 consecutive rows                    R8
+    groups8_only, // the sums alone, the residual is not stored                            R8, no STORE
+    aggregates    // ... and its sums over the aggregates of the segment tables            RAGG
+};
+
+// IN_PLACE (the kernel's TAG 1): r == y, the correction of a residual by the coarse iterate
+template <int NB, Walk W, Restrict R, int BV = kSharedValues, bool IN_PLACE = false, typename XT, typename RT, typename CT>
+static void launch_vc_residual(hipStream_t st, int nb, dim3 g, const SellView& A, const XT* x, const RT* r, float* y, CT* coarse,
+                               const int* seg_ptr = nullptr, const int* seg_cid = nullptr, const int* seg_pos = nullptr) {
+    using WA = WalkArgs<W>;
+    static_assert(!WA::NT && !WA::GIB, "the residual kernels have no non-temporal and no two-group form");
+    constexpr bool R8 = R == Restrict::groups8 || R == Restrict::groups8_only, RAGG = R == Restrict::aggregates;
+    constexpr bool STORE = R != Restrict::groups8_only;
+    vc_residual_kernel<NB, XT, RT, float, R8, BV, STORE, WA::DEEP, RAGG, WA::SPL, CT, IN_PLACE ? 1 : 0>
+        <<<WA::grid(g, nb), kBlock, 0, st>>>(
+        WA::nrows(A), A.nslices, A.slice_off, A.cols, A.vals, x, r, STORE ? y : nullptr, R8 || RAGG ? coarse : nullptr, nb,
+        RAGG ? seg_ptr : nullptr, RAGG ? seg_cid : nullptr, RAGG ? seg_pos : nullptr, WA::sl(A));
+}
+constexpr double* kNoRestriction = nullptr;
 
 // r in fp32: the copy of the Lanczos vector the MINRES loop keeps for the top level of a cycle (k::lincomb3) - gathered, and
 // read at the own row, as 128-byte rows instead of 256-byte ones - or the coarse right-hand side the level above wrote
@@ -1189,30 +1206,25 @@ static void vc_presmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     if (As.bv) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32: shared values expected");
     const dim3 g = grid_slices(As.nslices);
     if (As.split_log2) {
-        PMC_DISPATCH_NARROW(nb, {
-            vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, true><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb, As.split_log2);
+        dispatch_narrow(nb, [&](auto w) {
+            launch_vc_poly2<decltype(w)::value, Walk::split, false>(st, nb, g, As, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, kNoCoarse);
         });
-        check_launch();
-        return;
-    }
-    if (deep_level(As, nb)) {
-        vc_poly2_kernel<kGroup, RT, float, float, false, false, 0, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
-        check_launch();
-        return;
-    }
-    PMC_DISPATCH_NB(nb, {
+    } else if (deep_level(As, nb)) {
+        launch_vc_poly2<kGroup, Walk::deep2, false>(st, nb, g, As, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, kNoCoarse);
+    } else PMC_DISPATCH_NB(nb, {
         // (the 32-wide fp32 forms - the finest level of a cycle - know at compile time that the epilogue adds nothing)
-        constexpr bool EPS = NB == kGroup && sizeof(RT) == 4;
-        if (nt_poly(As, NB)) {
-            count_solve_path(PMC_COUNT_NT_POLY);
-            vc_poly2_kernel<NB, RT, float, float, false, true, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
-        } else
-            vc_poly2_kernel<NB, RT, float, float, false, false, 0, 1, false, false, double, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+        constexpr Epilogue E = NB == kGroup && sizeof(RT) == 4 ? Epilogue::nothing : Epilogue::dynamic;
+        const bool nt = nt_poly(As, NB);
+        if (nt) count_solve_path(PMC_COUNT_NT_POLY);
+        dispatch_bool(nt, [&](auto nt_c) {
+            constexpr Walk W = decltype(nt_c)::value ? Walk::lean_nt : Walk::lean;
+            launch_vc_poly2<NB, W, false, kSharedValues, E>(st, nb, g, As, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, kNoCoarse);
+        });
     });
     check_launch();
 }
 void vc_presmooth32(hipStream_t st, int nb, const SellView& As, const double* dinv, zvec r, float* xout, double c0, double c1) {
-    PMC_DISPATCH_F32(r.f32, RT, vc_presmooth32_t<RT>(st, nb, As, dinv, r.as<RT>(), xout, c0, c1));
+    dispatch_storage(r, [&](auto* rp) { vc_presmooth32_t(st, nb, As, dinv, rp, xout, c0, c1); });
 }
 
 void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse) {
@@ -1220,9 +1232,9 @@ void vc_residual_restrict8_32(hipStream_t st, int nb, const SellView& A, zvec r,
     if (A.nrows == 0) return;
     if (A.bv || A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict8_32: shared values and groups of 8 rows expected");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, RT, float, true, 0, true, 1, false, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb);
-    })));
+    PMC_DISPATCH_NB(nb, dispatch_storage(r, [&](auto* rp) {
+        dispatch_storage(coarse, [&](auto* cp) { launch_vc_residual<NB, Walk::lean, Restrict::groups8>(st, nb, g, A, x, rp, out, cp); });
+    }));
     check_launch();
 }
 
@@ -1233,24 +1245,16 @@ static void vc_residual32_t(hipStream_t st, int nb, const SellView& A, const RT*
     if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual32: shared values expected");
     const dim3 g = grid_slices(A.nslices);
     if (A.split_log2) {
-        PMC_DISPATCH_NARROW(nb, {
-            vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, false, true><<<g, kBlock, 0, st>>>(A.nrows >> A.split_log2, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb, nullptr, nullptr, nullptr, A.split_log2);
+        dispatch_narrow(nb, [&](auto w) {
+            launch_vc_residual<decltype(w)::value, Walk::split, Restrict::none>(st, nb, g, A, x, r, out, kNoRestriction);
         });
-        check_launch();
-        return;
-    }
-    if (deep_level(A, nb)) {
-        vc_residual_kernel<kGroup, float, RT, float, false, 0, true, 4><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
-        check_launch();
-        return;
-    }
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, RT, float, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
-    });
+    } else if (deep_level(A, nb)) {
+        launch_vc_residual<kGroup, Walk::deep4, Restrict::none>(st, nb, g, A, x, r, out, kNoRestriction);
+    } else PMC_DISPATCH_NB(nb, { launch_vc_residual<NB, Walk::lean, Restrict::none>(st, nb, g, A, x, r, out, kNoRestriction); });
     check_launch();
 }
 void vc_residual32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out) {
-    PMC_DISPATCH_F32(r.f32, RT, vc_residual32_t<RT>(st, nb, A, r.as<RT>(), x, out));
+    dispatch_storage(r, [&](auto* rp) { vc_residual32_t(st, nb, A, rp, x, out); });
 }
 
 void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec r, const float* x, float* out, zvec coarse,
@@ -1259,9 +1263,11 @@ void vc_residual_restrict_agg32(hipStream_t st, int nb, const SellView& A, zvec 
     if (A.nrows == 0) return;
     if (A.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_restrict_agg32: shared values expected");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_F32(r.f32, RT, PMC_DISPATCH_F32(coarse.f32, CT, PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, RT, float, false, 0, true, 1, true, false, CT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r.as<RT>(), out, coarse.as<CT>(), nb, seg_ptr, seg_cid, seg_pos);
-    })));
+    PMC_DISPATCH_NB(nb, dispatch_storage(r, [&](auto* rp) {
+        dispatch_storage(coarse, [&](auto* cp) {
+            launch_vc_residual<NB, Walk::lean, Restrict::aggregates>(st, nb, g, A, x, rp, out, cp, seg_ptr, seg_cid, seg_pos);
+        });
+    }));
     check_launch();
 }
 
@@ -1276,9 +1282,7 @@ void vc_restrict32(hipStream_t st, int nb, const SellView& Pt, const float* res,
     if (Pt.nrows == 0) return;
     if (Pt.bv) throw Error(PMC_ERR_INTERNAL, "vc_restrict32: shared values expected");
     const dim3 g = grid_slices(Pt.nslices);
-    PMC_DISPATCH_NB(nb, {
-        sell_spmm_kernel<NB, false, 0, false, 0, false, false, false, float, float><<<groups_xcd(g, nb), kBlock, 0, st>>>(Pt.nrows, Pt.nslices, Pt.slice_off, Pt.sched, Pt.cols, Pt.vals, res, coarse.as<float>(), nullptr, nullptr, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, { launch_spmm<NB, kSharedValues, Spmm::product>(st, nb, g, Pt, res, coarse.as<float>(), nullptr, nullptr, nullptr); });
     check_launch();
 }
 
@@ -1288,25 +1292,18 @@ static void vc_residual_coarse32_t(hipStream_t st, int nb, const SellView& SP, f
     if (SP.nrows == 0) return;
     if (SP.bv) throw Error(PMC_ERR_INTERNAL, "vc_residual_coarse32: shared values expected");
     const dim3 g = grid_slices(SP.nslices);
+    constexpr bool IN_PLACE = true;   // res -= SP xc
     if (SP.split_log2) {
-        PMC_DISPATCH_NARROW(nb, {
-            vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, true, double, 1><<<g, kBlock, 0, st>>>(SP.nrows >> SP.split_log2, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb, nullptr, nullptr, nullptr, SP.split_log2);
+        dispatch_narrow(nb, [&](auto w) {
+            launch_vc_residual<decltype(w)::value, Walk::split, Restrict::none, kSharedValues, IN_PLACE>(st, nb, g, SP, xc, res, res, kNoRestriction);
         });
-        check_launch();
-        return;
-    }
-    if (deep_level(SP, nb)) {
-        vc_residual_kernel<kGroup, XT, float, float, false, 0, true, 2, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
-        check_launch();
-        return;
-    }
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, XT, float, float, false, 0, true, 1, false, false, double, 1><<<groups_xcd(g, nb), kBlock, 0, st>>>(SP.nrows, SP.nslices, SP.slice_off, SP.cols, SP.vals, xc, res, res, nullptr, nb);
-    });
+    } else if (deep_level(SP, nb)) {
+        launch_vc_residual<kGroup, Walk::deep2, Restrict::none, kSharedValues, IN_PLACE>(st, nb, g, SP, xc, res, res, kNoRestriction);
+    } else PMC_DISPATCH_NB(nb, { launch_vc_residual<NB, Walk::lean, Restrict::none, kSharedValues, IN_PLACE>(st, nb, g, SP, xc, res, res, kNoRestriction); });
     check_launch();
 }
 void vc_residual_coarse32(hipStream_t st, int nb, const SellView& SP, float* res, zvec xc) {
-    PMC_DISPATCH_F32(xc.f32, XT, vc_residual_coarse32_t<XT>(st, nb, SP, res, xc.as<XT>()));
+    dispatch_storage(xc, [&](auto* xp) { vc_residual_coarse32_t(st, nb, SP, res, xp); });
 }
 
 template <typename OT, typename PT>
@@ -1319,17 +1316,16 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
     if (As.split_log2) {
         if (dot_partial) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: the row-split form serves inner levels (no fused dot)");
-        PMC_DISPATCH_NARROW(nb, {
-            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, true, false, PT><<<g, kBlock, 0, st>>>(As.nrows >> As.split_log2, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb, As.split_log2);
+        dispatch_narrow(nb, [&](auto w) {
+            launch_vc_poly2<decltype(w)::value, Walk::split, false>(st, nb, g, As, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc);
         });
         check_launch();
         return 0;
     }
     if (deep_level(As, nb)) {
-        if (dot_partial)
-            vc_poly2_kernel<kGroup, float, OT, float, true, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
-        else
-            vc_poly2_kernel<kGroup, float, OT, float, false, false, 0, 4, false, false, PT><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+            launch_vc_poly2<kGroup, Walk::deep4, decltype(dot)::value>(st, nb, g, As, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc);
+        });
         check_launch();
         return dot_partial ? dot_blocks(g, nb) : 0;
     }
@@ -1338,10 +1334,9 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     static const bool gib = [] { const char* e = lab_env("PMC_GIB"); return e && atoi(e) != 0; }();
     if (gib && nb == 2 * kGroup && nt_poly(As, kGroup) && !xcd_layout(g, nb)) {
         count_solve_path(PMC_COUNT_NT_POLY);
-        if (dot_partial)
-            vc_poly2_kernel<kGroup, float, OT, float, true, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
-        else
-            vc_poly2_kernel<kGroup, float, OT, float, false, true, 0, 1, false, true, PT><<<g, kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+            launch_vc_poly2<kGroup, Walk::both_groups, decltype(dot)::value>(st, nb, g, As, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc);
+        });
         check_launch();
         return dot_partial ? (int)g.x : 0;
     }
@@ -1350,17 +1345,15 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
     if (!x || !parent || !xc || (dot_partial && !r))
         throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32: iterate, parent table, coarse correction and the dot's vector expected");
     PMC_DISPATCH_NB(nb, {
-        constexpr bool EPS = NB == kGroup;
-        if (nt_poly(As, NB)) {
-            count_solve_path(PMC_COUNT_NT_POLY);
-            if (dot_partial)
-                vc_poly2_kernel<NB, float, OT, float, true, true, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
-            else
-                vc_poly2_kernel<NB, float, OT, float, false, true, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
-        } else if (dot_partial)
-            vc_poly2_kernel<NB, float, OT, float, true, false, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc, nb);
-        else
-            vc_poly2_kernel<NB, float, OT, float, false, false, 0, 1, false, false, PT, EPS, EPS, EPS><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, parent, xc, nb);
+        constexpr Epilogue E = NB == kGroup ? Epilogue::full : Epilogue::dynamic;
+        const bool nt = nt_poly(As, NB);
+        if (nt) count_solve_path(PMC_COUNT_NT_POLY);
+        dispatch_bool(nt, [&](auto nt_c) {
+            dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+                constexpr Walk W = decltype(nt_c)::value ? Walk::lean_nt : Walk::lean;
+                launch_vc_poly2<NB, W, decltype(dot)::value, kSharedValues, E>(st, nb, g, As, dinv, res, xout, c0, c1, dot_partial, x, r, parent, xc);
+            });
+        });
     });
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
@@ -1368,11 +1361,11 @@ static int vc_postsmooth32_t(hipStream_t st, int nb, const SellView& As, const d
 
 int vc_postsmooth32_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
                       zvec xout, double c0, double c1, const double* r, const int* parent, zvec xc, double* dot_partial) {
-    int nblk = 0;
-    PMC_DISPATCH_F32(xout.f32, OT, PMC_DISPATCH_F32(xc.f32, PT, {
-        nblk = vc_postsmooth32_t<OT, PT>(st, nb, As, dinv, res, x, xout.as<OT>(), c0, c1, r, parent, xc.as<PT>(), dot_partial);
-    }));
-    return nblk;
+    return dispatch_storage(xout, [&](auto* out) {
+        return dispatch_storage(xc, [&](auto* xp) {
+            return vc_postsmooth32_t(st, nb, As, dinv, res, x, out, c0, c1, r, parent, xp, dot_partial);
+        });
+    });
 }
 
 // ---- the same level with per-realization fp32 values (Darcy; SellView::f32) and per-realization diagonals
@@ -1383,7 +1376,7 @@ void vc_presmooth32_bv(hipStream_t st, int nb, const SellView& As, const double*
     if (!(As.bv && As.f32)) throw Error(PMC_ERR_INTERNAL, "vc_presmooth32_bv: per-realization fp32 values expected");
     const dim3 g = grid_slices(As.nslices);
     PMC_DISPATCH_NB(nb, {
-        vc_poly2_kernel<NB, double, float, float, false, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, nullptr, nb);
+        launch_vc_poly2<NB, Walk::lean, false, kValues32>(st, nb, g, As, dinv, r, xout, c0, c1, nullptr, nullptr, nullptr, nullptr, kNoCoarse);
     });
     check_launch();
 }
@@ -1393,9 +1386,7 @@ void vc_restrict8_32_bv(hipStream_t st, int nb, const SellView& A, const double*
     if (A.nrows == 0) return;
     if (!(A.bv && A.f32) || A.nrows % 8 != 0) throw Error(PMC_ERR_INTERNAL, "vc_restrict8_32_bv: operand mismatch");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, double, float, true, 2, false><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, nullptr, coarse, nb);
-    });
+    PMC_DISPATCH_NB(nb, { launch_vc_residual<NB, Walk::lean, Restrict::groups8_only, kValues32>(st, nb, g, A, x, r, nullptr, coarse); });
     check_launch();
 }
 
@@ -1410,9 +1401,7 @@ void vc_residual32_bv(hipStream_t st, int nb, const SellView& A, const double* r
     if (A.nrows == 0) return;
     if (!(A.bv && A.f32)) throw Error(PMC_ERR_INTERNAL, "vc_residual32_bv: per-realization fp32 values expected");
     const dim3 g = grid_slices(A.nslices);
-    PMC_DISPATCH_NB(nb, {
-        vc_residual_kernel<NB, float, double, float, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(A.nrows, A.nslices, A.slice_off, A.cols, A.vals, x, r, out, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, { launch_vc_residual<NB, Walk::lean, Restrict::none, kValues32>(st, nb, g, A, x, r, out, kNoRestriction); });
     check_launch();
 }
 
@@ -1423,12 +1412,9 @@ static int vc_postsmooth32_bv_t(hipStream_t st, int nb, const SellView& As, cons
     if (As.nrows == 0) return 0;
     if (!(As.bv && As.f32)) throw Error(PMC_ERR_INTERNAL, "vc_postsmooth32_bv: per-realization fp32 values expected");
     const dim3 g = grid_bounded(grid_slices(As.nslices), dot_partial != nullptr);
-    PMC_DISPATCH_NB(nb, {
-        if (dot_partial)
-            vc_poly2_kernel<NB, float, OT, float, true, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, dot_partial, x, r, nullptr, nullptr, nb);
-        else
-            vc_poly2_kernel<NB, float, OT, float, false, false, 2><<<groups_xcd(g, nb), kBlock, 0, st>>>(As.nrows, As.nslices, As.slice_off, As.cols, As.vals, dinv, res, xout, c0, c1, nullptr, x, nullptr, nullptr, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+        launch_vc_poly2<NB, Walk::lean, decltype(dot)::value, kValues32>(st, nb, g, As, dinv, res, xout, c0, c1, dot_partial, x, r, nullptr, kNoCoarse);
+    }));
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
@@ -1439,8 +1425,7 @@ int vc_postsmooth32_bv(hipStream_t st, int nb, const SellView& As, const double*
 }
 int vc_postsmooth32_bv_z(hipStream_t st, int nb, const SellView& As, const double* dinv, const float* res, const float* x,
                          zvec xout, double c0, double c1, const double* r, double* dot_partial) {
-    if (xout.f32) return vc_postsmooth32_bv_t<float>(st, nb, As, dinv, res, x, xout.as<float>(), c0, c1, r, dot_partial);
-    return vc_postsmooth32_bv_t<double>(st, nb, As, dinv, res, x, xout.as<double>(), c0, c1, r, dot_partial);
+    return dispatch_storage(xout, [&](auto* out) { return vc_postsmooth32_bv_t(st, nb, As, dinv, res, x, out, c0, c1, r, dot_partial); });
 }
 
 template <typename XT>
@@ -1451,20 +1436,19 @@ static int pair_spmm_t(hipStream_t st, int nb, const SellView& A1, const XT* x1,
     if (!A1.bv || A2.bv || A1.nrows != A2.nrows || A1.nslices != A2.nslices)
         throw Error(PMC_ERR_INTERNAL, "pair_spmm: operand mismatch");
     const dim3 g = grid_bounded(grid_slices(A1.nslices), dot_partial != nullptr);
-    PMC_DISPATCH_NB(nb, {
-        if (dot_partial)
-            sell_pair_spmm_kernel<NB, true, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A1.nrows, A1.nslices, A1.slice_off, A1.cols, A1.vals, A2.slice_off, A2.cols, A2.vals, x1, x2, y, dot_with, dot_partial, nb);
-        else
-            sell_pair_spmm_kernel<NB, false, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(A1.nrows, A1.nslices, A1.slice_off, A1.cols, A1.vals, A2.slice_off, A2.cols, A2.vals, x1, x2, y, nullptr, nullptr, nb);
-    });
+    PMC_DISPATCH_NB(nb, dispatch_bool(dot_partial != nullptr, [&](auto dot) {
+        constexpr bool DOT = decltype(dot)::value;
+        sell_pair_spmm_kernel<NB, DOT, XT><<<groups_xcd(g, nb), kBlock, 0, st>>>(
+            A1.nrows, A1.nslices, A1.slice_off, A1.cols, A1.vals, A2.slice_off, A2.cols, A2.vals, x1, x2, y,
+            DOT ? dot_with : nullptr, DOT ? dot_partial : nullptr, nb);
+    }));
     check_launch();
     return dot_partial ? dot_blocks(g, nb) : 0;
 }
 
 int pair_spmm_z(hipStream_t st, int nb, const SellView& A1, zvec x1, const SellView& A2, zvec x2, double* y,
                 double* dot_partial, zvec dot_with) {
-    if (x1.f32) return pair_spmm_t<float>(st, nb, A1, x1.as<float>(), A2, x2.as<float>(), y, dot_partial, dot_with.as<float>());
-    return pair_spmm_t<double>(st, nb, A1, x1.as<double>(), A2, x2.as<double>(), y, dot_partial, dot_with.as<double>());
+    return dispatch_storage(x1, [&](auto* p1, auto* p2, auto* dw) { return pair_spmm_t(st, nb, A1, p1, A2, p2, y, dot_partial, dw); }, x2, dot_with);
 }
 
 }  // namespace k

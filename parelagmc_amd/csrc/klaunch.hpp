@@ -1,5 +1,16 @@
 // Host-side launch helpers shared by the kernel units (k_*.hip): grids, column groups, the bounds of the fused dots, the
-// non-temporal thresholds, the launch check.  Included by the kernel sources only.
+// non-temporal thresholds, the launch check, and the dispatch helpers that turn a run-time fact of a launch into a template
+// argument of its kernel.  Included by the kernel sources only.
+//
+// How a launcher chooses its kernel.  Every kernel template has ONE launch site per unit.  A launcher decides the form at run
+// time (fused dot or not, value storage, non-temporal streams, ...) and hands each such fact to a dispatch_* helper below,
+// which calls a generic lambda with the fact as a compile-time constant:
+//     dispatch_bool(dot_partial != nullptr, [&](auto dot) { constexpr bool DOT = decltype(dot)::value; ... });
+// A lambda called for both values of a flag instantiates the kernel for both.  The set of instantiations is part of a unit's
+// machine code (see the head of k_sell.hip), so a form that must not exist is pruned where the flag is dispatched - the
+// helpers' EXISTS argument - not by leaving the launch unreachable.  The helpers and the lambdas they call are forced inline
+// (PMC_DISPATCH_INLINE): a dispatch compiles to the if / switch one would write by hand, no call is left on the launch path.
+// PMC_DISPATCH_NB (kdev.hpp) does the same for the batch width.
 // Every unit holds its own copy of the statics that cache a lab_env() lookup: lab_env() is constant for the life of a process.
 #pragma once
 #include "kdev.hpp"
@@ -7,8 +18,59 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace pmc {
+
+// ---- run-time fact -> compile-time constant
+#define PMC_DISPATCH_INLINE __attribute__((always_inline, flatten)) inline
+// a flag as std::bool_constant.  EXISTS = false: the kernel has no such form here - only the `false` instantiation is made,
+// and a set flag takes it too (the launcher has ruled it out, or the form without the flag serves the launch as well)
+template <bool EXISTS = true, typename F>
+PMC_DISPATCH_INLINE auto dispatch_bool(bool v, F&& f) {
+    if constexpr (EXISTS) {
+        if (v) return f(std::true_type{});
+    }
+    return f(std::false_type{});
+}
+// the kernels' BV argument - how a SellView stores its values - as std::integral_constant<int, BV>
+constexpr int kSharedValues = 0;   // one fp64 value per entry for all realizations
+constexpr int kValues64 = 1;       // per-realization fp64 values
+constexpr int kValues32 = 2;       // per-realization fp32 values (SellView::f32)
+// PER_REALIZATION = false: the launcher serves shared values only (it has thrown otherwise)
+template <bool PER_REALIZATION = true, typename F>
+PMC_DISPATCH_INLINE auto dispatch_values(const SellView& A, F&& f) {
+    if constexpr (PER_REALIZATION) {
+        if (A.bv && A.f32) return f(std::integral_constant<int, kValues32>{});
+        if (A.bv) return f(std::integral_constant<int, kValues64>{});
+    }
+    return f(std::integral_constant<int, kSharedValues>{});
+}
+// a stored vector (zvec) as the typed pointer to its elements, float* or double*; `same` are further vectors of that storage
+template <typename F, typename... Z>
+PMC_DISPATCH_INLINE auto dispatch_storage(zvec z, F&& f, Z... same) {
+    if (z.f32) return f(z.as<float>(), same.template as<float>()...);
+    return f(z.as<double>(), same.template as<double>()...);
+}
+// a bare storage flag (no vector at hand) as a tag of the element type: `typename decltype(t)::type` is float or double
+template <typename T>
+struct type_tag { using type = T; };
+template <typename F>
+PMC_DISPATCH_INLINE auto dispatch_f32(bool f32, F&& f) {
+    if (f32) return f(type_tag<float>{});
+    return f(type_tag<double>{});
+}
+// the widths of the row-split instantiations (SellView::split_log2), which exist for launches of at most 8 realizations
+template <typename F>
+PMC_DISPATCH_INLINE auto dispatch_narrow(int nb, F&& f) {
+    switch (nb) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: throw Error(PMC_ERR_INTERNAL, "row-split level kernels serve launches of 1, 2, 4 or 8 realizations");
+    }
+}
 
 // grid of a group-capable kernel: y = number of column groups of a batch of nb realizations (1 up to kGroup)
 static inline dim3 groups(dim3 g, int nb) { return dim3(g.x, nb > kGroup ? (unsigned)(nb / kGroup) : 1u); }
