@@ -602,23 +602,50 @@ void Darcy::compute_G(int level, int nbatch, const double* kf, double* G, double
     DarcyLevel& d = lv[level];
     PMC_REQUIRE(d.n_gobs > 0, "ComputeG: no observation functionals set on this level");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     std::vector<double> q(kMaxBatch);
+    enum { K, G_, STATS };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, (size_t)d.n_p, stage_k), ChunkArg::host(G, (size_t)d.n_gobs), ChunkArg::stats(stats)},
+               [&](const Chunk& c) {
+                   solve_chunk(level, c.nb, c.at<double>(K), q.data(), nullptr, c.at<pmc_stats>(STATS), 0, 0, c.at<double>(G_));
+                   for (int b = 0; b < c.nb; ++b) {
+                       if (Q) Q[c.done + b] = q[b];
+                       if (C) C[c.done + b] = (double)((size_t)d.n_u + d.n_p);
+                   }
+               });
+}
+
+// The launches of a batched entry (handles.hpp, ChunkArg): the widest width of the level first, halved until it fits what is
+// left.  Staging is sized by a chunk before anything of the chunk is enqueued; the first chunk of a call is the widest.
+void Darcy::for_chunks(int level, int nbatch, int memspace, std::vector<ChunkArg> args, const std::function<void(const Chunk&)>& body) {
+    hipStream_t st = ctx.stream;
+    const DarcyLevel& d = lv[level];
+    const bool host = memspace == PMC_MEM_HOST;
+    std::vector<void*> dev(args.size());
     int done = 0;
     while (done < nbatch) {
         int nb = batch_width((size_t)d.n_u + d.n_p, true, ctx.device);
         while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + (size_t)done * d.n_p;
-        if (memspace == PMC_MEM_HOST) {
-            ensure(level, nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * d.n_p * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
+        auto user = [&](const ChunkArg& a) { return a.user ? (char*)a.user + (size_t)done * a.len * a.size : nullptr; };
+        for (size_t i = 0; i < args.size(); ++i) {
+            const ChunkArg& a = args[i];
+            const bool made = a.kind == ChunkArg::Made || a.kind == ChunkArg::MadeHost;
+            dev[i] = made ? nullptr : user(a);
+            if (!dev[i] || !host || a.kind == ChunkArg::Host) continue;
+            a.stage->ensure(a.len * nb);
+            if (a.kind == ChunkArg::In) PMC_HIP(hipMemcpyAsync(a.stage->p, dev[i], a.size * a.len * nb, hipMemcpyHostToDevice, st));
+            dev[i] = a.stage->p;
         }
-        solve_chunk(level, nb, k_d, q.data(), nullptr, stats ? stats + done : nullptr, 0, 0, G + (size_t)done * d.n_gobs);
-        for (int b = 0; b < nb; ++b) {
-            if (Q) Q[done + b] = q[b];
-            if (C) C[done + b] = (double)((size_t)d.n_u + d.n_p);
+        body(Chunk{done, nb, dev.data()});
+        for (size_t i = 0; i < args.size(); ++i) {
+            const ChunkArg& a = args[i];
+            const bool made = a.kind == ChunkArg::Made || a.kind == ChunkArg::MadeHost;
+            if (!user(a) || !(made || (host && a.kind == ChunkArg::Out))) continue;
+            const bool to_host = host || a.kind == ChunkArg::MadeHost;
+            PMC_REQUIRE(dev[i] != nullptr, "for_chunks: the body left an output it makes unset");
+            PMC_HIP(hipMemcpyAsync(user(a), dev[i], a.size * a.len * nb, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
         }
+        PMC_HIP(hipStreamSynchronize(st));
         done += nb;
     }
 }
@@ -758,22 +785,43 @@ void gather_rows(hipStream_t st, int nb, int m, const int* rows, const double* x
 }
 }  // namespace
 
+Darcy::SaddleLaunch Darcy::saddle_launch(int level, int nb, const double* k_d, SolveMode mode, bool timed, bool setup_ends) {
+    DarcyLevel& d = lv[level];
+    ensure(level, nb);
+    if (timed) ctx.phase_mark(0);
+    setup_chunk(level, nb, k_d);             // M(k), Schur hierarchy, l1 diagonals: serves every solve of the launch
+    if (timed && setup_ends) ctx.phase_mark(1);   // "Darcy: Build Solver" ends here: everything below is the solve
+    SaddleLaunch L;
+    // in-loop event brackets are not recorded while the MINRES iterations may be captured into a hipGraph (as the sampler's)
+    chunk_ops(level, nb, opts.use_graph == 0, L.A, L.prec);
+    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
+    Multigrid* mgp = chain ? &chain->mg : &mg;
+    const int mg_l0 = chain ? 0 : level;
+    work.want_r32 = false;
+    L.key0 = hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb);
+    L.hint.key = hash_mix(L.key0, mode);
+    L.hint.sig = mgp->signature(mg_l0);
+    for (const void* p : {(const void*)cx.p, (const void*)cd.p, (const void*)cx2.p, (const void*)d.mvals.p, (const void*)d.mvals_scaled.p,
+                          (const void*)d.l1invM.p, (const void*)d.rhs_bc.p})
+        L.hint.sig = hash_ptr(L.hint.sig, p);
+    return L;
+}
+
+void Darcy::solve_done(const MinresResult& res, int nb, pmc_stats* stats) {
+    if (stats) {
+        ctx.phase_mark(2);
+        for (int kcol = 0; kcol < nb; ++kcol) stats[kcol] = res.col[kcol];
+        ctx.phase_report(stats, nb);
+    }
+    if (op_timer.on) op_timer.harvest();   // minres_solve has synchronised the stream
+    if (poly_timer.on) poly_timer.harvest();
+}
+
 void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                         int nrows, double* G_host) {
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const int n = d.n_u + d.n_p;
-    ensure(level, nb);
-    if (stats) ctx.phase_mark(0);
-    setup_chunk(level, nb, k_d);
-    if (stats) ctx.phase_mark(1);   // "Darcy: Build Solver" ends here: everything below is the solve
-    LinOp A;
-    PrecFn prec;
-    // in-loop event brackets are not recorded while the MINRES iterations may be captured into a hipGraph (as the sampler's)
-    chunk_ops(level, nb, opts.use_graph == 0, A, prec);
-    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
-    Multigrid* mgp = chain ? &chain->mg : &mg;
-    const int mg_l0 = chain ? 0 : level;
     // SolveFwd only needs Q = <obs, sol>: unless the solution itself is requested, MINRES maintains just the rows in
     // the support of obs (compact w / x vectors)
     // With a tracer on the level (pmc_darcy_set_tracer) Q is the travel-time QoI, which reads the whole flux block: the full
@@ -787,23 +835,11 @@ void Darcy::solve_chunk(int level, int nb, const double* k_d, double* Q_host, do
     const int ncomp = gmode ? d.n_grows : d.n_obs;
     const int* comp_rows = gmode ? d.g_rows.p : d.obs_rows.p;
     const double* comp_w = gmode ? d.g_obs_w.p : d.obs_w.p;
+    const SaddleLaunch L = saddle_launch(level, nb, k_d, gmode ? kSolveGRows : (compact ? kSolveObsRows : kSolveFull), stats != nullptr, true);
     sol_compact.ensure((size_t)std::max(ncomp, 1) * nb);
-    GraphHint hint;
-    hint.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), gmode ? 3 : (compact ? 1 : 2));
-    hint.sig = mgp->signature(mg_l0);
-    for (const void* p : {(const void*)cx.p, (const void*)cd.p, (const void*)cx2.p, (const void*)d.mvals.p, (const void*)d.mvals_scaled.p,
-                          (const void*)d.l1invM.p, (const void*)d.rhs_bc.p})
-        hint.sig = hash_ptr(hint.sig, p);
-    MinresResult res = compact ? minres_solve(ctx, nb, A, prec, d.rhs_bc.p, sol_compact.p, true, opts, work, 0, ncomp,
-                                              comp_rows, hint)
-                               : minres_solve(ctx, nb, A, prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, hint);
-    if (stats) {
-        ctx.phase_mark(2);
-        for (int kcol = 0; kcol < nb; ++kcol) stats[kcol] = res.col[kcol];
-        ctx.phase_report(stats, nb);
-    }
-    if (op_timer.on) op_timer.harvest();   // minres_solve has synchronised the stream
-    if (poly_timer.on) poly_timer.harvest();
+    solve_done(compact ? minres_solve(ctx, nb, L.A, L.prec, d.rhs_bc.p, sol_compact.p, true, opts, work, 0, ncomp, comp_rows, L.hint)
+                       : minres_solve(ctx, nb, L.A, L.prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, L.hint),
+               nb, stats);
     // SolveFwd_RtnPressure (row0 == n_u) returns the Q of SolveFwd bit for bit: the rows in supp(obs) of the full solution
     // carry the compact solve's values, and the same reduction runs over them (the MLMC manager's pressure statistics
     // leave its QoI sums unchanged)

@@ -328,43 +328,89 @@ void Darcy::ensure_loglik(int level) {
     d.has_gt = true;
 }
 
-// One launch: forward solve (all rows), adjoint right-hand side, adjoint solve on the same operator and preconditioner,
-// gradient kernel.  grad_d / sol_d / adj_d: device, sample-major.
-void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSpec& adj, bool wrt_log, double* Q_host,
-                           double* G_host, double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd,
-                           pmc_stats* stats_adj) {
+// ---- the adjoint right-hand sides: each forms adj_rhs (interleaved, essential rows zero) from the launch's solution sol ------
+// what the arms that write only the u rows end with: zero p rows (zero_p), zero essential rows
+void Darcy::rhs_finish(hipStream_t st, int nb, int level, bool zero_p) {
+    const DarcyLevel& d = lv[level];
+    if (zero_p) k::fill(st, (size_t)d.n_p * nb, adj_rhs.p + (size_t)d.n_u * nb, 0.0);
+    const size_t tu = (size_t)d.n_u * nb;
+    zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(1);
+}
+
+// the caller's dJ/dx (rhs_d: device, sample-major), or the level's obs broadcast (NULL): J = Q
+void Darcy::rhs_seed(hipStream_t st, int nb, int level, const double* rhs_d) {
+    const DarcyLevel& d = lv[level];
+    if (rhs_d) k::interleave(st, nb, d.n_u + d.n_p, rhs_d, nullptr, 1.0, adj_rhs.p);
+    else k::broadcast(st, nb, d.n_u + d.n_p, d.obs.p, adj_rhs.p);
+    rhs_finish(st, nb, level, false);
+}
+
+// the Gaussian log-likelihood of the observation functionals; data: host, n_gobs.  G_host (nb x n_gobs) has arrived once
+// the stream is synchronised.
+void Darcy::rhs_loglik(hipStream_t st, int nb, int level, const double* data, double noise, double* G_host) {
+    DarcyLevel& d = lv[level];
+    const int n_u = d.n_u, n_p = d.n_p;
+    ensure_loglik(level);
+    gtmp.ensure((size_t)d.n_gobs * nb);
+    gout.ensure((size_t)d.n_gobs * nb);
+    sol_compact.ensure((size_t)std::max(d.n_grows, 1) * nb);
+    obs_data.upload(data, (size_t)d.n_gobs, st);
+    // G_i = <g_i, p> / sum(g_i) on the rows compute_G maintains
+    const size_t tg = (size_t)d.n_grows * nb;
+    gather_rows_kernel<<<flat_blocks(tg), 256, 0, st>>>(tg, nb, d.g_rows.p, sol.p, sol_compact.p);
+    PMC_HIP(hipGetLastError());
+    k::spmm(st, nb, view(d.Gobs), sol_compact.p, gtmp.p, false, nullptr, nullptr);
+    k::deinterleave(st, nb, d.n_gobs, gtmp.p, nullptr, d.g_norm.p, false, gout.p);
+    PMC_HIP(hipMemcpyAsync(G_host, gout.p, sizeof(double) * d.n_gobs * nb, hipMemcpyDeviceToHost, st));
+    k::fill(st, (size_t)n_u * nb, adj_rhs.p, 0.0);
+    const size_t tp = (size_t)n_p * nb;
+    loglik_rhs_kernel<<<flat_blocks(tp), 256, 0, st>>>(tp, nb, d.gt_ptr.p, d.gt_obs.p, d.gt_val.p, gtmp.p, d.g_norm.p,
+                                                       obs_data.p, -1.0 / noise, adj_rhs.p + (size_t)n_u * nb);
+    PMC_HIP(hipGetLastError());
+    count_kernel_launches(2);
+}
+
+// J of the breakthrough data: the transport and its adjoint on the interleaved solution (minres_solve has synchronised the
+// stream, as Transport::qoi_interleaved requires), u_bar straight into the u rows.  Seeds curve_bar_d / stored_bar_d (device,
+// sample-major; NULL: zero), or with tdata_d (device, nreport) curve_bar = -(curve - data) / noise.  curve_d / stored_d: the
+// forward outputs of the launch (device, nb x nreport and nb); status_h: host, nb.
+void Darcy::rhs_transport(hipStream_t st, int nb, int level, Transport& T, const double* curve_bar_d, const double* stored_bar_d,
+                          const double* tdata_d, double noise, double* curve_d, double* stored_d, int32_t* status_h) {
+    T.adjoint_forward(st, nb, sol.p, nb, 1, curve_d, stored_d);
+    for (int kcol = 0; kcol < nb; ++kcol) status_h[kcol] = T.h_status[kcol];
+    const double* cb_d = tdata_d ? T.loglik_seed(st, nb, curve_d, tdata_d, noise) : curve_bar_d;
+    T.adjoint_backward(st, nb, sol.p, nb, 1, cb_d, tdata_d ? nullptr : stored_bar_d, nullptr, adj_rhs.p, nb, 1, nullptr);
+    rhs_finish(st, nb, level, true);
+}
+
+// J of the travel times: the walk and its adjoint on the interleaved solution, u_bar straight into the
+// u rows.  Seed tbar_d (device, nb x nparticles), or with trdata_d (device, nparticles) T_bar = -(T - data) / noise.
+// T_d / status_d: the forward outputs of the launch (device, nb x nparticles).
+void Darcy::rhs_tracer(hipStream_t st, int nb, int level, Tracer& T, const double* tbar_d, const double* trdata_d, double noise,
+                       double* T_d, int32_t* status_d) {
+    const size_t cnt = (size_t)nb * T.npart;
+    trc_i.ensure(2 * cnt);
+    T.adjoint_launch(st, nb, true, sol.p, nb, 1, tbar_d, nullptr, adj_rhs.p, nb, 1, nullptr, T_d, trc_i.p, status_d, trc_i.p + cnt,
+                     trdata_d, noise);
+    rhs_finish(st, nb, level, true);
+}
+
+// One launch: forward solve (all rows), adjoint right-hand side (form_rhs, one of the four above bound to the entry's
+// operands), adjoint solve on the same operator and preconditioner, gradient kernel.  grad_d / sol_d / adj_d: device,
+// sample-major.
+void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointRhs& form_rhs, bool wrt_log, double* Q_host,
+                           double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd, pmc_stats* stats_adj) {
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
-    const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p;
-    ensure(level, nb);
+    const int n_p = d.n_p, n = d.n_u + n_p;
     ensure_gradient(level);
     adj_rhs.ensure((size_t)n * nb);
     adj_sol.ensure((size_t)n * nb);
-    if (stats_fwd) ctx.phase_mark(0);
-    setup_chunk(level, nb, k_d);             // M(k), Schur hierarchy, l1 diagonals: serves both solves
-    if (stats_fwd) ctx.phase_mark(1);
-    LinOp A;
-    PrecFn prec;
-    chunk_ops(level, nb, opts.use_graph == 0, A, prec);
-    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
-    Multigrid* mgp = chain ? &chain->mg : &mg;
-    const int mg_l0 = chain ? 0 : level;
-    work.want_r32 = false;
     // forward solve on all rows: the configuration (and the captured graph) of solve_fwd with a solution requested
-    GraphHint hint;
-    hint.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), 2);
-    hint.sig = mgp->signature(mg_l0);
-    for (const void* p : {(const void*)cx.p, (const void*)cd.p, (const void*)cx2.p, (const void*)d.mvals.p, (const void*)d.mvals_scaled.p,
-                          (const void*)d.l1invM.p, (const void*)d.rhs_bc.p})
-        hint.sig = hash_ptr(hint.sig, p);
-    MinresResult res = minres_solve(ctx, nb, A, prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, hint);
-    if (stats_fwd) {
-        ctx.phase_mark(2);
-        for (int kcol = 0; kcol < nb; ++kcol) stats_fwd[kcol] = res.col[kcol];
-        ctx.phase_report(stats_fwd, nb);
-    }
-    if (op_timer.on) op_timer.harvest();
-    if (poly_timer.on) poly_timer.harvest();
+    const SaddleLaunch L = saddle_launch(level, nb, k_d, kSolveFull, stats_fwd != nullptr, true);
+    solve_done(minres_solve(ctx, nb, L.A, L.prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, L.hint), nb, stats_fwd);
     // Q = <obs, sol> over all rows, as solve_fwd forms it when the solution is requested - also on a level with a tracer
     // attached (pmc_darcy_set_tracer): the gradient is that of <obs, x>, so its Q stays <obs, x>
     const int qblocks = k::wdot(st, nb, n, d.obs.p, sol.p, qpartial.p);
@@ -372,75 +418,14 @@ void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSp
     PMC_HIP(hipMemcpyAsync(ctx.h_scal, qout.p, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
     if (sol_d) k::deinterleave(st, nb, n, sol.p, nullptr, nullptr, false, sol_d);
     if (stats_adj) ctx.phase_mark(0);
-    // adjoint right-hand side, essential rows zero
-    if (adj.loglik) {
-        ensure_loglik(level);
-        gtmp.ensure((size_t)d.n_gobs * nb);
-        gout.ensure((size_t)d.n_gobs * nb);
-        sol_compact.ensure((size_t)std::max(d.n_grows, 1) * nb);
-        obs_data.upload(adj.data, (size_t)d.n_gobs, st);
-        // G_i = <g_i, p> / sum(g_i) on the rows compute_G maintains
-        const size_t tg = (size_t)d.n_grows * nb;
-        gather_rows_kernel<<<flat_blocks(tg), 256, 0, st>>>(tg, nb, d.g_rows.p, sol.p, sol_compact.p);
-        PMC_HIP(hipGetLastError());
-        k::spmm(st, nb, view(d.Gobs), sol_compact.p, gtmp.p, false, nullptr, nullptr);
-        k::deinterleave(st, nb, d.n_gobs, gtmp.p, nullptr, d.g_norm.p, false, gout.p);
-        PMC_HIP(hipMemcpyAsync(G_host, gout.p, sizeof(double) * d.n_gobs * nb, hipMemcpyDeviceToHost, st));
-        k::fill(st, (size_t)n_u * nb, adj_rhs.p, 0.0);
-        const size_t tp = (size_t)n_p * nb;
-        loglik_rhs_kernel<<<flat_blocks(tp), 256, 0, st>>>(tp, nb, d.gt_ptr.p, d.gt_obs.p, d.gt_val.p, gtmp.p, d.g_norm.p,
-                                                           obs_data.p, -1.0 / adj.noise, adj_rhs.p + (size_t)n_u * nb);
-        PMC_HIP(hipGetLastError());
-        count_kernel_launches(2);
-    } else if (adj.transport) {
-        // J of the breakthrough data: the transport and its adjoint on the interleaved solution (minres_solve has synchronised
-        // the stream, as Transport::qoi_interleaved requires), u_bar straight into the u rows, zero p rows and essential rows
-        Transport& T = *adj.transport;
-        T.adjoint_forward(st, nb, sol.p, nb, 1, adj.curve_d, adj.stored_d);
-        for (int kcol = 0; kcol < nb; ++kcol) adj.status_h[kcol] = T.h_status[kcol];
-        const double* cb_d = adj.tdata_d ? T.loglik_seed(st, nb, adj.curve_d, adj.tdata_d, adj.noise) : adj.curve_bar_d;
-        T.adjoint_backward(st, nb, sol.p, nb, 1, cb_d, adj.tdata_d ? nullptr : adj.stored_bar_d, nullptr, adj_rhs.p, nb, 1, nullptr);
-        k::fill(st, (size_t)n_p * nb, adj_rhs.p + (size_t)n_u * nb, 0.0);
-        const size_t tu = (size_t)n_u * nb;
-        zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
-        PMC_HIP(hipGetLastError());
-        count_kernel_launches(1);
-    } else if (adj.tracer) {
-        // J of the travel times: the walk and its adjoint on the interleaved solution, u_bar straight into the u rows, zero
-        // p rows and essential rows
-        Tracer& T = *adj.tracer;
-        const size_t cnt = (size_t)nb * T.npart;
-        trc_i.ensure(2 * cnt);
-        T.adjoint_launch(st, nb, true, sol.p, nb, 1, adj.tbar_d, nullptr, adj_rhs.p, nb, 1, nullptr, adj.trT_d, trc_i.p,
-                         adj.trstatus_d, trc_i.p + cnt, adj.trdata_d, adj.noise);
-        k::fill(st, (size_t)n_p * nb, adj_rhs.p + (size_t)n_u * nb, 0.0);
-        const size_t tu = (size_t)n_u * nb;
-        zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
-        PMC_HIP(hipGetLastError());
-        count_kernel_launches(1);
-    } else {
-        if (adj.rhs_d) k::interleave(st, nb, n, adj.rhs_d, nullptr, 1.0, adj_rhs.p);
-        else k::broadcast(st, nb, n, d.obs.p, adj_rhs.p);
-        const size_t tu = (size_t)n_u * nb;
-        zero_ess_rows_kernel<<<flat_blocks(tu), 256, 0, st>>>(tu, nb, d.ess.p, adj_rhs.p);
-        PMC_HIP(hipGetLastError());
-        count_kernel_launches(1);
-    }
+    form_rhs(st, nb, level);
     PMC_HIP(hipStreamSynchronize(st));           // Q (and G) have arrived; the data of the right-hand side was read
     for (int kcol = 0; kcol < nb; ++kcol) Q_host[kcol] = ctx.h_scal[kcol];
     if (stats_adj) ctx.phase_mark(1);
     // adjoint solve: same A, prec and options, zero guess, a configuration (graph key) of its own
-    GraphHint hint_adj;
-    hint_adj.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), 5);
-    hint_adj.sig = hash_ptr(hash_ptr(hint.sig, adj_rhs.p), adj_sol.p);
-    MinresResult res_adj = minres_solve(ctx, nb, A, prec, adj_rhs.p, adj_sol.p, true, opts, work, 0, n, nullptr, hint_adj);
-    if (stats_adj) {
-        ctx.phase_mark(2);
-        for (int kcol = 0; kcol < nb; ++kcol) stats_adj[kcol] = res_adj.col[kcol];
-        ctx.phase_report(stats_adj, nb);
-    }
-    if (op_timer.on) op_timer.harvest();
-    if (poly_timer.on) poly_timer.harvest();
+    solve_done(minres_solve(ctx, nb, L.A, L.prec, adj_rhs.p, adj_sol.p, true, opts, work, 0, n, nullptr,
+                            L.follow_up(kSolveAdjoint, adj_rhs.p, adj_sol.p)),
+               nb, stats_adj);
     const k::ElemMassView E{n_p, d.grad_nslices, d.grad_nfe, d.grad_faces.p, d.grad_me.p};
     if (grad_timer.on) grad_timer.begin(st);
     k::darcy_mass_sensitivity(st, nb, E, k_d, sol.p, adj_sol.p, k_divides, wrt_log, grad_d);
@@ -450,6 +435,24 @@ void Darcy::gradient_chunk(int level, int nb, const double* k_d, const AdjointSp
     if (grad_timer.on) grad_timer.harvest();
 }
 
+namespace {
+// Gaussian log-likelihood of nb columns of len values against data (len): loglik_out[b] = -(1 / (2 noise)) sum_i (v_bi - data_i)^2,
+// the log of BayesianInverseProblem::ComputeLikelihood; values_out: the values themselves.  Either output may be NULL.
+void gauss_loglik(int nb, size_t len, const double* values, const double* data, double noise, double* loglik_out,
+                  double* values_out) {
+    for (int b = 0; b < nb; ++b) {
+        double s = 0.0;
+        for (size_t i = 0; i < len; ++i) {
+            const double dd = values[(size_t)b * len + i] - data[i];
+            s += dd * dd;
+            if (values_out) values_out[(size_t)b * len + i] = values[(size_t)b * len + i];
+        }
+        if (loglik_out) loglik_out[b] = (-1. / (noise * 2)) * s;
+    }
+}
+}  // namespace
+
+// ---- the batched entries: argument checks, the operands of for_chunks (handles.hpp), one launch as the body -------------------
 void Darcy::mass_sensitivity(int level, int nbatch, const double* kf, const double* x, const double* lam, bool wrt_log,
                              double* grad, int memspace) {
     PMC_REQUIRE(level >= 0 && level < n_mc, "mass_sensitivity: level out of range");
@@ -458,44 +461,23 @@ void Darcy::mass_sensitivity(int level, int nbatch, const double* kf, const doub
     ctx.activate();
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
-    const size_t n = (size_t)d.n_u + d.n_p;
+    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
     ensure_gradient(level);
     const k::ElemMassView E{d.n_p, d.grad_nslices, d.grad_nfe, d.grad_faces.p, d.grad_me.p};
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + (size_t)done * d.n_p;
-        const double* x_d = x + (size_t)done * n;
-        const double* l_d = lam + (size_t)done * n;
-        double* g_d = grad + (size_t)done * d.n_p;
-        sol.ensure(n * nb);
-        adj_sol.ensure(n * nb);
-        if (memspace == PMC_MEM_HOST) {
-            stage_k.ensure((size_t)d.n_p * nb);
-            stage_sol.ensure(n * nb);
-            stage_adj.ensure(n * nb);
-            stage_grad.ensure((size_t)d.n_p * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * d.n_p * nb, hipMemcpyHostToDevice, st));
-            PMC_HIP(hipMemcpyAsync(stage_sol.p, x_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-            PMC_HIP(hipMemcpyAsync(stage_adj.p, l_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
-            x_d = stage_sol.p;
-            l_d = stage_adj.p;
-            g_d = stage_grad.p;
-        }
-        k::interleave(st, nb, (int)n, x_d, nullptr, 1.0, sol.p);
-        k::interleave(st, nb, (int)n, l_d, nullptr, 1.0, adj_sol.p);
-        if (grad_timer.on) grad_timer.begin(st);
-        k::darcy_mass_sensitivity(st, nb, E, k_d, sol.p, adj_sol.p, k_divides, wrt_log, g_d);
-        if (grad_timer.on) grad_timer.end(st);
-        if (memspace == PMC_MEM_HOST)
-            PMC_HIP(hipMemcpyAsync(grad + (size_t)done * d.n_p, stage_grad.p, sizeof(double) * d.n_p * nb,
-                                   hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipStreamSynchronize(st));
-        if (grad_timer.on) grad_timer.harvest();
-        done += nb;
-    }
+    enum { K, X, LAM, GRAD };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(x, n, stage_sol), ChunkArg::in(lam, n, stage_adj),
+                ChunkArg::out(grad, np, stage_grad)},
+               [&](const Chunk& c) {
+                   sol.ensure(n * c.nb);
+                   adj_sol.ensure(n * c.nb);
+                   k::interleave(st, c.nb, (int)n, c.at<double>(X), nullptr, 1.0, sol.p);
+                   k::interleave(st, c.nb, (int)n, c.at<double>(LAM), nullptr, 1.0, adj_sol.p);
+                   if (grad_timer.on) grad_timer.begin(st);
+                   k::darcy_mass_sensitivity(st, c.nb, E, c.at<double>(K), sol.p, adj_sol.p, k_divides, wrt_log, c.at<double>(GRAD));
+                   if (grad_timer.on) grad_timer.end(st);
+               });
+    if (grad_timer.on) grad_timer.harvest();      // every launch's bracket: the stream is synchronised
 }
 
 void Darcy::solve_gradient(int level, int nbatch, const double* kf, const double* adj_rhs_in, bool wrt_log, double* Q,
@@ -504,52 +486,24 @@ void Darcy::solve_gradient(int level, int nbatch, const double* kf, const double
     PMC_REQUIRE(level >= 0 && level < n_mc, "solve_gradient: level out of range");
     PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr, "solve_gradient: bad arguments");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
-    const bool host = memspace == PMC_MEM_HOST;
     std::vector<double> q(kMaxBatch);
-    DevBuf<double> stage_out;                 // host memspace: the adjoint solution on its way out
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        struct { const double *k_d, *rhs_d; double *grad_d, *sol_d, *adj_d; } s{
-            kf + done * np, adj_rhs_in ? adj_rhs_in + done * n : nullptr, grad + done * np,
-            sol_out ? sol_out + done * n : nullptr, adj_out ? adj_out + done * n : nullptr};
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            s.k_d = stage_k.p;
-            if (s.rhs_d) {
-                stage_adj.ensure(n * nb);
-                PMC_HIP(hipMemcpyAsync(stage_adj.p, s.rhs_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-                s.rhs_d = stage_adj.p;
-            }
-            s.grad_d = stage_grad.p;
-            if (s.sol_d) s.sol_d = stage_sol.p;
-            if (s.adj_d) {
-                stage_out.ensure(n * nb);
-                s.adj_d = stage_out.p;
-            }
-        }
-        AdjointSpec adj;
-        adj.rhs_d = s.rhs_d;
-        gradient_chunk(level, nb, s.k_d, adj, wrt_log, q.data(), nullptr, s.grad_d, s.sol_d, s.adj_d,
-                       stats_fwd ? stats_fwd + done : nullptr, stats_adj ? stats_adj + done : nullptr);
-        if (host) {
-            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-            if (sol_out) PMC_HIP(hipMemcpyAsync(sol_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-            if (adj_out) PMC_HIP(hipMemcpyAsync(adj_out + done * n, stage_out.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-            PMC_HIP(hipStreamSynchronize(st));
-        }
-        for (int b = 0; b < nb; ++b) {
-            if (Q) Q[done + b] = q[b];
-            if (C) C[done + b] = (double)n;
-        }
-        done += nb;
-    }
+    enum { K, RHS, GRAD, SOL, ADJ, SF, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(adj_rhs_in, n, stage_adj), ChunkArg::out(grad, np, stage_grad),
+                ChunkArg::out(sol_out, n, stage_sol), ChunkArg::out(adj_out, n, stage_out), ChunkArg::stats(stats_fwd),
+                ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) { rhs_seed(st, nb, lvl, c.at<double>(RHS)); }, wrt_log,
+                                  q.data(), c.at<double>(GRAD), c.at<double>(SOL), c.at<double>(ADJ), c.at<pmc_stats>(SF),
+                                  c.at<pmc_stats>(SA));
+                   for (int b = 0; b < c.nb; ++b) {
+                       if (Q) Q[c.done + b] = q[b];
+                       if (C) C[c.done + b] = (double)n;
+                   }
+               });
 }
 
 void Darcy::loglik_gradient(int level, int nbatch, const double* kf, const double* data, double noise, bool wrt_log,
@@ -560,297 +514,154 @@ void Darcy::loglik_gradient(int level, int nbatch, const double* kf, const doubl
     DarcyLevel& d = lv[level];
     PMC_REQUIRE(d.n_gobs > 0, "loglik_gradient: no observation functionals set on this level");
     ctx.activate();
-    hipStream_t st = ctx.stream;
-    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
-    const int nobs = d.n_gobs;
-    const bool host = memspace == PMC_MEM_HOST;
-    std::vector<double> q(kMaxBatch), gh((size_t)nobs * kMaxBatch);
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + done * np;
-        double* grad_d = grad + done * np;
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
-            grad_d = stage_grad.p;
-        }
-        AdjointSpec adj;
-        adj.loglik = true;
-        adj.data = data;
-        adj.noise = noise;
-        gradient_chunk(level, nb, k_d, adj, wrt_log, q.data(), gh.data(), grad_d, nullptr, nullptr, nullptr,
-                       stats_adj ? stats_adj + done : nullptr);
-        if (host) {
-            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-            PMC_HIP(hipStreamSynchronize(st));
-        }
-        for (int b = 0; b < nb; ++b) {
-            double s = 0.0;
-            for (int i = 0; i < nobs; ++i) {
-                const double dd = gh[(size_t)b * nobs + i] - data[i];
-                s += dd * dd;
-                if (G) G[(size_t)(done + b) * nobs + i] = gh[(size_t)b * nobs + i];
-            }
-            if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;      // log of BayesianInverseProblem::ComputeLikelihood
-        }
-        done += nb;
-    }
+    const size_t np = (size_t)d.n_p, nobs = (size_t)d.n_gobs;
+    std::vector<double> q(kMaxBatch), gh(nobs * nbatch);
+    enum { K, GH, GRAD, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::host(gh.data(), nobs), ChunkArg::out(grad, np, stage_grad),
+                ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) { rhs_loglik(st, nb, lvl, data, noise, c.at<double>(GH)); },
+                                  wrt_log, q.data(), c.at<double>(GRAD), nullptr, nullptr, nullptr, c.at<pmc_stats>(SA));
+               });
+    gauss_loglik(nbatch, nobs, gh.data(), data, noise, loglik, G);
 }
 
-void Darcy::check_transport(int level, const Transport* t, const char* who) const {
-    PMC_REQUIRE(level >= 0 && level < n_mc, std::string(who) + ": level out of range");
-    PMC_REQUIRE(t != nullptr, std::string(who) + ": transport is NULL");
+// a Transport or a Tracer handed over with a call (noun: what the messages call it)
+template <class T>
+void Darcy::check_flux_user(int level, const T* t, const std::string& noun, const std::string& who) const {
+    PMC_REQUIRE(level >= 0 && level < n_mc, who + ": level out of range");
+    PMC_REQUIRE(t != nullptr, who + ": " + noun + " is NULL");
     PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
-                std::string(who) + ": the transport's mesh does not match the level (n_face != n_u or n_elem != n_p)");
-    PMC_REQUIRE(t->ctx.device == ctx.device, std::string(who) + ": the transport was created on another device");
+                who + ": the " + noun + "'s mesh does not match the level (n_face != n_u or n_elem != n_p)");
+    PMC_REQUIRE(t->ctx.device == ctx.device, who + ": the " + noun + " was created on another device");
 }
 
 void Darcy::transport_gradient(int level, Transport* t, int nbatch, const double* kf, const double* curve_bar,
                                const double* stored_bar, bool wrt_log, double* curve, double* stored, int32_t* status, double* grad,
                                double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd, pmc_stats* stats_adj) {
-    const char* who = "pmc_darcy_transport_gradient";
-    check_transport(level, t, who);
-    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr, std::string(who) + ": bad arguments");
-    PMC_REQUIRE(curve_bar != nullptr || stored_bar != nullptr, std::string(who) + ": curve_bar or stored_bar must be given");
-    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    const std::string who = "pmc_darcy_transport_gradient";
+    check_flux_user(level, t, "transport", who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr, who + ": bad arguments");
+    PMC_REQUIRE(curve_bar != nullptr || stored_bar != nullptr, who + ": curve_bar or stored_bar must be given");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, who + ": bad memspace");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, nr = (size_t)t->nreport;
-    const bool host = memspace == PMC_MEM_HOST;
     std::vector<double> q(kMaxBatch);
-    DevBuf<double> stage_out;
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        struct { const double *k_d, *cb_d, *sb_d; double *grad_d, *sol_d, *adj_d; } s{
-            kf + done * np, curve_bar ? curve_bar + done * nr : nullptr, stored_bar ? stored_bar + done : nullptr, grad + done * np,
-            sol_out ? sol_out + done * n : nullptr, adj_out ? adj_out + done * n : nullptr};
-        tr_curve.ensure(nr * nb);
-        tr_stored.ensure(nb);
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            s.k_d = stage_k.p;
-            if (s.cb_d) {
-                tr_cb.upload(s.cb_d, nr * nb, st);
-                s.cb_d = tr_cb.p;
-            }
-            if (s.sb_d) {
-                tr_sb.upload(s.sb_d, nb, st);
-                s.sb_d = tr_sb.p;
-            }
-            s.grad_d = stage_grad.p;
-            if (s.sol_d) s.sol_d = stage_sol.p;
-            if (s.adj_d) {
-                stage_out.ensure(n * nb);
-                s.adj_d = stage_out.p;
-            }
-        }
-        AdjointSpec adj;
-        adj.transport = t;
-        adj.curve_bar_d = s.cb_d;
-        adj.stored_bar_d = s.sb_d;
-        adj.curve_d = tr_curve.p;
-        adj.stored_d = tr_stored.p;
-        adj.status_h = status + done;
-        gradient_chunk(level, nb, s.k_d, adj, wrt_log, q.data(), nullptr, s.grad_d, s.sol_d, s.adj_d,
-                       stats_fwd ? stats_fwd + done : nullptr, stats_adj ? stats_adj + done : nullptr);
-        const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (curve) PMC_HIP(hipMemcpyAsync(curve + done * nr, tr_curve.p, sizeof(double) * nr * nb, back, st));
-        if (stored) PMC_HIP(hipMemcpyAsync(stored + done, tr_stored.p, sizeof(double) * nb, back, st));
-        if (host) {
-            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-            if (sol_out) PMC_HIP(hipMemcpyAsync(sol_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-            if (adj_out) PMC_HIP(hipMemcpyAsync(adj_out + done * n, stage_out.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-        }
-        PMC_HIP(hipStreamSynchronize(st));
-        done += nb;
-    }
+    enum { K, CB, SB, CURVE, STORED, GRAD, SOL, ADJ, STATUS, SF, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(curve_bar, nr, tr_cb), ChunkArg::in(stored_bar, 1, tr_sb),
+                ChunkArg::made(curve, nr), ChunkArg::made(stored, 1), ChunkArg::out(grad, np, stage_grad),
+                ChunkArg::out(sol_out, n, stage_sol), ChunkArg::out(adj_out, n, stage_out), ChunkArg::host(status, 1),
+                ChunkArg::stats(stats_fwd), ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   tr_curve.ensure(nr * c.nb);
+                   tr_stored.ensure(c.nb);
+                   c.dev[CURVE] = tr_curve.p;
+                   c.dev[STORED] = tr_stored.p;
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) {
+                                      rhs_transport(st, nb, lvl, *t, c.at<double>(CB), c.at<double>(SB), nullptr, 1.0, tr_curve.p,
+                                                    tr_stored.p, c.at<int32_t>(STATUS));
+                                  },
+                                  wrt_log, q.data(), c.at<double>(GRAD), c.at<double>(SOL), c.at<double>(ADJ), c.at<pmc_stats>(SF),
+                                  c.at<pmc_stats>(SA));
+               });
 }
 
 void Darcy::transport_loglik_gradient(int level, Transport* t, int nbatch, const double* kf, const double* data, double noise,
                                       bool wrt_log, double* loglik, double* curve, int32_t* status, double* grad, int memspace,
                                       pmc_stats* stats_adj) {
-    const char* who = "pmc_darcy_transport_loglik_gradient";
-    check_transport(level, t, who);
-    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && status != nullptr, std::string(who) + ": bad arguments");
-    PMC_REQUIRE(noise > 0.0, std::string(who) + ": the noise variance must be positive");
-    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    const std::string who = "pmc_darcy_transport_loglik_gradient";
+    check_flux_user(level, t, "transport", who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && status != nullptr, who + ": bad arguments");
+    PMC_REQUIRE(noise > 0.0, who + ": the noise variance must be positive");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, who + ": bad memspace");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
-    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
-    const int nr = t->nreport;
-    const bool host = memspace == PMC_MEM_HOST;
-    std::vector<double> q(kMaxBatch), ch((size_t)nr * kMaxBatch);
-    tr_data.upload(data, (size_t)nr, st);
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + done * np;
-        double* grad_d = grad + done * np;
-        tr_curve.ensure((size_t)nr * nb);
-        tr_stored.ensure(nb);
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
-            grad_d = stage_grad.p;
-        }
-        AdjointSpec adj;
-        adj.transport = t;
-        adj.tdata_d = tr_data.p;
-        adj.noise = noise;
-        adj.curve_d = tr_curve.p;
-        adj.stored_d = tr_stored.p;
-        adj.status_h = status + done;
-        gradient_chunk(level, nb, k_d, adj, wrt_log, q.data(), nullptr, grad_d, nullptr, nullptr, nullptr,
-                       stats_adj ? stats_adj + done : nullptr);
-        PMC_HIP(hipMemcpyAsync(ch.data(), tr_curve.p, sizeof(double) * nr * nb, hipMemcpyDeviceToHost, st));
-        if (host) PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipStreamSynchronize(st));
-        for (int b = 0; b < nb; ++b) {
-            double s = 0.0;
-            for (int i = 0; i < nr; ++i) {
-                const double dd = ch[(size_t)b * nr + i] - data[i];
-                s += dd * dd;
-                if (curve) curve[(size_t)(done + b) * nr + i] = ch[(size_t)b * nr + i];
-            }
-            if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;
-        }
-        done += nb;
-    }
-}
-
-void Darcy::check_tracer(int level, const Tracer* t, const char* who) const {
-    PMC_REQUIRE(level >= 0 && level < n_mc, std::string(who) + ": level out of range");
-    PMC_REQUIRE(t != nullptr, std::string(who) + ": tracer is NULL");
-    PMC_REQUIRE(t->n_face == lv[level].n_u && t->n_elem == lv[level].n_p,
-                std::string(who) + ": the tracer's mesh does not match the level (n_face != n_u or n_elem != n_p)");
-    PMC_REQUIRE(t->ctx.device == ctx.device, std::string(who) + ": the tracer was created on another device");
+    const size_t np = (size_t)d.n_p, nr = (size_t)t->nreport;
+    std::vector<double> q(kMaxBatch), ch(nr * nbatch);
+    tr_data.upload(data, nr, ctx.stream);
+    enum { K, CH, GRAD, STATUS, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::made_host(ch.data(), nr), ChunkArg::out(grad, np, stage_grad),
+                ChunkArg::host(status, 1), ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   tr_curve.ensure(nr * c.nb);
+                   tr_stored.ensure(c.nb);
+                   c.dev[CH] = tr_curve.p;
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) {
+                                      rhs_transport(st, nb, lvl, *t, nullptr, nullptr, tr_data.p, noise, tr_curve.p, tr_stored.p,
+                                                    c.at<int32_t>(STATUS));
+                                  },
+                                  wrt_log, q.data(), c.at<double>(GRAD), nullptr, nullptr, nullptr, c.at<pmc_stats>(SA));
+               });
+    gauss_loglik(nbatch, nr, ch.data(), data, noise, loglik, curve);
 }
 
 void Darcy::tracer_gradient(int level, Tracer* t, int nbatch, const double* kf, const double* T_bar, bool wrt_log, double* T,
                             int32_t* status, double* grad, double* sol_out, double* adj_out, int memspace, pmc_stats* stats_fwd,
                             pmc_stats* stats_adj) {
-    const char* who = "pmc_darcy_tracer_gradient";
-    check_tracer(level, t, who);
-    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr && T_bar != nullptr,
-                std::string(who) + ": bad arguments");
-    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    const std::string who = "pmc_darcy_tracer_gradient";
+    check_flux_user(level, t, "tracer", who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && status != nullptr && T_bar != nullptr, who + ": bad arguments");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, who + ": bad memspace");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, npt = (size_t)t->npart;
-    const bool host = memspace == PMC_MEM_HOST;
     std::vector<double> q(kMaxBatch);
-    DevBuf<double> stage_out;
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        struct { const double *k_d, *tb_d; double *grad_d, *sol_d, *adj_d; } s{
-            kf + done * np, T_bar + done * npt, grad + done * np, sol_out ? sol_out + done * n : nullptr,
-            adj_out ? adj_out + done * n : nullptr};
-        trc_T.ensure(npt * nb);
-        trc_i.ensure(3 * npt * nb);
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            s.k_d = stage_k.p;
-            trc_tb.upload(s.tb_d, npt * nb, st);
-            s.tb_d = trc_tb.p;
-            s.grad_d = stage_grad.p;
-            if (s.sol_d) s.sol_d = stage_sol.p;
-            if (s.adj_d) {
-                stage_out.ensure(n * nb);
-                s.adj_d = stage_out.p;
-            }
-        }
-        AdjointSpec adj;
-        adj.tracer = t;
-        adj.tbar_d = s.tb_d;
-        adj.trT_d = trc_T.p;
-        adj.trstatus_d = trc_i.p + 2 * npt * nb;
-        gradient_chunk(level, nb, s.k_d, adj, wrt_log, q.data(), nullptr, s.grad_d, s.sol_d, s.adj_d,
-                       stats_fwd ? stats_fwd + done : nullptr, stats_adj ? stats_adj + done : nullptr);
-        const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (T) PMC_HIP(hipMemcpyAsync(T + done * npt, trc_T.p, sizeof(double) * npt * nb, back, st));
-        PMC_HIP(hipMemcpyAsync(status + done * npt, adj.trstatus_d, sizeof(int32_t) * npt * nb, back, st));
-        if (host) {
-            PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-            if (sol_out) PMC_HIP(hipMemcpyAsync(sol_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-            if (adj_out) PMC_HIP(hipMemcpyAsync(adj_out + done * n, stage_out.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-        }
-        PMC_HIP(hipStreamSynchronize(st));
-        done += nb;
-    }
+    enum { K, TB, T_, STATUS, GRAD, SOL, ADJ, SF, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(T_bar, npt, trc_tb), ChunkArg::made(T, npt),
+                ChunkArg::made(status, npt), ChunkArg::out(grad, np, stage_grad), ChunkArg::out(sol_out, n, stage_sol),
+                ChunkArg::out(adj_out, n, stage_out), ChunkArg::stats(stats_fwd), ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   trc_T.ensure(npt * c.nb);
+                   trc_i.ensure(3 * npt * c.nb);
+                   int32_t* status_d = trc_i.p + 2 * npt * c.nb;
+                   c.dev[T_] = trc_T.p;
+                   c.dev[STATUS] = status_d;
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) {
+                                      rhs_tracer(st, nb, lvl, *t, c.at<double>(TB), nullptr, 1.0, trc_T.p, status_d);
+                                  },
+                                  wrt_log, q.data(), c.at<double>(GRAD), c.at<double>(SOL), c.at<double>(ADJ), c.at<pmc_stats>(SF),
+                                  c.at<pmc_stats>(SA));
+               });
 }
 
 void Darcy::tracer_loglik_gradient(int level, Tracer* t, int nbatch, const double* kf, const double* data, double noise,
                                    bool wrt_log, double* loglik, double* T, int32_t* not_exited, double* grad, int memspace,
                                    pmc_stats* stats_adj) {
-    const char* who = "pmc_darcy_tracer_loglik_gradient";
-    check_tracer(level, t, who);
-    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && not_exited != nullptr,
-                std::string(who) + ": bad arguments");
-    PMC_REQUIRE(noise > 0.0, std::string(who) + ": the noise variance must be positive");
-    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, std::string(who) + ": bad memspace");
+    const std::string who = "pmc_darcy_tracer_loglik_gradient";
+    check_flux_user(level, t, "tracer", who);
+    PMC_REQUIRE(nbatch >= 1 && kf != nullptr && grad != nullptr && data != nullptr && not_exited != nullptr, who + ": bad arguments");
+    PMC_REQUIRE(noise > 0.0, who + ": the noise variance must be positive");
+    PMC_REQUIRE(memspace == PMC_MEM_HOST || memspace == PMC_MEM_DEVICE, who + ": bad memspace");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
-    const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p, npt = (size_t)t->npart;
-    const bool host = memspace == PMC_MEM_HOST;
-    std::vector<double> q(kMaxBatch), th(npt * kMaxBatch);
-    trc_data.upload(data, npt, st);
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + done * np;
-        double* grad_d = grad + done * np;
-        trc_T.ensure(npt * nb);
-        trc_i.ensure(3 * npt * nb);
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
-            grad_d = stage_grad.p;
-        }
-        AdjointSpec adj;
-        adj.tracer = t;
-        adj.trdata_d = trc_data.p;
-        adj.noise = noise;
-        adj.trT_d = trc_T.p;
-        adj.trstatus_d = trc_i.p + 2 * npt * nb;
-        gradient_chunk(level, nb, k_d, adj, wrt_log, q.data(), nullptr, grad_d, nullptr, nullptr, nullptr,
-                       stats_adj ? stats_adj + done : nullptr);
-        PMC_HIP(hipMemcpyAsync(th.data(), trc_T.p, sizeof(double) * npt * nb, hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipMemcpyAsync(not_exited + done, t->nex.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
-        if (host) PMC_HIP(hipMemcpyAsync(grad + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipStreamSynchronize(st));
-        for (int b = 0; b < nb; ++b) {
-            double s = 0.0;
-            for (size_t i = 0; i < npt; ++i) {
-                const double dd = th[(size_t)b * npt + i] - data[i];
-                s += dd * dd;
-                if (T) T[(size_t)(done + b) * npt + i] = th[(size_t)b * npt + i];
-            }
-            if (loglik) loglik[done + b] = (-1. / (noise * 2)) * s;
-        }
-        done += nb;
-    }
+    const size_t np = (size_t)d.n_p, npt = (size_t)t->npart;
+    std::vector<double> q(kMaxBatch), th(npt * nbatch);
+    trc_data.upload(data, npt, ctx.stream);
+    enum { K, TH, NEX, GRAD, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::made_host(th.data(), npt), ChunkArg::made_host(not_exited, 1),
+                ChunkArg::out(grad, np, stage_grad), ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   trc_T.ensure(npt * c.nb);
+                   trc_i.ensure(3 * npt * c.nb);
+                   gradient_chunk(level, c.nb, c.at<double>(K),
+                                  [&](hipStream_t st, int nb, int lvl) {
+                                      rhs_tracer(st, nb, lvl, *t, nullptr, trc_data.p, noise, trc_T.p, trc_i.p + 2 * npt * c.nb);
+                                  },
+                                  wrt_log, q.data(), c.at<double>(GRAD), nullptr, nullptr, nullptr, c.at<pmc_stats>(SA));
+                   c.dev[TH] = trc_T.p;
+                   c.dev[NEX] = t->nex.p;                // the tracer's count of particles that did not exit, per column
+               });
+    gauss_loglik(nbatch, npt, th.data(), data, noise, loglik, T);
 }
 
 }  // namespace pmc

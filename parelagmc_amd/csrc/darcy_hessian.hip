@@ -210,42 +210,21 @@ void Darcy::mass_tangent(int level, int nbatch, const double* kf, const double* 
     const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
     ensure_gradient(level, true);
     const k::FaceMassView F = face_view(d);
-    const bool host = memspace == PMC_MEM_HOST;
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + (size_t)done * np;
-        const double* dk_d = dk + (size_t)done * np;
-        const double* x_d = x + (size_t)done * n;
-        double* t_d = t_out + (size_t)done * n;
-        sol.ensure(n * nb);
-        adj_rhs.ensure(n * nb);
-        if (host) {
-            stage_k.ensure(np * nb);
-            stage_dk.ensure(np * nb);
-            stage_sol.ensure(n * nb);
-            stage_adj.ensure(n * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            PMC_HIP(hipMemcpyAsync(stage_dk.p, dk_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            PMC_HIP(hipMemcpyAsync(stage_sol.p, x_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-            k_d = stage_k.p;
-            dk_d = stage_dk.p;
-            x_d = stage_sol.p;
-            t_d = stage_adj.p;
-        }
-        k::interleave(st, nb, (int)n, x_d, nullptr, 1.0, sol.p);
-        k::fill(st, np * nb, adj_rhs.p + (size_t)d.n_u * nb, 0.0);
-        if (tan_timer.on) tan_timer.begin(st);
-        k::darcy_mass_tangent(st, nb, F, k_d, dk_d, sol.p, d.ess.p, k_divides, wrt_log, adj_rhs.p);
-        if (tan_timer.on) tan_timer.end(st);
-        k::deinterleave(st, nb, (int)n, adj_rhs.p, nullptr, nullptr, false, t_d);
-        if (host)
-            PMC_HIP(hipMemcpyAsync(t_out + (size_t)done * n, stage_adj.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipStreamSynchronize(st));
-        if (tan_timer.on) tan_timer.harvest();
-        done += nb;
-    }
+    enum { K, DK, X, T_ };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(dk, np, stage_dk), ChunkArg::in(x, n, stage_sol),
+                ChunkArg::out(t_out, n, stage_adj)},
+               [&](const Chunk& c) {
+                   sol.ensure(n * c.nb);
+                   adj_rhs.ensure(n * c.nb);
+                   k::interleave(st, c.nb, (int)n, c.at<double>(X), nullptr, 1.0, sol.p);
+                   k::fill(st, np * c.nb, adj_rhs.p + (size_t)d.n_u * c.nb, 0.0);
+                   if (tan_timer.on) tan_timer.begin(st);
+                   k::darcy_mass_tangent(st, c.nb, F, c.at<double>(K), c.at<double>(DK), sol.p, d.ess.p, k_divides, wrt_log, adj_rhs.p);
+                   if (tan_timer.on) tan_timer.end(st);
+                   k::deinterleave(st, c.nb, (int)n, adj_rhs.p, nullptr, nullptr, false, c.at<double>(T_));
+               });
+    if (tan_timer.on) tan_timer.harvest();        // every launch's bracket: the stream is synchronised
 }
 
 // One launch: the forward solution (given, or solved on all rows as gradient_chunk solves it), tangent right-hand side,
@@ -257,7 +236,6 @@ void Darcy::gn_hessvec_chunk(int level, int nb, const double* k_d, const double*
     hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const int n_u = d.n_u, n_p = d.n_p, n = n_u + n_p;
-    ensure(level, nb);
     ensure_gradient(level, true);
     ensure_loglik(level);
     adj_rhs.ensure((size_t)n * nb);
@@ -266,28 +244,12 @@ void Darcy::gn_hessvec_chunk(int level, int nb, const double* k_d, const double*
     gtmp.ensure((size_t)d.n_gobs * nb);
     gout.ensure((size_t)d.n_gobs * nb);
     sol_compact.ensure((size_t)std::max(d.n_grows, 1) * nb);
-    if (stats_tan) ctx.phase_mark(0);
-    setup_chunk(level, nb, k_d);             // M(k), Schur hierarchy, l1 diagonals: serves every solve of the launch
-    LinOp A;
-    PrecFn prec;
-    chunk_ops(level, nb, opts.use_graph == 0, A, prec);
-    DarcyChain* chain = (level < (int)chains.size()) ? chains[level].get() : nullptr;
-    Multigrid* mgp = chain ? &chain->mg : &mg;
-    const int mg_l0 = chain ? 0 : level;
-    work.want_r32 = false;
-    GraphHint hint;
-    hint.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), 2);
-    hint.sig = mgp->signature(mg_l0);
-    for (const void* p : {(const void*)cx.p, (const void*)cd.p, (const void*)cx2.p, (const void*)d.mvals.p, (const void*)d.mvals_scaled.p,
-                          (const void*)d.l1invM.p, (const void*)d.rhs_bc.p})
-        hint.sig = hash_ptr(hint.sig, p);
+    const SaddleLaunch L = saddle_launch(level, nb, k_d, kSolveFull, stats_tan != nullptr, false);   // the tangent right-hand side is setup too
     if (x_in_d) {
         k::interleave(st, nb, n, x_in_d, nullptr, 1.0, sol.p);
     } else {
         // the forward solve of gradient_chunk: same configuration, same graph
-        minres_solve(ctx, nb, A, prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, hint);
-        if (op_timer.on) op_timer.harvest();
-        if (poly_timer.on) poly_timer.harvest();
+        solve_done(minres_solve(ctx, nb, L.A, L.prec, d.rhs_bc.p, sol.p, true, opts, work, 0, n, nullptr, L.hint), nb, nullptr);
         if (x_out_d) k::deinterleave(st, nb, n, sol.p, nullptr, nullptr, false, x_out_d);
     }
     // tangent right-hand side: u-rows from the kernel (essential rows zero), p-rows zero
@@ -298,18 +260,10 @@ void Darcy::gn_hessvec_chunk(int level, int nb, const double* k_d, const double*
     if (tan_timer.on) tan_timer.end(st);
     if (stats_tan) ctx.phase_mark(1);
     // tangent solve: same A, prec and options, zero guess, a configuration (graph key) of its own
-    GraphHint hint_tan;
-    hint_tan.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), 6);
-    hint_tan.sig = hash_ptr(hash_ptr(hint.sig, adj_rhs.p), tan_sol.p);
-    MinresResult res_tan = minres_solve(ctx, nb, A, prec, adj_rhs.p, tan_sol.p, true, opts, work, 0, n, nullptr, hint_tan);
-    if (stats_tan) {
-        ctx.phase_mark(2);
-        for (int kcol = 0; kcol < nb; ++kcol) stats_tan[kcol] = res_tan.col[kcol];
-        ctx.phase_report(stats_tan, nb);
-    }
+    solve_done(minres_solve(ctx, nb, L.A, L.prec, adj_rhs.p, tan_sol.p, true, opts, work, 0, n, nullptr,
+                            L.follow_up(kSolveTangent, adj_rhs.p, tan_sol.p)),
+               nb, stats_tan);
     if (tan_timer.on) tan_timer.harvest();
-    if (op_timer.on) op_timer.harvest();
-    if (poly_timer.on) poly_timer.harvest();
     if (stats_adj) ctx.phase_mark(0);
     // dG_i = <g_i, dp> / sum(g_i) on the rows compute_G maintains, then the adjoint right-hand side (u-rows zero)
     const size_t tg = (size_t)d.n_grows * nb;
@@ -327,17 +281,9 @@ void Darcy::gn_hessvec_chunk(int level, int nb, const double* k_d, const double*
     PMC_HIP(hipGetLastError());
     count_kernel_launches(2);
     if (stats_adj) ctx.phase_mark(1);
-    GraphHint hint_adj;
-    hint_adj.key = hash_mix(hash_mix(hash_mix(0xda, (uint64_t)level + 1), (uint64_t)nb), 7);
-    hint_adj.sig = hash_ptr(hash_ptr(hint.sig, adj_rhs.p), adj_sol.p);
-    MinresResult res_adj = minres_solve(ctx, nb, A, prec, adj_rhs.p, adj_sol.p, true, opts, work, 0, n, nullptr, hint_adj);
-    if (stats_adj) {
-        ctx.phase_mark(2);
-        for (int kcol = 0; kcol < nb; ++kcol) stats_adj[kcol] = res_adj.col[kcol];
-        ctx.phase_report(stats_adj, nb);
-    }
-    if (op_timer.on) op_timer.harvest();
-    if (poly_timer.on) poly_timer.harvest();
+    solve_done(minres_solve(ctx, nb, L.A, L.prec, adj_rhs.p, adj_sol.p, true, opts, work, 0, n, nullptr,
+                            L.follow_up(kSolveGnAdjoint, adj_rhs.p, adj_sol.p)),
+               nb, stats_adj);
     const k::ElemMassView E{n_p, d.grad_nslices, d.grad_nfe, d.grad_faces.p, d.grad_me.p};
     if (grad_timer.on) grad_timer.begin(st);
     k::darcy_mass_sensitivity(st, nb, E, k_d, sol.p, adj_sol.p, k_divides, wrt_log, hv_d);
@@ -359,43 +305,17 @@ void Darcy::gn_hessvec(int level, int nbatch, const double* kf, const double* x_
     DarcyLevel& d = lv[level];
     PMC_REQUIRE(d.n_gobs > 0, "gn_hessvec: no observation functionals set on this level");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     const size_t n = (size_t)d.n_u + d.n_p, np = (size_t)d.n_p;
-    const int nobs = d.n_gobs;
-    const bool host = memspace == PMC_MEM_HOST;
     DevBuf<double> stage_x;                   // host memspace: the caller's forward solution on its way in
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width(n, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        struct { const double *k_d, *x_d, *dk_d; double *hv_d, *xo_d; } s{
-            kf + done * np, x_in ? x_in + done * n : nullptr, dk + done * np, hv + done * np,
-            x_out ? x_out + done * n : nullptr};
-        if (host) {
-            ensure(level, nb);
-            stage_grad.ensure(np * nb);
-            stage_dk.ensure(np * nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, s.k_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            PMC_HIP(hipMemcpyAsync(stage_dk.p, s.dk_d, sizeof(double) * np * nb, hipMemcpyHostToDevice, st));
-            s.k_d = stage_k.p;
-            s.dk_d = stage_dk.p;
-            if (s.x_d) {
-                stage_x.ensure(n * nb);
-                PMC_HIP(hipMemcpyAsync(stage_x.p, s.x_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-                s.x_d = stage_x.p;
-            }
-            s.hv_d = stage_grad.p;
-            if (s.xo_d) s.xo_d = stage_sol.p;
-        }
-        gn_hessvec_chunk(level, nb, s.k_d, s.x_d, s.dk_d, noise, wrt_log, s.hv_d, dG ? dG + (size_t)done * nobs : nullptr,
-                         s.xo_d, stats_tan ? stats_tan + done : nullptr, stats_adj ? stats_adj + done : nullptr);
-        if (host) {
-            PMC_HIP(hipMemcpyAsync(hv + done * np, stage_grad.p, sizeof(double) * np * nb, hipMemcpyDeviceToHost, st));
-            if (x_out) PMC_HIP(hipMemcpyAsync(x_out + done * n, stage_sol.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-            PMC_HIP(hipStreamSynchronize(st));
-        }
-        done += nb;
-    }
+    enum { K, DK, X, HV, XO, DG, ST, SA };
+    for_chunks(level, nbatch, memspace,
+               {ChunkArg::in(kf, np, stage_k), ChunkArg::in(dk, np, stage_dk), ChunkArg::in(x_in, n, stage_x),
+                ChunkArg::out(hv, np, stage_grad), ChunkArg::out(x_out, n, stage_sol), ChunkArg::host(dG, (size_t)d.n_gobs),
+                ChunkArg::stats(stats_tan), ChunkArg::stats(stats_adj)},
+               [&](const Chunk& c) {
+                   gn_hessvec_chunk(level, c.nb, c.at<double>(K), c.at<double>(X), c.at<double>(DK), noise, wrt_log, c.at<double>(HV),
+                                    c.at<double>(DG), c.at<double>(XO), c.at<pmc_stats>(ST), c.at<pmc_stats>(SA));
+               });
 }
 
 }  // namespace pmc

@@ -508,8 +508,9 @@ struct Darcy {
     OpTimer tan_timer;
     double mass_tangent_bytes(int level, int nb);       // builds the level's face-major data when it is not there yet
     DevBuf<double> sol, sol_compact, cx, cd, cx2, stage_k, stage_sol, qpartial, qout, gtmp, gout;
-    // adjoint solve (darcy_gradient.hip): right-hand side and second full solution, host staging; allocated at first use
-    DevBuf<double> adj_rhs, adj_sol, stage_adj, stage_grad, obs_data;
+    // adjoint solve (darcy_gradient.hip): right-hand side and second full solution, host staging (stage_out: the adjoint
+    // solution on its way out); allocated at first use
+    DevBuf<double> adj_rhs, adj_sol, stage_adj, stage_grad, stage_out, obs_data;
     // tangent solve (darcy_hessian.hip): third full solution, host staging of the direction; allocated at first use
     DevBuf<double> tan_sol, stage_dk;
     // travel-time QoI (pmc_darcy_set_tracer): with a tracer on a level, the Q of solve_fwd there is the tracer's reduction of
@@ -584,6 +585,65 @@ struct Darcy {
     void ensure(int level, int nb);
     void setup_chunk(int level, int nb, const double* k_d);
     void chunk_ops(int level, int nb, bool timing_ok, LinOp& A, PrecFn& prec);
+    // The launches of a batched entry (for_chunks, darcy.hip).  The entry lists its per-column operands once; for every
+    // launch of nb columns starting at column `done` the body finds the pointer to use in Chunk::dev, in the order listed:
+    //   In / Out   sample-major device arrays of the kernels.  Device memspace: the caller's array at column `done`.  Host
+    //              memspace: `stage`, uploaded before the body (In) or copied back behind it (Out).
+    //   Made       an output the body leaves in a device buffer of the handle: the body sets dev[i], and it is copied out
+    //              behind the body in both memspaces (device to device or device to host).  MadeHost: the caller's array is
+    //              host memory whatever the memspace.
+    //   Host       a host array with one entry of `len` per column (stats, Q, status words): the offset only.
+    // An absent optional operand (user == NULL) yields NULL and is never copied.  Uploads and copies run in the listed
+    // order; every launch ends with a synchronisation of the stream.
+    struct ChunkArg {
+        enum Kind { In, Out, Made, MadeHost, Host } kind;
+        const void* user;                 // the caller's array, all columns
+        size_t len, size;                 // entries per column, bytes per entry
+        DevBuf<double>* stage = nullptr;  // In / Out
+        static ChunkArg in(const double* p, size_t len, DevBuf<double>& stage) { return {In, p, len, sizeof(double), &stage}; }
+        static ChunkArg out(double* p, size_t len, DevBuf<double>& stage) { return {Out, p, len, sizeof(double), &stage}; }
+        template <class T>
+        static ChunkArg made(T* p, size_t len) { return {Made, p, len, sizeof(T)}; }
+        template <class T>
+        static ChunkArg made_host(T* p, size_t len) { return {MadeHost, p, len, sizeof(T)}; }
+        template <class T>
+        static ChunkArg host(T* p, size_t len) { return {Host, p, len, sizeof(T)}; }
+        static ChunkArg stats(pmc_stats* p) { return host(p, 1); }
+    };
+    struct Chunk {
+        int done, nb;
+        void** dev;
+        template <class T>
+        T* at(int i) const { return static_cast<T*>(dev[i]); }
+    };
+    void for_chunks(int level, int nbatch, int memspace, std::vector<ChunkArg> args, const std::function<void(const Chunk&)>& body);
+    // One launch configuration for the saddle-point solves of a launch.  SolveMode is the last word of the key under which
+    // a MINRES loop is captured and replayed as a graph: a solve finds its graph again only under the same level, width
+    // and mode, and solves that share a mode (the forward solve of solve_fwd, gradient_chunk and gn_hessvec_chunk) share
+    // the graph.
+    enum SolveMode : uint64_t {
+        kSolveObsRows = 1,     // forward solve that maintains only the rows in supp(obs) (solve_fwd without a solution)
+        kSolveFull = 2,        // forward solve on all rows (solve_fwd with a solution, gradient_chunk, gn_hessvec_chunk)
+        kSolveGRows = 3,       // forward solve that maintains the rows of the observation functionals (compute_G)
+        kSolveAdjoint = 5,     // adjoint solve of gradient_chunk
+        kSolveTangent = 6,     // tangent solve of gn_hessvec_chunk
+        kSolveGnAdjoint = 7,   // Gauss-Newton adjoint solve of gn_hessvec_chunk
+    };
+    struct SaddleLaunch {
+        LinOp A;
+        PrecFn prec;
+        uint64_t key0 = 0;     // level and width; the mode completes a key
+        GraphHint hint;        // of the forward solve: right-hand side rhs_bc, the mode asked for
+        // a further solve of the launch with the same operator and preconditioner
+        GraphHint follow_up(SolveMode mode, const void* rhs, const void* x) const {
+            return GraphHint{hash_mix(key0, mode), hash_ptr(hash_ptr(hint.sig, rhs), x)};
+        }
+    };
+    // ensure, phase mark 0 (timed), setup_chunk, phase mark 1 (timed and setup_ends: "Build Solver" ends with the setup; a
+    // caller whose setup phase goes on marks 1 itself), chunk_ops and the forward hint
+    SaddleLaunch saddle_launch(int level, int nb, const double* k_d, SolveMode mode, bool timed, bool setup_ends);
+    // behind a minres_solve: phase mark 2, the columns' results and the phase times into stats (NULL: none), the in-loop timers
+    void solve_done(const MinresResult& res, int nb, pmc_stats* stats);
     void solve_chunk(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                      int nrows, double* G_host);
     void build_hybrid(int level, const pmc_darcy_level& L);
@@ -595,29 +655,24 @@ struct Darcy {
     void apply_one(int level, int nb, const double* k, const double* in, double* out, int memspace, bool precond);
     void solve_chunk_hybrid(int level, int nb, const double* k_d, double* Q_host, double* sol_d, pmc_stats* stats, int row0,
                             int nrows);
-    // darcy_gradient.hip
-    struct AdjointSpec {
-        const double* rhs_d = nullptr;    // caller's dJ/dx, sample-major on the device (NULL with !loglik: obs)
-        bool loglik = false;              // right-hand side of the Gaussian log-likelihood, formed on the device
-        const double* data = nullptr;     // loglik: observed values (host, n_gobs)
-        double noise = 1.0;
-        // third mode: dJ/du of a transport's J on the internal solution, written straight into the u rows
-        Transport* transport = nullptr;
-        const double* curve_bar_d = nullptr;   // seeds: device, sample-major (NULL: zero); ignored with tdata_d
-        const double* stored_bar_d = nullptr;
-        const double* tdata_d = nullptr;       // breakthrough data (device, nreport): curve_bar = -(curve - data) / noise
-        double* curve_d = nullptr;             // forward outputs of the launch: device, nb x nreport and nb
-        double* stored_d = nullptr;
-        int32_t* status_h = nullptr;           // host, nb
-        // fourth mode: dJ/du of the travel times of a tracer on the internal solution
-        Tracer* tracer = nullptr;
-        const double* tbar_d = nullptr;        // seed: device, nb x nparticles; ignored with trdata_d
-        const double* trdata_d = nullptr;      // travel-time data (device, nparticles): T_bar = -(T - data) / noise
-        double* trT_d = nullptr;               // forward outputs of the launch: device, nb x nparticles
-        int32_t* trstatus_d = nullptr;
-    };
-    void check_transport(int level, const Transport* t, const char* who) const;
-    void check_tracer(int level, const Tracer* t, const char* who) const;
+    // darcy_gradient.hip.  gradient_chunk is one launch of every gradient entry; what differs between them is the adjoint
+    // right-hand side, which the entry hands over as a callable: it runs once per launch behind the forward solve (st: the
+    // stream, nb, the level) and leaves the right-hand side in adj_rhs, essential rows zero, from the solution in sol.
+    // There are four, and an entry binds its own operands to one of them: rhs_seed (the caller's dJ/dx, or obs), rhs_loglik
+    // (the observation functionals; also delivers G), rhs_transport and rhs_tracer (the adjoint of a transport / of a tracer
+    // on the flux block, with given seeds or with data).  rhs_finish is their common end.
+    using AdjointRhs = std::function<void(hipStream_t st, int nb, int level)>;
+    void gradient_chunk(int level, int nb, const double* k_d, const AdjointRhs& form_rhs, bool wrt_log, double* Q_host,
+                        double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd, pmc_stats* stats_adj);
+    void rhs_seed(hipStream_t st, int nb, int level, const double* rhs_d);
+    void rhs_loglik(hipStream_t st, int nb, int level, const double* data, double noise, double* G_host);
+    void rhs_transport(hipStream_t st, int nb, int level, Transport& T, const double* curve_bar_d, const double* stored_bar_d,
+                       const double* tdata_d, double noise, double* curve_d, double* stored_d, int32_t* status_h);
+    void rhs_tracer(hipStream_t st, int nb, int level, Tracer& T, const double* tbar_d, const double* trdata_d, double noise,
+                    double* T_d, int32_t* status_d);
+    void rhs_finish(hipStream_t st, int nb, int level, bool zero_p);
+    template <class T>
+    void check_flux_user(int level, const T* t, const std::string& noun, const std::string& who) const;
     DevBuf<double> tr_curve, tr_stored, tr_cb, tr_sb, tr_data;
     DevBuf<double> trc_T, trc_tb, trc_data;
     DevBuf<int32_t> trc_i;
@@ -627,9 +682,6 @@ struct Darcy {
     void gn_hessvec_chunk(int level, int nb, const double* k_d, const double* x_in_d, const double* dk_d, double noise,
                           bool wrt_log, double* hv_d, double* dG_host, double* x_out_d, pmc_stats* stats_tan,
                           pmc_stats* stats_adj);
-    void gradient_chunk(int level, int nb, const double* k_d, const AdjointSpec& adj, bool wrt_log, double* Q_host,
-                        double* G_host, double* grad_d, double* sol_d, double* adj_d, pmc_stats* stats_fwd,
-                        pmc_stats* stats_adj);
 };
 
 // Batched CG vector algebra for Newton-CG (pmc_ncg_*; newton_cg.hip)
