@@ -615,41 +615,6 @@ void Darcy::compute_G(int level, int nbatch, const double* kf, double* G, double
                });
 }
 
-// The launches of a batched entry (handles.hpp, ChunkArg): the widest width of the level first, halved until it fits what is
-// left.  Staging is sized by a chunk before anything of the chunk is enqueued; the first chunk of a call is the widest.
-void Darcy::for_chunks(int level, int nbatch, int memspace, std::vector<ChunkArg> args, const std::function<void(const Chunk&)>& body) {
-    hipStream_t st = ctx.stream;
-    const DarcyLevel& d = lv[level];
-    const bool host = memspace == PMC_MEM_HOST;
-    std::vector<void*> dev(args.size());
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width((size_t)d.n_u + d.n_p, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        auto user = [&](const ChunkArg& a) { return a.user ? (char*)a.user + (size_t)done * a.len * a.size : nullptr; };
-        for (size_t i = 0; i < args.size(); ++i) {
-            const ChunkArg& a = args[i];
-            const bool made = a.kind == ChunkArg::Made || a.kind == ChunkArg::MadeHost;
-            dev[i] = made ? nullptr : user(a);
-            if (!dev[i] || !host || a.kind == ChunkArg::Host) continue;
-            a.stage->ensure(a.len * nb);
-            if (a.kind == ChunkArg::In) PMC_HIP(hipMemcpyAsync(a.stage->p, dev[i], a.size * a.len * nb, hipMemcpyHostToDevice, st));
-            dev[i] = a.stage->p;
-        }
-        body(Chunk{done, nb, dev.data()});
-        for (size_t i = 0; i < args.size(); ++i) {
-            const ChunkArg& a = args[i];
-            const bool made = a.kind == ChunkArg::Made || a.kind == ChunkArg::MadeHost;
-            if (!user(a) || !(made || (host && a.kind == ChunkArg::Out))) continue;
-            const bool to_host = host || a.kind == ChunkArg::MadeHost;
-            PMC_REQUIRE(dev[i] != nullptr, "for_chunks: the body left an output it makes unset");
-            PMC_HIP(hipMemcpyAsync(user(a), dev[i], a.size * a.len * nb, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-        }
-        PMC_HIP(hipStreamSynchronize(st));
-        done += nb;
-    }
-}
-
 // Per-realization setup of a saddle-point launch (buffers sized by ensure): M(k), elimination, rhs_bc and the values of
 // the Schur hierarchy.  solve_chunk and apply_preconditioner / apply_operator enqueue exactly these kernels.
 void Darcy::setup_chunk(int level, int nb, const double* k_d) {
@@ -1239,36 +1204,28 @@ void Darcy::solve_fwd(int level, int nbatch, const double* kf, double* Q, double
     PMC_REQUIRE(level >= 0 && level < n_mc, "SolveFwd: level out of range");
     PMC_REQUIRE(nbatch >= 1 && kf != nullptr && Q != nullptr, "SolveFwd: bad arguments");
     ctx.activate();
-    hipStream_t st = ctx.stream;
     DarcyLevel& d = lv[level];
     const size_t n = (size_t)d.n_u + d.n_p;
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width((size_t)d.n_u + d.n_p, true, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* k_d = kf + (size_t)done * d.n_p;
-        const int row0 = (sol_kind == 2) ? d.n_u : 0;
-        const size_t nout = (sol_kind == 2) ? (size_t)d.n_p : n;
-        double* sol_d = sol_out ? sol_out + (size_t)done * nout : nullptr;
-        auto chunk = [&](const double* kd, double* q, double* so, pmc_stats* stt) {
-            if (hybrid) solve_chunk_hybrid(level, nb, kd, q, so, stt, row0, (int)nout);
-            else solve_chunk(level, nb, kd, q, so, stt, row0, (int)nout, nullptr);
-        };
-        if (memspace == PMC_MEM_HOST) {
-            ensure(level, nb);
-            PMC_HIP(hipMemcpyAsync(stage_k.p, k_d, sizeof(double) * d.n_p * nb, hipMemcpyHostToDevice, st));
-            chunk(stage_k.p, Q + done, sol_d ? stage_sol.p : nullptr, stats ? stats + done : nullptr);
-            if (sol_d) {
-                PMC_HIP(hipMemcpyAsync(sol_d, stage_sol.p, sizeof(double) * nout * nb, hipMemcpyDeviceToHost, st));
-                PMC_HIP(hipStreamSynchronize(st));
-            }
-        } else {
-            chunk(k_d, Q + done, sol_d, stats ? stats + done : nullptr);
-        }
-        if (C)
-            for (int b = 0; b < nb; ++b) C[done + b] = (double)n;   // global true dofs (DarcySolver.cpp:429)
-        done += nb;
-    }
+    const int row0 = (sol_kind == 2) ? d.n_u : 0;
+    const size_t nout = (sol_kind == 2) ? (size_t)d.n_p : n;
+    const int width = batch_width(n, true, ctx.device);
+    const bool host = memspace == PMC_MEM_HOST;
+    if (host) ensure(level, first_chunk(width, nbatch));   // also on a hybridized handle, whose launches size only their own buffers
+    // the launches synchronise themselves on the way to Q; a solution staged to the host is copied behind that
+    enum { K, SOL, Q_, STATS };
+    pmc::for_chunks(ctx, width, nbatch, memspace, host && sol_out != nullptr,
+                    {ChunkArg::in(kf, (size_t)d.n_p, stage_k), ChunkArg::out(sol_out, nout, stage_sol), ChunkArg::host(Q, 1),
+                     ChunkArg::stats(stats)},
+                    [&](const Chunk& c) {
+                        if (hybrid)
+                            solve_chunk_hybrid(level, c.nb, c.at<double>(K), c.at<double>(Q_), c.at<double>(SOL), c.at<pmc_stats>(STATS),
+                                               row0, (int)nout);
+                        else
+                            solve_chunk(level, c.nb, c.at<double>(K), c.at<double>(Q_), c.at<double>(SOL), c.at<pmc_stats>(STATS), row0,
+                                        (int)nout, nullptr);
+                        if (C)
+                            for (int b = 0; b < c.nb; ++b) C[c.done + b] = (double)n;   // global true dofs (DarcySolver.cpp:429)
+                    });
 }
 
 void Darcy::apply_one(int level, int nb, const double* k_in, const double* in, double* out, int memspace, bool precond) {

@@ -452,7 +452,7 @@ void gauss_loglik(int nb, size_t len, const double* values, const double* data, 
 }
 }  // namespace
 
-// ---- the batched entries: argument checks, the operands of for_chunks (handles.hpp), one launch as the body -------------------
+// ---- the batched entries: argument checks, the operands of for_chunks (chunks.hpp), one launch as the body -------------------
 void Darcy::mass_sensitivity(int level, int nbatch, const double* kf, const double* x, const double* lam, bool wrt_log,
                              double* grad, int memspace) {
     PMC_REQUIRE(level >= 0 && level < n_mc, "mass_sensitivity: level out of range");

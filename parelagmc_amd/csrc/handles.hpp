@@ -1,5 +1,6 @@
 // Device-side objects behind the opaque C handles.
 #pragma once
+#include "chunks.hpp"
 #include "solver.hpp"
 
 namespace pmc {
@@ -147,7 +148,12 @@ struct Sampler {
     // key_salt != 0: a solver configuration (graph key) apart from Eval's with the same level / width / rows
     void solve_system(int level, int nb, bool zero_guess, int x_row0, int x_nrows, pmc_stats* stats, const RhsFn* rhs = nullptr,
                       uint64_t key_salt = 0);
-    PrecFn preconditioner(int level, int nb, int degM, Multigrid* mgp, int mg_l0);
+    PrecFn preconditioner(int level, int nb);
+    // ... that hierarchy for the solves themselves, which set per-solve state on it (the handle's own amg[level] or mg)
+    Multigrid& cycle_mg(int level) { return const_cast<Multigrid&>(cycle_hierarchy(level).g); }
+    int degree_M(int level) const;
+    const double* level_walk(int nb, int from, int to, const double* src, double* dst, const Sell* last = nullptr);
+    RhsFn multiplier_rhs(int level, const double* fz);
     void eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                     int init_level, bool use_init, double* emb_d, pmc_stats* stats);
     // Eval of a KL handle: every realization in one launch
@@ -585,38 +591,11 @@ struct Darcy {
     void ensure(int level, int nb);
     void setup_chunk(int level, int nb, const double* k_d);
     void chunk_ops(int level, int nb, bool timing_ok, LinOp& A, PrecFn& prec);
-    // The launches of a batched entry (for_chunks, darcy.hip).  The entry lists its per-column operands once; for every
-    // launch of nb columns starting at column `done` the body finds the pointer to use in Chunk::dev, in the order listed:
-    //   In / Out   sample-major device arrays of the kernels.  Device memspace: the caller's array at column `done`.  Host
-    //              memspace: `stage`, uploaded before the body (In) or copied back behind it (Out).
-    //   Made       an output the body leaves in a device buffer of the handle: the body sets dev[i], and it is copied out
-    //              behind the body in both memspaces (device to device or device to host).  MadeHost: the caller's array is
-    //              host memory whatever the memspace.
-    //   Host       a host array with one entry of `len` per column (stats, Q, status words): the offset only.
-    // An absent optional operand (user == NULL) yields NULL and is never copied.  Uploads and copies run in the listed
-    // order; every launch ends with a synchronisation of the stream.
-    struct ChunkArg {
-        enum Kind { In, Out, Made, MadeHost, Host } kind;
-        const void* user;                 // the caller's array, all columns
-        size_t len, size;                 // entries per column, bytes per entry
-        DevBuf<double>* stage = nullptr;  // In / Out
-        static ChunkArg in(const double* p, size_t len, DevBuf<double>& stage) { return {In, p, len, sizeof(double), &stage}; }
-        static ChunkArg out(double* p, size_t len, DevBuf<double>& stage) { return {Out, p, len, sizeof(double), &stage}; }
-        template <class T>
-        static ChunkArg made(T* p, size_t len) { return {Made, p, len, sizeof(T)}; }
-        template <class T>
-        static ChunkArg made_host(T* p, size_t len) { return {MadeHost, p, len, sizeof(T)}; }
-        template <class T>
-        static ChunkArg host(T* p, size_t len) { return {Host, p, len, sizeof(T)}; }
-        static ChunkArg stats(pmc_stats* p) { return host(p, 1); }
-    };
-    struct Chunk {
-        int done, nb;
-        void** dev;
-        template <class T>
-        T* at(int i) const { return static_cast<T*>(dev[i]); }
-    };
-    void for_chunks(int level, int nbatch, int memspace, std::vector<ChunkArg> args, const std::function<void(const Chunk&)>& body);
+    // The launches of a batched entry: ChunkArg, Chunk and the driver are in chunks.hpp.  This forwards with the level's
+    // launch width and a synchronisation behind every launch.
+    void for_chunks(int level, int nbatch, int memspace, const std::vector<ChunkArg>& args, const std::function<void(const Chunk&)>& body) {
+        pmc::for_chunks(ctx, batch_width((size_t)lv[level].n_u + lv[level].n_p, true, ctx.device), nbatch, memspace, true, args, body);
+    }
     // One launch configuration for the saddle-point solves of a launch.  SolveMode is the last word of the key under which
     // a MINRES loop is captured and replayed as a graph: a solve finds its graph again only under the same level, width
     // and mode, and solves that share a mode (the forward solve of solve_fwd, gradient_chunk and gn_hessvec_chunk) share

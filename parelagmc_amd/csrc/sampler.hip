@@ -550,6 +550,38 @@ void Sampler::sample(int level, uint64_t first_id, int nbatch, double* xi, int m
 static std::atomic<uint64_t> g_fused_field_evals{0};
 uint64_t fused_field_eval_count() { return g_fused_field_evals.load(std::memory_order_relaxed); }
 
+// Interleaved vectors from level `from` to level `to` through the transfer operators of the caller's hierarchy: restriction
+// with P^T down the levels (from < to; `last`, when given, takes the place of the last P^T) or prolongation with P up them
+// (from > to).  The products ping-pong between tA and tB; the last one goes to `dst`, or stays in scratch when dst is NULL.
+// Returns where the result is: src itself when from == to.
+const double* Sampler::level_walk(int nb, int from, int to, const double* src, double* dst, const Sell* last) {
+    hipStream_t st = ctx.stream;
+    const int step = from < to ? 1 : -1;
+    const double* cur = src;
+    for (int l = from; l != to; l += step) {
+        const bool final_step = l + step == to;
+        const Sell& T = step < 0 ? mg.L[l - 1].P : (final_step && last) ? *last : mg.L[l].Pt;
+        double* out = (final_step && dst) ? dst : (cur == tA.p ? tB.p : tA.p);
+        k::spmm(st, nb, view(T), cur, out, false, nullptr, nullptr);
+        cur = out;
+    }
+    return cur;
+}
+
+// The right-hand side of the multiplier system of `level`, Gz fz, as the kernel that writes it: the product is handed to the
+// solve, which has it write the first Lanczos vector and its fp32 copy where it can (RhsFn); nothing reads the multiplier
+// rows of rhs after the solve, only fz behind them
+RhsFn Sampler::multiplier_rhs(int level, const double* fz) {
+    const SellView Gzv = view(lv[level].Gz);
+    RhsFn make_rhs;
+    make_rhs.store = rhs.p;
+    make_rhs.write = [Gzv, fz](const Lanes& L, int nb_, double* y, float* y32) {
+        if (y32) k::spmm_store32(L.main, nb_, Gzv, fz, y, y32);
+        else k::spmm(L.main, nb_, Gzv, fz, y, false, nullptr, nullptr);
+    };
+    return make_rhs;
+}
+
 void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, double* s_d, const double* init_d,
                          int init_level, bool use_init, double* emb_d, pmc_stats* stats) {
     hipStream_t st = ctx.stream;
@@ -557,31 +589,19 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
     const int n_u = d.n_u, n_s = d.n_s;
     ensure(level, nb);
     if (stats) ctx.phase_mark(0);
+    // rhs / sol hold [u- resp. lambda-sized vector | s-sized vector]: n_u + n_s rows each.
+    // saddle-point: rhs_s = -g W^{1/2} xi on xi_level, restricted with Ps^T (PDESampler.cpp:423-438); rhs_u = 0 (:441-442).
+    // hybridized: rhs_s = fz = z f with f the same vector, the last restriction (or the scale, without one) landing on z f
+    // directly; rhs = G f = Gz fz; lambda = H^-1 rhs; s = fz - G^T lambda
+    if (!hybrid) k::fill(st, (size_t)n_u * nb, rhs.p, 0.0);
+    double* rhs_s = rhs.p + (size_t)n_u * nb;
+    const double* scale = (hybrid && xi_level == level) ? d.zw_sqrt.p : lv[xi_level].w_sqrt.p;
+    double* xi_il = xi_level == level ? rhs_s : tA.p;
+    k::interleave(st, nb, lv[xi_level].n_s, xi_d, scale, -g, xi_il);
+    level_walk(nb, xi_level, level, xi_il, rhs_s, hybrid ? &d.Ptz : nullptr);
     if (hybrid) {
-        // fz = z f with f = -g W^{1/2} xi (restricted from xi_level); rhs = G f = Gz fz; lambda = H^-1 rhs; s = fz - G^T lambda.
-        // rhs / sol hold [lambda-sized vector | fz resp. s]: n_u + n_s rows each, as in the saddle-point layout
-        double* fz = rhs.p + (size_t)n_u * nb;
-        if (xi_level == level) {
-            k::interleave(st, nb, n_s, xi_d, d.zw_sqrt.p, -g, fz);
-        } else {
-            double* cur = tA.p;
-            double* nxt = tB.p;
-            k::interleave(st, nb, lv[xi_level].n_s, xi_d, lv[xi_level].w_sqrt.p, -g, cur);
-            for (int l = xi_level; l < level; ++l) {
-                const bool final_step = l + 1 == level;
-                k::spmm(st, nb, final_step ? view(d.Ptz) : view(mg.L[l].Pt), cur, final_step ? fz : nxt, false, nullptr, nullptr);
-                std::swap(cur, nxt);
-            }
-        }
-        // the product is handed to the solve, which has it write the first Lanczos vector and its fp32 copy where it can
-        // (RhsFn); nothing reads the multiplier rows of rhs after the solve, only fz behind them
-        const SellView Gzv = view(d.Gz);
-        RhsFn make_rhs;
-        make_rhs.store = rhs.p;
-        make_rhs.write = [Gzv, fz](const Lanes& L, int nb_, double* y, float* y32) {
-            if (y32) k::spmm_store32(L.main, nb_, Gzv, fz, y, y32);
-            else k::spmm(L.main, nb_, Gzv, fz, y, false, nullptr, nullptr);
-        };
+        const double* fz = rhs_s;
+        const RhsFn make_rhs = multiplier_rhs(level, fz);
         if (stats) ctx.phase_mark(1);
         solve_system(level, nb, true, 0, n_u, stats, &make_rhs);
         const SellView Glv = view(d.Gl);
@@ -595,43 +615,16 @@ void Sampler::eval_chunk(int level, int xi_level, int nb, const double* xi_d, do
         double* field = sol.p + (size_t)n_u * nb;
         k::residual(st, nb, Glv, fz, sol.p, field);
     } else {
-    // rhs_s = -g W^{1/2} xi on xi_level, restricted with Ps^T (PDESampler.cpp:423-438); rhs_u = 0 (:441-442)
-    k::fill(st, (size_t)n_u * nb, rhs.p, 0.0);
-    double* rhs_s = rhs.p + (size_t)n_u * nb;
-    if (xi_level == level) {
-        k::interleave(st, nb, n_s, xi_d, lv[xi_level].w_sqrt.p, -g, rhs_s);
-    } else {
-        double* cur = tA.p;
-        double* nxt = tB.p;
-        k::interleave(st, nb, lv[xi_level].n_s, xi_d, lv[xi_level].w_sqrt.p, -g, cur);
-        for (int l = xi_level; l < level; ++l) {
-            double* dst = (l + 1 == level) ? rhs_s : nxt;
-            k::spmm(st, nb, view(mg.L[l].Pt), cur, dst, false, nullptr, nullptr);
-            std::swap(cur, nxt);
+        if (use_init) {   // initial guess (:498-515)
+            double* sol_s = sol.p + (size_t)n_u * nb;
+            k::fill(st, (size_t)n_u * nb, sol.p, 0.0);
+            double* init_il = init_level == level ? sol_s : tA.p;
+            k::interleave(st, nb, lv[init_level].n_s, init_d, nullptr, 1.0, init_il);
+            level_walk(nb, init_level, level, init_il, sol_s);
         }
-    }
-    // initial guess (:498-515)
-    bool zero_guess = true;
-    if (use_init) {
-        double* sol_s = sol.p + (size_t)n_u * nb;
-        k::fill(st, (size_t)n_u * nb, sol.p, 0.0);
-        if (init_level == level) {
-            k::interleave(st, nb, n_s, init_d, nullptr, 1.0, sol_s);
-        } else {
-            double* cur = tA.p;
-            double* nxt = tB.p;
-            k::interleave(st, nb, lv[init_level].n_s, init_d, nullptr, 1.0, cur);
-            for (int l = init_level; l > level; --l) {
-                double* dst = (l - 1 == level) ? sol_s : nxt;
-                k::spmm(st, nb, view(mg.L[l - 1].P), cur, dst, false, nullptr, nullptr);
-                std::swap(cur, nxt);
-            }
-        }
-        zero_guess = false;
-    }
-    if (stats) ctx.phase_mark(1);
-    // only the s-block of the solution is ever read (PDESampler.cpp:526): maintain only those rows
-    solve_system(level, nb, zero_guess, n_u, n_s, stats);
+        if (stats) ctx.phase_mark(1);
+        // only the s-block of the solution is ever read (PDESampler.cpp:526): maintain only those rows
+        solve_system(level, nb, !use_init, n_u, n_s, stats);
     }
     // outputs (:526-533 and the embedded variants' maps)
     const double* sol_s = sol.p + (size_t)n_u * nb;
@@ -655,9 +648,8 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
     hipStream_t st = ctx.stream;
     SamplerLevel& d = lv[level];
     const int n_u = d.n_u, n_s = d.n_s, n = (int)system_rows(level);
-    const bool use_amg = level < (int)amg.size() && amg[level];
-    Multigrid* mgp = use_amg ? amg[level].get() : &mg;
-    const int mg_l0 = use_amg ? 0 : level;
+    Multigrid* mgp = &cycle_mg(level);
+    const int mg_l0 = cycle_hierarchy(level).first;
     // small level whose whole Schur V-cycle fits the LDS tail: one persistent workgroup per realization runs the entire
     // MINRES solve (k::mini_sampler_solve) instead of ~7 kernel launches per iteration
     static const int mini_env = [] {      // tuning override of opts.mini_max_rows
@@ -665,10 +657,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
         return e ? atoi(e) : -1;
     }();
     const int mini_max_rows = mini_env >= 0 ? mini_env : opts.mini_max_rows;
-    // M-block degree: as asked for, or by the measured Chebyshev interval of the level - meshes with badly shaped cells
-    // (cube_tet_embed: lambda_max / lambda_min = 22 against 8 on uniform tetrahedra) pay for degree 4 (69.6 -> 55.9
-    // iterations, 20.0 -> 19.5 ms per batch at 314 k DoF), well shaped ones do not
-    const int degM = opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (d.ratio_M > 16.0 ? 4 : 2);
+    const int degM = degree_M(level);
     const bool mini = !hybrid && n <= mini_max_rows && degM == 2 && opts.use_graph == 0 &&
                       mg_l0 < (int)mgp->tail.size() && mgp->tail[mg_l0].p != nullptr;
     if (mini) {
@@ -716,7 +705,7 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
             k::spmm_z_update(L.main, nb_, Av, x, lz, v, v_zero);
         };
     }
-    PrecFn prec = preconditioner(level, nb, degM, mgp, mg_l0);
+    PrecFn prec = preconditioner(level, nb);
     // hybridized solver: the Lanczos update also writes the fp32 copy the cycle's first two kernels read (LAB_NOTES 10.9)
     work.want_r32 = hybrid && opts.precond_storage != PMC_STORAGE_FP64 && mgp->top_reads_r32(mg_l0, nb);
     if (const char* e = lab_env("PMC_R32")) work.want_r32 = work.want_r32 && atoi(e) != 0;
@@ -738,11 +727,13 @@ void Sampler::solve_system(int level, int nb, bool zero_guess, int x_row0, int x
 }
 
 // z = B^-1 r of `level`: the block-diagonal preconditioner of the MINRES solve (M-block polynomial | V-cycle on the Schur block)
-PrecFn Sampler::preconditioner(int level, int nb, int degM, Multigrid* mgp, int mg_l0) {
+PrecFn Sampler::preconditioner(int level, int nb) {
     SamplerLevel& d = lv[level];
     const int n_u = d.n_u;
+    Multigrid* mgp = &cycle_mg(level);
+    const int mg_l0 = cycle_hierarchy(level).first;
     if (hybrid) {   // SPD multiplier system: the V-cycle alone
-        (void)nb; (void)degM;
+        (void)nb;
         return [=](const Lanes& L, int nb_, const double* r, zvec z, double* dot_partial, double*) {
             // inside the MINRES loop the Lanczos update has left an fp32 copy of r (MinresWork::r32): the cycle's first two
             // kernels on the finest level read that
@@ -754,7 +745,7 @@ PrecFn Sampler::preconditioner(int level, int nb, int degM, Multigrid* mgp, int 
     }
     const SellView Mv = view(d.M);
     const double* dinvM = d.dinvM.p;
-    ChebParams cpM{degM, 1.0, d.ratio_M, d.M_scaled.p};
+    ChebParams cpM{degree_M(level), 1.0, d.ratio_M, d.M_scaled.p};
     if (!cheb_fused(cpM, true)) cx2.ensure((size_t)n_u * nb);   // higher degrees iterate in fp64 scratch (cheb_apply_z)
     double* cxp = cx.p;
     double* cx2p = cx2.p;
@@ -804,10 +795,7 @@ void Sampler::apply_preconditioner(int level, int nbatch, const double* r_in, do
     }
     // hybrid handles: multiplier vectors cross the boundary in the caller's numbering (see lam_new2old)
     k::interleave(st, nb, (int)n, r_d, nullptr, 1.0, rhs.p, hybrid ? d.lam_new2old.p : nullptr);
-    const bool use_amg = level < (int)amg.size() && amg[level];
-    Multigrid* mgp = use_amg ? amg[level].get() : &mg;
-    const int degM = opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (d.ratio_M > 16.0 ? 4 : 2);
-    PrecFn prec = preconditioner(level, nb, degM, mgp, use_amg ? 0 : level);
+    PrecFn prec = preconditioner(level, nb);
     // the result is taken in fp64: with PMC_STORAGE_FP32 the solver additionally rounds it to fp32 (6e-8 relative)
     prec(ctx.lanes(false), nb, rhs.p, zvec(zi.p, false), part.p, part.p + (size_t)dot_capacity((int)n, nb) * nb);
     double* out_d = memspace == PMC_MEM_HOST ? stage.p : z_out;
@@ -822,33 +810,24 @@ void Sampler::mult(int level, int nbatch, const double* rhs_in, double* sol_io, 
     ctx.activate();
     hipStream_t st = ctx.stream;
     const size_t n = system_rows(level);
+    const int width = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
+    ensure(level, first_chunk(width, nbatch));
+    // sol_io is read only with a guess and always written: an In (absent without a guess) and an Out on one staging buffer
     DevBuf<double> stage_r, stage_x;
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        ensure(level, nb);
-        const double* r_d = rhs_in + (size_t)done * n;
-        double* x_d = sol_io + (size_t)done * n;
-        if (memspace == PMC_MEM_HOST) {
-            stage_r.ensure(n * nb);
-            stage_x.ensure(n * nb);
-            PMC_HIP(hipMemcpyAsync(stage_r.p, r_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-            if (use_guess) PMC_HIP(hipMemcpyAsync(stage_x.p, x_d, sizeof(double) * n * nb, hipMemcpyHostToDevice, st));
-            r_d = stage_r.p;
-        }
-        double* xdev = memspace == PMC_MEM_HOST ? stage_x.p : x_d;
-        if (stats) ctx.phase_mark(0);
-        const int* n2o = hybrid ? lv[level].lam_new2old.p : nullptr;
-        k::interleave(st, nb, (int)n, r_d, nullptr, 1.0, rhs.p, n2o);
-        if (use_guess) k::interleave(st, nb, (int)n, xdev, nullptr, 1.0, sol.p, n2o);
-        if (stats) ctx.phase_mark(1);
-        solve_system(level, nb, !use_guess, 0, (int)n, stats ? stats + done : nullptr);
-        k::deinterleave(st, nb, (int)n, sol.p, hybrid ? lv[level].lam_old2new.p : nullptr, nullptr, false, xdev);
-        if (memspace == PMC_MEM_HOST) PMC_HIP(hipMemcpyAsync(x_d, stage_x.p, sizeof(double) * n * nb, hipMemcpyDeviceToHost, st));
-        PMC_HIP(hipStreamSynchronize(st));
-        done += nb;
-    }
+    enum { RHS, GUESS, SOL, STATS };
+    for_chunks(ctx, width, nbatch, memspace, true,
+               {ChunkArg::in(rhs_in, n, stage_r), ChunkArg::in(use_guess ? sol_io : nullptr, n, stage_x), ChunkArg::out(sol_io, n, stage_x),
+                ChunkArg::stats(stats)},
+               [&](const Chunk& c) {
+                   if (stats) ctx.phase_mark(0);
+                   // hybrid handles: multiplier vectors cross the boundary in the caller's numbering (see lam_new2old)
+                   const int* n2o = hybrid ? lv[level].lam_new2old.p : nullptr;
+                   k::interleave(st, c.nb, (int)n, c.at<double>(RHS), nullptr, 1.0, rhs.p, n2o);
+                   if (use_guess) k::interleave(st, c.nb, (int)n, c.at<double>(GUESS), nullptr, 1.0, sol.p, n2o);
+                   if (stats) ctx.phase_mark(1);
+                   solve_system(level, c.nb, !use_guess, 0, (int)n, c.at<pmc_stats>(STATS));
+                   k::deinterleave(st, c.nb, (int)n, sol.p, hybrid ? lv[level].lam_old2new.p : nullptr, nullptr, false, c.at<double>(SOL));
+               });
 }
 
 void Sampler::apply_operator(int level, int nb, const double* x, double* y, int memspace, int repeat, double* avg_ms,
@@ -928,44 +907,36 @@ void Sampler::eval(int level, int xi_level, int nbatch, const double* xi, double
     hipStream_t st = ctx.stream;
     const int n_xi = lv[xi_level].n_s, n_out = lv[level].out_size, n_s = lv[level].n_s;
     const int n_init = use_init ? lv[init_level].n_s : 0;
-    // embed_s_out may alias init_s (the managers pass one buffer for both).  With several chunks and a coarser
-    // init_level a chunk's embed rows (n_s each) would overwrite init rows (n_init < n_s each) of later chunks before
-    // they are read: keep a private copy of init_s for the whole call then.
+    const int width = launch_width(level);
+    const int widest = first_chunk(width, nbatch);
+    // embed_s_out may alias init_s (the managers pass one buffer for both).  With several launches and a coarser
+    // init_level a launch's embed rows (n_s each) would overwrite init rows (n_init < n_s each) of later launches before
+    // they are read: keep a private copy of init_s for the whole call then.  (Device memory only; host memory: DESIGN.md,
+    // "How a batched call becomes launches".)
     DevBuf<double> init_copy;
-    const int width = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
-    const bool several_chunks = !valid_batch(nbatch) || nbatch > width;   // exactly when the loop below cuts the call
-    if (use_init && memspace == PMC_MEM_DEVICE && emb_out == init_s && n_init != n_s && several_chunks) {
+    if (use_init && memspace == PMC_MEM_DEVICE && emb_out == init_s && n_init != n_s && widest < nbatch) {
         init_copy.alloc((size_t)n_init * nbatch);
         PMC_HIP(hipMemcpyAsync(init_copy.p, init_s, sizeof(double) * n_init * nbatch, hipMemcpyDeviceToDevice, st));
         init_s = init_copy.p;
     }
-    int done = 0;
-    while (done < nbatch) {
-        int nb = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* xi_d = xi + (size_t)done * n_xi;
-        const double* init_d = use_init ? init_s + (size_t)done * n_init : nullptr;
-        double* s_d = s_out + (size_t)done * n_out;
-        double* emb_d = emb_out ? emb_out + (size_t)done * n_s : nullptr;
-        if (memspace == PMC_MEM_HOST) {
-            ensure(level, nb);
-            PMC_HIP(hipMemcpyAsync(stage_in.p, xi_d, sizeof(double) * n_xi * nb, hipMemcpyHostToDevice, st));
-            const double* init_dev = nullptr;
-            if (use_init) {
-                PMC_HIP(hipMemcpyAsync(stage_emb.p, init_d, sizeof(double) * n_init * nb, hipMemcpyHostToDevice, st));
-                init_dev = stage_emb.p;
-            }
-            eval_chunk(level, xi_level, nb, stage_in.p, stage_out.p, init_dev, init_level, use_init,
-                       emb_d ? stage_emb.p : nullptr, stats ? stats + done : nullptr);
-            PMC_HIP(hipMemcpyAsync(s_d, stage_out.p, sizeof(double) * n_out * nb, hipMemcpyDeviceToHost, st));
-            if (emb_d) PMC_HIP(hipMemcpyAsync(emb_d, stage_emb.p, sizeof(double) * n_s * nb, hipMemcpyDeviceToHost, st));
-            PMC_HIP(hipStreamSynchronize(st));
-        } else {
-            eval_chunk(level, xi_level, nb, xi_d, s_d, init_d, init_level, use_init, emb_d, stats ? stats + done : nullptr);
-        }
-        done += nb;
-    }
+    ensure(level, widest);   // the staging buffers are among what it sizes: no launch may grow them behind an upload
+    // init_s and embed_s_out share stage_emb: a launch has consumed the guess before it writes the embedded field
+    enum { XI, INIT, S, EMB, STATS };
+    for_chunks(ctx, width, nbatch, memspace, memspace == PMC_MEM_HOST,
+               {ChunkArg::in(xi, (size_t)n_xi, stage_in), ChunkArg::in(use_init ? init_s : nullptr, (size_t)n_init, stage_emb),
+                ChunkArg::out(s_out, (size_t)n_out, stage_out), ChunkArg::out(emb_out, (size_t)n_s, stage_emb), ChunkArg::stats(stats)},
+               [&](const Chunk& c) {
+                   eval_chunk(level, xi_level, c.nb, c.at<double>(XI), c.at<double>(S), c.at<double>(INIT), init_level, use_init,
+                              c.at<double>(EMB), c.at<pmc_stats>(STATS));
+               });
     if (init_copy.p) PMC_HIP(hipStreamSynchronize(st));   // the private copy is released on return
+}
+
+// M-block degree of `level`: as asked for, or by the measured Chebyshev interval of the level - meshes with badly shaped
+// cells (cube_tet_embed: lambda_max / lambda_min = 22 against 8 on uniform tetrahedra) pay for degree 4 (69.6 -> 55.9
+// iterations, 20.0 -> 19.5 ms per batch at 314 k DoF), well shaped ones do not
+int Sampler::degree_M(int level) const {
+    return opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (lv[level].ratio_M > 16.0 ? 4 : 2);
 }
 
 // the hierarchy the solves of `level` cycle on: the level's internal one from its level 0, or the caller's from `level`
@@ -1019,7 +990,7 @@ void Sampler::vcycle_level(int level, int vlevel, int* nvlevels, double* info) c
     info[6] = m.is_last ? m.last_ratio : g.coarse_ratio;
     info[7] = own ? 1.0 : 0.0;   // internal hierarchies are plain Galerkin products; the caller's levels are rediscretized
     info[8] = hybrid ? 0.0 : d.ratio_M;
-    info[9] = hybrid ? 0.0 : (opts.cheb_degree_M > 0 ? opts.cheb_degree_M : (d.ratio_M > 16.0 ? 4 : 2));
+    info[9] = hybrid ? 0.0 : degree_M(level);
     info[10] = hybrid ? 2.0 : own ? 1.0 : 0.0;
     info[11] = g.dense_nb;
     info[12] = role_narrow;

@@ -242,32 +242,18 @@ void Sampler::eval_adjoint_chunk(int level, int xi_level, int nb, const double* 
     }
     if (hybrid) {
         // rhs = Gz (z q) = G q; lambda = H^-1 rhs; S q = z q - G^T lambda: eval_chunk's solve and back-substitution
-        const SellView Gzv = view(d.Gz);
-        double* fz = rhs_s;
-        RhsFn make_rhs;
-        make_rhs.store = rhs.p;
-        make_rhs.write = [Gzv, fz](const Lanes& L, int nb_, double* y, float* y32) {
-            if (y32) k::spmm_store32(L.main, nb_, Gzv, fz, y, y32);
-            else k::spmm(L.main, nb_, Gzv, fz, y, false, nullptr, nullptr);
-        };
+        const RhsFn make_rhs = multiplier_rhs(level, rhs_s);
         if (stats) ctx.phase_mark(1);
         solve_system(level, nb, true, 0, n_u, stats, &make_rhs, kAdjointKey);
-        k::residual(st, nb, view(d.Gl), fz, sol.p, sol.p + (size_t)n_u * nb);
+        k::residual(st, nb, view(d.Gl), rhs_s, sol.p, sol.p + (size_t)n_u * nb);
     } else {
         k::fill(st, (size_t)n_u * nb, rhs.p, 0.0);
         if (stats) ctx.phase_mark(1);
         solve_system(level, nb, true, n_u, n_s, stats, nullptr, kAdjointKey);
     }
     // R^T: down the levels with the prolongators, then the row scale of D
-    const double* cur = sol.p + (size_t)n_u * nb;
-    double* nxt = tA.p;
-    double* other = tB.p;
-    for (int l = level - 1; l >= xi_level; --l) {
-        k::spmm(st, nb, view(mg.L[l].P), cur, nxt, false, nullptr, nullptr);
-        cur = nxt;
-        std::swap(nxt, other);
-    }
-    k::deinterleave(st, nb, lv[xi_level].n_s, cur, nullptr, lv[xi_level].w_sqrt.p, false, grad_d);
+    const double* fine = level_walk(nb, level, xi_level, sol.p + (size_t)n_u * nb, nullptr);
+    k::deinterleave(st, nb, lv[xi_level].n_s, fine, nullptr, lv[xi_level].w_sqrt.p, false, grad_d);
 }
 
 void Sampler::eval_adjoint(int level, int xi_level, int nbatch, const double* v, const double* s_out, double* grad_xi,
@@ -285,38 +271,25 @@ void Sampler::eval_adjoint(int level, int xi_level, int nbatch, const double* v,
         return;
     }
     ctx.activate();
-    hipStream_t st = ctx.stream;
     ensure_adjoint(level);
     const int n_xi = lv[xi_level].n_s, n_out = lv[level].out_size;
-    int done = 0;
-    while (done < nbatch) {   // the launch widths of Sampler::eval
-        int nb = batch_width((size_t)lv[level].n_u + lv[level].n_s, false, ctx.device);
-        while (nb > nbatch - done) nb >>= 1;
-        const double* v_d = v + (size_t)done * n_out;
-        const double* s_d = s_out ? s_out + (size_t)done * n_out : nullptr;
-        double* g_d = grad_xi + (size_t)done * n_xi;
-        if (memspace == PMC_MEM_HOST) {
-            ensure(level, nb);
-            PMC_HIP(hipMemcpyAsync(stage_in.p, v_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
-            if (s_d) PMC_HIP(hipMemcpyAsync(stage_emb.p, s_d, sizeof(double) * n_out * nb, hipMemcpyHostToDevice, st));
-            v_d = stage_in.p;
-            if (s_d) s_d = stage_emb.p;
-        }
-        if (cond) {   // w = Gamma^T (v o f') per launch, then the unconditioned path with v := w, s_out := NULL
-            cond->hook_w.ensure((size_t)n_out * nb);
-            cond->apply_adjoint_device(level, nb, v_d, s_d, cond->hook_w.p, nbatch);
-            v_d = cond->hook_w.p;
-            s_d = nullptr;
-        }
-        if (memspace == PMC_MEM_HOST) {
-            eval_adjoint_chunk(level, xi_level, nb, v_d, s_d, stage_out.p, stats ? stats + done : nullptr);
-            PMC_HIP(hipMemcpyAsync(g_d, stage_out.p, sizeof(double) * n_xi * nb, hipMemcpyDeviceToHost, st));
-            PMC_HIP(hipStreamSynchronize(st));
-        } else {
-            eval_adjoint_chunk(level, xi_level, nb, v_d, s_d, g_d, stats ? stats + done : nullptr);
-        }
-        done += nb;
-    }
+    const int width = launch_width(level);   // the launch widths of Sampler::eval
+    ensure(level, first_chunk(width, nbatch));   // the staging buffers are among what it sizes
+    enum { V, S, GRAD, STATS };
+    for_chunks(ctx, width, nbatch, memspace, memspace == PMC_MEM_HOST,
+               {ChunkArg::in(v, (size_t)n_out, stage_in), ChunkArg::in(s_out, (size_t)n_out, stage_emb),
+                ChunkArg::out(grad_xi, (size_t)n_xi, stage_out), ChunkArg::stats(stats)},
+               [&](const Chunk& c) {
+                   const double* v_d = c.at<double>(V);
+                   const double* s_d = c.at<double>(S);
+                   if (cond) {   // w = Gamma^T (v o f') per launch, then the unconditioned path with v := w, s_out := NULL
+                       cond->hook_w.ensure((size_t)n_out * c.nb);
+                       cond->apply_adjoint_device(level, c.nb, v_d, s_d, cond->hook_w.p, nbatch);
+                       v_d = cond->hook_w.p;
+                       s_d = nullptr;
+                   }
+                   eval_adjoint_chunk(level, xi_level, c.nb, v_d, s_d, c.at<double>(GRAD), c.at<pmc_stats>(STATS));
+               });
 }
 
 }  // namespace pmc
